@@ -15,21 +15,23 @@ by rank with heamd.sharding, no data-path collective; the RCCL all-gather of the
                     plaintexts per GPU); 8 GPUs = the 2^20 products of configs[4], the database sharded by column as
                     PirUtil.computeResponseForOneChunk groups columns (IndexPir/PirUtil.swift:427-445)
 
-The contract's measurement (W warm-up steps, K timed steps) runs twice in the process.  The first pass, straight after
-set-up, is reported as `value_without_pre_roll` / `ms_per_step_without_pre_roll`: the device idles while the host builds
-contexts and inputs, and at ~1 ms per step W = 5 warm-up steps end before its clocks have settled under the power cap
-(20 steps then read 5-8 % slower than after 100 warm-up steps).  Then the job runs untimed for `pre_roll_s` (0.25 s) and
-the same W + K steps are measured again: `value` / `ms_per_step`, the steady state a server sees and the roofline leg
-measures.
+A plain run does only what the headline needs: set-up, the job run untimed for `pre_roll_s` (0.25 s: the device idles
+while the host builds contexts and inputs, and at ~1 ms per step W = 5 warm-up steps end before its clocks have settled
+under the power cap), W warm-up steps, K timed steps -> `value` / `ms_per_step`, the steady state a server sees and the
+roofline leg measures.  `--dump-outputs DIR` then writes what the last timed step computed (write_outputs).
 
-The JSON line carries
+`--full` adds everything else.  The contract's measurement (W warm-up steps, K timed steps) then runs twice in the
+process: the first pass, straight after set-up, is reported as `value_without_pre_roll` / `ms_per_step_without_pre_roll`
+(20 steps read 5-8 % slower than after 100 warm-up steps), then the pre-roll and the same W + K steps as in a plain run.
+With --full the JSON line also carries
   * roofline     -- achieved algorithmic HBM bytes/s of the workload's dominant kernel, timed live with HIP events on
                     the launch stream, against the 8 TB/s HBM3E peak; `traffic` = the HBM bytes rocprofv3's counters
                     saw for the same launch (committed under profiles/), at this run's launch time;
   * cpu_baseline -- (c2, one GPU) the CPU oracle (a C port of the reference's Harvey NTT, oracle/he_oracle.c) timed
                     on this box's host cores on a bounded sample of the same workload, plus BASELINE configs[0]
                     (forwardNtt N=4096, 2 moduli, one thread);
-  * extras       -- separately measured rates (not part of `value`).
+  * extras       -- separately measured rates (not part of `value`); with --gpus 1 and c2, the other BASELINE configs
+                    (bench_tools/path_bench.py); with N > 1, the RCCL all-gather of the result shards.
 
 Launch: `python bench.py --gpus 1` or, for N > 1,
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N`.
@@ -76,7 +78,15 @@ def parse_args():
                     help="c5 in ONE process over a he_device_group of this many members (the visible GPUs in turn; all on GPU 0 "
                          "when there is one): the C ABI's own multi-GPU split instead of one process per GPU")
     ap.add_argument("--skip-other-configs", action="store_true", help="do not time configs 3-5 (extras only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the pass without pre-roll, the roofline leg, the all-gather, the other configs and the CPU "
+                         "baseline (off: only what value / ms_per_step need)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of what the last step computed to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def synthetic_slab(torch, moduli, prefix, degree, seed):
@@ -417,6 +427,15 @@ class NttWorkload:
     def result(self):
         return self.slab, self.total
 
+    def outputs(self, pick):
+        """--dump-outputs: the slab after the last step (forward then inverse, in place: back in coefficient form) and, for
+        the same sampled polynomials, the forward transform the step computed on its way (the step's input is the slab
+        as it is now, so one forward NTT of the sample reproduces it)."""
+        index, rows = pick(self.slab)
+        forward = rows.clone()
+        self.ctx.forward_ntt_(forward)
+        return {"ntt_roundtrip": (index, rows), "forward_ntt": (index, forward)}
+
     def describe(self, world):
         return {
             "metric": "polynomial NTT throughput (forward+inverse, N=8192, L=4 RNS moduli)",
@@ -551,6 +570,9 @@ class CtMulWorkload:
     def result(self):
         return self.out, self.total
 
+    def outputs(self, pick):
+        return {"relinearized_product": pick(self.out)}
+
     def describe(self, world):
         return {
             "metric": "ciphertext-mul/s (Bfv ct x ct + relinearize, N=8192, L=4)",
@@ -633,6 +655,9 @@ class ModSwitchWorkload:
 
     def result(self):
         return self.out, self.total
+
+    def outputs(self, pick):
+        return {"divide_and_round_q_last": pick(self.out)}
 
     def describe(self, world):
         return {
@@ -737,6 +762,9 @@ class PirDim0Workload:
     def result(self):
         return self.out, self.total_columns
 
+    def outputs(self, pick):
+        return {"pir_dim0_columns": pick(self.out)}
+
     def consume(self, gathered):
         """What follows the all-gather in a column-sharded deployment: the remaining dimension over ALL columns'
         intermediate ciphertexts (he_pir_remaining_dimensions_device; it overwrites its input)."""
@@ -790,18 +818,54 @@ class PirDim0Workload:
 
 WORKLOADS = {w.key: w for w in (NttWorkload, CtMulWorkload, ModSwitchWorkload, PirDim0Workload)}
 
+DUMP_BYTES_PER_OUTPUT = 24 << 20  # --dump-outputs: .npy bytes per output array (at most two per workload, < 64 MB)
+DUMP_SEED = 0xD0D0
+
+
+def pick_rows(tensor, seed=DUMP_SEED):
+    """A fixed, seeded sample of dim 0 of `tensor` (units: polynomials, ciphertexts, columns), as many as fit
+    DUMP_BYTES_PER_OUTPUT once every word is stored as two float64; every unit when they all fit.  Returns (indices, rows)."""
+    import numpy as np
+    import torch
+
+    units = tensor.shape[0]
+    per_unit = max(1, tensor[0].numel() * 16) if units else 1
+    count = min(units, max(1, DUMP_BYTES_PER_OUTPUT // per_unit))
+    index = np.sort(np.random.default_rng(seed).choice(units, size=count, replace=False))
+    return index, tensor[torch.as_tensor(index, device=tensor.device)]
+
+
+def write_outputs(job, directory, rank=0, world=1):
+    """--dump-outputs: what the job's last step computed, as DIR/<name>.npy (and the units sampled, DIR/<name>_rows.npy).
+    The words are uint64 residues up to 62 bits, more than a float64 holds exactly, so each is written as float64
+    [..., 2] = (high 32 bits, low 32 bits): exact, and two builds compare with np.array_equal."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    outputs = job.outputs(pick_rows) if hasattr(job, "outputs") else {"result": pick_rows(job.result()[0])}
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, (index, rows) in outputs.items():
+        words = rows.detach().cpu().contiguous().numpy().view(np.uint64)
+        split = np.stack([(words >> np.uint64(32)).astype(np.float64), (words & np.uint64(0xFFFFFFFF)).astype(np.float64)],
+                         axis=-1)
+        np.save(os.path.join(directory, name + suffix + ".npy"), split)
+        np.save(os.path.join(directory, name + suffix + "_rows.npy"), index.astype(np.float64))
+
 
 def run_benchmark(args, make_job, rank, world, device="cuda", dist=None):
     """The timed part of the contract, independent of the workload and of the device: W warm-up steps, a barrier, exactly
-    K steps bracketed by synchronisation, max over ranks, the units of all ranks; then the workload's roofline leg and the
-    result gather.  `dist` is torch.distributed (initialised) when world > 1.  Returns the JSON line's dict on rank 0,
-    None elsewhere.  (tests/test_sharding_gloo.py drives this function with two gloo ranks and a CPU workload.)"""
+    K steps bracketed by synchronisation, max over ranks, the units of all ranks; then, when `args.dump_outputs` names a
+    directory, what the last step computed (write_outputs); with `args.full` also the pass without pre-roll, the
+    workload's roofline leg and the result gather.  `dist` is torch.distributed (initialised) when world > 1.  Returns the
+    JSON line's dict on rank 0, None elsewhere.  (tests/test_sharding_gloo.py drives this function with two gloo ranks and
+    a CPU workload.)"""
     import torch
 
     from heamd import sharding
 
     distributed = world > 1
     on_gpu = device == "cuda"
+    full = getattr(args, "full", False)
 
     def synchronize():
         if on_gpu:
@@ -816,7 +880,7 @@ def run_benchmark(args, make_job, rank, world, device="cuda", dist=None):
     job = make_job()
     # Pre-roll: the device sat idle while the host built contexts and inputs and is in its idle power state; at 1 ms per
     # step the contract's W warm-up steps end before the clocks have settled under the power cap (20 steps after 5
-    # warm-ups read 5-8 % slower than after 100).  Both readings are reported (see timed_steps below).
+    # warm-ups read 5-8 % slower than after 100).  --full reports both readings (see timed_steps below).
     def timed_steps():
         """The contract's measurement: W warm-up steps, a barrier, exactly K steps bracketed by synchronisation, the
         maximum over ranks."""
@@ -833,26 +897,28 @@ def run_benchmark(args, make_job, rank, world, device="cuda", dist=None):
             seconds = sharding.max_over_ranks(seconds, device=device)
         return seconds
 
-    # the same measurement twice in one process: first as the bare contract reads it (W warm-ups straight after set-up:
-    # `value_without_pre_roll`), then again after the pre-roll (`value`)
+    # with --full the same measurement twice in one process: first as the bare contract reads it (W warm-ups straight
+    # after set-up: `value_without_pre_roll`), then again after the pre-roll (`value`); a plain run only the second
     synchronize()
-    elapsed_cold = timed_steps()
+    elapsed_cold = timed_steps() if full else None
     pre_roll_start = time.perf_counter()
     while on_gpu and time.perf_counter() - pre_roll_start < PRE_ROLL_S:
         job.step()
         synchronize()
     elapsed = timed_steps()
+    if getattr(args, "dump_outputs", None):
+        write_outputs(job, args.dump_outputs, rank, world)
     units_all_ranks = job.units
     if distributed:
         counter = torch.tensor([job.units], dtype=torch.int64, device=device)
         dist.all_reduce(counter)
         units_all_ranks = int(counter.item())
 
-    # ---- separately timed kernels: the workload's dominant kernel for the roofline figure
-    roofline, extras = job.roofline(args.steps, rank)
+    # ---- separately timed kernels (--full): the workload's dominant kernel for the roofline figure
+    roofline, extras = job.roofline(args.steps, rank) if full else (None, {})
 
     gather_ms = with_gather_elapsed = gather_bytes = None
-    if distributed and not args.skip_gather:
+    if full and distributed and not args.skip_gather:
         gather_bytes = job.result()[0].numel() * job.result()[0].element_size()  # what this rank contributes
         # the only collective on the path: gather the per-GPU result shards (RCCL all-gather over xGMI); also the same
         # K steps with the gather after every step, max over ranks
@@ -881,7 +947,7 @@ def run_benchmark(args, make_job, rank, world, device="cuda", dist=None):
     if rank != 0:
         return None
     description = job.describe(world)
-    return {
+    line = {
         "metric": description["metric"],
         "value": units_all_ranks * args.steps / elapsed,
         "unit": description["unit"],
@@ -890,24 +956,27 @@ def run_benchmark(args, make_job, rank, world, device="cuda", dist=None):
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
         "pre_roll_s": PRE_ROLL_S if on_gpu else 0.0,
-        "value_without_pre_roll": units_all_ranks * args.steps / elapsed_cold,
-        "ms_per_step_without_pre_roll": elapsed_cold / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": description["dtype"],
         "data": "synthetic",
+        "full": full,
         "config": dict(description["config"],
-                       pre_roll="W warm-ups + K timed steps are run twice in this process: straight after set-up "
-                                "(value_without_pre_roll: the device is still leaving its idle power state) and again "
-                                "after the job has run untimed for pre_roll_s (value: the steady state the roofline leg "
-                                "measures); DESIGN.md section 6"),
+                       pre_roll="the job runs untimed for pre_roll_s before the W warm-ups and K timed steps (value: the "
+                                "steady state the roofline leg measures); with --full, W warm-ups + K timed steps also run "
+                                "once straight after set-up (value_without_pre_roll: the device is still leaving its idle "
+                                "power state); DESIGN.md section 6"),
         "roofline": roofline,
-        "extras": dict(extras, all_gather_ms=gather_ms, all_gather_bytes_per_gpu=gather_bytes,
-                       value_with_all_gather=(units_all_ranks * args.steps / with_gather_elapsed
-                                              if with_gather_elapsed else None)),
+        "extras": extras,
     }
-
+    if full:
+        line["value_without_pre_roll"] = units_all_ranks * args.steps / elapsed_cold
+        line["ms_per_step_without_pre_roll"] = elapsed_cold / args.steps * 1e3
+        line["extras"] = dict(extras, all_gather_ms=gather_ms, all_gather_bytes_per_gpu=gather_bytes,
+                              value_with_all_gather=(units_all_ranks * args.steps / with_gather_elapsed
+                                                     if with_gather_elapsed else None))
+    return line
 
 def main():
     args = parse_args()
@@ -935,14 +1004,14 @@ def main():
                            "cuda", dist)
     if rank == 0:
         result["extras"]["library"] = heamd.version()
-        if args.workload == "c2" and world == 1 and not args.skip_other_configs:
+        if args.full and args.workload == "c2" and world == 1 and not args.skip_other_configs:
             # the other BASELINE.json configs on this GPU (ciphertext-mul/s, mod-switch, PIR inner loop); not `value`
             sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
             import path_bench
 
             torch.cuda.empty_cache()
             result["extras"]["other_configs"] = path_bench.run_all(quick=False)
-        if args.workload == "c2" and not args.no_cpu_baseline and world == 1:
+        if args.full and args.workload == "c2" and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(heamd.generate_primes(MODULI_BITS, False, DEGREE), args.cpu_sample)
         else:
             result["cpu_baseline"] = None

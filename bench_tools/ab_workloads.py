@@ -23,7 +23,7 @@ def main():
                 if path:
                     env["HEAMD_LIBRARY"] = path
                 result = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps",
-                                         "8", "--warmup", "2", "--no-cpu-baseline", "--skip-other-configs"], env=env,
+                                         "8", "--warmup", "2", "--full", "--no-cpu-baseline", "--skip-other-configs"], env=env,
                                         capture_output=True, text=True)
                 if result.returncode != 0:
                     print(f"round {round_index} {workload} {name}: FAILED {result.stderr[-300:]}")

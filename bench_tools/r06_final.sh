@@ -30,16 +30,16 @@ python bench_tools/valu_json.py $O/c3_valu_counters.txt $O/r06_c3_valu.json && c
 sed -i 's#"source": "[^"]*"#"source": "profiles/r06z_c3_valu_counters.txt (rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_INT32 over bench_tools/c3_profile_target.py, closing pass)"#' profiles/r06_c3_valu.json
 rm -rf $O/valu
 ./bench_tools/microbench > $O/microbench.txt 2>&1
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || tail -5 $O/bench.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || tail -5 $O/bench.err
 cut -c1-400 $O/bench.json
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python bench.py --gpus 1 --steps 20 --warmup 5 --skip-other-configs --no-cpu-baseline > $O/bench_ntt_only.json 2> $O/bench_stats.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python bench.py --gpus 1 --steps 20 --warmup 5 --full --skip-other-configs --no-cpu-baseline > $O/bench_ntt_only.json 2> $O/bench_stats.err
 f=$(find $O/bench_stats -name "*kernel_stats.csv" | head -1); cp "$f" $O/bench_ntt_only_kernel_stats.csv; python bench_tools/kernel_stats_summary.py $O/bench_ntt_only_kernel_stats.csv | head -6
 for w in c3 c4 c5; do
-  timeout 600 python bench.py --workload $w --steps 10 --warmup 2 > $O/bench_$w.json 2> $O/bench_$w.err || tail -5 $O/bench_$w.err
+  timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --full > $O/bench_$w.json 2> $O/bench_$w.err || tail -5 $O/bench_$w.err
 done
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c3_stats -- python bench_tools/c3_profile_target.py > $O/c3_stats.log 2>&1
 f=$(find $O/c3_stats -name "*kernel_stats.csv" | head -1); cp "$f" $O/c3_kernel_stats.csv
-timeout 600 python bench.py --workload c5 --device-group 2 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_c5_group2.json 2> $O/bench_c5_group2.err || tail -5 $O/bench_c5_group2.err
+timeout 600 python bench.py --workload c5 --device-group 2 --steps 10 --warmup 2 --full --no-cpu-baseline > $O/bench_c5_group2.json 2> $O/bench_c5_group2.err || tail -5 $O/bench_c5_group2.err
 timeout 600 python bench_tools/whole_query_spread.py after_legs 30 > $O/whole_query_spread.txt 2>&1
 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/pir_trace -- python bench_tools/pir_loop_profile_target.py > $O/pir_loop.txt 2>&1
 f=$(find $O/pir_trace -name "*kernel_trace.csv" | head -1); python bench_tools/kernel_gaps.py "$f" inner_product_plain_rows_kernel 40 > $O/pir_loop_timeline.txt 2>&1; rm -rf $O/pir_trace

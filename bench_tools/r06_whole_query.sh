@@ -7,7 +7,7 @@ O=gpurun_out/$T
 mkdir -p $O
 export TMPDIR=/tmp
 for i in 1 2; do
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_$i.json 2> $O/bench_$i.err || tail -5 $O/bench_$i.err
+  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_$i.json 2> $O/bench_$i.err || tail -5 $O/bench_$i.err
   python - $O/bench_$i.json <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")][-1]

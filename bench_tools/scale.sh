@@ -18,7 +18,7 @@ for workload in $WORKLOADS; do
       python bench.py --gpus 1 --workload $workload --steps 10 --warmup 3 --skip-other-configs --no-cpu-baseline
     else
       python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-        --master-port $((29500 + n)) bench.py --gpus $n --workload $workload --steps 10 --warmup 3
+        --master-port $((29500 + n)) bench.py --gpus $n --workload $workload --steps 10 --warmup 3 --full
     fi | tail -1 | tee -a "$OUT" | python -c 'import json,sys; r=json.loads(sys.stdin.read()); print(r["config"]["workload"][:40], "n =", r["n_gpus"], "value =", "%.4g" % r["value"], r["unit"], "gather ms =", r["extras"].get("all_gather_ms"))'
   done
 done

@@ -172,7 +172,7 @@ def _bench_worker(rank, world, port, results):
             jobs.append(CpuJob())
             return jobs[-1]
 
-        args = argparse.Namespace(steps=3, warmup=2, skip_gather=False)
+        args = argparse.Namespace(steps=3, warmup=2, skip_gather=False, full=True)
         line = bench.run_benchmark(args, make_job, rank, world, device="cpu", dist=dist)
         results[rank] = (line, jobs[0].steps_run, jobs[0].units)
     finally:
@@ -264,7 +264,7 @@ def _c5_flow_worker(rank, world, port, results):
             jobs.append(PirJob())
             return jobs[-1]
 
-        args = argparse.Namespace(steps=2, warmup=1, skip_gather=False)
+        args = argparse.Namespace(steps=2, warmup=1, skip_gather=False, full=True)
         line = bench.run_benchmark(args, make_job, rank, world, device="cpu", dist=dist)
         whole = oracle.pir.compute_response_for_one_chunk(bfv, dims, dim0, rest, database.reshape(-1, bfv.L, degree), None, key)
         results[rank] = (line, jobs[0].consumed, bool(np.array_equal(jobs[0].response, whole)), jobs[0].units)

@@ -80,17 +80,6 @@ def test_gpu_bfv_overrides_both_twins_of_what_it_accelerates():
         assert re.search(r"try %s\(" % helper, read(os.path.join(SWIFT, "Sources", "HeAmd", "GpuBfv.swift"))), helper
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Sources/HomomorphicEncryption"),
-                    reason="the reference checkout exists in the build container only")
-def test_the_golden_member_list_is_the_reference_s():
-    reference = "/root/reference/Sources/HomomorphicEncryption"
-    noop = static_members(read(os.path.join(reference, "NoOpScheme.swift")), "NoOpScheme")
-    assert sorted(noop) == GOLDEN["noop_scheme_static_members"]
-    protocol = static_members(read(os.path.join(reference, "HeScheme.swift")), "HeScheme", kind="protocol")
-    for requirement in GOLDEN["accelerated_protocol_requirements"]:
-        assert requirement in protocol, requirement
-
-
 def test_gpu_pir_util_answers_the_server_side_requirements():
     text = read(os.path.join(SWIFT, "Sources", "HeAmd", "GpuPirUtil.swift"))
     assert re.search(r"public enum GpuPirUtil<Scheme: HeScheme>: PirUtilProtocol", text)

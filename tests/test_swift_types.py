@@ -4,7 +4,7 @@ here compiles Swift): every requirement of `HeScheme` (Sources/HomomorphicEncryp
 (Sources/PrivateInformationRetrieval/IndexPir/PirUtil.swift:22-147), must have a witness whose parameter labels, ownership
 modifiers (`inout`, `consuming`), parameter and return types (typealiases expanded on both sides), `async` / `throws` and
 generic / `where` clauses are the requirement's.  The requirements travel as tests/golden/swift_protocol_signatures.json
-(re-derived from the reference checkout whenever it is present, like the other goldens); the checker itself is held by
+(derived from a checkout of the reference by tests/golden/check_reference.py); the checker itself is held by
 mutations of real signatures that must each be reported."""
 import copy
 import glob
@@ -14,7 +14,6 @@ import os
 import swift_types as st
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference/Sources"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "swift_protocol_signatures.json")
 
 
@@ -22,39 +21,7 @@ def _read(*paths):
     return "\n".join(open(p).read() for p in paths)
 
 
-def _derive_from_reference():
-    he = _read(os.path.join(REFERENCE, "HomomorphicEncryption", "HeScheme.swift"))
-    he_extensions = _read(os.path.join(REFERENCE, "HomomorphicEncryption", "HeScheme.swift"),
-                          os.path.join(REFERENCE, "HomomorphicEncryption", "HeSchemeAsync.swift"))
-    pir = _read(os.path.join(REFERENCE, "PrivateInformationRetrieval", "IndexPir", "PirUtil.swift"))
-    return {
-        "source": "HeScheme.swift:190-1090 + extensions (HeScheme.swift, HeSchemeAsync.swift); PirUtil.swift:22-147 + extension "
-                  "(reference checkout of this build)",
-        "HeScheme": {
-            "requirements": st.static_function_signatures(he, "HeScheme", kinds=("protocol",)),
-            "aliases": st.typealiases(he, "HeScheme", kinds=("protocol",)),
-            "defaults": st.static_function_signatures(he_extensions, "HeScheme", kinds=("extension",)),
-        },
-        "PirUtilProtocol": {
-            "requirements": st.static_function_signatures(pir, "PirUtilProtocol", kinds=("protocol",)),
-            "aliases": st.typealiases(pir, "PirUtilProtocol", kinds=("protocol",)),
-            "defaults": st.static_function_signatures(pir, "PirUtilProtocol", kinds=("extension",)),
-        },
-    }
-
-
-def _listify(value):  # tuples -> lists, as JSON round-trips them
-    return json.loads(json.dumps(value))
-
-
 def _protocols():
-    if os.path.isdir(REFERENCE):
-        derived = _listify(_derive_from_reference())
-        stored = json.load(open(GOLDEN)) if os.path.exists(GOLDEN) else None
-        if stored != derived:
-            with open(GOLDEN, "w") as f:
-                json.dump(derived, f, indent=1, sort_keys=True)
-                f.write("\n")
     protocols = json.load(open(GOLDEN))
     for protocol in ("HeScheme", "PirUtilProtocol"):
         for group in ("requirements", "defaults"):
