@@ -550,6 +550,47 @@ int he_pir_compute_response_to_query_device(const he_bfv_context* ctx, const uin
                                             const uint8_t* const* present_masks, size_t database_count, size_t chunk_count,
                                             uint64_t* out, he_stream s);
 
+/* MulPirServer.process(database:with:using:) (PrivateInformationRetrieval/IndexPir/MulPir.swift:431-556) -- the database
+ * a server answers from, built on the device from the raw entry bytes.  The IndexPirParameter is given as its fields:
+ * dimensions, entry_size_in_bytes, encoding_entry_size (nonzero: every entry is preceded by its byte count in
+ * IndexPirConfig.entrySizeEncodingWidth little-endian bytes, IndexPirProtocol.swift:60-73,106-150); entry_count is the
+ * number of entries handed in (the reference's PirError.invalidDatabaseEntryCount is the caller's check: it holds both).
+ * he_pir_database_shape is the plan (MulPir.swift:445-450; no device work, host-only contexts too):
+ *   out_chunk_count               ceil((width + entry_size_in_bytes) / bytes per plaintext)
+ *   out_plaintexts_per_chunk      prod(dimensions)
+ *   out_bytes_per_plaintext       N floor(log2 t) / 8          (EncryptionParameters.swift:101-110)
+ *   out_entries_per_plaintext     floor(bytes per plaintext / (width + entry_size_in_bytes)) in pack mode (one chunk),
+ *                                 0 in split mode (more than one chunk: entry r is row r, chunk k its k-th plaintext)
+ *   out_entry_size_encoding_width 0 without a size prefix, else 1, 2, 4 or 8
+ * Any out pointer may be NULL.  HE_ERR_INVALID_ARGUMENT: empty or zero dimensions; split mode with more entries than
+ * prod(dimensions); pack mode with more plaintexts than prod(dimensions); entries of zero bytes without a prefix. */
+int he_pir_database_shape(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
+                          size_t entry_count, size_t entry_size_in_bytes, int encoding_entry_size, size_t* out_chunk_count,
+                          size_t* out_plaintexts_per_chunk, size_t* out_bytes_per_plaintext,
+                          size_t* out_entries_per_plaintext, size_t* out_entry_size_encoding_width);
+/* The database itself, in the layout every he_pir_compute_response_* entry reads:
+ *   entries      DEVICE [entry_count][entry_size_in_bytes]; bytes past an entry's own size are ignored (need not be zero)
+ *   entry_sizes  HOST [entry_count] byte counts, or NULL: every entry is entry_size_in_bytes long.  Given, they are checked
+ *                first -- an entry longer than entry_size_in_bytes is the reference's invalidDatabaseEntrySize,
+ *                HE_ERR_INVALID_ARGUMENT -- and uploaded: the call returns once that copy is done (a stream synchronisation).
+ *                NULL: the call is enqueue-only.
+ *   database     DEVICE [chunk_count][prod(dimensions)][L][N] Eval at the top level (Plaintext.convertToEvalFormat of
+ *                context.encode(values:format: .coefficient), Bfv+Encode.swift:44-50); a nil plaintext is all zeros
+ *   present      DEVICE [chunk_count][prod(dimensions)]: 0 where the reference's plaintext is nil (its bytes are all zero or
+ *                there are none), 1 elsewhere
+ * Plaintexts are placed as the reference reorders them: plaintext j of chunk k at slot (j % R) d0 + j / R, d0 =
+ * dimensions[0], R = prod(dimensions) / d0.  Errors are returned before anything is written.  A host-only context:
+ * HE_ERR_DEVICE. */
+int he_pir_process_database_device(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
+                                   const uint8_t* entries, const uint64_t* entry_sizes, size_t entry_count,
+                                   size_t entry_size_in_bytes, int encoding_entry_size, uint64_t* database, uint8_t* present,
+                                   he_stream s);
+/* The same for a Bfv<UInt32> context, the database in packed 4-byte words (he_pir_compute_response_device_u32's). */
+int he_pir_process_database_device_u32(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
+                                       const uint8_t* entries, const uint64_t* entry_sizes, size_t entry_count,
+                                       size_t entry_size_in_bytes, int encoding_entry_size, uint32_t* database,
+                                       uint8_t* present, he_stream s);
+
 /* PirUtil.expand(ciphertexts:outputCount:using:) (PrivateInformationRetrieval/IndexPir/PirUtil.swift:196-355):
  * oblivious expansion of `ciphertext_count` query ciphertexts [..][2][L][N] (Coeff, top level) into `output_count`
  * ciphertexts, in the reference's output order.  The evaluation key is given as parallel host arrays:

@@ -101,6 +101,10 @@ class ExpandPlanCache {
 // bfv_api.cpp: the cache a context owns
 ExpandPlanCache& expand_plans(const he_bfv_context* ctx);
 
+// bfv_api.cpp: the context behind a handle (the PIR database plan reads its degree, t and word size; not exported)
+class BfvContext;
+const BfvContext& bfv_impl(const he_bfv_context* ctx);
+
 // bfv_api.cpp: one PirUtil.expand level through the fused Galois key switch (not exported)
 constexpr int kExpandStepUnavailable = -1;
 // `rotated`: what the key switch rotates when it is not the parents themselves -- the parents already taken through the

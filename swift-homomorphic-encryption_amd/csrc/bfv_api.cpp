@@ -31,6 +31,7 @@ struct he_bfv_context {
 
 namespace heamd {
 ExpandPlanCache& expand_plans(const he_bfv_context* ctx) { return ctx->expand_plans; }
+const BfvContext& bfv_impl(const he_bfv_context* ctx) { return *ctx->impl; }
 LanePool& lane_pool(const he_bfv_context* ctx) { return ctx->lanes; }
 }  // namespace heamd
 

@@ -200,6 +200,13 @@ SIGNATURES = [
      [vp, c_u32, vp, c_u64, ctypes.POINTER(vp), c_size, c_size, vp, vp, c_size, vp]),
     ("he_pir_expand_device", ctypes.c_int,
      [vp, vp, c_size, c_size, U64P, ctypes.POINTER(vp), c_size, vp, vp]),
+    ("he_pir_database_shape", ctypes.c_int,
+     [vp, ctypes.POINTER(c_u32), c_u32, c_size, c_size, ctypes.c_int, ctypes.POINTER(c_size), ctypes.POINTER(c_size),
+      ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
+    ("he_pir_process_database_device", ctypes.c_int,
+     [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
+    ("he_pir_process_database_device_u32", ctypes.c_int,
+     [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
     # diagnostics / test hooks
     ("he_poly_context_create_host_only", ctypes.c_int, [c_u32, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_poly_context_copy_ntt_tables", ctypes.c_int, [vp, c_u32, U64P, U64P, U64P, U64P, U64P, U64P]),
@@ -1043,6 +1050,70 @@ class BfvContext:
                                                                          _stream(stream)))
         return out
 
+    def pir_database_shape(self, dimensions, entry_count, entry_size_in_bytes, encoding_entry_size=False):
+        """he_pir_database_shape: MulPirServer.process's plan for an IndexPirParameter -> dict with chunk_count,
+        plaintexts_per_chunk, bytes_per_plaintext, entries_per_plaintext (0: split mode) and entry_size_encoding_width."""
+        dims = (c_u32 * max(len(dimensions), 1))(*[int(d) for d in dimensions])
+        outs = [c_size() for _ in range(5)]
+        _check(load_library().he_pir_database_shape(self.h, dims, len(dimensions), int(entry_count), int(entry_size_in_bytes),
+                                                    int(bool(encoding_entry_size)), *[ctypes.byref(o) for o in outs]))
+        names = ("chunk_count", "plaintexts_per_chunk", "bytes_per_plaintext", "entries_per_plaintext",
+                 "entry_size_encoding_width")
+        return {name: int(o.value) for name, o in zip(names, outs)}
+
+    _process_entry = "he_pir_process_database_device"
+
+    def _database_tensor(self, shape, device):
+        import torch
+
+        return torch.empty(shape, dtype=torch.int64, device=device)
+
+    def _database_ptr(self, database):
+        return _ptr(database)
+
+    def pir_process_database(self, entries, dimensions, entry_size_in_bytes, encoding_entry_size=False, entry_sizes=None,
+                             entry_count=None, out=None, device="cuda", stream=None):
+        """MulPirServer.process(database:with:using:) on the device -> (database [chunks][prod(dims)][L][N] Eval, present
+        uint8 [chunks][prod(dims)]).  entries: a list of bytes-like entries, or a uint8 array / tensor
+        [count][entry_size_in_bytes] padded past each entry's size (entry_sizes: their byte counts; None: all full).
+        entry_count: IndexPirParameter.entryCount (None: the number given); out: (database, present) to write into."""
+        import torch
+
+        sizes = None
+        if isinstance(entries, (list, tuple)):
+            sizes = np.array([len(e) for e in entries], dtype=np.uint64)
+            padded = np.zeros((len(entries), int(entry_size_in_bytes)), dtype=np.uint8)
+            for row, entry in enumerate(entries):  # an entry too long is cut here and rejected by the size check
+                data = np.frombuffer(bytes(entry), dtype=np.uint8)[:int(entry_size_in_bytes)]
+                padded[row, :len(data)] = data
+            entries = padded
+        if entry_sizes is not None:
+            sizes = np.ascontiguousarray(entry_sizes, dtype=np.uint64)
+        count = int(entries.shape[0])
+        if entry_count is not None and int(entry_count) != count:  # PirError.invalidDatabaseEntryCount (MulPir.swift:433-436)
+            raise HeError(16, f"Invalid database: Database has {count} entries, expected {int(entry_count)}")
+        if sizes is not None and len(sizes) != count:
+            raise ValueError("entry_sizes must give one size per entry")
+        shape = self.pir_database_shape(dimensions, count, entry_size_in_bytes, encoding_entry_size)
+        chunks, per_chunk = shape["chunk_count"], shape["plaintexts_per_chunk"]
+        if isinstance(entries, np.ndarray):
+            entries = torch.from_numpy(np.ascontiguousarray(entries, dtype=np.uint8)).to(device)
+        if entries.dtype != torch.uint8 or not entries.is_cuda or not entries.is_contiguous():
+            raise ValueError("entries must be a contiguous uint8 device tensor")
+        if out is None:
+            database = self._database_tensor((chunks, per_chunk, self.L, self.degree), entries.device)
+            present = torch.empty((chunks, per_chunk), dtype=torch.uint8, device=entries.device)
+        else:
+            database, present = out
+            if database.numel() != chunks * per_chunk * self.L * self.degree or present.numel() != chunks * per_chunk:
+                raise ValueError("out tensors do not hold the database's shape")
+        dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
+        size_ptr = sizes.ctypes.data_as(U64P) if sizes is not None else None
+        _check(getattr(load_library(), self._process_entry)(
+            self.h, dims, len(dimensions), vp(entries.data_ptr()), size_ptr, count, int(entry_size_in_bytes),
+            int(bool(encoding_entry_size)), self._database_ptr(database), vp(present.data_ptr()), _stream(stream)))
+        return database, present
+
     def packed_plaintext_words(self, moduli_count=None):
         return int(load_library().he_bfv_packed_plaintext_words(self.h, self._L(moduli_count)))
 
@@ -1261,6 +1332,16 @@ class BfvContext32(BfvContext):
             element_array.ctypes.data_as(U64P), key_array, len(elements), relin, database_array, mask_array,
             len(database_list), chunk_count, _ptr32(out), _stream(stream)))
         return out
+
+    _process_entry = "he_pir_process_database_device_u32"
+
+    def _database_tensor(self, shape, device):
+        import torch
+
+        return torch.empty(shape, dtype=torch.int32, device=device)
+
+    def _database_ptr(self, database):
+        return _ptr32(database)
 
     def plaintext_to_eval(self, plaintext, moduli_count=None, stream=None):
         L = self._L(moduli_count)

@@ -4,7 +4,8 @@
 // overridden, everything else keeps the protocol's default implementation:
 //   computeResponse(to:using:databases:parameter:context:callOptions:)   PirUtil.swift:490-568 -- the whole server side of a
 //       Query in ONE C call over databases and evaluation keys that stay resident in HBM (GpuResidentCache): expansion,
-//       dim-0 to Eval, every chunk; only the query goes up and the response comes down;
+//       dim-0 to Eval, every chunk; only the query goes up and the response comes down (a second form,
+//       computeResponse(to:using:residentDatabases:parameter:context:), answers from GpuResidentDatabase objects directly);
 //   expand(ciphertexts:outputCount:using:callOptions:)                    PirUtil.swift:313-355 -- the oblivious expansion;
 //   computeResponseForOneChunk(...)                                       PirUtil.swift:408-486 -- for callers that drive
 //       chunks themselves: the chunk is a slice of a database the cache already holds, or is uploaded for this call.
@@ -42,13 +43,38 @@ public enum GpuPirUtil<Scheme: HeScheme>: PirUtilProtocol
             throw HeError.incompatibleCiphertextCount("empty query")
         }
         let polyContext = first.polys[0].context
-        let degree = polyContext.degree, polyWords = polyContext.moduli.count * degree
         // chunks per database: every chunk holds prod(dimensions) plaintexts (PirUtil.swift:507, :536-537)
         let perChunk = parameter.dimensions.reduce(1, *)
         let chunkCount = databases[0].count / perChunk
         precondition(databases.allSatisfy { $0.count == chunkCount * perChunk })
 
         let resident = try databases.map { try GpuResidentCache.shared.resident($0, polyContext: polyContext) }
+        return try await computeResponse(to: query, using: evaluationKey, residentDatabases: resident, parameter: parameter,
+                                         context: context)
+    }
+
+    /// The same over databases that already live in HBM -- built there from raw entries
+    /// (`GpuResidentDatabase(processing:with:using:)`, `GpuResidentCache.register(processing:token:with:using:)`) or
+    /// uploaded from a ProcessedDatabase.
+    public static func computeResponse(
+        to query: Query<Scheme>,
+        using evaluationKey: EvaluationKey<Scheme>,
+        residentDatabases resident: [GpuResidentDatabase<Scheme>],
+        parameter: IndexPirParameter,
+        context: Scheme.Context) async throws -> Response<Scheme>
+    {
+        guard resident.count == 1 || resident.count >= query.indicesCount else { // PirUtil.swift:498-500
+            throw PirError.invalidBatchSize(queryCount: query.indicesCount, databaseCount: resident.count)
+        }
+        guard let first = query.ciphertexts.first else {
+            throw HeError.incompatibleCiphertextCount("empty query")
+        }
+        let polyContext = first.polys[0].context
+        let degree = polyContext.degree, polyWords = polyContext.moduli.count * degree
+        let perChunk = parameter.dimensions.reduce(1, *)
+        let chunkCount = resident[0].plaintextCount / perChunk
+        precondition(resident.allSatisfy { $0.plaintextCount == chunkCount * perChunk })
+
         let keys = try GpuResidentCache.shared.resident(evaluationKey)
         if parameter.dimensions.count > 1, keys.relinearizationKey == nil {
             throw HeError.missingRelinearizationKey // PirUtil.swift:448-479 relinearizes after every further dimension

@@ -1,6 +1,7 @@
 // What a PIR server keeps in HBM between queries, and the caches that find it again from the reference's VALUE types:
 //   * GpuResidentDatabase   a ProcessedDatabase (IndexPirProtocol.swift:249-290): every Eval plaintext of every chunk
-//                           plus the nil mask, uploaded once;
+//                           plus the nil mask, uploaded once -- or built on the device from the raw entries
+//                           (MulPirServer.process, MulPir.swift:431-556);
 //   * GpuEvaluationKey      an EvaluationKey (Keys.swift:186-219): its Galois keys by element and its relinearization
 //                           key in the layout the C ABI takes;
 //   * GpuResidentCache      ProcessedDatabase and EvaluationKey are structs (no object identity), so residency is keyed by
@@ -35,6 +36,53 @@ public final class GpuResidentDatabase<Scheme: HeScheme>: @unchecked Sendable wh
         }
     }
 
+    /// MulPirServer.process(database:with:using:) (MulPir.swift:431-556) on the device: the raw entries go up in pinned
+    /// blocks of `blockBytes` (each entry padded to `entrySizeInBytes`), and he_pir_process_database_device builds the Eval
+    /// plaintexts and the mask in HBM -- N floor(log2 t) / 8 bytes per plaintext cross PCIe instead of L N 8.
+    public init(processing database: some Collection<[UInt8]>, with context: Scheme.Context,
+                using parameter: IndexPirParameter, blockBytes: Int = 256 << 20) throws
+    {
+        guard database.count == parameter.entryCount else { // PirError.invalidDatabaseEntryCount, MulPir.swift:433-437
+            throw HeError.unsupportedHeOperation(description: """
+                Invalid database: Database has \(database.count) entries, expected \(parameter.entryCount)
+                """)
+        }
+        let entrySize = parameter.entrySizeInBytes
+        let maxEntrySize = database.map(\.count).max() ?? 0
+        guard maxEntrySize <= entrySize else { // PirError.invalidDatabaseEntrySize, MulPir.swift:438-444
+            throw HeError.unsupportedHeOperation(description: """
+                Invalid database: Database has entry with size \(maxEntrySize) plaintexts, \
+                expected all entry sizes to be <= \(entrySize)
+                """)
+        }
+        let handle = try context.gpu
+        let dimensions = parameter.dimensions.map { UInt32($0) }
+        let encoding: Int32 = parameter.encodingEntrySize ? 1 : 0
+        var chunkCount = 0, perChunk = 0
+        try dimensions.withUnsafeBufferPointer { dims in
+            try heAmdCheck(he_pir_database_shape(handle, dims.baseAddress, UInt32(dims.count), database.count, entrySize,
+                                                 encoding, &chunkCount, &perChunk, nil, nil, nil))
+        }
+        let polyWords = context.ciphertextContext.moduli.count * context.degree
+        let stream = try HeAmdStream()
+        plaintextCount = chunkCount * perChunk
+        plaintexts = try DeviceBuffer(count: plaintextCount * polyWords)
+        present = try DeviceBuffer(count: (plaintextCount + 7) / 8)
+        let entries = try DeviceBuffer(count: (database.count * entrySize + 7) / 8)
+        try entries.upload(entries: database, entrySize: entrySize, on: stream, blockBytes: blockBytes)
+        let sizes = database.map { UInt64($0.count) }
+        let mask = UnsafeMutableRawPointer(present.pointer).assumingMemoryBound(to: UInt8.self)
+        let entryBytes = UnsafeRawPointer(entries.pointer).assumingMemoryBound(to: UInt8.self)
+        try dimensions.withUnsafeBufferPointer { dims in
+            try sizes.withUnsafeBufferPointer { entrySizes in
+                try heAmdCheck(he_pir_process_database_device(
+                    handle, dims.baseAddress, UInt32(dims.count), entryBytes, entrySizes.baseAddress, database.count,
+                    entrySize, encoding, plaintexts.pointer, mask, stream.raw))
+            }
+        }
+        try withExtendedLifetime(entries) { try stream.synchronize() } // the raw entries are freed after the kernels
+    }
+
     /// Bytes of HBM the database occupies.
     public var byteCount: Int {
         (plaintexts.count + present.count) * MemoryLayout<UInt64>.stride
@@ -42,6 +90,35 @@ public final class GpuResidentDatabase<Scheme: HeScheme>: @unchecked Sendable wh
 
     var maskPointer: UnsafePointer<UInt8> {
         UnsafePointer(UnsafeRawPointer(present.pointer).assumingMemoryBound(to: UInt8.self))
+    }
+}
+
+extension DeviceBuffer {
+    /// Raw database entries to byte offset 0, entry e at e * entrySize (bytes past an entry's own size are left as they
+    /// are: the kernels never read them), through ONE reusable pinned block of at most `blockBytes`.
+    func upload(entries: some Collection<[UInt8]>, entrySize: Int, on stream: HeAmdStream, blockBytes: Int) throws {
+        guard entrySize > 0, !entries.isEmpty else { return }
+        precondition(entries.count * entrySize <= count * MemoryLayout<UInt64>.stride)
+        let perBlock = max(1, blockBytes / entrySize)
+        let staging = try HostStaging(capacity: (min(perBlock, entries.count) * entrySize + 7) / 8)
+        let bytes = UnsafeMutableRawPointer(staging.pointer).assumingMemoryBound(to: UInt8.self)
+        var blockStart = 0, inBlock = 0
+        func flush() throws {
+            guard inBlock > 0 else { return }
+            try heAmdCheck(he_memcpy_h2d(UnsafeMutableRawPointer(pointer) + blockStart * entrySize, staging.pointer,
+                                         inBlock * entrySize, stream.raw))
+            try heAmdCheck(he_stream_synchronize(stream.raw)) // the block is reused
+            blockStart += inBlock
+            inBlock = 0
+        }
+        for entry in entries {
+            entry.withUnsafeBufferPointer { source in
+                if let base = source.baseAddress { (bytes + inBlock * entrySize).update(from: base, count: source.count) }
+            }
+            inBlock += 1
+            if inBlock == perBlock { try flush() }
+        }
+        try flush()
     }
 }
 
@@ -187,6 +264,22 @@ public final class GpuResidentCache: @unchecked Sendable {
         defer { lock.unlock() }
         tokenDatabases["\(device):\(token)"] = uploaded
         return uploaded
+    }
+
+    /// The same for raw entries: MulPirServer.process(database:with:using:) runs on the device
+    /// (`GpuResidentDatabase(processing:with:using:)`) and the result is filed under `token`.
+    @discardableResult
+    public func register<Scheme: HeScheme>(processing database: some Collection<[UInt8]>, token: String,
+                                           with context: Scheme.Context,
+                                           using parameter: IndexPirParameter) throws -> GpuResidentDatabase<Scheme>
+        where Scheme.Scalar == UInt64
+    {
+        let device = try GpuContextCache.currentDevice()
+        let processed = try GpuResidentDatabase<Scheme>(processing: database, with: context, using: parameter)
+        lock.lock()
+        defer { lock.unlock() }
+        tokenDatabases["\(device):\(token)"] = processed
+        return processed
     }
 
     /// The database filed under `token` on the current device, if any.
