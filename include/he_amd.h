@@ -591,6 +591,88 @@ int he_pir_process_database_device_u32(const he_bfv_context* ctx, const uint32_t
                                        size_t entry_size_in_bytes, int encoding_entry_size, uint32_t* database,
                                        uint8_t* present, he_stream s);
 
+/* ---- SimplePirServer (PrivateInformationRetrieval/SimplePir/) ------------------------------------------------------------
+ * The other index-PIR server: a database matrix of plaintext_bits-wide elements, a hint for the clients, and replies that
+ * are one wrap-around integer matrix product.  word_bits is the reference's Scalar: 64 (entries without suffix) or 32
+ * (_u32: 4-byte request / response / hint words).
+ *
+ * Device layout of the database: the reference's transposed processedDatabase, [column_size][database_columns] row-major,
+ * each element in element_bytes = 1 (plaintext_bits <= 8), 2 (<= 16), 4 (<= 32) or 8 bytes instead of a whole Scalar;
+ * padding elements are zero.  A reply streams the database once, so its stored bytes are the reply's time.  Every `database`
+ * pointer below must be aligned to element_bytes (HE_ERR_INVALID_ARGUMENT otherwise); the reply reads 16 bytes per lane when
+ * the pointer is 16-byte aligned and database_columns x element_bytes is a multiple of 16, element by element otherwise.
+ *
+ * he_simple_pir_shape -- SimplePirServerProtocol.computingParams (SimplePir+Database.swift:209-243), the padded column size
+ * of process (:262-268), SimplePirParameters.aPolyCount (:171-175) and SimplePirContext.init's modulus
+ * (SimplePirContext.swift:76-87).  Host only: no device is touched.
+ *   out_entry_size_in_scalar  ceil(8 entry_size_in_bytes / plaintext_bits)
+ *   out_entries_per_column, out_chunks_per_entry, out_database_columns   as the reference rounds them (Double.rounded():
+ *                             halves away from zero; the max(.., 1) clamps)
+ *   out_column_size           rows of the database = words of one reply
+ *   out_a_poly_count          ceil(database_columns / lattice_dimension)
+ *   out_modulus               the NTT-friendly prime p of ciphertext_bits + 1 significant bits, preferring small
+ *   out_element_bytes         1, 2, 4 or 8
+ * Any out pointer may be NULL.  HE_ERR_INVALID_ARGUMENT: word_bits not 32 / 64, plaintext_bits 0, ciphertext_bits <=
+ * plaintext_bits, ciphertext_bits above 29 (word_bits 32: p must be a PolyRq<UInt32> modulus) or 60 (word_bits 64),
+ * lattice_dimension not a power of two, an empty database, or a shape with entries_per_column and chunks_per_entry both
+ * above 1 (SimplePirParameters.init's precondition, SimplePir.swift:157).  HE_ERR_NOT_ENOUGH_PRIMES: no such prime. */
+int he_simple_pir_shape(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t lattice_dimension, uint32_t word_bits,
+                        size_t entry_count, size_t entry_size_in_bytes, size_t* out_entry_size_in_scalar,
+                        size_t* out_entries_per_column, size_t* out_chunks_per_entry, size_t* out_database_columns,
+                        size_t* out_column_size, size_t* out_a_poly_count, uint64_t* out_modulus,
+                        uint32_t* out_element_bytes);
+/* SimplePirContext<Scalar>.init(params:) (SimplePirContext.swift:76-87) for process: the plan above and extraContext
+ * (degree lattice_dimension, the one modulus p) on the current device.  Same errors as he_simple_pir_shape, and
+ * HE_ERR_DEVICE without a device.  Synchronises (tables are uploaded).  Destroy with he_simple_pir_context_destroy (NULL
+ * is accepted) once the work enqueued with it is done. */
+typedef struct he_simple_pir_context he_simple_pir_context;
+int he_simple_pir_context_create(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t lattice_dimension,
+                                 uint32_t word_bits, size_t entry_count, size_t entry_size_in_bytes,
+                                 he_simple_pir_context** out);
+void he_simple_pir_context_destroy(he_simple_pir_context* ctx);
+/* SimplePirServerProtocol.process(database:encryptionParams:seed:) (SimplePir+Database.swift:252-290) on the device.
+ *   entries   DEVICE [entry_count][entry_size_in_bytes] (RawDatabase)
+ *   seed      DEVICE [32], the NistAes128Ctr seed of generateAPolynomials (:178-181)
+ *   database  DEVICE [column_size][database_columns] elements of element_bytes (layout above), written whole
+ *   hint      DEVICE [column_size][lattice_dimension] words mod p, 16-byte aligned: database x A mod p (:279-281)
+ * The matrix A (materializeAMatrix, :186-206) is not formed: with a_k the seeded polynomials and d_{r,k} the k-th block of
+ * lattice_dimension elements of database row r, hint row r = sum_k d_{r,k} * a_k(x^(2N-1)) in Z_p[x]/(x^N + 1), computed
+ * with the forward / inverse NTT in blocks of rows.  Enqueue-only on `s`; scratch comes from the library's stream-ordered
+ * cache.  The context must be of the entry's word size (HE_ERR_INVALID_ARGUMENT otherwise). */
+int he_simple_pir_process_database_device(const he_simple_pir_context* ctx, const uint8_t* entries, const uint8_t* seed,
+                                          void* database, uint64_t* hint, he_stream s);
+int he_simple_pir_process_database_device_u32(const he_simple_pir_context* ctx, const uint8_t* entries, const uint8_t* seed,
+                                              void* database, uint32_t* hint, he_stream s);
+/* The reference's wide image of a processed database (Array2d<Scalar>.data of SimplePirDatabase, `elements` words) to the
+ * device layout and back: what a server that loaded a saved database (SimplePirDatabase.init(from:),
+ * SimplePir+Database.swift:86-106) calls before it answers.  Both DEVICE, element-wise, enqueue-only.  pack keeps the low
+ * plaintext_bits of every word: a word at or above 2^plaintext_bits is masked, not rejected (rejecting would need a
+ * read-back).  HE_ERR_INVALID_ARGUMENT: plaintext_bits 0 or above the word. */
+int he_simple_pir_pack_database_device(uint32_t plaintext_bits, const uint64_t* wide, void* database, size_t elements,
+                                       he_stream s);
+int he_simple_pir_pack_database_device_u32(uint32_t plaintext_bits, const uint32_t* wide, void* database, size_t elements,
+                                           he_stream s);
+int he_simple_pir_unpack_database_device(uint32_t plaintext_bits, const void* database, uint64_t* wide, size_t elements,
+                                         he_stream s);
+int he_simple_pir_unpack_database_device_u32(uint32_t plaintext_bits, const void* database, uint32_t* wide, size_t elements,
+                                             he_stream s);
+/* SimplePirServer.computeResponse(to:) (SimplePir+Server.swift:31-38; Array2d.multiply(transposing:mask:),
+ * SimplePir+Precompute.swift:51-114) for a batch of stacked requests:
+ *   responses[q][r] = (sum_c database[r][c] * requests[q][c]) & (2^ciphertext_bits - 1)
+ *   database   DEVICE [column_size][database_columns] in the layout above (plaintext_bits selects element_bytes)
+ *   requests   DEVICE [query_count][database_columns] words (Requests, one request per row)
+ *   responses  DEVICE [query_count][column_size] words (the reference's transposed result)
+ * query_count is free: requests are answered eight to a pass over the database.  Enqueue-only on `s`, no scratch.
+ * ciphertext_bits may be anything up to the word here (the product needs no prime; he_simple_pir_shape stops at 29 / 60
+ * because process does).  HE_ERR_INVALID_ARGUMENT: ciphertext_bits <= plaintext_bits or above the word, a misaligned
+ * database. */
+int he_simple_pir_compute_response_device(uint32_t plaintext_bits, uint32_t ciphertext_bits, const void* database,
+                                          size_t column_size, size_t database_columns, const uint64_t* requests,
+                                          size_t query_count, uint64_t* responses, he_stream s);
+int he_simple_pir_compute_response_device_u32(uint32_t plaintext_bits, uint32_t ciphertext_bits, const void* database,
+                                              size_t column_size, size_t database_columns, const uint32_t* requests,
+                                              size_t query_count, uint32_t* responses, he_stream s);
+
 /* PirUtil.expand(ciphertexts:outputCount:using:) (PrivateInformationRetrieval/IndexPir/PirUtil.swift:196-355):
  * oblivious expansion of `ciphertext_count` query ciphertexts [..][2][L][N] (Coeff, top level) into `output_count`
  * ciphertexts, in the reference's output order.  The evaluation key is given as parallel host arrays:

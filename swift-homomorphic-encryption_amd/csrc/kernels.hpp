@@ -236,4 +236,37 @@ hipError_t launch_plaintext_unlift(W* rows, uint64_t q0, uint64_t t, size_t word
 template <typename W>
 hipError_t launch_first_rows(const W* in, W* out, const DeviceContext& ctx, size_t batch, hipStream_t stream);
 
+// ---- simple_pir_kernels.hip: SimplePirServer (PrivateInformationRetrieval/SimplePir/) -----------------------------------
+// The database is [column_size][database_columns] row-major in elements of element_bytes = 1 / 2 / 4 / 8 bytes.
+struct SimplePirLayout {
+    size_t entry_count, entry_size_in_bytes, entry_size_in_scalar, padded_entry_size, column_size, database_columns;
+    uint32_t plaintext_bits, element_bytes;
+};
+// process, the database half (SimplePir+Database.swift:252-275): entries [entry_count][entry_size_in_bytes] -> database
+hipError_t launch_simple_pir_database(const SimplePirLayout& layout, const uint8_t* entries, void* database,
+                                      hipStream_t stream);
+// rows [first_row, first_row + rows) of the database as `blocks` zero-padded polynomials of N 8-byte coefficients each:
+// staging [rows][blocks][N]
+hipError_t launch_simple_pir_widen(const void* database, uint32_t element_bytes, size_t columns, size_t first_row, size_t rows,
+                                   uint32_t blocks, uint32_t log_degree, uint64_t* staging, hipStream_t stream);
+// out [rows][N] = sum_k staging[row][k] * a_eval[k] mod p, Eval form, reduced every `cadence` products (ctx: one modulus)
+hipError_t launch_simple_pir_hint_mac(const uint64_t* staging, const uint64_t* a_eval, uint64_t* out, size_t rows,
+                                      uint32_t blocks, uint64_t cadence, const DeviceContext& ctx, hipStream_t stream);
+// out[0 .. count) = ctx.moduli[0]: the table that lets launch_seeded_uniform draw `count` polynomials from ONE stream
+hipError_t launch_simple_pir_replicate_modulus(const DeviceContext& ctx, DeviceModulus* out, uint32_t count,
+                                               hipStream_t stream);
+// the reference's wide Array2d<Scalar> image <-> the narrow layout (pack keeps the low plaintext_bits of every word)
+template <typename W>
+hipError_t launch_simple_pir_pack(const W* wide, void* database, uint32_t element_bytes, uint32_t plaintext_bits,
+                                  size_t elements, hipStream_t stream);
+template <typename W>
+hipError_t launch_simple_pir_unpack(const void* database, uint32_t element_bytes, W* wide, size_t elements,
+                                    hipStream_t stream);
+// computeResponse: responses [query_count][rows] = (database x requests[q]) & (2^ciphertext_bits - 1), requests
+// [query_count][columns]
+template <typename W>
+hipError_t launch_simple_pir_response(const void* database, uint32_t element_bytes, size_t rows, size_t columns,
+                                      const W* requests, size_t query_count, W* responses, uint32_t ciphertext_bits,
+                                      hipStream_t stream);
+
 }  // namespace heamd

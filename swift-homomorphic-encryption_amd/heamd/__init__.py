@@ -13,6 +13,8 @@ from .binding import (  # noqa: F401
     DeviceGroup,
     HeError,
     PolyContext,
+    SimplePirServer,
+    SimplePirServer32,
     current_device,
     device_count,
     galois_element_rotating_columns,
@@ -24,6 +26,7 @@ from .binding import (  # noqa: F401
     set_device,
     scratch_cached_bytes,
     shard_bounds,
+    simple_pir_shape,
     set_scratch_cache,
     stream_copy,
     to_device,

@@ -207,6 +207,19 @@ SIGNATURES = [
      [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
     ("he_pir_process_database_device_u32", ctypes.c_int,
      [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
+    ("he_simple_pir_shape", ctypes.c_int,
+     [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
+      ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_u64), ctypes.POINTER(c_u32)]),
+    ("he_simple_pir_context_create", ctypes.c_int, [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(vp)]),
+    ("he_simple_pir_context_destroy", None, [vp]),
+    ("he_simple_pir_process_database_device", ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
+    ("he_simple_pir_process_database_device_u32", ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
+    ("he_simple_pir_pack_database_device", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
+    ("he_simple_pir_pack_database_device_u32", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
+    ("he_simple_pir_unpack_database_device", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
+    ("he_simple_pir_unpack_database_device_u32", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
+    ("he_simple_pir_compute_response_device", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
+    ("he_simple_pir_compute_response_device_u32", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
     # diagnostics / test hooks
     ("he_poly_context_create_host_only", ctypes.c_int, [c_u32, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_poly_context_copy_ntt_tables", ctypes.c_int, [vp, c_u32, U64P, U64P, U64P, U64P, U64P, U64P]),
@@ -1358,3 +1371,133 @@ class BfvContext32(BfvContext):
         _check(load_library().he_bfv_plaintext_to_coeff_device_u32(self.h, L, _ptr32(plaintext_eval), _ptr32(out), batch,
                                                                    _stream(stream)))
         return out
+
+
+def simple_pir_shape(plaintext_bits, ciphertext_bits, lattice_dimension, entry_count, entry_size_in_bytes, word_bits=64):
+    """he_simple_pir_shape: SimplePirServerProtocol.computingParams, process's padded column size and SimplePirContext's
+    modulus -> dict.  Host only."""
+    sizes = [c_size(0) for _ in range(6)]
+    modulus, element_bytes = c_u64(0), c_u32(0)
+    _check(load_library().he_simple_pir_shape(int(plaintext_bits), int(ciphertext_bits), int(lattice_dimension), int(word_bits),
+                                              int(entry_count), int(entry_size_in_bytes), *[ctypes.byref(v) for v in sizes],
+                                              ctypes.byref(modulus), ctypes.byref(element_bytes)))
+    names = ("entry_size_in_scalar", "entries_per_column", "chunks_per_entry", "database_columns", "column_size", "a_poly_count")
+    out = {name: v.value for name, v in zip(names, sizes)}
+    out.update(modulus=modulus.value, element_bytes=element_bytes.value, plaintext_bits=int(plaintext_bits),
+               ciphertext_bits=int(ciphertext_bits), lattice_dimension=int(lattice_dimension),
+               entry_size_in_bytes=int(entry_size_in_bytes), entry_count=int(entry_count))
+    return out
+
+
+_SIMPLE_PIR_ELEMENT_DTYPES = {1: "uint8", 2: "int16", 4: "int32", 8: "int64"}
+
+
+class SimplePirServer:
+    """SimplePirServer<UInt64> (PrivateInformationRetrieval/SimplePir/SimplePir+Server.swift) on the device: `database` is a
+    torch tensor [column_size][database_columns] of element_bytes-wide elements, `hint` [column_size][lattice_dimension]
+    words mod params["modulus"], requests and responses torch tensors of words (int64 storage; int32 in SimplePirServer32)."""
+
+    word_bits = 64
+    _suffix = ""
+
+    def __init__(self, database, hint, params, _handle=None):
+        self.database, self.hint, self.params = database, hint, params
+        self.h = _handle  # he_simple_pir_context of a server made by process(); None for one made from a wide image
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            load_library().he_simple_pir_context_destroy(self.h)
+            self.h = None
+
+    @classmethod
+    def _words(cls, shape, device):
+        import torch
+
+        return torch.empty(shape, dtype=torch.int64 if cls.word_bits == 64 else torch.int32, device=device)
+
+    @classmethod
+    def _entry(cls, name):
+        return getattr(load_library(), name + cls._suffix)
+
+    @classmethod
+    def process(cls, entries, plaintext_bits, ciphertext_bits, lattice_dimension, seed, stream=None):
+        """SimplePirServerProtocol.process: entries a uint8 CUDA tensor [entry_count][entry_size_in_bytes], seed 32 bytes
+        (bytes-like, uploaded here, or a uint8 CUDA tensor).  Creates the server's he_simple_pir_context (that synchronises:
+        tables are uploaded), which the server keeps until it is collected; the database and hint are then enqueued on
+        `stream` and the call returns with that work in flight."""
+        if entries.dim() != 2:
+            raise ValueError("expected entries [entry_count][entry_size_in_bytes]")
+        entry_count, entry_size = entries.shape
+        params = simple_pir_shape(plaintext_bits, ciphertext_bits, lattice_dimension, entry_count, entry_size, cls.word_bits)
+        handle = vp()
+        _check(load_library().he_simple_pir_context_create(int(plaintext_bits), int(ciphertext_bits), int(lattice_dimension),
+                                                           cls.word_bits, entry_count, entry_size, ctypes.byref(handle)))
+        server = cls(None, None, params, handle)
+        return server.reprocess(entries, seed, stream)
+
+    def reprocess(self, entries, seed, stream=None, out=None):
+        """process again with the server's context (entries of the same shape; another seed or other bytes): enqueue-only
+        when the seed is a CUDA tensor.  out = (database, hint) tensors to write into instead of fresh ones."""
+        import torch
+
+        if self.h is None:
+            raise ValueError("this server was not made by process()")
+        params = self.params
+        if (not entries.is_cuda or not entries.is_contiguous() or entries.element_size() != 1
+                or tuple(entries.shape) != (params["entry_count"], params["entry_size_in_bytes"])):
+            raise ValueError("expected a contiguous CUDA uint8 tensor [entry_count][entry_size_in_bytes]")
+        if not torch.is_tensor(seed):
+            seed = torch.from_numpy(np.frombuffer(bytes(seed), dtype=np.uint8).copy()).to(entries.device)
+        if seed.numel() != 32 or seed.element_size() != 1 or not seed.is_cuda:
+            raise ValueError("expected a 32-byte seed")
+        if out is None:
+            database = torch.empty((params["column_size"], params["database_columns"]), device=entries.device,
+                                   dtype=getattr(torch, _SIMPLE_PIR_ELEMENT_DTYPES[params["element_bytes"]]))
+            hint = self._words((params["column_size"], params["lattice_dimension"]), entries.device)
+        else:
+            database, hint = out
+        _check(self._entry("he_simple_pir_process_database_device")(self.h, vp(entries.data_ptr()), vp(seed.data_ptr()),
+                                                                    vp(database.data_ptr()), vp(hint.data_ptr()),
+                                                                    _stream(stream)))
+        self.database, self.hint = database, hint
+        return self
+
+    @classmethod
+    def from_wide(cls, wide, hint, params, stream=None):
+        """init(processedDatabase:hint:params:) from the reference's wide image [column_size][database_columns] of words."""
+        import torch
+
+        database = torch.empty(tuple(wide.shape), device=wide.device,
+                               dtype=getattr(torch, _SIMPLE_PIR_ELEMENT_DTYPES[params["element_bytes"]]))
+        _check(cls._entry("he_simple_pir_pack_database_device")(params["plaintext_bits"], cls._word_ptr(wide),
+                                                                vp(database.data_ptr()), wide.numel(), _stream(stream)))
+        return cls(database, hint, params)
+
+    @classmethod
+    def _word_ptr(cls, tensor):
+        return _ptr(tensor) if cls.word_bits == 64 else _ptr32(tensor)
+
+    def wide_database(self, stream=None):
+        """The database as the reference stores it: one word per element."""
+        wide = self._words(tuple(self.database.shape), self.database.device)
+        _check(self._entry("he_simple_pir_unpack_database_device")(self.params["plaintext_bits"], vp(self.database.data_ptr()),
+                                                                   vp(wide.data_ptr()), wide.numel(), _stream(stream)))
+        return wide
+
+    def compute_response(self, requests, stream=None):
+        """computeResponse(to:): requests [query_count][database_columns] -> responses [query_count][column_size]."""
+        if requests.dim() != 2 or requests.shape[1] != self.params["database_columns"]:
+            raise ValueError("expected requests [query_count][database_columns]")
+        responses = self._words((requests.shape[0], self.params["column_size"]), requests.device)
+        _check(self._entry("he_simple_pir_compute_response_device")(
+            self.params["plaintext_bits"], self.params["ciphertext_bits"], vp(self.database.data_ptr()),
+            self.params["column_size"], self.params["database_columns"], self._word_ptr(requests), requests.shape[0],
+            vp(responses.data_ptr()), _stream(stream)))
+        return responses
+
+
+class SimplePirServer32(SimplePirServer):
+    """SimplePirServer<UInt32>: 4-byte request / response / hint words."""
+
+    word_bits = 32
+    _suffix = "_u32"
