@@ -55,7 +55,8 @@ enum he_status {
     HE_ERR_UNSUPPORTED = 18,       /* unsupportedHeOperation */
     HE_ERR_MISSING_GALOIS_KEY = 19, /* missingGaloisKey / missingGaloisElement  Bfv/Bfv.swift:184-189 */
     HE_ERR_SERIALIZED_BUFFER_SIZE_MISMATCH = 20, /* serializedBufferSizeMismatch  PolyRq/PolyRq+Serialize.swift:41-51 */
-    HE_ERR_INVALID_COEFFICIENT_PACKING = 21      /* invalidCoefficientPacking     CoefficientPacking.swift:27-31 */
+    HE_ERR_INVALID_COEFFICIENT_PACKING = 21,     /* invalidCoefficientPacking     CoefficientPacking.swift:27-31 */
+    HE_ERR_SIMD_ENCODING_NOT_SUPPORTED = 22      /* simdEncodingNotSupported      Encoding.swift:225 */
 };
 
 typedef struct he_poly_context he_poly_context; /* PolyContext<UInt64>   PolyRq/PolyContext.swift:19-35 */
@@ -590,6 +591,59 @@ int he_pir_process_database_device_u32(const he_bfv_context* ctx, const uint32_t
                                        const uint8_t* entries, const uint64_t* entry_sizes, size_t entry_count,
                                        size_t entry_size_in_bytes, int encoding_entry_size, uint32_t* database,
                                        uint8_t* present, he_stream s);
+
+/* ---- PNNS server database (PrivateNearestNeighborSearch/) ------------------------------------------------------------------
+ * Database.process (ProcessedDatabase.swift:194-229) for one context, on the device: the float vectors are normalised,
+ * scaled and rounded, packed diagonally into SIMD plaintexts (PlaintextMatrix.swift:417-483) and converted to Eval form.
+ * The result is the PlaintextMatrix<Scheme, Eval> that mulTranspose(vector:) (MatrixMultiplication.swift:131-226) reads with
+ * he_bfv_apply_galois(_grouped)_device, he_ntt_*_device and he_bfv_inner_product_plain_resident_device.
+ *
+ * he_pnns_context -- what a he_bfv_context lacks for Context.encode(values:format: .simd): plaintextContext, the PolyContext
+ * over [t] (Context.swift:128-130) with its NTT tables on the device, and simdEncodingMatrix (generateEncodingMatrix,
+ * Encoding.swift:197-219), built on the host and uploaded once.  t not an NTT modulus for N: HE_ERR_SIMD_ENCODING_NOT_SUPPORTED
+ * (Encoding.swift:225).  A host-only BFV context gives a host-only PNNS context: he_pnns_matrix_shape works, device entry
+ * points return HE_ERR_DEVICE.  The BFV context is borrowed and must outlive the PNNS context.  he_pnns_context_create takes a
+ * Context<Bfv<UInt64>>, he_pnns_context_create_u32 a Context<Bfv<UInt32>> (HE_ERR_INVALID_ARGUMENT for the other kind).
+ * Synchronises (tables are uploaded).  Destroy (NULL is accepted) once the work enqueued with it is done. */
+typedef struct he_pnns_context he_pnns_context;
+int he_pnns_context_create(const he_bfv_context* ctx, he_pnns_context** out);
+int he_pnns_context_create_u32(const he_bfv_context* ctx, he_pnns_context** out);
+void he_pnns_context_destroy(he_pnns_context* ctx);
+/* MatrixPacking (PlaintextMatrix.swift:21-37), in the reference's case order */
+enum { HE_PNNS_PACKING_DENSE_COLUMN = 0, HE_PNNS_PACKING_DENSE_ROW = 1, HE_PNNS_PACKING_DIAGONAL = 2 };
+/* PlaintextMatrix.plaintextCount (PlaintextMatrix.swift:246-275) and BabyStepGiantStep.init (MatrixMultiplication.swift:
+ * 33-60).  Host only.  baby_step 0: the default, ceil(sqrt(nextPowerOfTwo(column_count))); otherwise giant_step =
+ * ceil(nextPowerOfTwo(column_count) / baby_step).  Any out pointer may be NULL.  HE_ERR_INVALID_ARGUMENT: baby_step <
+ * giant_step (the reference's precondition), zero rows or columns (invalidMatrixDimensions), column_count > N / 2 under
+ * denseRow or diagonal, an unknown packing. */
+int he_pnns_matrix_shape(const he_pnns_context* ctx, size_t row_count, size_t column_count, int packing, uint32_t baby_step,
+                         size_t* out_plaintext_count, uint32_t* out_baby_step, uint32_t* out_giant_step);
+/* Array2d<Float>.normalizedScaledAndRounded (PrivateNearestNeighborSearch/Util.swift:74-89), bit-exact: per row the float32
+ * sum of squares accumulated left to right from 0, its correctly rounded square root, then (v * scaling_factor) / norm
+ * rounded half away from zero; a row of norm 0 gives zeros.  vectors DEVICE [rows][cols] float32 row-major, out DEVICE
+ * [rows][cols] int64 (the reference's Array2d<SignedScalar>).  Enqueue-only on `s`. */
+int he_pnns_quantize_rows_device(const float* vectors, size_t rows, size_t cols, float scaling_factor, int64_t* out,
+                                 he_stream s);
+/* PlaintextMatrix(context:dimensions:packing: .diagonal(bsgs), signedValues:reduce:).convertToEvalFormat(moduliCount:)
+ * (PlaintextMatrix.swift:165-188, 417-483; Encoding.swift:222-234; Plaintext.swift:149-170).
+ *   signed_values  DEVICE [rows][cols] int64 row-major
+ *   baby_step      as in he_pnns_matrix_shape
+ *   reduce         nonzero: values go through Modulus.reduce for signed input (the plaintext-CRT case,
+ *                  ProcessedDatabase.swift:213-220); 0: centeredToRemainder, and a value outside [-(t >> 1), (t - 1) >> 1]
+ *                  sets *out_of_range to 1 (its plaintext is then unspecified)
+ *   out            DEVICE [plaintext_count][moduli_count][N] Eval; plaintext index = diagonal * plaintextsPerColumn + chunk,
+ *                  the reference's append order
+ *   out_of_range   DEVICE, one word the caller zeroes; may be NULL
+ * Enqueue-only on `s` and capturable; staging comes from the library's stream-ordered scratch, in groups of plaintexts of
+ * about 1 GiB of output.  Argument errors (those of he_pnns_matrix_shape, a moduli_count out of range, a null pointer, a
+ * context of the other word size) are returned before anything is enqueued.  A host-only context: HE_ERR_DEVICE. */
+int he_pnns_diagonal_matrix_device(const he_pnns_context* ctx, const int64_t* signed_values, size_t rows, size_t cols,
+                                   uint32_t baby_step, int reduce, uint32_t moduli_count, uint64_t* out,
+                                   uint32_t* out_of_range, he_stream s);
+/* The same for a Bfv<UInt32> context, the matrix in packed 4-byte words. */
+int he_pnns_diagonal_matrix_device_u32(const he_pnns_context* ctx, const int64_t* signed_values, size_t rows, size_t cols,
+                                       uint32_t baby_step, int reduce, uint32_t moduli_count, uint32_t* out,
+                                       uint32_t* out_of_range, he_stream s);
 
 /* ---- SimplePirServer (PrivateInformationRetrieval/SimplePir/) ------------------------------------------------------------
  * The other index-PIR server: a database matrix of plaintext_bits-wide elements, a hint for the clients, and replies that

@@ -324,6 +324,7 @@ const char* he_status_string(int status) {
         case HE_ERR_MISSING_GALOIS_KEY: return "missingGaloisKey";
         case HE_ERR_SERIALIZED_BUFFER_SIZE_MISMATCH: return "serializedBufferSizeMismatch";
         case HE_ERR_INVALID_COEFFICIENT_PACKING: return "invalidCoefficientPacking";
+        case HE_ERR_SIMD_ENCODING_NOT_SUPPORTED: return "simdEncodingNotSupported";
         default: return "unknown";
     }
 }

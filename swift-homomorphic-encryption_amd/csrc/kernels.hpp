@@ -269,4 +269,22 @@ hipError_t launch_simple_pir_response(const void* database, uint32_t element_byt
                                       const W* requests, size_t query_count, W* responses, uint32_t ciphertext_bits,
                                       hipStream_t stream);
 
+// ---- pnns_kernels.hip: the PNNS server database (PrivateNearestNeighborSearch/) ------------------------------------------
+// normalizedScaledAndRounded (Util.swift:74-89), bit-exact: vectors [rows][cols] float32 -> out [rows][cols] int64
+hipError_t launch_pnns_quantize_rows(const float* vectors, size_t rows, size_t cols, float scaling_factor, int64_t* out,
+                                     hipStream_t stream);
+// The diagonal packing of one [rows][cols] matrix (PlaintextMatrix.swift:417-483)
+struct PnnsMatrixLayout {
+    size_t rows, cols, padded_cols /* nextPowerOfTwo(cols) */, plaintexts_per_column /* ceil(rows / N) */;
+    uint64_t plaintext_modulus;
+    uint32_t log_degree, baby_step;
+    int reduce;  // Modulus.reduce instead of centeredToRemainder
+};
+// Plaintexts [first, first + count) (index = diagonal * plaintexts_per_column + chunk) as the slabs encodeSimd hands to
+// inverseNtt: staging [count][N] words mod t, every word written.  slot_of_word: the inverse of simdEncodingMatrix, [N].
+// out_of_range (may be nullptr): set to 1 when reduce == 0 and a value is outside the centred range of t.
+template <typename W>
+hipError_t launch_pnns_diagonal_pack(const int64_t* values, const uint32_t* slot_of_word, const PnnsMatrixLayout& layout,
+                                     size_t first, size_t count, W* staging, uint32_t* out_of_range, hipStream_t stream);
+
 }  // namespace heamd

@@ -12,6 +12,7 @@ from .binding import (  # noqa: F401
     BfvContext32,
     DeviceGroup,
     HeError,
+    PnnsContext,
     PolyContext,
     SimplePirServer,
     SimplePirServer32,

@@ -22,7 +22,7 @@ STATUS_NAMES = {
     9: "incompatibleCiphertexts", 10: "incompatibleCiphertextAndPlaintext", 11: "missingRelinearizationKey",
     12: "unequalContexts", 13: "notEnoughPrimes", 14: "notInvertible", 15: "invalidEncryptionParameters",
     16: "invalidArgument", 17: "deviceError", 18: "unsupportedHeOperation", 19: "missingGaloisKey",
-    20: "serializedBufferSizeMismatch", 21: "invalidCoefficientPacking",
+    20: "serializedBufferSizeMismatch", 21: "invalidCoefficientPacking", 22: "simdEncodingNotSupported",
 }
 
 
@@ -220,6 +220,14 @@ SIGNATURES = [
     ("he_simple_pir_unpack_database_device_u32", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
     ("he_simple_pir_compute_response_device", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
     ("he_simple_pir_compute_response_device_u32", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
+    ("he_pnns_context_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    ("he_pnns_context_create_u32", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    ("he_pnns_context_destroy", None, [vp]),
+    ("he_pnns_matrix_shape", ctypes.c_int,
+     [vp, c_size, c_size, ctypes.c_int, c_u32, ctypes.POINTER(c_size), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    ("he_pnns_quantize_rows_device", ctypes.c_int, [vp, c_size, c_size, ctypes.c_float, vp, vp]),
+    ("he_pnns_diagonal_matrix_device", ctypes.c_int, [vp, vp, c_size, c_size, c_u32, ctypes.c_int, c_u32, vp, vp, vp]),
+    ("he_pnns_diagonal_matrix_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_u32, ctypes.c_int, c_u32, vp, vp, vp]),
     # diagnostics / test hooks
     ("he_poly_context_create_host_only", ctypes.c_int, [c_u32, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_poly_context_copy_ntt_tables", ctypes.c_int, [vp, c_u32, U64P, U64P, U64P, U64P, U64P, U64P]),
@@ -762,6 +770,7 @@ class BfvContext:
         _check(create(degree, plaintext_modulus, arr.ctypes.data_as(U64P), len(arr), ctypes.byref(h)))
         self.h = h
         self.degree = degree
+        self.word_bits = word_bits
         self.t = plaintext_modulus
         self.coefficient_moduli = [int(v) for v in arr]
         self.L = int(lib.he_bfv_ciphertext_moduli_count(self.h))
@@ -1501,3 +1510,83 @@ class SimplePirServer32(SimplePirServer):
 
     word_bits = 32
     _suffix = "_u32"
+
+
+PNNS_PACKINGS = {"denseColumn": 0, "denseRow": 1, "diagonal": 2}  # MatrixPacking's case order (HE_PNNS_PACKING_*)
+
+
+class PnnsContext:
+    """he_pnns_context: the SIMD encoding side of a BfvContext / BfvContext32 (plaintextContext over [t] and
+    simdEncodingMatrix on the device) and the PNNS server database built with it (PrivateNearestNeighborSearch/
+    ProcessedDatabase.swift:194-229).  Borrows `bfv`, which it keeps alive."""
+
+    def __init__(self, bfv):
+        lib = load_library()
+        self.bfv = bfv
+        self.word32 = bfv.word_bits == 32  # Bfv<UInt32>: packed 4-byte words, as BfvContext32 lays its slabs out
+        h = vp()
+        create = lib.he_pnns_context_create_u32 if self.word32 else lib.he_pnns_context_create
+        _check(create(bfv.h, ctypes.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.he_pnns_context_destroy(self.h)
+            self.h = None
+
+    def matrix_shape(self, row_count, column_count, packing="diagonal", baby_step=0):
+        """he_pnns_matrix_shape: PlaintextMatrix.plaintextCount and BabyStepGiantStep.init -> dict with plaintext_count,
+        baby_step and giant_step.  packing: "denseColumn", "denseRow", "diagonal" or the HE_PNNS_PACKING_* number."""
+        count, baby, giant = c_size(), c_u32(), c_u32()
+        _check(load_library().he_pnns_matrix_shape(self.h, int(row_count), int(column_count),
+                                                   int(PNNS_PACKINGS.get(packing, packing)), int(baby_step),
+                                                   ctypes.byref(count), ctypes.byref(baby), ctypes.byref(giant)))
+        return {"plaintext_count": int(count.value), "baby_step": int(baby.value), "giant_step": int(giant.value)}
+
+    def quantize_rows(self, vectors, scaling_factor, stream=None):
+        """Array2d<Float>.normalizedScaledAndRounded: float32 CUDA tensor [rows][cols] -> int64 tensor [rows][cols]."""
+        import torch
+
+        if vectors.dtype != torch.float32 or not vectors.is_cuda or not vectors.is_contiguous() or vectors.dim() != 2:
+            raise ValueError("vectors must be a contiguous float32 device tensor [rows][cols]")
+        out = torch.empty(vectors.shape, dtype=torch.int64, device=vectors.device)
+        _check(load_library().he_pnns_quantize_rows_device(vp(vectors.data_ptr()), vectors.shape[0], vectors.shape[1],
+                                                           float(scaling_factor), vp(out.data_ptr()), _stream(stream)))
+        return out
+
+    def diagonal_matrix(self, signed_values, baby_step=0, reduce=False, moduli_count=None, stream=None):
+        """PlaintextMatrix(.diagonal, signedValues:reduce:).convertToEvalFormat(moduliCount:): int64 CUDA tensor [rows][cols]
+        -> (matrix [plaintext_count][moduli_count][N] Eval words, int64 storage or int32 for a BfvContext32; out_of_range, a
+        one-word int32 device tensor: 1 when reduce is off and a value was outside the centred range of t)."""
+        import torch
+
+        if (signed_values.dtype != torch.int64 or not signed_values.is_cuda or not signed_values.is_contiguous()
+                or signed_values.dim() != 2):
+            raise ValueError("signed_values must be a contiguous int64 device tensor [rows][cols]")
+        rows, cols = signed_values.shape
+        L = self.bfv._L(moduli_count)
+        count = self.matrix_shape(rows, cols, "diagonal", baby_step)["plaintext_count"]
+        # (a fill on the caller's stream, ahead of the build that may set the word)
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            matrix = torch.empty((count, L, self.bfv.degree), dtype=torch.int32 if self.word32 else torch.int64,
+                                 device=signed_values.device)
+            out_of_range = torch.zeros(1, dtype=torch.int32, device=signed_values.device)
+        entry = "he_pnns_diagonal_matrix_device_u32" if self.word32 else "he_pnns_diagonal_matrix_device"
+        _check(getattr(load_library(), entry)(self.h, vp(signed_values.data_ptr()), rows, cols, int(baby_step),
+                                              int(bool(reduce)), L, vp(matrix.data_ptr()), vp(out_of_range.data_ptr()),
+                                              _stream(stream)))
+        return matrix, out_of_range
+
+    def process_database(self, vectors, scaling_factor, baby_step=0, reduce=False, moduli_count=None, stream=None):
+        """Database.process for this context: quantize_rows, then diagonal_matrix -> (matrix, out_of_range)."""
+        import torch
+
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            rounded = self.quantize_rows(vectors, scaling_factor, stream=stream)
+        return self.diagonal_matrix(rounded, baby_step=baby_step, reduce=reduce, moduli_count=moduli_count, stream=stream)
+
+
+def _no_stream():
+    import contextlib
+
+    return contextlib.nullcontext()
