@@ -595,8 +595,8 @@ int he_pir_process_database_device_u32(const he_bfv_context* ctx, const uint32_t
 /* ---- PNNS server database (PrivateNearestNeighborSearch/) ------------------------------------------------------------------
  * Database.process (ProcessedDatabase.swift:194-229) for one context, on the device: the float vectors are normalised,
  * scaled and rounded, packed diagonally into SIMD plaintexts (PlaintextMatrix.swift:417-483) and converted to Eval form.
- * The result is the PlaintextMatrix<Scheme, Eval> that mulTranspose(vector:) (MatrixMultiplication.swift:131-226) reads with
- * he_bfv_apply_galois(_grouped)_device, he_ntt_*_device and he_bfv_inner_product_plain_resident_device.
+ * The result is the PlaintextMatrix<Scheme, Eval> that mulTranspose(vector:) (MatrixMultiplication.swift:131-226) reads:
+ * he_pnns_mul_transpose_device / he_pnns_compute_response_device below.
  *
  * he_pnns_context -- what a he_bfv_context lacks for Context.encode(values:format: .simd): plaintextContext, the PolyContext
  * over [t] (Context.swift:128-130) with its NTT tables on the device, and simdEncodingMatrix (generateEncodingMatrix,
@@ -644,6 +644,47 @@ int he_pnns_diagonal_matrix_device(const he_pnns_context* ctx, const int64_t* si
 int he_pnns_diagonal_matrix_device_u32(const he_pnns_context* ctx, const int64_t* signed_values, size_t rows, size_t cols,
                                        uint32_t baby_step, int reduce, uint32_t moduli_count, uint32_t* out,
                                        uint32_t* out_of_range, he_stream s);
+
+/* ---- PNNS server response (PrivateNearestNeighborSearch/Server.swift:61-88) ------------------------------------------------
+ * PlaintextMatrix.mulTranspose(vector:using:) (MatrixMultiplication.swift:131-226) for `query_count` independent one-row
+ * query vectors against one diagonally packed matrix, in one call.  For a one-row CiphertextMatrix, mulTranspose(matrix:using:)
+ * (:236-276) is this: extractDenseRow returns the ciphertext itself and the column packing is rotateColumnsAndSum of one
+ * element.  With P = nextPowerOfTwo(cols), G = ceil(P / baby_step), C = ceil(rows / N), L = he_bfv_ciphertext_moduli_count:
+ *   matrix                  DEVICE [P C][L][N] Eval, 16-byte aligned: what he_pnns_diagonal_matrix_device writes at moduli_count L
+ *   matrix_plaintext_count  the plaintexts the matrix holds; anything but P C is the reference's invalidMatrixDimensions
+ *                           (:147-149: the query's column count does not match the matrix): HE_ERR_INVALID_ARGUMENT
+ *   rows, cols              the matrix's dimensions; shape errors as he_pnns_matrix_shape under HE_PNNS_PACKING_DIAGONAL
+ *   baby_step               the one the matrix was packed with (the packing carries it, :137); 0 is HE_ERR_INVALID_ARGUMENT
+ *   queries                 DEVICE [query_count][2][L][N] Coeff: each client's dense-row packed vector
+ *   galois_keys             HOST [query_count][2] device pointers (he_bfv_apply_galois_device's key layout): query q's keys of
+ *                           rotatingColumns(by: -1) at [2 q] and of rotatingColumns(by: -baby_step) at [2 q + 1].  The first is
+ *                           needed when baby_step > 1 (:182-187), the second when G > 1 (HeScheme.swift:113-133); a needed key
+ *                           that is NULL (or the array) is HE_ERR_MISSING_GALOIS_KEY; one that is not needed is not read
+ *   out                     DEVICE [query_count][C][2][L][N] Coeff: mulTranspose's result ciphertexts per query
+ * The order of operations is the reference's and every word equals its: baby_step - 1 serial rotations by -1 (not hoisted),
+ * each one batch over the queries; every state to Eval; the inner products of all giant steps (Bfv.swift:476-505) in one pass
+ * over the matrix for up to four queries at a time; inverse NTT; then G - 1 times rotate by -baby_step and add, each one batched
+ * key switch over all query_count x C accumulators.  Enqueue-only on `s`; scratch comes from the library's stream-ordered
+ * cache, the inner products in groups of result ciphertexts of about 2 GiB.  Argument errors are returned before anything is
+ * enqueued, in the order above; query_count 0 is HE_OK.  A host-only context: HE_ERR_DEVICE. */
+int he_pnns_mul_transpose_device(const he_pnns_context* ctx, const uint64_t* matrix, size_t matrix_plaintext_count, size_t rows,
+                                 size_t cols, uint32_t baby_step, const uint64_t* queries, size_t query_count,
+                                 const uint64_t* const* galois_keys, uint64_t* out, he_stream s);
+/* The same for a Bfv<UInt32> context on packed 4-byte words (matrix, queries, keys and out).  The 4-byte Galois entry takes
+ * one key per call, so here a rotation step is one call per query, not one batch over all of them; the pass over the matrix
+ * and the transforms are batched as above. */
+int he_pnns_mul_transpose_device_u32(const he_pnns_context* ctx, const uint32_t* matrix, size_t matrix_plaintext_count,
+                                     size_t rows, size_t cols, uint32_t baby_step, const uint32_t* queries, size_t query_count,
+                                     const uint32_t* const* galois_keys, uint32_t* out, he_stream s);
+/* Server.computeResponse (Server.swift:61-88) for such queries: the same, then Ciphertext.modSwitchDownToSingle
+ * (Bfv.swift:163-171) and Coeff form (:84-86).  out DEVICE [query_count][C][2][1][N] Coeff over q_0: what
+ * Response.ciphertextMatrices holds. */
+int he_pnns_compute_response_device(const he_pnns_context* ctx, const uint64_t* matrix, size_t matrix_plaintext_count,
+                                    size_t rows, size_t cols, uint32_t baby_step, const uint64_t* queries, size_t query_count,
+                                    const uint64_t* const* galois_keys, uint64_t* out, he_stream s);
+int he_pnns_compute_response_device_u32(const he_pnns_context* ctx, const uint32_t* matrix, size_t matrix_plaintext_count,
+                                        size_t rows, size_t cols, uint32_t baby_step, const uint32_t* queries,
+                                        size_t query_count, const uint32_t* const* galois_keys, uint32_t* out, he_stream s);
 
 /* ---- SimplePirServer (PrivateInformationRetrieval/SimplePir/) ------------------------------------------------------------
  * The other index-PIR server: a database matrix of plaintext_bits-wide elements, a hint for the clients, and replies that

@@ -287,4 +287,27 @@ template <typename W>
 hipError_t launch_pnns_diagonal_pack(const int64_t* values, const uint32_t* slot_of_word, const PnnsMatrixLayout& layout,
                                      size_t first, size_t count, W* staging, uint32_t* out_of_range, hipStream_t stream);
 
+// The inner products of every giant step of PlaintextMatrix.mulTranspose(vector:using:) (MatrixMultiplication.swift:195-212)
+// for `queries` (1..pnns_bsgs_queries_per_pass) queries in one pass over the matrix:
+//   rot     [baby_step][..][2][L][N] Eval: step j of query q at rot + j * rot_step_words + q * 2 L N
+//   matrix  [P * columns][L][N] Eval, plaintext (diagonal d, result c) at d * columns + c; 16-byte aligned
+//   out     [giant_step][out_queries][group_columns][2][L][N] Eval, given from the launch's first query (giant-step major: a
+//           step of rotateColumnsAndSum then adds one contiguous slab over all queries):
+//           out[g][q][c] = sum_{j < min(baby_step, padded_cols - g baby_step)} rot[j][q] * matrix[(g baby_step + j) columns +
+//           first_column + c]
+// max_lazy / cadence / narrow_moduli: as launch_inner_product_plain.
+constexpr size_t kPnnsBsgsTileLimit = size_t(128) << 10;  // LDS bytes of a workgroup's rotated rows (baby_step x queries x 2 KiB)
+struct PnnsBsgsLayout {
+    size_t rot_step_words;
+    uint32_t log_degree, moduli_count, baby_step, giant_step, padded_cols, columns, first_column, group_columns;
+    uint32_t out_queries;  // queries of the whole call (>= those of a launch)
+    uint64_t max_lazy, cadence;
+    bool narrow_moduli;
+};
+// how many of `queries` one launch takes (the tile must fit LDS; degrees below 64 lanes x 16 bytes: one)
+unsigned pnns_bsgs_queries_per_pass(const PnnsBsgsLayout& layout, size_t word_bytes, size_t queries);
+template <typename W>
+hipError_t launch_pnns_bsgs_inner_product(const W* rot, const W* matrix, W* out, const DeviceContext& ctx,
+                                          const PnnsBsgsLayout& layout, unsigned queries, hipStream_t stream);
+
 }  // namespace heamd

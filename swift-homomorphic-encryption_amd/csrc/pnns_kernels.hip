@@ -2,6 +2,8 @@
 // Array2d<Float>.normalizedScaledAndRounded (Util.swift:74-89) and the diagonal packing of PlaintextMatrix.diagonalPlaintexts
 // (PlaintextMatrix.swift:417-483) up to the slab Context.encodeSimd (Encoding.swift:222-234) hands to inverseNtt.  The
 // inverse NTT over [t] and Plaintext.convertToEvalFormat that follow are the existing kernels (pnns_api.cpp).
+// And the server's response: the baby-step giant-step inner products of PlaintextMatrix.mulTranspose(vector:using:)
+// (MatrixMultiplication.swift:195-212) for all giant steps and up to four queries in one pass over the matrix.
 #include "kernels.hpp"
 
 namespace heamd {
@@ -151,6 +153,230 @@ __global__ __launch_bounds__(kPackThreads) void pnns_diagonal_pack_kernel(const 
     }
 }
 
+// ---- mulTranspose(vector:): the inner products of every giant step ----------------------------------------------------------
+// With b the baby step, G the giant step, P = nextPowerOfTwo(cols), C = ceil(rows / N) and rot[j] the query rotated j times
+// (Eval), MatrixMultiplication.swift:195-212 computes, per giant step g and result c,
+//     w[g][c] = sum_{j < min(b, P - g b)} rot[j] * matrix[(g b + j) C + c]           (Bfv.innerProduct, Bfv.swift:476-505)
+// Every plaintext of the matrix belongs to exactly one (g, c), and rot depends on neither: a workgroup owns 64 lanes' worth of
+// (modulus, coefficient) columns -- 16 bytes per lane, contiguous along N -- keeps the b x QN x 2 rotated ciphertext rows of
+// those columns in LDS for its whole life, and its wavefronts walk the (g, c) items, each streaming its item's plaintexts
+// once from HBM, kBsgsDepth 16-byte loads ahead across item boundaries.  The last giant step's shorter sum is the item's own
+// loop bound.  QN queries share every plaintext word.  Sums are lazy and folded on `cadence` (at most the reference's
+// maxLazyProductAccumulationCount; the canonical result does not depend on it).
+// FAST: N >= 64 lanes x 16 bytes, so a wavefront's columns lie in one residue row (wave-uniform modulus: the carry-counting
+// sums of device_math.hpp) and the LDS tile is used.  !FAST (tiny degrees, or a baby step whose tile does not fit LDS): one
+// query, the rotated rows straight from memory, per-lane modulus, 128-bit sums.
+// Four queries of 8-byte words keep 16 carry-counting sums per lane: more registers than a lane of a 512-lane workgroup has,
+// so that form runs four wavefronts (twice the registers each) and keeps twice the loads in flight per wavefront instead.
+template <typename W, int QN>
+constexpr unsigned kBsgsThreads = (sizeof(W) == 8 && QN == 4) ? 256 : 512;
+template <typename W, int QN>
+constexpr unsigned kBsgsDepth = (sizeof(W) == 8 && QN == 4) ? 8 : 4;
+
+struct BsgsShape {
+    size_t plaintext_words;  // L N: words of a plaintext, of a ciphertext polynomial
+    size_t rot_step_words;   // from rot[j] to rot[j + 1]
+    uint32_t baby_step, giant_step, padded_cols;
+    uint32_t columns, first_column, group_columns;  // C; this launch covers results [first_column, first_column + group_columns)
+    uint32_t out_queries;                           // queries of the whole call: out is [giant_step][out_queries][group_columns]
+    uint64_t cadence;
+};
+
+template <typename W, bool FAST, bool NARROW, int R>
+struct BsgsSums;
+template <bool NARROW, int R>
+struct BsgsSums<uint64_t, true, NARROW, R> {
+    using Sum = ProductSum;
+    static __device__ __forceinline__ Sum zero() { return product_sum_zero(); }
+    static __device__ __forceinline__ void add_all(Sum (&s)[R], const uint64_t (&x)[R], uint64_t y) {
+        product_sum_add_all<R, NARROW>(s, x, y);
+    }
+    static __device__ __forceinline__ uint64_t reduce(const Sum& s, const DeviceModulus& m) { return reduce_product_sum(s, m); }
+    static __device__ __forceinline__ Sum from_residue(uint64_t r) {
+        Sum s = product_sum_zero();
+        s.t = r;
+        return s;
+    }
+};
+template <bool NARROW, int R>
+struct BsgsSums<uint64_t, false, NARROW, R> {
+    using Sum = U128;
+    static __device__ __forceinline__ Sum zero() { return U128{0, 0}; }
+    static __device__ __forceinline__ void add_all(Sum (&s)[R], const uint64_t (&x)[R], uint64_t y) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) mac128(s[r], x[r], y);
+    }
+    static __device__ __forceinline__ uint64_t reduce(const Sum& s, const DeviceModulus& m) {
+        return barrett_reduce128(s, m.p, m.barrett128_lo, m.barrett128_hi);
+    }
+    static __device__ __forceinline__ Sum from_residue(uint64_t r) { return U128{r, 0}; }
+};
+template <bool FAST, bool NARROW, int R>
+struct BsgsSums<uint32_t, FAST, NARROW, R> {  // products below 2^60: 64-bit sums, folded at least every 15 terms
+    using Sum = uint64_t;
+    static __device__ __forceinline__ Sum zero() { return 0; }
+    static __device__ __forceinline__ void add_all(Sum (&s)[R], const uint64_t (&x)[R], uint64_t y) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) s[r] = mad32(lo32(x[r]), lo32(y), s[r]);
+    }
+    static __device__ __forceinline__ uint64_t reduce(const Sum& s, const DeviceModulus& m) {
+        if constexpr (FAST) return barrett_reduce64_uniform(s, m.p, m.barrett64);
+        else return barrett_reduce64(s, m.p, m.barrett64);
+    }
+    static __device__ __forceinline__ Sum from_residue(uint64_t r) { return r; }
+};
+
+// the 16 bytes of a lane as words
+template <typename W>
+__device__ __forceinline__ void bsgs_words(const uint4& v, uint64_t (&out)[16 / sizeof(W)]) {
+    if constexpr (sizeof(W) == 8) {
+        out[0] = pack64(v.x, v.y);
+        out[1] = pack64(v.z, v.w);
+    } else {
+        out[0] = v.x;
+        out[1] = v.y;
+        out[2] = v.z;
+        out[3] = v.w;
+    }
+}
+
+// where a wavefront is in its sequence of (item, j) steps; every field is wave-uniform
+struct BsgsCursor {
+    uint32_t item, giant, column, j, count;
+    bool done;
+};
+
+template <typename W, int QN, bool NARROW, bool FAST>
+__global__ __launch_bounds__((kBsgsThreads<W, QN>)) void pnns_bsgs_inner_product_kernel(const W* __restrict__ rot,
+                                                                                      const W* __restrict__ matrix,
+                                                                                      W* __restrict__ out,
+                                                                                      const DeviceContext ctx,
+                                                                                      const BsgsShape shape) {
+    constexpr unsigned kVector = 16 / sizeof(W), kThreads = kBsgsThreads<W, QN>, kWaves = kThreads / 64;
+    constexpr unsigned kDepth = kBsgsDepth<W, QN>;
+    constexpr int R = 2 * QN;  // rotated ciphertext rows per step: (query, polynomial)
+    static_assert(FAST || QN == 1, "the general form answers one query per launch");
+    using Sums = BsgsSums<W, FAST, NARROW, R>;
+    extern __shared__ __attribute__((aligned(16))) uint4 bsgs_tile[];  // FAST: [baby_step][R][64 lanes]
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t words = shape.plaintext_words;
+    const size_t block_word = static_cast<size_t>(blockIdx.x) * 64u * kVector;
+    const size_t word = block_word + static_cast<size_t>(lane) * kVector;  // words is a multiple of kVector
+    if constexpr (FAST) {  // every lane is inside the polynomial: words is a multiple of 64 kVector
+        const uint32_t rows = shape.baby_step * R;
+        for (uint32_t i = threadIdx.x; i < rows * 64u; i += kThreads) {
+            const uint32_t row = i >> 6, j = row / R, r = row - j * R;
+            bsgs_tile[i] = *reinterpret_cast<const uint4*>(rot + j * shape.rot_step_words + r * words + block_word +
+                                                           static_cast<size_t>(i & 63u) * kVector);
+        }
+        __syncthreads();
+    } else {
+        if (word >= words) return;  // no barrier below
+    }
+    const DeviceModulus m = ctx.moduli[(FAST ? block_word : word) >> ctx.log_degree];
+    const uint32_t total = shape.giant_step * shape.group_columns;
+    const uint32_t stride = gridDim.y * kWaves;
+    auto enter = [&](BsgsCursor& at) {  // at.item < total
+        at.giant = at.item / shape.group_columns;
+        at.column = at.item - at.giant * shape.group_columns;
+        at.j = 0;
+        const uint32_t left = shape.padded_cols - at.giant * shape.baby_step;
+        at.count = left < shape.baby_step ? left : shape.baby_step;
+    };
+    auto advance = [&](BsgsCursor& at) {  // past the last step the cursor stays on it, done
+        if (at.done) return;
+        if (at.j + 1 < at.count) {
+            ++at.j;
+        } else if (at.item + stride < total) {
+            at.item += stride;
+            enter(at);
+        } else {
+            at.done = true;
+        }
+    };
+    BsgsCursor fetch{};
+    fetch.item = blockIdx.y * kWaves + wave;
+    if (fetch.item >= total) return;  // after the barrier
+    enter(fetch);
+    BsgsCursor use = fetch;
+    const W* lane_matrix = matrix + word;
+    auto load = [&](const BsgsCursor& at) {  // the matrix is read once: streamed past the caches
+        const size_t plaintext =
+            (static_cast<size_t>(at.giant) * shape.baby_step + at.j) * shape.columns + shape.first_column + at.column;
+        typedef uint32_t Words4 __attribute__((ext_vector_type(4)));
+        const Words4 v = __builtin_nontemporal_load(reinterpret_cast<const Words4*>(lane_matrix + plaintext * words));
+        return uint4{v.x, v.y, v.z, v.w};
+    };
+    // a wavefront's loads end with its steps: past the last one nothing is fetched (the branch is wave-uniform)
+    uint4 ring[kDepth];
+#pragma unroll
+    for (unsigned d = 0; d < kDepth; ++d) {
+        ring[d] = uint4{0, 0, 0, 0};
+        if (!fetch.done) ring[d] = load(fetch);
+        advance(fetch);
+    }
+    typename Sums::Sum acc[kVector][R];
+#pragma unroll
+    for (unsigned v = 0; v < kVector; ++v)
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[v][r] = Sums::zero();
+    uint64_t since_reduce = 0;
+    while (!use.done) {
+#pragma unroll
+        for (unsigned d = 0; d < kDepth; ++d) {
+            if (use.done) break;
+            uint64_t y[kVector];
+            bsgs_words<W>(ring[d], y);
+            if (!fetch.done) ring[d] = load(fetch);
+            advance(fetch);
+            uint64_t x[kVector][R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                uint4 operand;
+                if constexpr (FAST) operand = bsgs_tile[(use.j * R + r) * 64u + lane];
+                else operand = *reinterpret_cast<const uint4*>(rot + use.j * shape.rot_step_words + r * words + word);
+                uint64_t parts[kVector];
+                bsgs_words<W>(operand, parts);
+#pragma unroll
+                for (unsigned v = 0; v < kVector; ++v) x[v][r] = parts[v];
+            }
+#pragma unroll
+            for (unsigned v = 0; v < kVector; ++v) Sums::add_all(acc[v], x[v], y[v]);
+            ++since_reduce;
+            if (use.j + 1 == use.count) {  // the item's sum is complete: out[giant][query][column][polynomial]
+                since_reduce = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    W folded[kVector];
+#pragma unroll
+                    for (unsigned v = 0; v < kVector; ++v) {
+                        folded[v] = static_cast<W>(Sums::reduce(acc[v][r], m));
+                        acc[v][r] = Sums::zero();
+                    }
+                    const size_t polynomial =
+                        ((static_cast<size_t>(use.giant) * shape.out_queries + (r >> 1)) * shape.group_columns + use.column) * 2 +
+                        (r & 1);
+                    uint4 packed;
+                    if constexpr (sizeof(W) == 8) {
+                        packed = uint4{lo32(folded[0]), hi32(folded[0]), lo32(folded[1]), hi32(folded[1])};
+                    } else {
+                        packed = uint4{folded[0], folded[1], folded[2], folded[3]};
+                    }
+                    *reinterpret_cast<uint4*>(out + polynomial * words + word) = packed;
+                }
+            } else if (since_reduce >= shape.cadence) {
+                since_reduce = 0;
+#pragma unroll
+                for (unsigned v = 0; v < kVector; ++v)
+#pragma unroll
+                    for (int r = 0; r < R; ++r) acc[v][r] = Sums::from_residue(Sums::reduce(acc[v][r], m));
+            }
+            advance(use);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_pnns_quantize_rows(const float* vectors, size_t rows, size_t cols, float scaling_factor, int64_t* out,
@@ -202,5 +428,94 @@ template hipError_t launch_pnns_diagonal_pack<uint64_t>(const int64_t*, const ui
                                                         uint64_t*, uint32_t*, hipStream_t);
 template hipError_t launch_pnns_diagonal_pack<uint32_t>(const int64_t*, const uint32_t*, const PnnsMatrixLayout&, size_t, size_t,
                                                         uint32_t*, uint32_t*, hipStream_t);
+
+namespace {
+template <typename W, int QN, bool NARROW, bool FAST>
+hipError_t launch_bsgs(const W* rot, const W* matrix, W* out, const DeviceContext& ctx, const BsgsShape& shape,
+                       size_t tile_bytes, hipStream_t stream) {
+    constexpr unsigned kVector = 16 / sizeof(W), kThreads = kBsgsThreads<W, QN>, kWaves = kThreads / 64;
+    auto kernel = pnns_bsgs_inner_product_kernel<W, QN, NARROW, FAST>;
+    const size_t word_blocks = (shape.plaintext_words + 64 * kVector - 1) / (64 * kVector);
+    const size_t items = static_cast<size_t>(shape.giant_step) * shape.group_columns;
+    // workgroups over the (g, c) items of one word block: what the tile leaves room for on a compute unit (160 KiB of LDS,
+    // 2048 lanes), a few rounds of it across the chip, and no more than the items can feed
+    size_t resident = FAST ? (size_t(160) << 10) / tile_bytes : 4;
+    if (resident > 2048 / kThreads) resident = 2048 / kThreads;
+    if (resident == 0) resident = 1;
+    size_t splits = (256 * resident * 2 + word_blocks - 1) / word_blocks;
+    const size_t useful = (items + kWaves - 1) / kWaves;
+    if (splits > useful) splits = useful;
+    if (splits == 0) splits = 1;
+    if (word_blocks >= (size_t(1) << 31) || splits > 65535) return hipErrorInvalidValue;
+    if (FAST && tile_bytes > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_bytes));
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(word_blocks), static_cast<unsigned>(splits)), dim3(kThreads),
+                       FAST ? tile_bytes : 0, stream, rot, matrix, out, ctx, shape);
+    return hipGetLastError();
+}
+}  // namespace
+
+unsigned pnns_bsgs_queries_per_pass(const PnnsBsgsLayout& layout, size_t word_bytes, size_t queries) {
+    const size_t vector = 16 / word_bytes;
+    const size_t words = static_cast<size_t>(layout.moduli_count) << layout.log_degree;
+    if (queries == 0 || words % (64 * vector) != 0 || (size_t(1) << layout.log_degree) < 64 * vector) return 1;  // general form
+    size_t per_pass = queries < 4 ? queries : 4;
+    while (per_pass > 0 && size_t(layout.baby_step) * 2 * per_pass * 1024 > kPnnsBsgsTileLimit) --per_pass;
+    return per_pass == 0 ? 1 : static_cast<unsigned>(per_pass);
+}
+
+template <typename W>
+hipError_t launch_pnns_bsgs_inner_product(const W* rot, const W* matrix, W* out, const DeviceContext& ctx,
+                                          const PnnsBsgsLayout& layout, unsigned queries, hipStream_t stream) {
+    if (layout.group_columns == 0 || queries == 0) return hipSuccess;
+    constexpr size_t kVector = 16 / sizeof(W);
+    BsgsShape shape{};
+    shape.plaintext_words = static_cast<size_t>(layout.moduli_count) << layout.log_degree;
+    shape.rot_step_words = layout.rot_step_words;
+    shape.baby_step = layout.baby_step;
+    shape.giant_step = layout.giant_step;
+    shape.padded_cols = layout.padded_cols;
+    shape.columns = layout.columns;
+    shape.first_column = layout.first_column;
+    shape.group_columns = layout.group_columns;
+    shape.out_queries = layout.out_queries;
+    if (shape.plaintext_words % kVector != 0 || ctx.moduli_count != layout.moduli_count) return hipErrorInvalidValue;
+    if (static_cast<size_t>(layout.giant_step) * layout.group_columns >= (size_t(1) << 31)) return hipErrorInvalidValue;
+    const size_t tile_bytes = size_t(layout.baby_step) * 2 * queries * 1024;
+    const bool fast = shape.plaintext_words % (64 * kVector) == 0 && (size_t(1) << layout.log_degree) >= 64 * kVector &&
+                      tile_bytes <= kPnnsBsgsTileLimit;
+    uint64_t cadence = layout.cadence < layout.max_lazy ? layout.cadence : layout.max_lazy;
+    if (sizeof(W) == 4) {
+        if (cadence > 15) cadence = 15;  // 15 x 2^60 + a folded residue stays below 2^64
+    } else if (!fast) {
+        cadence = layout.max_lazy;  // the 128-bit accumulator wraps where the reference's does
+    }
+    const bool narrow = sizeof(W) == 8 && fast && layout.narrow_moduli;
+    if (narrow && cadence > kNarrowProductSumCadence) cadence = kNarrowProductSumCadence;
+    shape.cadence = cadence == 0 ? 1 : cadence;
+    if (!fast) {
+        if (queries != 1) return hipErrorInvalidValue;
+        return launch_bsgs<W, 1, false, false>(rot, matrix, out, ctx, shape, 0, stream);
+    }
+#define HEAMD_BSGS_CASE(QN)                                                                                       \
+    case QN:                                                                                                      \
+        return narrow ? launch_bsgs<W, QN, sizeof(W) == 8, true>(rot, matrix, out, ctx, shape, tile_bytes, stream) \
+                      : launch_bsgs<W, QN, false, true>(rot, matrix, out, ctx, shape, tile_bytes, stream)
+    switch (queries) {
+        HEAMD_BSGS_CASE(1);
+        HEAMD_BSGS_CASE(2);
+        HEAMD_BSGS_CASE(3);
+        HEAMD_BSGS_CASE(4);
+        default: return hipErrorInvalidValue;
+    }
+#undef HEAMD_BSGS_CASE
+}
+template hipError_t launch_pnns_bsgs_inner_product<uint64_t>(const uint64_t*, const uint64_t*, uint64_t*, const DeviceContext&,
+                                                             const PnnsBsgsLayout&, unsigned, hipStream_t);
+template hipError_t launch_pnns_bsgs_inner_product<uint32_t>(const uint32_t*, const uint32_t*, uint32_t*, const DeviceContext&,
+                                                             const PnnsBsgsLayout&, unsigned, hipStream_t);
 
 }  // namespace heamd

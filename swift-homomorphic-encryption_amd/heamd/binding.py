@@ -228,6 +228,10 @@ SIGNATURES = [
     ("he_pnns_quantize_rows_device", ctypes.c_int, [vp, c_size, c_size, ctypes.c_float, vp, vp]),
     ("he_pnns_diagonal_matrix_device", ctypes.c_int, [vp, vp, c_size, c_size, c_u32, ctypes.c_int, c_u32, vp, vp, vp]),
     ("he_pnns_diagonal_matrix_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_u32, ctypes.c_int, c_u32, vp, vp, vp]),
+    ("he_pnns_mul_transpose_device", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
+    ("he_pnns_mul_transpose_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
+    ("he_pnns_compute_response_device", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
+    ("he_pnns_compute_response_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
     # diagnostics / test hooks
     ("he_poly_context_create_host_only", ctypes.c_int, [c_u32, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_poly_context_copy_ntt_tables", ctypes.c_int, [vp, c_u32, U64P, U64P, U64P, U64P, U64P, U64P]),
@@ -1584,6 +1588,52 @@ class PnnsContext:
         with torch.cuda.stream(stream) if stream is not None else _no_stream():
             rounded = self.quantize_rows(vectors, scaling_factor, stream=stream)
         return self.diagonal_matrix(rounded, baby_step=baby_step, reduce=reduce, moduli_count=moduli_count, stream=stream)
+
+    def _respond(self, entry, matrix, rows, cols, queries, galois_keys, baby_step, out_moduli, stream):
+        import torch
+
+        word = torch.int32 if self.word32 else torch.int64
+        L, n = self.bfv.L, self.bfv.degree
+        for name, tensor in (("matrix", matrix), ("queries", queries)):
+            if tensor.dtype != word or not tensor.is_cuda or not tensor.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous device tensor of the context's words")
+        if matrix.dim() != 3 or tuple(matrix.shape[1:]) != (L, n):
+            raise ValueError("matrix must be [plaintext_count][L][N]")
+        if queries.dim() != 4 or tuple(queries.shape[1:]) != (2, L, n):
+            raise ValueError("queries must be [Q][2][L][N]")
+        count = queries.shape[0]
+        shape = self.matrix_shape(rows, cols, "diagonal", baby_step or 0)
+        keys = (vp * (2 * count))()
+        if galois_keys is not None:
+            if len(galois_keys) != count:
+                raise ValueError("galois_keys must hold one (key of -1, key of -baby_step) pair per query")
+            for q, pair in enumerate(galois_keys):
+                for k, key in enumerate(pair):
+                    if key is not None:
+                        if key.dtype != word or not key.is_cuda or not key.is_contiguous():
+                            raise ValueError("a Galois key must be a contiguous device tensor of the context's words")
+                        keys[2 * q + k] = key.data_ptr()
+        results = -(-int(rows) // n)
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            out = torch.empty((count, results, 2, out_moduli, n), dtype=word, device=queries.device)
+        name = entry + ("_u32" if self.word32 else "")
+        _check(getattr(load_library(), name)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
+                                             shape["baby_step"], vp(queries.data_ptr()), count,
+                                             keys if galois_keys is not None else None, vp(out.data_ptr()), _stream(stream)))
+        return out
+
+    def mul_transpose(self, matrix, rows, cols, queries, galois_keys, baby_step=None, stream=None):
+        """he_pnns_mul_transpose_device(_u32): PlaintextMatrix.mulTranspose(vector:using:) for Q one-row queries.  matrix
+        [P C][L][N] Eval as diagonal_matrix returns it (baby_step None: the default it was packed with), queries [Q][2][L][N]
+        Coeff, galois_keys a list of Q pairs (key of rotatingColumns(by: -1), key of (by: -baby_step)) of device tensors, an
+        entry None where the shape does not need it -> [Q][ceil(rows / N)][2][L][N] Coeff."""
+        return self._respond("he_pnns_mul_transpose_device", matrix, rows, cols, queries, galois_keys, baby_step, self.bfv.L,
+                             stream)
+
+    def compute_response(self, matrix, rows, cols, queries, galois_keys, baby_step=None, stream=None):
+        """he_pnns_compute_response_device(_u32): Server.computeResponse for Q one-row queries: mul_transpose, then
+        modSwitchDownToSingle -> [Q][ceil(rows / N)][2][1][N] Coeff over q_0."""
+        return self._respond("he_pnns_compute_response_device", matrix, rows, cols, queries, galois_keys, baby_step, 1, stream)
 
 
 def _no_stream():
