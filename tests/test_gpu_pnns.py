@@ -35,9 +35,14 @@ def parameters(oracle, degree, word32=False):
 
 
 class Setup:
-    def __init__(self, oracle, degree, word32=False):
+    def __init__(self, oracle, degree, word32=False, t=None, q=None):
+        """t / q: a plaintext modulus / coefficient moduli other than parameters()'."""
         self.degree, self.word32 = degree, word32
         self.t, self.q = parameters(oracle, degree, word32)
+        if t is not None:
+            self.t = t
+        if q is not None:
+            self.q = list(q)
         if word32:
             self.bfv = heamd.BfvContext32(degree, self.t, self.q)
             self.ref = oracle.BfvContext(degree, self.t, self.q, word_bits=32)
