@@ -686,6 +686,71 @@ int he_pnns_compute_response_device_u32(const he_pnns_context* ctx, const uint32
                                         size_t rows, size_t cols, uint32_t baby_step, const uint32_t* queries,
                                         size_t query_count, const uint32_t* const* galois_keys, uint32_t* out, he_stream s);
 
+/* ---- PNNS server response to query matrices of several rows ---------------------------------------------------------------
+ * PlaintextMatrix.mulTranspose(matrix:using:) (MatrixMultiplication.swift:236-298) for `query_count` clients, each with a
+ * dense-row packed CiphertextMatrix of `query_rows` rows: per row CiphertextMatrix.extractDenseRow (CiphertextMatrix.swift:
+ * 252-370) and mulTranspose(vector:), then the dense-column packing of the per-row results (:267-290).  With N the degree,
+ * P = nextPowerOfTwo(cols), R = query_rows, C = ceil(rows / N), cps = (N / 2) / rows (columnsPerSimdRowCount):
+ *   K = ceil(R / (2 (N / 2) / P))    ciphertexts of a query (PlaintextMatrix.plaintextCount under denseRow)
+ *   M = ceil(R / (2 cps)) when cps > 0, else R C    result ciphertexts of a client, in the order of `innerProducts` (:265, :289)
+ *
+ * he_pnns_query_matrix_shape -- host only: K, M and which keys the shape needs: bit i of *out_pack_needs for slot i < 4 of
+ * galois_keys below, bit 4 for the rotation plan and its keys.  Bits 0 and 1 are those of the default baby step (baby_step is
+ * no argument here); for another one they are as in he_pnns_mul_transpose_device.  Any out pointer may be NULL.
+ * HE_ERR_INVALID_ARGUMENT: cols > N / 2, zero rows, columns or query rows (invalidMatrixDimensions). */
+int he_pnns_query_matrix_shape(const he_pnns_context* ctx, size_t matrix_rows, size_t cols, size_t query_rows,
+                               size_t* out_query_ciphertexts, size_t* out_result_ciphertexts, uint32_t* out_pack_needs);
+/* One step of the plan rotateColumnsMultiStep(by: rows) executes (_HomomorphicEncryptionExtras/HeScheme.swift:21-60):
+ * `count` rotations by `step` columns. */
+typedef struct he_pnns_pack_step {
+    int64_t step;
+    uint32_t count;
+} he_pnns_pack_step;
+/*   matrix .. baby_step     as in he_pnns_mul_transpose_device
+ *   queries                 DEVICE [query_count][K][2][L][N] Coeff, 16-byte aligned: each client's query (denseRowPlaintexts,
+ *                           PlaintextMatrix.swift:341-406)
+ *   pack_steps              HOST [pack_step_count], in application order: the plan of rotateColumnsMultiStep(by: rows).  The
+ *                           reference iterates a Swift Dictionary, so its order -- and with it every word of the result -- is
+ *                           the caller's to know.  The single pair {rows, 1} when the key holds rotatingColumns(by: rows).
+ *                           HE_ERR_INVALID_ARGUMENT when the steps do not sum to rows mod N / 2 or one is outside
+ *                           [1, N / 2 - 1].  Read only when cps >= 2 and R >= 2
+ *   galois_keys             HOST [query_count][4 + pack_step_count] device pointers per client: [0] rotatingColumns(by: -1),
+ *                           [1] (by: -baby_step), [2] swappingRows, [3] rotatingColumns(by: P), [4 + i] the key of
+ *                           pack_steps[i].step.  Needed: [0] and [1] as in he_pnns_mul_transpose_device; [2] when R > 1
+ *                           (extractDenseRow) or cps > 0 and R > cps (swapRowsAndAdd); [3] when R > 1 and some row's
+ *                           rotateCount > 0; the plan's when cps >= 2 and R >= 2.  A needed key that is NULL is
+ *                           HE_ERR_MISSING_GALOIS_KEY; one that is not needed is not read
+ *   out                     DEVICE [query_count][M][2][L][N] Coeff
+ * The order of operations is the reference's and every word equals its; only independent items share a launch.  The masks
+ * depend on (N, cols, R) alone and are built once per call; every query ciphertext goes to Eval once and is read once for all
+ * the rows packed in it; a step of the replication (:347-353) is one key switch over every (client, row) that still rotates;
+ * the rows of all clients share the passes over the matrix four at a time; a step of the packing sums (HeScheme.swift:113-133)
+ * is one key switch over every half-chunk of every client that has an element left.  With R = 1 every word is
+ * he_pnns_mul_transpose_device's.  Enqueue-only on `s`, scratch from the stream-ordered cache; argument errors in the order
+ * above, before anything is enqueued; query_count 0 is HE_OK; a host-only context: HE_ERR_DEVICE. */
+int he_pnns_mul_transpose_matrix_device(const he_pnns_context* ctx, const uint64_t* matrix, size_t matrix_plaintext_count,
+                                        size_t rows, size_t cols, uint32_t baby_step, const uint64_t* queries,
+                                        size_t query_rows, size_t query_count, const he_pnns_pack_step* pack_steps,
+                                        size_t pack_step_count, const uint64_t* const* galois_keys, uint64_t* out, he_stream s);
+/* The same on packed 4-byte words; a rotation step is one Galois call per client, as in he_pnns_mul_transpose_device_u32. */
+int he_pnns_mul_transpose_matrix_device_u32(const he_pnns_context* ctx, const uint32_t* matrix, size_t matrix_plaintext_count,
+                                            size_t rows, size_t cols, uint32_t baby_step, const uint32_t* queries,
+                                            size_t query_rows, size_t query_count, const he_pnns_pack_step* pack_steps,
+                                            size_t pack_step_count, const uint32_t* const* galois_keys, uint32_t* out,
+                                            he_stream s);
+/* Server.computeResponse (Server.swift:61-88) for such queries: the same, then modSwitchDownToSingle over the M results of
+ * every client.  out DEVICE [query_count][M][2][1][N] Coeff over q_0. */
+int he_pnns_compute_response_matrix_device(const he_pnns_context* ctx, const uint64_t* matrix, size_t matrix_plaintext_count,
+                                           size_t rows, size_t cols, uint32_t baby_step, const uint64_t* queries,
+                                           size_t query_rows, size_t query_count, const he_pnns_pack_step* pack_steps,
+                                           size_t pack_step_count, const uint64_t* const* galois_keys, uint64_t* out,
+                                           he_stream s);
+int he_pnns_compute_response_matrix_device_u32(const he_pnns_context* ctx, const uint32_t* matrix,
+                                               size_t matrix_plaintext_count, size_t rows, size_t cols, uint32_t baby_step,
+                                               const uint32_t* queries, size_t query_rows, size_t query_count,
+                                               const he_pnns_pack_step* pack_steps, size_t pack_step_count,
+                                               const uint32_t* const* galois_keys, uint32_t* out, he_stream s);
+
 /* ---- SimplePirServer (PrivateInformationRetrieval/SimplePir/) ------------------------------------------------------------
  * The other index-PIR server: a database matrix of plaintext_bits-wide elements, a hint for the clients, and replies that
  * are one wrap-around integer matrix product.  word_bits is the reference's Scalar: 64 (entries without suffix) or 32

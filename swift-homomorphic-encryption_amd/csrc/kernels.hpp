@@ -310,4 +310,28 @@ template <typename W>
 hipError_t launch_pnns_bsgs_inner_product(const W* rot, const W* matrix, W* out, const DeviceContext& ctx,
                                           const PnnsBsgsLayout& layout, unsigned queries, hipStream_t stream);
 
+// ---- pnns_kernels.hip: CiphertextMatrix.extractDenseRow (CiphertextMatrix.swift:252-370) for query matrices of several rows --
+// The mask of a row on the SIMD slots: 1 on slot i iff lower <= i < min(N, lower + copies * period) and
+// (i - lower) mod period < padded_cols (period a power of two).
+struct PnnsRowMask {
+    uint32_t lower, period, copies;
+};
+// The masks as the slabs encodeSimd hands to inverseNtt: staging [count][N] words (0 or 1), every word written.  The patterns
+// travel in the kernel arguments, kPnnsRowsPerLaunch rows to a launch.
+constexpr unsigned kPnnsRowsPerLaunch = 32;
+template <typename W>
+hipError_t launch_pnns_row_masks(const uint32_t* slot_of_word, const PnnsRowMask* rows, size_t count, uint32_t padded_cols,
+                                 uint32_t log_degree, W* staging, hipStream_t stream);
+// ciphertextEval *= plaintextMask (:340-341) for the `count` rows packed in query ciphertext `ciphertext` of every client:
+//   queries  [clients][query_ciphertexts][2][L][N] Eval        masks  [..][L][N] Eval, row first_row + i for the i-th row
+//   out      ciphertext positions[i] * row_stride + client * client_stride is (client, i-th row), Eval
+// Each 16 bytes of a query ciphertext are read once for all its rows.  All three 16-byte aligned.
+struct PnnsExtractLayout {
+    size_t clients, query_ciphertexts, row_stride, client_stride;
+};
+template <typename W>
+hipError_t launch_pnns_extract_rows(const W* queries, const W* masks, W* out, const DeviceContext& ctx,
+                                    const PnnsExtractLayout& layout, uint32_t ciphertext, uint32_t first_row,
+                                    const uint32_t* positions, size_t count, hipStream_t stream);
+
 }  // namespace heamd

@@ -11,6 +11,11 @@
 // vector:using:) (MatrixMultiplication.swift:131-226) over Q independent queries, then modSwitchDownToSingle.  Rotations, the
 // transforms, additions and the mod-switch are the library's own entry points, batched over the queries; the one kernel of its
 // own is the pass over the matrix (pnns_kernels.hip, pnns_bsgs_inner_product_kernel).
+//
+// And PlaintextMatrix.mulTranspose(matrix:using:) (MatrixMultiplication.swift:236-298) for query matrices of several rows:
+// CiphertextMatrix.extractDenseRow per row (masks and masked products: pnns_row_mask_kernel, pnns_extract_rows_kernel), the
+// product above over all rows of all clients, and the dense-column packing of the per-row results.
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <memory>
@@ -303,41 +308,20 @@ size_t response_group(size_t result_count, size_t queries, size_t giant_step, si
     return group ? group : 1;
 }
 
+// mulTranspose(vector:using:) (MatrixMultiplication.swift:131-226) for `vectors` one-row vectors already on the device:
+// `groups` runs of `group_size` consecutive vectors, run g under the keys keys[g * key_stride] (rotatingColumns(by: -1)) and
+// keys[g * key_stride + 1] ((by: -babyStep)).  Everything has been validated.  out [vectors][C][2][L][N], or [..][2][1][N]
+// through modSwitchDownToSingle.
 template <typename Ops>
-int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, size_t matrix_plaintext_count, size_t rows,
-                  size_t cols, uint32_t baby_step, const typename Ops::Word* queries, size_t query_count,
-                  const typename Ops::Word* const* galois_keys, typename Ops::Word* out, bool to_single, he_stream s) {
+int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typename Ops::Word* matrix,
+                 const typename Ops::Word* queries, const typename Ops::Word* const* galois_keys, size_t key_stride,
+                 size_t groups, size_t group_size, typename Ops::Word* out, bool to_single, he_stream s) {
     using W = typename Ops::Word;
-    if (ctx == nullptr) return invalid_argument("null context");
-    if (baby_step == 0) return invalid_argument("baby_step must be the one the matrix was packed with");
-    MatrixPlan plan;
-    const int planned = matrix_plan(ctx, rows, cols, HE_PNNS_PACKING_DIAGONAL, baby_step, plan);
-    if (planned != HE_OK) return planned;
-    if (matrix_plaintext_count != plan.plaintext_count)  // PnnsError.invalidMatrixDimensions, MatrixMultiplication.swift:147-149
-        return invalid_argument("the matrix does not hold nextPowerOfTwo(cols) x ceil(rows / N) plaintexts");
     const heamd::BfvContext& bfv = heamd::bfv_impl(ctx->bfv);
-    if (bfv.word_bits() != 8 * sizeof(W)) return invalid_argument("context of the other word size");
-    if (query_count == 0) return HE_OK;
     const uint32_t b = plan.baby_step, G = plan.giant_step, L = bfv.top_level();
-    const size_t n = bfv.degree(), C = plan.plaintexts_per_column, Q = query_count;
-    if (C > (size_t(1) << 24) || Q > (size_t(1) << 16)) return invalid_argument("too many result ciphertexts or queries");
-    // rotatingColumns(by: -1) for the baby steps, (by: -babyStep) for the sum (MatrixMultiplication.swift:185,221-224)
+    const size_t n = bfv.degree(), C = plan.plaintexts_per_column, Q = groups * group_size;
     const bool need_one = b > 1, need_baby = G > 1;
-    if (need_one || need_baby) {
-        bool missing = galois_keys == nullptr || !bfv.has_key_switching();
-        for (size_t q = 0; !missing && q < Q; ++q)
-            missing = (need_one && galois_keys[2 * q] == nullptr) || (need_baby && galois_keys[2 * q + 1] == nullptr);
-        if (missing) {
-            heamd::set_last_error("no Galois key for a rotation mulTranspose needs");
-            return HE_ERR_MISSING_GALOIS_KEY;
-        }
-    }
-    if (matrix == nullptr || queries == nullptr || out == nullptr) return invalid_argument("null buffer");
-    if (reinterpret_cast<uintptr_t>(matrix) % 16 != 0) return invalid_argument("the matrix must be 16-byte aligned");
-    if (n < 16 / sizeof(W)) return invalid_argument("degree below one 16-byte access");
     const heamd::PolyContext* q_ctx = bfv.ciphertext(L);
-    const int on_device = q_ctx->check_device();
-    if (on_device != HE_OK) return on_device;
     const he_poly_context* ring = he_bfv_ciphertext_context(ctx->bfv, L);
     hipStream_t stream = as_stream(s);
     const size_t poly = size_t(L) * n, ct = 2 * poly, ct_bytes = ct * sizeof(W);
@@ -352,8 +336,8 @@ int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, 
     W* rot = static_cast<W*>(rot_mem.get());
     HEAMD_HIP_TRY(hipMemcpyAsync(rot, queries, Q * ct_bytes, hipMemcpyDeviceToDevice, stream));
     for (uint32_t j = 1; j < b; ++j)
-        HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, rot + size_t(j - 1) * Q * ct, element_one, galois_keys, 2, Q, 1,
-                                     rot + size_t(j) * Q * ct, s));
+        HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, rot + size_t(j - 1) * Q * ct, element_one, galois_keys, key_stride, groups,
+                                     group_size, rot + size_t(j) * Q * ct, s));
     HEAMD_TRY_STATUS(Ops::forward_ntt(ring, rot, size_t(b) * Q * 2, s));
 
     heamd::PnnsBsgsLayout layout{};
@@ -404,7 +388,8 @@ int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, 
         W* current = products + size_t(G - 1) * Q * now * ct;
         W* other = sums;
         for (uint32_t g = G - 1; g-- > 0;) {
-            HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, current, element_baby, galois_keys + 1, 2, Q, now, other, s));
+            HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, current, element_baby, galois_keys + 1, key_stride, groups, group_size * now,
+                                         other, s));
             HEAMD_TRY_STATUS(Ops::add(ring, other, products + size_t(g) * Q * now * ct, Q * now * 2, s));
             current = other;
             other = current == sums ? sums + Q * now * ct : sums;
@@ -420,6 +405,442 @@ int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, 
             HEAMD_HIP_TRY(hipMemcpy2DAsync(out + first * out_ct, C * out_ct * sizeof(W), current, now * out_ct * sizeof(W),
                                            now * out_ct * sizeof(W), Q, hipMemcpyDeviceToDevice, stream));
         }
+    }
+    return HE_OK;
+}
+
+// the argument checks the one-row and the several-rows entries share, in the documented order, up to the word size
+template <typename W>
+int response_plan(const he_pnns_context* ctx, size_t matrix_plaintext_count, size_t rows, size_t cols, uint32_t baby_step,
+                  MatrixPlan& plan) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    if (baby_step == 0) return invalid_argument("baby_step must be the one the matrix was packed with");
+    const int planned = matrix_plan(ctx, rows, cols, HE_PNNS_PACKING_DIAGONAL, baby_step, plan);
+    if (planned != HE_OK) return planned;
+    if (matrix_plaintext_count != plan.plaintext_count)  // PnnsError.invalidMatrixDimensions, MatrixMultiplication.swift:147-149
+        return invalid_argument("the matrix does not hold nextPowerOfTwo(cols) x ceil(rows / N) plaintexts");
+    if (heamd::bfv_impl(ctx->bfv).word_bits() != 8 * sizeof(W)) return invalid_argument("context of the other word size");
+    return HE_OK;
+}
+
+template <typename W>
+int response_buffers(const he_pnns_context* ctx, const W* matrix, const W* queries, const W* out) {
+    if (matrix == nullptr || queries == nullptr || out == nullptr) return invalid_argument("null buffer");
+    if (reinterpret_cast<uintptr_t>(matrix) % 16 != 0) return invalid_argument("the matrix must be 16-byte aligned");
+    const heamd::BfvContext& bfv = heamd::bfv_impl(ctx->bfv);
+    if (bfv.degree() < 16 / sizeof(W)) return invalid_argument("degree below one 16-byte access");
+    return bfv.ciphertext(bfv.top_level())->check_device();
+}
+
+template <typename Ops>
+int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, size_t matrix_plaintext_count, size_t rows,
+                  size_t cols, uint32_t baby_step, const typename Ops::Word* queries, size_t query_count,
+                  const typename Ops::Word* const* galois_keys, typename Ops::Word* out, bool to_single, he_stream s) {
+    using W = typename Ops::Word;
+    MatrixPlan plan;
+    HEAMD_TRY_STATUS(response_plan<W>(ctx, matrix_plaintext_count, rows, cols, baby_step, plan));
+    if (query_count == 0) return HE_OK;
+    const heamd::BfvContext& bfv = heamd::bfv_impl(ctx->bfv);
+    const size_t C = plan.plaintexts_per_column, Q = query_count;
+    if (C > (size_t(1) << 24) || Q > (size_t(1) << 16)) return invalid_argument("too many result ciphertexts or queries");
+    // rotatingColumns(by: -1) for the baby steps, (by: -babyStep) for the sum (MatrixMultiplication.swift:185,221-224)
+    const bool need_one = plan.baby_step > 1, need_baby = plan.giant_step > 1;
+    if (need_one || need_baby) {
+        bool missing = galois_keys == nullptr || !bfv.has_key_switching();
+        for (size_t q = 0; !missing && q < Q; ++q)
+            missing = (need_one && galois_keys[2 * q] == nullptr) || (need_baby && galois_keys[2 * q + 1] == nullptr);
+        if (missing) {
+            heamd::set_last_error("no Galois key for a rotation mulTranspose needs");
+            return HE_ERR_MISSING_GALOIS_KEY;
+        }
+    }
+    HEAMD_TRY_STATUS(response_buffers<W>(ctx, matrix, queries, out));
+    return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, 2, Q, 1, out, to_single, s);
+}
+
+// ---- mulTranspose(matrix:using:): query matrices of several rows ------------------------------------------------------------
+// What extractDenseRow (CiphertextMatrix.swift:252-370) does to row `r` of an R-row dense-row packed query: the mask is 1 on
+// slot i iff lower <= i < min(N, lower + copies period) and (i - lower) mod period < P; then `rotate_count` times "rotate the
+// running copy by P and add it", then the row swap.
+struct QueryRow {
+    uint32_t lower, period, copies, rotate_count;
+};
+enum : uint32_t {  // he_pnns_query_matrix_shape's out_pack_needs: the slots of galois_keys, and the pack plan
+    kNeedsOne = 1u << 0, kNeedsBaby = 1u << 1, kNeedsSwap = 1u << 2, kNeedsReplicate = 1u << 3, kNeedsPack = 1u << 4
+};
+struct QueryPlan {
+    size_t padded_cols = 0, rows_per_ciphertext = 0, query_ciphertexts = 0, columns_per_simd_row = 0, result_ciphertexts = 0;
+    uint32_t needs = 0;
+    std::vector<QueryRow> rows;  // empty for a one-row query: extractDenseRow returns the ciphertext itself (:268-270)
+};
+
+// simdSlotIndices and rowCountInBatch restated line for line (:281-318), then reduced to the mask rule.  The closure reads the
+// ciphertext index of the row being extracted, also where it is asked about another row, and the backward scan starts at
+// rowIndex - 1: both are kept.
+QueryRow query_row(size_t n, size_t padded_cols, size_t row_count, size_t row_index, size_t ciphertext_count) {
+    const size_t simd_columns = n / 2;
+    const size_t rows_per_ciphertext = 2 * (simd_columns / padded_cols);
+    const size_t ciphertext_index = row_index / rows_per_ciphertext;
+    auto slot_indices = [&](size_t index, size_t& lower, size_t& upper) {
+        const size_t batch_start = (index % rows_per_ciphertext) * padded_cols;
+        lower = batch_start;
+        upper = batch_start + padded_cols;
+        if (lower <= simd_columns && simd_columns < upper) {  // overflowsSimdRow
+            lower = simd_columns;
+            upper = simd_columns + padded_cols;
+        } else if (upper > simd_columns) {
+            const size_t padding = simd_columns % padded_cols;
+            lower += padding;
+            upper += padding;
+        }
+        if (ciphertext_index == ciphertext_count - 1)  // the last ciphertext pads until the end of the ciphertext
+            upper = dividing_ceil(upper, simd_columns) * simd_columns;
+    };
+    size_t lower = 0, upper = 0, other_lower = 0, other_upper = 0;
+    slot_indices(row_index, lower, upper);
+    size_t last = row_index + 1;
+    while (last < row_count && (slot_indices(last, other_lower, other_upper), other_upper == upper)) ++last;
+    size_t first = row_index > 0 ? row_index - 1 : 0;
+    while (first > 0 && (slot_indices(first, other_lower, other_upper), other_upper == upper)) --first;
+    const size_t rows_in_batch = last - first;
+    QueryRow row{};
+    row.lower = static_cast<uint32_t>(lower);
+    row.period = static_cast<uint32_t>(next_power_of_two(padded_cols * rows_in_batch));
+    row.copies = static_cast<uint32_t>(dividing_ceil(upper - lower, row.period));  // while mask.count < upperBound: append
+    row.rotate_count = static_cast<uint32_t>(simd_columns / (size_t(row.copies) * padded_cols) - 1);
+    return row;
+}
+
+int query_plan(const he_pnns_context* ctx, size_t matrix_rows, size_t cols, size_t query_rows, uint32_t baby_step,
+               uint32_t giant_step, QueryPlan& plan) {
+    if (query_rows == 0) return invalid_argument("the query matrix has no rows");  // MatrixDimensions.init
+    if (query_rows > (size_t(1) << 16)) return invalid_argument("too many query rows");
+    const size_t n = ctx->plaintext->degree(), simd_columns = n / 2;
+    plan = QueryPlan{};
+    plan.padded_cols = next_power_of_two(cols);
+    plan.rows_per_ciphertext = 2 * (simd_columns / plan.padded_cols);
+    plan.query_ciphertexts = dividing_ceil(query_rows, plan.rows_per_ciphertext);
+    plan.columns_per_simd_row = simd_columns / matrix_rows;
+    plan.result_ciphertexts = plan.columns_per_simd_row > 0 ? dividing_ceil(query_rows, 2 * plan.columns_per_simd_row)
+                                                            : query_rows * dividing_ceil(matrix_rows, n);
+    bool replicate = false;
+    if (query_rows > 1) {
+        plan.rows.resize(query_rows);
+        for (size_t r = 0; r < query_rows; ++r) {
+            plan.rows[r] = query_row(n, plan.padded_cols, query_rows, r, plan.query_ciphertexts);
+            replicate = replicate || plan.rows[r].rotate_count > 0;
+        }
+    }
+    const size_t cps = plan.columns_per_simd_row;
+    plan.needs = (baby_step > 1 ? kNeedsOne : 0u) | (giant_step > 1 ? kNeedsBaby : 0u) |
+                 (query_rows > 1 || (cps > 0 && query_rows > cps) ? kNeedsSwap : 0u) | (replicate ? kNeedsReplicate : 0u) |
+                 (cps >= 2 && query_rows >= 2 ? kNeedsPack : 0u);
+    return HE_OK;
+}
+
+// Ciphertexts of (position, client): the rows of the clients' queries, later the half-chunks of their results.  A Galois call
+// of 8-byte words takes a key per ciphertext, so there positions are the outer index and a prefix of positions over all clients
+// is one contiguous batch; the 4-byte call takes one key, so there a client's positions are contiguous and a step is one call per
+// client.
+template <typename Ops>
+struct Grid {
+    using W = typename Ops::Word;
+    static constexpr bool kClientMajor = sizeof(W) == 4;
+    const he_pnns_context* ctx;
+    size_t positions, clients, ct;  // ct: words of a ciphertext
+    uint32_t L;
+    const W* const* keys;           // [clients][key_stride]
+    size_t key_stride;
+    const std::vector<const W*>* tiled;  // 8-byte words: [slot][position-major over clients], as many positions as any grid has
+    size_t tiled_stride;
+    he_stream s;
+
+    size_t index(size_t position, size_t client) const {
+        return kClientMajor ? client * positions + position : position * clients + client;
+    }
+    // positions [0, count) of every client: out = in under the Galois element, with the clients' keys of `slot`
+    int rotate(const W* in, W* out, uint64_t element, size_t slot, size_t first, size_t count) const {
+        if (count == 0) return HE_OK;
+        if constexpr (!kClientMajor) {
+            return Ops::rotate(ctx->bfv, L, in + first * clients * ct, element, tiled->data() + slot * tiled_stride, 1,
+                               count * clients, 1, out + first * clients * ct, s);
+        } else {
+            for (size_t q = 0; q < clients; ++q)
+                HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, in + index(first, q) * ct, element, keys + q * key_stride + slot,
+                                             key_stride, 1, count, out + index(first, q) * ct, s));
+            return HE_OK;
+        }
+    }
+    // lhs positions [first, first + count) += rhs positions [rhs_first, ..) of a grid of `rhs_positions` positions
+    int add(const he_poly_context* ring, W* lhs, size_t first, const W* rhs, size_t rhs_positions, size_t rhs_first,
+            size_t count) const {
+        if (count == 0) return HE_OK;
+        if constexpr (!kClientMajor) {
+            return Ops::add(ring, lhs + first * clients * ct, rhs + rhs_first * clients * ct, count * clients * 2, s);
+        } else {
+            for (size_t q = 0; q < clients; ++q)
+                HEAMD_TRY_STATUS(Ops::add(ring, lhs + index(first, q) * ct, rhs + (q * rhs_positions + rhs_first) * ct,
+                                          count * 2, s));
+            return HE_OK;
+        }
+    }
+    // dst positions [first, first + count) = src positions [src_first, ..) of a grid of `src_positions` positions
+    hipError_t copy(W* dst, size_t first, const W* src, size_t src_positions, size_t src_first, size_t count) const {
+        if (count == 0) return hipSuccess;
+        hipStream_t stream = as_stream(s);
+        if constexpr (!kClientMajor) {
+            return hipMemcpyAsync(dst + first * clients * ct, src + src_first * clients * ct, count * clients * ct * sizeof(W),
+                                  hipMemcpyDeviceToDevice, stream);
+        } else {
+            return hipMemcpy2DAsync(dst + first * ct, positions * ct * sizeof(W), src + src_first * ct,
+                                    src_positions * ct * sizeof(W), count * ct * sizeof(W), clients, hipMemcpyDeviceToDevice,
+                                    stream);
+        }
+    }
+};
+
+// src: `unit` words per (position, client) in the layout of Grid<Ops> with `positions` positions; position `from` of every
+// client goes to dst [clients][dst_positions][unit] at `to`
+template <typename Ops>
+hipError_t to_client_major(typename Ops::Word* dst, size_t dst_positions, size_t to, const typename Ops::Word* src,
+                           size_t positions, size_t from, size_t clients, size_t unit, hipStream_t stream) {
+    using W = typename Ops::Word;
+    const size_t src_index = Grid<Ops>::kClientMajor ? from : from * clients;
+    const size_t src_pitch = Grid<Ops>::kClientMajor ? positions * unit : unit;
+    return hipMemcpy2DAsync(dst + to * unit, dst_positions * unit * sizeof(W), src + src_index * unit, src_pitch * sizeof(W),
+                            unit * sizeof(W), clients, hipMemcpyDeviceToDevice, stream);
+}
+
+template <typename Ops>
+int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* matrix, size_t matrix_plaintext_count,
+                         size_t rows, size_t cols, uint32_t baby_step, const typename Ops::Word* queries, size_t query_rows,
+                         size_t query_count, const he_pnns_pack_step* pack_steps, size_t pack_step_count,
+                         const typename Ops::Word* const* galois_keys, typename Ops::Word* out, bool to_single, he_stream s) {
+    using W = typename Ops::Word;
+    MatrixPlan plan;
+    HEAMD_TRY_STATUS(response_plan<W>(ctx, matrix_plaintext_count, rows, cols, baby_step, plan));
+    QueryPlan query;
+    HEAMD_TRY_STATUS(query_plan(ctx, rows, cols, query_rows, plan.baby_step, plan.giant_step, query));
+    if (query_count == 0) return HE_OK;
+    const heamd::BfvContext& bfv = heamd::bfv_impl(ctx->bfv);
+    const size_t n = bfv.degree(), C = plan.plaintexts_per_column, Q = query_count, R = query_rows, V = Q * R;
+    const size_t P = plan.padded_cols, K = query.query_ciphertexts, cps = query.columns_per_simd_row;
+    const size_t M = query.result_ciphertexts;
+    const uint32_t L = bfv.top_level();
+    if (C > (size_t(1) << 24) || V > (size_t(1) << 16)) return invalid_argument("too many result ciphertexts or query rows");
+    // the plan rotateColumnsMultiStep(by: rows) executes, in the caller's order
+    const bool packs = (query.needs & kNeedsPack) != 0;
+    const size_t key_stride = 4 + pack_step_count;  // the caller's array, whether or not the plan is read
+    if (!packs) pack_step_count = 0;
+    if (packs) {
+        if (pack_steps == nullptr || pack_step_count == 0) return invalid_argument("the packing needs a rotation plan");
+        if (pack_step_count > 64) return invalid_argument("rotation plan too long");
+        uint64_t total = 0;
+        for (size_t i = 0; i < pack_step_count; ++i) {
+            if (pack_steps[i].step < 1 || pack_steps[i].step > static_cast<int64_t>(n / 2) - 1)
+                return invalid_argument("a step of the rotation plan is outside [1, N / 2 - 1]");
+            total = (total + static_cast<uint64_t>(pack_steps[i].step) * pack_steps[i].count) % (n / 2);
+        }
+        if (total != rows % (n / 2)) return invalid_argument("the rotation plan does not rotate by the matrix's row count");
+    }
+    {
+        bool missing = false;
+        if (query.needs != 0) {
+            missing = galois_keys == nullptr || !bfv.has_key_switching();
+            for (size_t q = 0; !missing && q < Q; ++q) {
+                for (size_t slot = 0; slot < 4; ++slot)
+                    missing = missing || ((query.needs >> slot) & 1u && galois_keys[q * key_stride + slot] == nullptr);
+                for (size_t i = 0; i < pack_step_count; ++i)
+                    missing = missing || (pack_steps[i].count != 0 && galois_keys[q * key_stride + 4 + i] == nullptr);
+            }
+        }
+        if (missing) {
+            heamd::set_last_error("no Galois key for a rotation mulTranspose(matrix:) needs");
+            return HE_ERR_MISSING_GALOIS_KEY;
+        }
+    }
+    HEAMD_TRY_STATUS(response_buffers<W>(ctx, matrix, queries, out));
+    if (R == 1)  // one row: the vector's own ciphertext, and rotateColumnsAndSum of one element
+        return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, key_stride, Q, 1, out, to_single, s);
+    if (reinterpret_cast<uintptr_t>(queries) % 16 != 0) return invalid_argument("the queries must be 16-byte aligned");
+    HEAMD_TRY_STATUS(ctx->plaintext->check_device());
+    const heamd::PolyContext* q_ctx = bfv.ciphertext(L);
+    const he_poly_context* ring = he_bfv_ciphertext_context(ctx->bfv, L);
+    hipStream_t stream = as_stream(s);
+    const size_t poly = size_t(L) * n, ct = 2 * poly, ct_bytes = ct * sizeof(W);
+
+    // the rows in the order of their replication steps, longest first: the rows of step i are a prefix
+    std::vector<uint32_t> row_of(R), position_of(R);
+    for (size_t r = 0; r < R; ++r) row_of[r] = static_cast<uint32_t>(r);
+    std::stable_sort(row_of.begin(), row_of.end(), [&](uint32_t a, uint32_t b) {
+            return query.rows[a].rotate_count > query.rows[b].rotate_count;
+        });
+    for (size_t k = 0; k < R; ++k) position_of[row_of[k]] = static_cast<uint32_t>(k);
+    const size_t halves = cps > 0 ? dividing_ceil(R, cps) : 0;
+    const size_t most_positions = R > halves ? R : halves;
+    std::vector<const W*> tiled;  // [slot][position][client]: the key of `slot` for every ciphertext of a batch
+    if (!Grid<Ops>::kClientMajor && galois_keys != nullptr) {
+        tiled.resize(key_stride * most_positions * Q);
+        for (size_t slot = 0; slot < key_stride; ++slot)
+            for (size_t v = 0; v < most_positions * Q; ++v)
+                tiled[slot * most_positions * Q + v] = galois_keys[(v % Q) * key_stride + slot];
+    }
+    Grid<Ops> grid{ctx, R, Q, ct, L, galois_keys, key_stride, &tiled, most_positions * Q, s};
+
+    Scratch rows_mem(stream);
+    HEAMD_HIP_TRY(rows_mem.allocate(V * ct_bytes));
+    W* extracted = static_cast<W*>(rows_mem.get());  // the grid of extracted rows
+    {
+        // 1) the masks (:323-338), once for all clients: slot patterns into the [t] slabs, inverse NTT, to Eval at the top level
+        Scratch staging_mem(stream), masks_mem(stream), eval_mem(stream), copies_mem(stream);
+        HEAMD_HIP_TRY(staging_mem.allocate(R * n * sizeof(W)));
+        HEAMD_HIP_TRY(masks_mem.allocate(R * poly * sizeof(W)));
+        W* staging = static_cast<W*>(staging_mem.get());
+        W* masks = static_cast<W*>(masks_mem.get());
+        std::vector<heamd::PnnsRowMask> patterns(R);
+        for (size_t r = 0; r < R; ++r) patterns[r] = heamd::PnnsRowMask{query.rows[r].lower, query.rows[r].period, query.rows[r].copies};
+        HEAMD_HIP_TRY(heamd::launch_pnns_row_masks<W>(ctx->slot_of_word_device, patterns.data(), R, static_cast<uint32_t>(P),
+                                                       ctx->plaintext->log_degree(), staging, stream));
+        HEAMD_TRY_STATUS(inverse_ntt(*ctx->plaintext, staging, R, stream));
+        HEAMD_TRY_STATUS(to_eval(ctx->bfv, L, staging, masks, R, s));
+        // 2) every query ciphertext to Eval once; each is read once for all the rows packed in it (:340-342)
+        HEAMD_HIP_TRY(eval_mem.allocate(Q * K * ct_bytes));
+        W* eval = static_cast<W*>(eval_mem.get());
+        HEAMD_HIP_TRY(hipMemcpyAsync(eval, queries, Q * K * ct_bytes, hipMemcpyDeviceToDevice, stream));
+        HEAMD_TRY_STATUS(Ops::forward_ntt(ring, eval, Q * K * 2, s));
+        heamd::PnnsExtractLayout layout{};
+        layout.clients = Q;
+        layout.query_ciphertexts = K;
+        layout.row_stride = Grid<Ops>::kClientMajor ? 1 : Q;
+        layout.client_stride = Grid<Ops>::kClientMajor ? R : 1;
+        const heamd::DeviceContext dc = q_ctx->device_context(L);
+        for (size_t k = 0; k < K; ++k) {
+            const size_t first = k * query.rows_per_ciphertext;
+            const size_t count = R - first < query.rows_per_ciphertext ? R - first : query.rows_per_ciphertext;
+            HEAMD_HIP_TRY(heamd::launch_pnns_extract_rows<W>(eval, masks, extracted, dc, layout, static_cast<uint32_t>(k),
+                                                              static_cast<uint32_t>(first), position_of.data() + first, count,
+                                                              stream));
+        }
+        HEAMD_TRY_STATUS(Ops::inverse_ntt(ring, extracted, V * 2, s));
+        // 3) replication over a SIMD row (:347-353), then both SIMD rows (:358-361)
+        HEAMD_HIP_TRY(copies_mem.allocate(2 * V * ct_bytes));
+        W* ahead = static_cast<W*>(copies_mem.get());
+        W* behind = ahead + V * ct;
+        const uint32_t most = query.rows[row_of[0]].rotate_count;
+        uint64_t element_columns = 0, element_swap = 0;
+        if (most > 0) HEAMD_TRY_STATUS(he_galois_element_rotating_columns(static_cast<int64_t>(P), n, &element_columns));
+        HEAMD_TRY_STATUS(he_galois_element_swapping_rows(n, &element_swap));
+        const W* running = extracted;
+        size_t live = R;
+        for (uint32_t step = 0; step < most; ++step) {
+            while (query.rows[row_of[live - 1]].rotate_count <= step) --live;
+            HEAMD_TRY_STATUS(grid.rotate(running, ahead, element_columns, 3, 0, live));
+            HEAMD_TRY_STATUS(grid.add(ring, extracted, 0, ahead, R, 0, live));
+            running = ahead;
+            std::swap(ahead, behind);
+        }
+        HEAMD_TRY_STATUS(grid.rotate(extracted, ahead, element_swap, 2, 0, R));
+        HEAMD_TRY_STATUS(grid.add(ring, extracted, 0, ahead, R, 0, R));
+    }
+
+    // 4) mulTranspose(vector:) of every row: the rows share the passes over the matrix
+    std::vector<const W*> pairs;
+    if (!Grid<Ops>::kClientMajor && galois_keys != nullptr) {
+        pairs.resize(2 * V);
+        for (size_t v = 0; v < V; ++v) {
+            pairs[2 * v] = galois_keys[(v % Q) * key_stride];
+            pairs[2 * v + 1] = galois_keys[(v % Q) * key_stride + 1];
+        }
+    }
+    Scratch results_mem(stream), single_mem(stream), levels_mem(stream);
+    HEAMD_HIP_TRY(results_mem.allocate(V * C * ct_bytes));
+    W* results = static_cast<W*>(results_mem.get());  // the grid of [C] results
+    if (Grid<Ops>::kClientMajor) {
+        HEAMD_TRY_STATUS(bsgs_product<Ops>(ctx, plan, matrix, extracted, galois_keys, key_stride, Q, R, results, false, s));
+    } else {
+        HEAMD_TRY_STATUS(bsgs_product<Ops>(ctx, plan, matrix, extracted, galois_keys != nullptr ? pairs.data() : nullptr, 2, V, 1,
+                                           results, false, s));
+    }
+    const size_t out_ct = to_single ? 2 * n : ct;
+    auto allocate_levels = [&](size_t batch) -> hipError_t {
+        const size_t words = to_single ? Ops::to_single_scratch_words(L, batch, n) : 0;
+        return words != 0 ? levels_mem.allocate(words * sizeof(W)) : hipSuccess;
+    };
+    if (cps == 0) {  // no packing: innerProducts is every row's C results, in row order (:265)
+        const W* source = results;
+        if (to_single) {
+            HEAMD_HIP_TRY(single_mem.allocate(V * C * out_ct * sizeof(W)));
+            HEAMD_HIP_TRY(allocate_levels(V * C));
+            HEAMD_TRY_STATUS(Ops::to_single(ctx->bfv, L, results, static_cast<W*>(single_mem.get()), V * C,
+                                            static_cast<W*>(levels_mem.get()), s));
+            source = static_cast<const W*>(single_mem.get());
+        }
+        for (size_t r = 0; r < R; ++r)
+            HEAMD_HIP_TRY(to_client_major<Ops>(out, R, r, source, R, position_of[r], Q, C * out_ct, stream));
+        return HE_OK;
+    }
+
+    // 5) the dense-column packing (:267-290), C = 1.  Half-chunk j holds the results of rows [j cps, (j + 1) cps); the halves of
+    //    the last one's parity lie behind the others, so the one half that may be short is the last position, and the second
+    //    halves of the chunks are one run.
+    const size_t last_parity = (halves - 1) & 1, before = last_parity == 1 ? (halves + 1) / 2 : halves / 2;
+    auto half_position = [&](size_t j) { return ((j & 1) == last_parity ? before : 0) + (j >> 1); };
+    const size_t last_length = R - (halves - 1) * cps;
+    Grid<Ops> sums{ctx, halves, Q, ct, L, galois_keys, key_stride, &tiled, most_positions * Q, s};
+    Scratch sums_mem(stream);
+    HEAMD_HIP_TRY(sums_mem.allocate(2 * halves * Q * ct_bytes));
+    W* current = static_cast<W*>(sums_mem.get());
+    W* other = current + halves * Q * ct;
+    std::vector<uint64_t> elements(pack_step_count);
+    for (size_t i = 0; i < pack_step_count; ++i)
+        HEAMD_TRY_STATUS(he_galois_element_rotating_columns(pack_steps[i].step, n, &elements[i]));
+    for (size_t j = 0; j < halves; ++j) {  // the accumulator is the half's last element (HeScheme.swift:118)
+        const size_t length = j + 1 < halves ? cps : last_length;
+        HEAMD_HIP_TRY(sums.copy(current, half_position(j), results, R, position_of[j * cps + length - 1], 1));
+    }
+    size_t live = halves;
+    W* short_half = nullptr;  // where the short half's sum was when it ran out of elements
+    for (size_t step = 0; step + 1 < cps && live > 0; ++step) {
+        if (live == halves && last_length - 1 <= step) {
+            short_half = current;
+            --live;
+            if (live == 0) break;
+        }
+        for (size_t i = 0; i < pack_step_count; ++i)
+            for (uint32_t repeat = 0; repeat < pack_steps[i].count; ++repeat) {
+                HEAMD_TRY_STATUS(sums.rotate(current, other, elements[i], 4 + i, 0, live));
+                std::swap(current, other);
+            }
+        for (size_t j = 0; j < halves; ++j) {
+            if (half_position(j) >= live) continue;
+            const size_t length = j + 1 < halves ? cps : last_length;
+            HEAMD_TRY_STATUS(sums.add(ring, current, half_position(j), results, R, position_of[j * cps + length - 2 - step], 1));
+        }
+    }
+    if (short_half != nullptr && short_half != current) HEAMD_HIP_TRY(sums.copy(current, halves - 1, short_half, halves, halves - 1, 1));
+    // swapRowsAndAdd (:281-286, HeScheme.swift:143-151): the second half's sum is swapped, the first half's added to it
+    const size_t seconds = halves / 2;
+    const size_t second_first = half_position(1 < halves ? 1 : 0), first_first = half_position(0);
+    if (seconds > 0) {
+        uint64_t element_swap = 0;
+        HEAMD_TRY_STATUS(he_galois_element_swapping_rows(n, &element_swap));
+        HEAMD_TRY_STATUS(sums.rotate(current, other, element_swap, 2, second_first, seconds));
+        HEAMD_TRY_STATUS(sums.add(ring, other, second_first, current, halves, first_first, seconds));
+    }
+    // 6) the M packed ciphertexts of every client, through modSwitchDownToSingle for the response
+    W* packed = out;
+    if (to_single) {
+        HEAMD_HIP_TRY(single_mem.allocate(Q * M * ct_bytes));
+        packed = static_cast<W*>(single_mem.get());
+    }
+    for (size_t m = 0; m < M; ++m) {
+        const bool whole = m < seconds;
+        HEAMD_HIP_TRY(to_client_major<Ops>(packed, M, m, whole ? other : current, halves, (whole ? second_first : first_first) + m,
+                                           Q, ct, stream));
+    }
+    if (to_single) {
+        HEAMD_HIP_TRY(allocate_levels(Q * M));
+        HEAMD_TRY_STATUS(Ops::to_single(ctx->bfv, L, packed, out, Q * M, static_cast<W*>(levels_mem.get()), s));
     }
     return HE_OK;
 }
@@ -501,3 +922,32 @@ extern "C" int he_pnns_compute_response_device_u32(const he_pnns_context* ctx, c
     return mul_transpose<Ops32>(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
                                 out, true, s);
 }
+
+extern "C" int he_pnns_query_matrix_shape(const he_pnns_context* ctx, size_t matrix_rows, size_t cols, size_t query_rows,
+                                          size_t* out_query_ciphertexts, size_t* out_result_ciphertexts,
+                                          uint32_t* out_pack_needs) {
+    MatrixPlan plan;
+    const int status = matrix_plan(ctx, matrix_rows, cols, HE_PNNS_PACKING_DIAGONAL, 0, plan);
+    if (status != HE_OK) return status;
+    QueryPlan query;
+    const int planned = query_plan(ctx, matrix_rows, cols, query_rows, plan.baby_step, plan.giant_step, query);
+    if (planned != HE_OK) return planned;
+    if (out_query_ciphertexts != nullptr) *out_query_ciphertexts = query.query_ciphertexts;
+    if (out_result_ciphertexts != nullptr) *out_result_ciphertexts = query.result_ciphertexts;
+    if (out_pack_needs != nullptr) *out_pack_needs = query.needs;
+    return HE_OK;
+}
+
+#define HEAMD_PNNS_MATRIX_ENTRY(NAME, OPS, WORD, TO_SINGLE)                                                                   \
+    extern "C" int NAME(const he_pnns_context* ctx, const WORD* matrix, size_t matrix_plaintext_count, size_t rows, size_t cols, \
+                        uint32_t baby_step, const WORD* queries, size_t query_rows, size_t query_count,                        \
+                        const he_pnns_pack_step* pack_steps, size_t pack_step_count, const WORD* const* galois_keys, WORD* out, \
+                        he_stream s) {                                                                                         \
+        return mul_transpose_matrix<OPS>(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_rows,      \
+                                         query_count, pack_steps, pack_step_count, galois_keys, out, TO_SINGLE, s);            \
+    }
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_mul_transpose_matrix_device, Ops64, uint64_t, false)
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_mul_transpose_matrix_device_u32, Ops32, uint32_t, false)
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_compute_response_matrix_device, Ops64, uint64_t, true)
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_compute_response_matrix_device_u32, Ops32, uint32_t, true)
+#undef HEAMD_PNNS_MATRIX_ENTRY

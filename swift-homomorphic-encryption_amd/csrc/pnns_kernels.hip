@@ -4,6 +4,8 @@
 // inverse NTT over [t] and Plaintext.convertToEvalFormat that follow are the existing kernels (pnns_api.cpp).
 // And the server's response: the baby-step giant-step inner products of PlaintextMatrix.mulTranspose(vector:using:)
 // (MatrixMultiplication.swift:195-212) for all giant steps and up to four queries in one pass over the matrix.
+// And CiphertextMatrix.extractDenseRow (CiphertextMatrix.swift:252-370) for query matrices of several rows: the masks, and the
+// product of every query ciphertext with the masks of all the rows packed in it.
 #include "kernels.hpp"
 
 namespace heamd {
@@ -517,5 +519,145 @@ template hipError_t launch_pnns_bsgs_inner_product<uint64_t>(const uint64_t*, co
                                                              const PnnsBsgsLayout&, unsigned, hipStream_t);
 template hipError_t launch_pnns_bsgs_inner_product<uint32_t>(const uint32_t*, const uint32_t*, uint32_t*, const DeviceContext&,
                                                              const PnnsBsgsLayout&, unsigned, hipStream_t);
+
+// ---- extractDenseRow: the masks and the masked rows -----------------------------------------------------------------------
+namespace {
+constexpr unsigned kRowThreads = 256;
+
+struct RowMaskBatch {
+    PnnsRowMask rows[kPnnsRowsPerLaunch];
+    uint32_t padded_cols, log_degree;
+};
+
+// Word w of the slab holds SIMD slot slot_of_word[w] (Encoding.swift:228-230): the stores are contiguous, the pattern is
+// evaluated at the slot.  blockIdx.y: the row of this launch.
+template <typename W>
+__global__ __launch_bounds__(kRowThreads) void pnns_row_mask_kernel(const uint32_t* __restrict__ slot_of_word,
+                                                                    const RowMaskBatch batch, W* __restrict__ staging) {
+    const size_t n = size_t(1) << batch.log_degree;
+    const size_t word = static_cast<size_t>(blockIdx.x) * kRowThreads + threadIdx.x;
+    if (word >= n) return;
+    const PnnsRowMask row = batch.rows[blockIdx.y];
+    const uint64_t slot = slot_of_word[word];
+    uint64_t end = row.lower + static_cast<uint64_t>(row.copies) * row.period;  // mask.prefix(degree)
+    if (end > n) end = n;
+    const bool one = slot >= row.lower && slot < end && ((slot - row.lower) & (row.period - 1u)) < batch.padded_cols;
+    staging[static_cast<size_t>(blockIdx.y) * n + word] = one ? W(1) : W(0);
+}
+
+struct ExtractBatch {
+    uint32_t positions[kPnnsRowsPerLaunch];  // where in `out` each row goes
+    uint32_t count, first_row;               // the rows of this launch: masks first_row + i
+    uint32_t ciphertext, query_ciphertexts;
+    size_t poly_words;                       // L N
+    size_t row_stride, client_stride;        // in ciphertexts
+};
+
+// A lane owns 16 bytes of one polynomial of one client's query ciphertext (blockIdx.y: polynomial, blockIdx.z: client): it
+// reads them once and, per row packed in the ciphertext, multiplies them with the same 16 bytes of the row's mask and stores
+// the product into the row's own ciphertext.  The masks are re-read by every client and both polynomials (cached); queries
+// and rows are touched once (streamed).  UNIFORM: N >= 64 lanes x 16 bytes, so a wavefront lies in one residue row and the
+// modulus is wave-uniform.  The product is he_bfv_mul_plain_device's (device_math.hpp barrett_mul).
+template <typename W, bool UNIFORM>
+__global__ __launch_bounds__(kRowThreads) void pnns_extract_rows_kernel(const W* __restrict__ queries,
+                                                                        const W* __restrict__ masks, W* __restrict__ out,
+                                                                        const DeviceContext ctx, const ExtractBatch batch) {
+    constexpr unsigned kVector = 16 / sizeof(W);
+    typedef uint32_t Words4 __attribute__((ext_vector_type(4)));
+    const size_t word = (static_cast<size_t>(blockIdx.x) * kRowThreads + threadIdx.x) * kVector;
+    if (word >= batch.poly_words) return;  // poly_words is a multiple of kVector
+    uint32_t row_of_modulus = static_cast<uint32_t>(word >> ctx.log_degree);
+    if constexpr (UNIFORM) row_of_modulus = __builtin_amdgcn_readfirstlane(row_of_modulus);
+    const DeviceModulus* modulus = ctx.moduli + row_of_modulus;
+    const uint64_t p = modulus->p, factor = modulus->product_factor;
+    const int shift = static_cast<int>(modulus->product_shift);
+    const size_t client = blockIdx.z, polynomial = blockIdx.y;
+    const size_t source = ((client * batch.query_ciphertexts + batch.ciphertext) * 2 + polynomial) * batch.poly_words + word;
+    const Words4 loaded = __builtin_nontemporal_load(reinterpret_cast<const Words4*>(queries + source));
+    uint64_t x[kVector];
+    bsgs_words<W>(uint4{loaded.x, loaded.y, loaded.z, loaded.w}, x);
+    for (uint32_t i = 0; i < batch.count; ++i) {  // wave-uniform
+        const uint4 mask = *reinterpret_cast<const uint4*>(masks + static_cast<size_t>(batch.first_row + i) * batch.poly_words + word);
+        uint64_t y[kVector];
+        bsgs_words<W>(mask, y);
+        uint64_t product[kVector];
+#pragma unroll
+        for (unsigned v = 0; v < kVector; ++v) product[v] = barrett_mul(x[v], y[v], p, factor, shift);
+        Words4 packed;
+        if constexpr (sizeof(W) == 8) {
+            packed = Words4{lo32(product[0]), hi32(product[0]), lo32(product[1]), hi32(product[1])};
+        } else {
+            packed = Words4{lo32(product[0]), lo32(product[1]), lo32(product[2]), lo32(product[3])};
+        }
+        const size_t target = batch.positions[i] * batch.row_stride + client * batch.client_stride;
+        __builtin_nontemporal_store(packed, reinterpret_cast<Words4*>(out + (target * 2 + polynomial) * batch.poly_words + word));
+    }
+}
+}  // namespace
+
+template <typename W>
+hipError_t launch_pnns_row_masks(const uint32_t* slot_of_word, const PnnsRowMask* rows, size_t count, uint32_t padded_cols,
+                                 uint32_t log_degree, W* staging, hipStream_t stream) {
+    const size_t n = size_t(1) << log_degree;
+    const unsigned blocks = static_cast<unsigned>((n + kRowThreads - 1) / kRowThreads);
+    for (size_t first = 0; first < count; first += kPnnsRowsPerLaunch) {
+        const unsigned now = static_cast<unsigned>(count - first < kPnnsRowsPerLaunch ? count - first : kPnnsRowsPerLaunch);
+        RowMaskBatch batch{};
+        for (unsigned i = 0; i < now; ++i) batch.rows[i] = rows[first + i];
+        batch.padded_cols = padded_cols;
+        batch.log_degree = log_degree;
+        hipLaunchKernelGGL(pnns_row_mask_kernel<W>, dim3(blocks, now), dim3(kRowThreads), 0, stream, slot_of_word, batch,
+                           staging + first * n);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+template hipError_t launch_pnns_row_masks<uint64_t>(const uint32_t*, const PnnsRowMask*, size_t, uint32_t, uint32_t, uint64_t*,
+                                                    hipStream_t);
+template hipError_t launch_pnns_row_masks<uint32_t>(const uint32_t*, const PnnsRowMask*, size_t, uint32_t, uint32_t, uint32_t*,
+                                                    hipStream_t);
+
+template <typename W>
+hipError_t launch_pnns_extract_rows(const W* queries, const W* masks, W* out, const DeviceContext& ctx,
+                                    const PnnsExtractLayout& layout, uint32_t ciphertext, uint32_t first_row,
+                                    const uint32_t* positions, size_t count, hipStream_t stream) {
+    constexpr size_t kVector = 16 / sizeof(W);
+    if (count == 0 || layout.clients == 0) return hipSuccess;
+    const size_t n = size_t(1) << ctx.log_degree;
+    const size_t poly_words = static_cast<size_t>(ctx.moduli_count) * n;
+    const size_t blocks = (poly_words / kVector + kRowThreads - 1) / kRowThreads;
+    if (poly_words % kVector != 0 || blocks >= (size_t(1) << 31) || layout.clients > 65535) return hipErrorInvalidValue;
+    const bool uniform = n >= 64 * kVector;
+    for (size_t first = 0; first < count; first += kPnnsRowsPerLaunch) {
+        const unsigned now = static_cast<unsigned>(count - first < kPnnsRowsPerLaunch ? count - first : kPnnsRowsPerLaunch);
+        ExtractBatch batch{};
+        for (unsigned i = 0; i < now; ++i) batch.positions[i] = positions[first + i];
+        batch.count = now;
+        batch.first_row = first_row + static_cast<uint32_t>(first);
+        batch.ciphertext = ciphertext;
+        batch.query_ciphertexts = static_cast<uint32_t>(layout.query_ciphertexts);
+        batch.poly_words = poly_words;
+        batch.row_stride = layout.row_stride;
+        batch.client_stride = layout.client_stride;
+        const dim3 grid(static_cast<unsigned>(blocks), 2, static_cast<unsigned>(layout.clients));
+        if (uniform) {
+            hipLaunchKernelGGL((pnns_extract_rows_kernel<W, true>), grid, dim3(kRowThreads), 0, stream, queries, masks, out, ctx,
+                               batch);
+        } else {
+            hipLaunchKernelGGL((pnns_extract_rows_kernel<W, false>), grid, dim3(kRowThreads), 0, stream, queries, masks, out, ctx,
+                               batch);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+template hipError_t launch_pnns_extract_rows<uint64_t>(const uint64_t*, const uint64_t*, uint64_t*, const DeviceContext&,
+                                                       const PnnsExtractLayout&, uint32_t, uint32_t, const uint32_t*, size_t,
+                                                       hipStream_t);
+template hipError_t launch_pnns_extract_rows<uint32_t>(const uint32_t*, const uint32_t*, uint32_t*, const DeviceContext&,
+                                                       const PnnsExtractLayout&, uint32_t, uint32_t, const uint32_t*, size_t,
+                                                       hipStream_t);
 
 }  // namespace heamd

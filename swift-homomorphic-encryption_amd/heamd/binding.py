@@ -232,6 +232,15 @@ SIGNATURES = [
     ("he_pnns_mul_transpose_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
     ("he_pnns_compute_response_device", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
     ("he_pnns_compute_response_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
+    ("he_pnns_query_matrix_shape", ctypes.c_int, [vp, c_size, c_size, c_size, vp, vp, vp]),
+    ("he_pnns_mul_transpose_matrix_device", ctypes.c_int,
+     [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
+    ("he_pnns_mul_transpose_matrix_device_u32", ctypes.c_int,
+     [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
+    ("he_pnns_compute_response_matrix_device", ctypes.c_int,
+     [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
+    ("he_pnns_compute_response_matrix_device_u32", ctypes.c_int,
+     [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
     # diagnostics / test hooks
     ("he_poly_context_create_host_only", ctypes.c_int, [c_u32, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_poly_context_copy_ntt_tables", ctypes.c_int, [vp, c_u32, U64P, U64P, U64P, U64P, U64P, U64P]),
@@ -1519,6 +1528,12 @@ class SimplePirServer32(SimplePirServer):
 PNNS_PACKINGS = {"denseColumn": 0, "denseRow": 1, "diagonal": 2}  # MatrixPacking's case order (HE_PNNS_PACKING_*)
 
 
+class PnnsPackStep(ctypes.Structure):
+    """he_pnns_pack_step: `count` rotations by `step` columns."""
+
+    _fields_ = [("step", ctypes.c_int64), ("count", ctypes.c_uint32)]
+
+
 class PnnsContext:
     """he_pnns_context: the SIMD encoding side of a BfvContext / BfvContext32 (plaintextContext over [t] and
     simdEncodingMatrix on the device) and the PNNS server database built with it (PrivateNearestNeighborSearch/
@@ -1634,6 +1649,77 @@ class PnnsContext:
         """he_pnns_compute_response_device(_u32): Server.computeResponse for Q one-row queries: mul_transpose, then
         modSwitchDownToSingle -> [Q][ceil(rows / N)][2][1][N] Coeff over q_0."""
         return self._respond("he_pnns_compute_response_device", matrix, rows, cols, queries, galois_keys, baby_step, 1, stream)
+
+    def query_matrix_shape(self, matrix_rows, cols, query_rows):
+        """he_pnns_query_matrix_shape -> dict with query_ciphertexts (K), result_ciphertexts (M) and needs: the set of slots of
+        galois_keys the shape reads (0..3), plus "pack" for the rotation plan and its keys."""
+        k, m, needs = c_size(), c_size(), c_u32()
+        _check(load_library().he_pnns_query_matrix_shape(self.h, int(matrix_rows), int(cols), int(query_rows), ctypes.byref(k),
+                                                         ctypes.byref(m), ctypes.byref(needs)))
+        bits = int(needs.value)
+        return {"query_ciphertexts": int(k.value), "result_ciphertexts": int(m.value),
+                "needs": {slot for slot in range(4) if bits >> slot & 1} | ({"pack"} if bits >> 4 & 1 else set())}
+
+    def _matrix_entry(self, entry, matrix, rows, cols, queries, query_rows, pack_steps, galois_keys, baby_step, out_moduli,
+                      stream):
+        import torch
+
+        word = torch.int32 if self.word32 else torch.int64
+        L, n = self.bfv.L, self.bfv.degree
+        for name, tensor in (("matrix", matrix), ("queries", queries)):
+            if tensor.dtype != word or not tensor.is_cuda or not tensor.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous device tensor of the context's words")
+        if matrix.dim() != 3 or tuple(matrix.shape[1:]) != (L, n):
+            raise ValueError("matrix must be [plaintext_count][L][N]")
+        if queries.dim() != 5 or tuple(queries.shape[2:]) != (2, L, n):
+            raise ValueError("queries must be [Q][K][2][L][N]")
+        count = queries.shape[0]
+        shape = self.matrix_shape(rows, cols, "diagonal", baby_step or 0)
+        query_shape = self.query_matrix_shape(rows, cols, query_rows)
+        if queries.shape[1] != query_shape["query_ciphertexts"]:
+            raise ValueError("queries must hold ceil(query_rows / rows per ciphertext) ciphertexts per client")
+        pack_steps = list(pack_steps or [])
+        plan = (PnnsPackStep * max(len(pack_steps), 1))()
+        for i, (step, repeat) in enumerate(pack_steps):
+            plan[i].step, plan[i].count = int(step), int(repeat)
+        stride = 4 + len(pack_steps)
+        keys = (vp * (stride * max(count, 1)))()
+        if galois_keys is not None:
+            if len(galois_keys) != count:
+                raise ValueError("galois_keys must hold one list of 4 + len(pack_steps) keys per client")
+            for q, row in enumerate(galois_keys):
+                if len(row) != stride:
+                    raise ValueError("galois_keys must hold one list of 4 + len(pack_steps) keys per client")
+                for k, key in enumerate(row):
+                    if key is not None:
+                        if key.dtype != word or not key.is_cuda or not key.is_contiguous():
+                            raise ValueError("a Galois key must be a contiguous device tensor of the context's words")
+                        keys[stride * q + k] = key.data_ptr()
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            out = torch.empty((count, query_shape["result_ciphertexts"], 2, out_moduli, n), dtype=word, device=queries.device)
+        name = entry + ("_u32" if self.word32 else "")
+        _check(getattr(load_library(), name)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
+                                             shape["baby_step"], vp(queries.data_ptr()), int(query_rows), count,
+                                             plan if pack_steps else None, len(pack_steps),
+                                             keys if galois_keys is not None else None, vp(out.data_ptr()), _stream(stream)))
+        return out
+
+    def mul_transpose_matrix(self, matrix, rows, cols, queries, query_rows, pack_steps, galois_keys, baby_step=None,
+                             stream=None):
+        """he_pnns_mul_transpose_matrix_device(_u32): PlaintextMatrix.mulTranspose(matrix:using:) for Q clients with query
+        matrices of query_rows rows.  queries [Q][K][2][L][N] Coeff (dense-row packed), pack_steps the ordered plan of
+        rotateColumnsMultiStep(by: rows) as (step, count) pairs, galois_keys per client a list of 4 + len(pack_steps) device
+        tensors (keys of -1, -baby_step, swappingRows, P, then the plan's steps), None where the shape does not need one
+        -> [Q][M][2][L][N] Coeff, M as query_matrix_shape gives it."""
+        return self._matrix_entry("he_pnns_mul_transpose_matrix_device", matrix, rows, cols, queries, query_rows, pack_steps,
+                                  galois_keys, baby_step, self.bfv.L, stream)
+
+    def compute_response_matrix(self, matrix, rows, cols, queries, query_rows, pack_steps, galois_keys, baby_step=None,
+                                stream=None):
+        """he_pnns_compute_response_matrix_device(_u32): Server.computeResponse for such queries: mul_transpose_matrix, then
+        modSwitchDownToSingle -> [Q][M][2][1][N] Coeff over q_0."""
+        return self._matrix_entry("he_pnns_compute_response_matrix_device", matrix, rows, cols, queries, query_rows,
+                                  pack_steps, galois_keys, baby_step, 1, stream)
 
 
 def _no_stream():
