@@ -2,8 +2,11 @@
 he_pnns_compute_response_device) at 2^20 rows x 128 columns, N = 8192, L = 4 x 55-bit moduli, a 20-bit t: b = 12, G = 11,
 C = 128, a 4.3 GB matrix.  One JSON line, also written to --out:
 
-    python bench_tools/pnns_response_bench.py [--queries 1,4] [--steps K] [--warmup W] [--no-composition]
+    python bench_tools/pnns_response_bench.py [--queries 1,4] [--steps K] [--warmup W] [--no-composition] [--word32]
                                               [--stats Q=kernel_stats.csv ...] [--out profiles/pnns_response.json]
+
+--word32: the same shape on a Bfv<UInt32> context (he_pnns_compute_response_device_u32), moduli as the 4-byte tests take them
+(27, 28, 28 and 29 bits, a 17-bit t; a 1.6 GB matrix); the composition is of 8-byte entry points and is not run.
 
 Per query count: the median of --steps calls by events around the enqueue-only call, per query.  The baseline, in the same
 process: the same response of ONE query composed from the entry points the library had before (the sequence of
@@ -28,11 +31,11 @@ for path in (ROOT, os.path.join(ROOT, "swift-homomorphic-encryption_amd"), os.pa
 DEGREE, ROWS, COLS, SCALE = 8192, 1 << 20, 128, 4096.0
 
 
-def uniform(torch, moduli, before, seed):
+def uniform(torch, moduli, before, seed, dtype=None):
     generator = torch.Generator("cuda").manual_seed(seed)
     rows = [torch.randint(0, int(m), tuple(before) + (DEGREE,), dtype=torch.int64, device="cuda", generator=generator)
             for m in moduli]
-    return torch.stack(rows, dim=len(before)).contiguous()
+    return torch.stack(rows, dim=len(before)).to(dtype or torch.int64).contiguous()
 
 
 def composition(heamd, torch, bfv, matrix, baby_step, giant_step, results, query, key_one, key_baby):
@@ -83,6 +86,7 @@ def main():
     parser.add_argument("--steps", type=int, default=30)
     parser.add_argument("--warmup", type=int, default=3)
     parser.add_argument("--no-composition", action="store_true")
+    parser.add_argument("--word32", action="store_true", help="Bfv<UInt32>: packed 4-byte words through the _u32 entry")
     parser.add_argument("--stats", action="append", default=[], help="Q=kernel_stats.csv of a traced run with --queries Q")
     parser.add_argument("--out")
     args = parser.parse_args()
@@ -93,9 +97,18 @@ def main():
     from pnns_database_bench import kernels_per_call
 
     heamd.load_library().he_set_scratch_cache(2 ** 64 - 1)  # what a server sets once: the calls are enqueue-only
-    t = heamd.generate_primes([20], False, DEGREE)[0]
-    q = heamd.generate_primes([55] * 5, False, DEGREE)
-    bfv = heamd.BfvContext(DEGREE, t, q)
+    if args.word32:
+        import oracle
+
+        t = oracle.generate_primes([17], True, DEGREE)[0]
+        q = oracle.generate_primes([27, 28, 28, 29], False, DEGREE, word_bits=32)
+        bfv = heamd.BfvContext32(DEGREE, t, q)
+        args.no_composition = True
+    else:
+        t = heamd.generate_primes([20], False, DEGREE)[0]
+        q = heamd.generate_primes([55] * 5, False, DEGREE)
+        bfv = heamd.BfvContext(DEGREE, t, q)
+    word = torch.int32 if args.word32 else torch.int64
     ctx = heamd.PnnsContext(bfv)
     L = bfv.L
     shape = ctx.matrix_shape(ROWS, COLS)
@@ -104,15 +117,15 @@ def main():
     matrix, flag = ctx.process_database(vectors, SCALE)
     assert int(flag.item()) == 0
     del vectors
-    matrix_bytes = matrix.numel() * 8
+    matrix_bytes = matrix.numel() * matrix.element_size()
     properties = torch.cuda.get_device_properties(0)
-    result = {"tool": "pnns_response_bench", "degree": DEGREE, "L": L, "rows": ROWS, "cols": COLS, "baby_step": baby_step,
+    result = {"tool": "pnns_response_bench", "word_bits": 32 if args.word32 else 64, "degree": DEGREE, "L": L, "rows": ROWS, "cols": COLS, "baby_step": baby_step,
               "giant_step": giant_step, "result_ciphertexts": results, "matrix_bytes": matrix_bytes, "steps": args.steps,
               "device": properties.name, "clock_rate_khz": getattr(properties, "clock_rate", None),
               "compute_units": properties.multi_processor_count, "entry": {}}
     most = max(int(v) for v in args.queries.split(","))
-    queries = uniform(torch, q[:L], (most, 2), 2)
-    keys = [(uniform(torch, q, (L, 2), 10 + 2 * k), uniform(torch, q, (L, 2), 11 + 2 * k)) for k in range(most)]
+    queries = uniform(torch, q[:L], (most, 2), 2, word)
+    keys = [(uniform(torch, q, (L, 2), 10 + 2 * k, word), uniform(torch, q, (L, 2), 11 + 2 * k, word)) for k in range(most)]
     for count in (int(v) for v in args.queries.split(",")):
         ms, times = timed(torch, args.steps, args.warmup,
                           lambda: ctx.compute_response(matrix, ROWS, COLS, queries[:count].contiguous(), keys[:count]))

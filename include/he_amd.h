@@ -670,9 +670,7 @@ int he_pnns_diagonal_matrix_device_u32(const he_pnns_context* ctx, const int64_t
 int he_pnns_mul_transpose_device(const he_pnns_context* ctx, const uint64_t* matrix, size_t matrix_plaintext_count, size_t rows,
                                  size_t cols, uint32_t baby_step, const uint64_t* queries, size_t query_count,
                                  const uint64_t* const* galois_keys, uint64_t* out, he_stream s);
-/* The same for a Bfv<UInt32> context on packed 4-byte words (matrix, queries, keys and out).  The 4-byte Galois entry takes
- * one key per call, so here a rotation step is one call per query, not one batch over all of them; the pass over the matrix
- * and the transforms are batched as above. */
+/* The same for a Bfv<UInt32> context on packed 4-byte words (matrix, queries, keys and out), batched as above. */
 int he_pnns_mul_transpose_device_u32(const he_pnns_context* ctx, const uint32_t* matrix, size_t matrix_plaintext_count,
                                      size_t rows, size_t cols, uint32_t baby_step, const uint32_t* queries, size_t query_count,
                                      const uint32_t* const* galois_keys, uint32_t* out, he_stream s);
@@ -732,7 +730,7 @@ int he_pnns_mul_transpose_matrix_device(const he_pnns_context* ctx, const uint64
                                         size_t rows, size_t cols, uint32_t baby_step, const uint64_t* queries,
                                         size_t query_rows, size_t query_count, const he_pnns_pack_step* pack_steps,
                                         size_t pack_step_count, const uint64_t* const* galois_keys, uint64_t* out, he_stream s);
-/* The same on packed 4-byte words; a rotation step is one Galois call per client, as in he_pnns_mul_transpose_device_u32. */
+/* The same on packed 4-byte words. */
 int he_pnns_mul_transpose_matrix_device_u32(const he_pnns_context* ctx, const uint32_t* matrix, size_t matrix_plaintext_count,
                                             size_t rows, size_t cols, uint32_t baby_step, const uint32_t* queries,
                                             size_t query_rows, size_t query_count, const he_pnns_pack_step* pack_steps,

@@ -114,6 +114,12 @@ int bfv_expand_step_fused(const he_bfv_context* ctx, uint32_t L, const uint64_t*
                           const uint32_t* leaf_table, size_t leaf_stride, void* workspace, size_t workspace_bytes,
                           hipStream_t stream, const uint64_t* rotated = nullptr);
 
+// bfv_api.cpp: he_bfv_apply_galois_grouped_device for either word size (uint64_t, uint32_t), checks included (not exported)
+template <typename W>
+int bfv_apply_galois_grouped(const he_bfv_context* ctx, uint32_t L, const W* ct, uint64_t element, const W* const* keys,
+                             size_t groups, size_t group_size, W* out, void* workspace, size_t workspace_bytes,
+                             hipStream_t stream);
+
 // bfv_api.cpp: `items` ct x ct inner products that share lhs, the right-hand side given in Eval form over Q (the first remaining
 // dimension of a PIR response; not exported)
 constexpr int kInnerProductEvalUnavailable = -2;

@@ -366,45 +366,42 @@ hipError_t key_mac_and_finish(const uint32_t* spread, const uint32_t* key, uint3
 
 // _computeKeySwitchingUpdate (Bfv+Keys.swift:123-208) on polynomial `target` of every item, then
 // out[item][c] = (c < added_polys ? ct[item][c] : 0) + update[item][c]  (relinearize: added 2; applyGalois: added 1)
-template <typename W>
-int key_switch_pipeline(const he_bfv_context* ctx, uint32_t L, const W* target, size_t target_stride, const W* ct_base,
-                        size_t ct_stride, const W* key, W* out, size_t batch, uint32_t added_polys, W* spread, W* prod,
-                        hipStream_t stream) {
-    const PolyContext* ks_ctx = ctx->impl->key_switching(L);
-    HEAMD_HIP_TRY(spread_to_eval(target, target_stride, spread, *ks_ctx, L, batch, stream));
-    const hipError_t fused = key_mac_and_finish(spread, key, prod, ct_base, ct_stride, out, *ks_ctx, L,
-                                                ctx->impl->top_level() + 1, batch, added_polys, stream);
-    if (fused != hipErrorNotSupported) {
-        HEAMD_HIP_TRY(fused);
-        return HE_OK;
-    }
-    HEAMD_HIP_TRY(key_mac_to_coeff(spread, key, prod, *ks_ctx, L, ctx->impl->top_level() + 1, batch, stream));
-    HEAMD_HIP_TRY(heamd::launch_key_switch_finish(prod, ct_base, ct_stride, out, ks_ctx->device_context(), L, batch,
-                                                  added_polys, stream));
-    return HE_OK;
-}
-
-// The same with one key per group of `group_size` consecutive items (ciphertexts of different clients in one batch):
-// decomposition and finish run over the whole batch, only the inner product with the key is launched per run of equal
-// keys.
+// One key per group of `group_size` consecutive items (ciphertexts of different clients in one batch): one decomposition
+// over the whole batch, then the inner product with the key per run of equal keys -- through the key switch's last step where
+// the run has that kernel, otherwise to Coeff, and the last step follows in one launch over every stretch of such runs.
 template <typename W>
 int key_switch_pipeline_grouped(const he_bfv_context* ctx, uint32_t L, const W* target, size_t target_stride,
                                 const W* ct_base, size_t ct_stride, const W* const* keys, size_t groups, size_t group_size,
                                 W* out, uint32_t added_polys, W* spread, W* prod, hipStream_t stream) {
     const PolyContext* ks_ctx = ctx->impl->key_switching(L);
     const size_t n = ctx->impl->degree(), batch = groups * group_size;
+    const uint32_t top_rows = ctx->impl->top_level() + 1;
     HEAMD_HIP_TRY(spread_to_eval(target, target_stride, spread, *ks_ctx, L, batch, stream));
+    auto finish = [&](size_t first, size_t end) {  // the last step for the items [first, end) left in Coeff form
+        if (first == end) return hipSuccess;
+        return heamd::launch_key_switch_finish(static_cast<const W*>(prod) + first * 2 * (L + 1) * n,
+                                               ct_base + first * ct_stride, ct_stride, out + first * 2 * L * n,
+                                               ks_ctx->device_context(), L, end - first, added_polys, stream);
+    };
+    size_t unfinished = 0;  // the first item whose last step is still to come
     for (size_t g = 0; g < groups;) {
         size_t run = 1;
         while (g + run < groups && keys[g + run] == keys[g]) ++run;
         const size_t first = g * group_size, polys = run * group_size;
-        HEAMD_HIP_TRY(key_mac_to_coeff(static_cast<const W*>(spread) + first * L * (L + 1) * n, keys[g],
-                                       prod + first * 2 * (L + 1) * n, *ks_ctx, L, ctx->impl->top_level() + 1, polys,
-                                       stream));
+        const W* run_spread = static_cast<const W*>(spread) + first * L * (L + 1) * n;
+        W* run_prod = prod + first * 2 * (L + 1) * n;
+        const hipError_t fused = key_mac_and_finish(run_spread, keys[g], run_prod, ct_base + first * ct_stride, ct_stride,
+                                                    out + first * 2 * L * n, *ks_ctx, L, top_rows, polys, added_polys, stream);
+        if (fused == hipErrorNotSupported) {
+            HEAMD_HIP_TRY(key_mac_to_coeff(run_spread, keys[g], run_prod, *ks_ctx, L, top_rows, polys, stream));
+        } else {
+            HEAMD_HIP_TRY(fused);
+            HEAMD_HIP_TRY(finish(unfinished, first));
+            unfinished = first + polys;
+        }
         g += run;
     }
-    HEAMD_HIP_TRY(heamd::launch_key_switch_finish(static_cast<const W*>(prod), ct_base, ct_stride, out,
-                                                  ks_ctx->device_context(), L, batch, added_polys, stream));
+    HEAMD_HIP_TRY(finish(unfinished, batch));
     return HE_OK;
 }
 
@@ -481,8 +478,8 @@ int relinearize_pipeline(const he_bfv_context* ctx, uint32_t L, const W* ct3, co
     W* spread = reinterpret_cast<W*>(raw);                // [batch][L][L+1][N]
     W* prod = spread + batch * L * (L + 1) * n;           // [batch][2][L+1][N]
     const size_t ct_stride = 3 * size_t(L) * n;
-    return key_switch_pipeline(ctx, L, ct3 + 2 * size_t(L) * n, ct_stride, ct3, ct_stride, key, out, batch, 2, spread, prod,
-                               stream);
+    return key_switch_pipeline_grouped(ctx, L, ct3 + 2 * size_t(L) * n, ct_stride, ct3, ct_stride, &key, 1, batch, out, 2,
+                                       spread, prod, stream);
 }
 
 }  // namespace
@@ -706,25 +703,29 @@ size_t he_bfv_apply_galois_workspace_bytes(const he_bfv_context* ctx, uint32_t m
 }
 
 extern "C++" {
-namespace {
+namespace heamd {
+// Bfv.applyGalois (Bfv.swift:174-198) on groups * group_size ciphertexts, group g under keys[g]: the checks of the three
+// entries below in their order, the fused key switch where the words and the degree have it, else the rotated copy and
+// key_switch_pipeline_grouped.
 template <typename W>
-int apply_galois_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* ct, uint64_t element, const W* galois_key,
-                       W* out, size_t batch, void* workspace, size_t workspace_bytes, he_stream s) {
+int bfv_apply_galois_grouped(const he_bfv_context* ctx, uint32_t L, const W* ct, uint64_t element, const W* const* keys,
+                             size_t groups, size_t group_size, W* out, void* workspace, size_t workspace_bytes,
+                             hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, L, &tool);
     if (status != HE_OK) return status;
     if (sizeof(W) == 4 && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
-    if (galois_key == nullptr || !ctx->impl->has_key_switching()) {
+    bool missing = keys == nullptr || !ctx->impl->has_key_switching();
+    for (size_t g = 0; !missing && g < groups; ++g) missing = keys[g] == nullptr;
+    if (missing) {
         heamd::set_last_error("no Galois key for this element");
         return HE_ERR_MISSING_GALOIS_KEY;  // Bfv.swift:184-189
     }
     if (!is_valid_galois_element(element, ctx->impl->degree())) return invalid_argument("invalid Galois element");
+    const size_t batch = groups * group_size;
     if (batch == 0) return HE_OK;
     if (ct == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    hipStream_t stream = as_stream(s);
-    const uint32_t L = moduli_count;
     const size_t n = ctx->impl->degree();
-    const PolyContext* q_ctx = ctx->impl->ciphertext(L);
     Scratch scratch(stream);
     uint64_t* raw = nullptr;
     const size_t words = batch * (2 * size_t(L) + size_t(L) * (L + 1) + 2 * (L + 1)) * n;
@@ -737,78 +738,44 @@ int apply_galois_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W
     // Bfv.swift:190-196: c0' = galois(c0) + update0, c1' = update1, update = keySwitch(galois(c1))
     const uint32_t galois_inverse = inverse_mod_power_of_two(element, 2 * n);
     if constexpr (sizeof(W) == 8) {
-        if (static_cast<const void*>(ct) != static_cast<const void*>(out)) {  // the fused kernels read ct to the end
-            const uint64_t* key = reinterpret_cast<const uint64_t*>(galois_key);
-            const hipError_t e = galois_switch_fused(ctx, L, reinterpret_cast<const uint64_t*>(ct), galois_inverse, &key, 1,
-                                                     batch, reinterpret_cast<uint64_t*>(out), 0,
-                                                     heamd::ExpandTargets{nullptr, 1, 0}, reinterpret_cast<uint64_t*>(spread),
-                                                     reinterpret_cast<uint64_t*>(prod), stream);
+        if (ct != out) {  // the fused kernels read ct to the end
+            const hipError_t e = galois_switch_fused(ctx, L, ct, galois_inverse, keys, groups, group_size, out, 0,
+                                                     heamd::ExpandTargets{nullptr, 1, 0}, spread, prod, stream);
             if (e == hipSuccess) return HE_OK;
             if (e != hipErrorNotSupported) HEAMD_HIP_TRY(e);
             (void)hipGetLastError();
         }
     }
+    const PolyContext* q_ctx = ctx->impl->ciphertext(L);
     HEAMD_HIP_TRY(heamd::launch_galois_coeff(ct, rotated, q_ctx->device_context(L), galois_inverse, batch * 2 * L, stream));
-    return key_switch_pipeline(ctx, L, static_cast<const W*>(rotated) + size_t(L) * n, ct_stride,
-                               static_cast<const W*>(rotated), ct_stride, galois_key, out, batch, 1, spread, prod, stream);
+    return key_switch_pipeline_grouped<W>(ctx, L, rotated + size_t(L) * n, ct_stride, rotated, ct_stride, keys, groups,
+                                          group_size, out, 1, spread, prod, stream);
 }
-}  // namespace
+template int bfv_apply_galois_grouped(const he_bfv_context*, uint32_t, const uint64_t*, uint64_t, const uint64_t* const*, size_t,
+                                      size_t, uint64_t*, void*, size_t, hipStream_t);
+template int bfv_apply_galois_grouped(const he_bfv_context*, uint32_t, const uint32_t*, uint64_t, const uint32_t* const*, size_t,
+                                      size_t, uint32_t*, void*, size_t, hipStream_t);
+}  // namespace heamd
 }  // extern "C++"
 
 int he_bfv_apply_galois_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* ct, uint64_t element,
                                const uint64_t* galois_key, uint64_t* out, size_t batch, void* workspace,
                                size_t workspace_bytes, he_stream s) {
-    return apply_galois_entry(ctx, moduli_count, ct, element, galois_key, out, batch, workspace, workspace_bytes, s);
+    return heamd::bfv_apply_galois_grouped(ctx, moduli_count, ct, element, &galois_key, 1, batch, out, workspace,
+                                           workspace_bytes, as_stream(s));
 }
 int he_bfv_apply_galois_grouped_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* ct,
                                        uint64_t element, const uint64_t* const* galois_keys, size_t groups,
                                        size_t group_size, uint64_t* out, void* workspace, size_t workspace_bytes,
                                        he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (galois_keys == nullptr || !ctx->impl->has_key_switching()) {
-        heamd::set_last_error("no Galois key for this element");
-        return HE_ERR_MISSING_GALOIS_KEY;
-    }
-    for (size_t g = 0; g < groups; ++g)
-        if (galois_keys[g] == nullptr) {
-            heamd::set_last_error("no Galois key for this element");
-            return HE_ERR_MISSING_GALOIS_KEY;
-        }
-    if (!is_valid_galois_element(element, ctx->impl->degree())) return invalid_argument("invalid Galois element");
-    const size_t batch = groups * group_size;
-    if (batch == 0) return HE_OK;
-    if (ct == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    hipStream_t stream = as_stream(s);
-    const uint32_t L = moduli_count;
-    const size_t n = ctx->impl->degree();
-    const PolyContext* q_ctx = ctx->impl->ciphertext(L);
-    Scratch scratch(stream);
-    uint64_t* ws = nullptr;
-    status = resolve_workspace(workspace, workspace_bytes, he_bfv_apply_galois_workspace_bytes(ctx, L, batch), scratch, &ws);
-    if (status != HE_OK) return status;
-    uint64_t* rotated = ws;                                     // [batch][2][L][N]
-    uint64_t* spread = rotated + batch * 2 * L * n;             // [batch][L][L+1][N]
-    uint64_t* prod = spread + batch * L * (L + 1) * n;          // [batch][2][L+1][N]
-    const size_t ct_stride = 2 * size_t(L) * n;
-    const uint32_t galois_inverse = inverse_mod_power_of_two(element, 2 * n);
-    if (ct != out) {
-        const hipError_t e =
-            galois_switch_fused(ctx, L, ct, galois_inverse, galois_keys, groups, group_size, out, 0,
-                                heamd::ExpandTargets{nullptr, 1, 0}, spread, prod, stream);
-        if (e == hipSuccess) return HE_OK;
-        if (e != hipErrorNotSupported) HEAMD_HIP_TRY(e);
-        (void)hipGetLastError();
-    }
-    HEAMD_HIP_TRY(heamd::launch_galois_coeff(ct, rotated, q_ctx->device_context(L), galois_inverse, batch * 2 * L, stream));
-    return key_switch_pipeline_grouped<uint64_t>(ctx, L, rotated + size_t(L) * n, ct_stride, rotated, ct_stride,
-                                                 galois_keys, groups, group_size, out, 1, spread, prod, stream);
+    return heamd::bfv_apply_galois_grouped(ctx, moduli_count, ct, element, galois_keys, groups, group_size, out, workspace,
+                                           workspace_bytes, as_stream(s));
 }
 int he_bfv_apply_galois_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* ct, uint64_t element,
                                    const uint32_t* galois_key, uint32_t* out, size_t batch, void* workspace,
                                    size_t workspace_bytes, he_stream s) {
-    return apply_galois_entry(ctx, moduli_count, ct, element, galois_key, out, batch, workspace, workspace_bytes, s);
+    return heamd::bfv_apply_galois_grouped(ctx, moduli_count, ct, element, &galois_key, 1, batch, out, workspace,
+                                           workspace_bytes, as_stream(s));
 }
 
 // ------------------------------------------------------------------------------------------ scaleAndRound

@@ -324,10 +324,10 @@ hipError_t launch_pnns_row_masks(const uint32_t* slot_of_word, const PnnsRowMask
                                  uint32_t log_degree, W* staging, hipStream_t stream);
 // ciphertextEval *= plaintextMask (:340-341) for the `count` rows packed in query ciphertext `ciphertext` of every client:
 //   queries  [clients][query_ciphertexts][2][L][N] Eval        masks  [..][L][N] Eval, row first_row + i for the i-th row
-//   out      ciphertext positions[i] * row_stride + client * client_stride is (client, i-th row), Eval
+//   out      ciphertext positions[i] * clients + client is (client, i-th row), Eval
 // Each 16 bytes of a query ciphertext are read once for all its rows.  All three 16-byte aligned.
 struct PnnsExtractLayout {
-    size_t clients, query_ciphertexts, row_stride, client_stride;
+    size_t clients, query_ciphertexts;
 };
 template <typename W>
 hipError_t launch_pnns_extract_rows(const W* queries, const W* masks, W* out, const DeviceContext& ctx,

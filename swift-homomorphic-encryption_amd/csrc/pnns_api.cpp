@@ -228,15 +228,19 @@ int diagonal_matrix(const he_pnns_context* ctx, const int64_t* values, size_t ro
 }
 
 // ---- mulTranspose(vector:using:) and computeResponse ---------------------------------------------------------------------------
-// The library's entry points by word size.  rotate: `groups` runs of `group_size` ciphertexts, run g under keys[g * key_stride].
+// applyGalois on `groups` runs of `group_size` ciphertexts, run g under keys[g * key_stride]
+template <typename W>
+int apply_galois(const he_bfv_context* ctx, uint32_t L, const W* in, uint64_t element, const W* const* keys,
+                 size_t key_stride, size_t groups, size_t group_size, W* out, he_stream s) {
+    std::vector<const W*> per_group(groups);
+    for (size_t g = 0; g < groups; ++g) per_group[g] = keys[g * key_stride];
+    return heamd::bfv_apply_galois_grouped(ctx, L, in, element, per_group.data(), groups, group_size, out, nullptr, 0,
+                                           as_stream(s));
+}
+
+// The library's entry points by word size
 struct Ops64 {
     using Word = uint64_t;
-    static int rotate(const he_bfv_context* ctx, uint32_t L, const Word* in, uint64_t element, const Word* const* keys,
-                      size_t key_stride, size_t groups, size_t group_size, Word* out, he_stream s) {
-        std::vector<const Word*> per_group(groups);
-        for (size_t g = 0; g < groups; ++g) per_group[g] = keys[g * key_stride];
-        return he_bfv_apply_galois_grouped_device(ctx, L, in, element, per_group.data(), groups, group_size, out, nullptr, 0, s);
-    }
     static int forward_ntt(const he_poly_context* ring, Word* slab, size_t polys, he_stream s) {
         return he_ntt_forward_device(ring, slab, polys, s);
     }
@@ -253,16 +257,6 @@ struct Ops64 {
 };
 struct Ops32 {
     using Word = uint32_t;
-    static int rotate(const he_bfv_context* ctx, uint32_t L, const Word* in, uint64_t element, const Word* const* keys,
-                      size_t key_stride, size_t groups, size_t group_size, Word* out, he_stream s) {
-        const size_t ct = 2 * size_t(L) * heamd::bfv_impl(ctx).degree();
-        for (size_t g = 0; g < groups; ++g) {  // the 4-byte Galois entry takes one key per call
-            const int status = he_bfv_apply_galois_device_u32(ctx, L, in + g * group_size * ct, element, keys[g * key_stride],
-                                                              out + g * group_size * ct, group_size, nullptr, 0, s);
-            if (status != HE_OK) return status;
-        }
-        return HE_OK;
-    }
     static int forward_ntt(const he_poly_context* ring, Word* slab, size_t polys, he_stream s) {
         return he_ntt_forward_device_u32(ring, slab, polys, s);
     }
@@ -309,17 +303,16 @@ size_t response_group(size_t result_count, size_t queries, size_t giant_step, si
 }
 
 // mulTranspose(vector:using:) (MatrixMultiplication.swift:131-226) for `vectors` one-row vectors already on the device:
-// `groups` runs of `group_size` consecutive vectors, run g under the keys keys[g * key_stride] (rotatingColumns(by: -1)) and
-// keys[g * key_stride + 1] ((by: -babyStep)).  Everything has been validated.  out [vectors][C][2][L][N], or [..][2][1][N]
-// through modSwitchDownToSingle.
+// vector v under the keys keys[v * key_stride] (rotatingColumns(by: -1)) and keys[v * key_stride + 1] ((by: -babyStep)).
+// Everything has been validated.  out [vectors][C][2][L][N], or [..][2][1][N] through modSwitchDownToSingle.
 template <typename Ops>
 int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typename Ops::Word* matrix,
                  const typename Ops::Word* queries, const typename Ops::Word* const* galois_keys, size_t key_stride,
-                 size_t groups, size_t group_size, typename Ops::Word* out, bool to_single, he_stream s) {
+                 size_t vectors, typename Ops::Word* out, bool to_single, he_stream s) {
     using W = typename Ops::Word;
     const heamd::BfvContext& bfv = heamd::bfv_impl(ctx->bfv);
     const uint32_t b = plan.baby_step, G = plan.giant_step, L = bfv.top_level();
-    const size_t n = bfv.degree(), C = plan.plaintexts_per_column, Q = groups * group_size;
+    const size_t n = bfv.degree(), C = plan.plaintexts_per_column, Q = vectors;
     const bool need_one = b > 1, need_baby = G > 1;
     const heamd::PolyContext* q_ctx = bfv.ciphertext(L);
     const he_poly_context* ring = he_bfv_ciphertext_context(ctx->bfv, L);
@@ -336,8 +329,8 @@ int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typen
     W* rot = static_cast<W*>(rot_mem.get());
     HEAMD_HIP_TRY(hipMemcpyAsync(rot, queries, Q * ct_bytes, hipMemcpyDeviceToDevice, stream));
     for (uint32_t j = 1; j < b; ++j)
-        HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, rot + size_t(j - 1) * Q * ct, element_one, galois_keys, key_stride, groups,
-                                     group_size, rot + size_t(j) * Q * ct, s));
+        HEAMD_TRY_STATUS(apply_galois(ctx->bfv, L, rot + size_t(j - 1) * Q * ct, element_one, galois_keys, key_stride, Q, 1,
+                                      rot + size_t(j) * Q * ct, s));
     HEAMD_TRY_STATUS(Ops::forward_ntt(ring, rot, size_t(b) * Q * 2, s));
 
     heamd::PnnsBsgsLayout layout{};
@@ -388,8 +381,7 @@ int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typen
         W* current = products + size_t(G - 1) * Q * now * ct;
         W* other = sums;
         for (uint32_t g = G - 1; g-- > 0;) {
-            HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, current, element_baby, galois_keys + 1, key_stride, groups, group_size * now,
-                                         other, s));
+            HEAMD_TRY_STATUS(apply_galois(ctx->bfv, L, current, element_baby, galois_keys + 1, key_stride, Q, now, other, s));
             HEAMD_TRY_STATUS(Ops::add(ring, other, products + size_t(g) * Q * now * ct, Q * now * 2, s));
             current = other;
             other = current == sums ? sums + Q * now * ct : sums;
@@ -455,7 +447,7 @@ int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, 
         }
     }
     HEAMD_TRY_STATUS(response_buffers<W>(ctx, matrix, queries, out));
-    return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, 2, Q, 1, out, to_single, s);
+    return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, 2, Q, out, to_single, s);
 }
 
 // ---- mulTranspose(matrix:using:): query matrices of several rows ------------------------------------------------------------
@@ -539,75 +531,42 @@ int query_plan(const he_pnns_context* ctx, size_t matrix_rows, size_t cols, size
 }
 
 // Ciphertexts of (position, client): the rows of the clients' queries, later the half-chunks of their results.  A Galois call
-// of 8-byte words takes a key per ciphertext, so there positions are the outer index and a prefix of positions over all clients
-// is one contiguous batch; the 4-byte call takes one key, so there a client's positions are contiguous and a step is one call per
-// client.
+// takes a key per ciphertext, so positions are the outer index and a run of positions over all clients is one contiguous batch.
 template <typename Ops>
 struct Grid {
     using W = typename Ops::Word;
-    static constexpr bool kClientMajor = sizeof(W) == 4;
     const he_pnns_context* ctx;
-    size_t positions, clients, ct;  // ct: words of a ciphertext
+    size_t clients, ct;  // ct: words of a ciphertext
     uint32_t L;
-    const W* const* keys;           // [clients][key_stride]
-    size_t key_stride;
-    const std::vector<const W*>* tiled;  // 8-byte words: [slot][position-major over clients], as many positions as any grid has
+    const std::vector<const W*>* tiled;  // [slot][position-major over clients], as many positions as any grid has
     size_t tiled_stride;
     he_stream s;
 
-    size_t index(size_t position, size_t client) const {
-        return kClientMajor ? client * positions + position : position * clients + client;
-    }
-    // positions [0, count) of every client: out = in under the Galois element, with the clients' keys of `slot`
+    // positions [first, first + count) of every client: out = in under the Galois element, with the clients' keys of `slot`
     int rotate(const W* in, W* out, uint64_t element, size_t slot, size_t first, size_t count) const {
         if (count == 0) return HE_OK;
-        if constexpr (!kClientMajor) {
-            return Ops::rotate(ctx->bfv, L, in + first * clients * ct, element, tiled->data() + slot * tiled_stride, 1,
-                               count * clients, 1, out + first * clients * ct, s);
-        } else {
-            for (size_t q = 0; q < clients; ++q)
-                HEAMD_TRY_STATUS(Ops::rotate(ctx->bfv, L, in + index(first, q) * ct, element, keys + q * key_stride + slot,
-                                             key_stride, 1, count, out + index(first, q) * ct, s));
-            return HE_OK;
-        }
+        return apply_galois(ctx->bfv, L, in + first * clients * ct, element, tiled->data() + slot * tiled_stride, 1,
+                            count * clients, 1, out + first * clients * ct, s);
     }
-    // lhs positions [first, first + count) += rhs positions [rhs_first, ..) of a grid of `rhs_positions` positions
-    int add(const he_poly_context* ring, W* lhs, size_t first, const W* rhs, size_t rhs_positions, size_t rhs_first,
-            size_t count) const {
+    // lhs positions [first, first + count) += rhs positions [rhs_first, ..)
+    int add(const he_poly_context* ring, W* lhs, size_t first, const W* rhs, size_t rhs_first, size_t count) const {
         if (count == 0) return HE_OK;
-        if constexpr (!kClientMajor) {
-            return Ops::add(ring, lhs + first * clients * ct, rhs + rhs_first * clients * ct, count * clients * 2, s);
-        } else {
-            for (size_t q = 0; q < clients; ++q)
-                HEAMD_TRY_STATUS(Ops::add(ring, lhs + index(first, q) * ct, rhs + (q * rhs_positions + rhs_first) * ct,
-                                          count * 2, s));
-            return HE_OK;
-        }
+        return Ops::add(ring, lhs + first * clients * ct, rhs + rhs_first * clients * ct, count * clients * 2, s);
     }
-    // dst positions [first, first + count) = src positions [src_first, ..) of a grid of `src_positions` positions
-    hipError_t copy(W* dst, size_t first, const W* src, size_t src_positions, size_t src_first, size_t count) const {
+    // dst positions [first, first + count) = src positions [src_first, ..)
+    hipError_t copy(W* dst, size_t first, const W* src, size_t src_first, size_t count) const {
         if (count == 0) return hipSuccess;
-        hipStream_t stream = as_stream(s);
-        if constexpr (!kClientMajor) {
-            return hipMemcpyAsync(dst + first * clients * ct, src + src_first * clients * ct, count * clients * ct * sizeof(W),
-                                  hipMemcpyDeviceToDevice, stream);
-        } else {
-            return hipMemcpy2DAsync(dst + first * ct, positions * ct * sizeof(W), src + src_first * ct,
-                                    src_positions * ct * sizeof(W), count * ct * sizeof(W), clients, hipMemcpyDeviceToDevice,
-                                    stream);
-        }
+        return hipMemcpyAsync(dst + first * clients * ct, src + src_first * clients * ct, count * clients * ct * sizeof(W),
+                              hipMemcpyDeviceToDevice, as_stream(s));
     }
 };
 
-// src: `unit` words per (position, client) in the layout of Grid<Ops> with `positions` positions; position `from` of every
-// client goes to dst [clients][dst_positions][unit] at `to`
-template <typename Ops>
-hipError_t to_client_major(typename Ops::Word* dst, size_t dst_positions, size_t to, const typename Ops::Word* src,
-                           size_t positions, size_t from, size_t clients, size_t unit, hipStream_t stream) {
-    using W = typename Ops::Word;
-    const size_t src_index = Grid<Ops>::kClientMajor ? from : from * clients;
-    const size_t src_pitch = Grid<Ops>::kClientMajor ? positions * unit : unit;
-    return hipMemcpy2DAsync(dst + to * unit, dst_positions * unit * sizeof(W), src + src_index * unit, src_pitch * sizeof(W),
+// src: `unit` words per (position, client) in the layout of Grid; position `from` of every client goes to
+// dst [clients][dst_positions][unit] at `to`
+template <typename W>
+hipError_t to_client_major(W* dst, size_t dst_positions, size_t to, const W* src, size_t from, size_t clients, size_t unit,
+                           hipStream_t stream) {
+    return hipMemcpy2DAsync(dst + to * unit, dst_positions * unit * sizeof(W), src + from * clients * unit, unit * sizeof(W),
                             unit * sizeof(W), clients, hipMemcpyDeviceToDevice, stream);
 }
 
@@ -661,7 +620,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
     }
     HEAMD_TRY_STATUS(response_buffers<W>(ctx, matrix, queries, out));
     if (R == 1)  // one row: the vector's own ciphertext, and rotateColumnsAndSum of one element
-        return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, key_stride, Q, 1, out, to_single, s);
+        return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, key_stride, Q, out, to_single, s);
     if (reinterpret_cast<uintptr_t>(queries) % 16 != 0) return invalid_argument("the queries must be 16-byte aligned");
     HEAMD_TRY_STATUS(ctx->plaintext->check_device());
     const heamd::PolyContext* q_ctx = bfv.ciphertext(L);
@@ -678,14 +637,12 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
     for (size_t k = 0; k < R; ++k) position_of[row_of[k]] = static_cast<uint32_t>(k);
     const size_t halves = cps > 0 ? dividing_ceil(R, cps) : 0;
     const size_t most_positions = R > halves ? R : halves;
-    std::vector<const W*> tiled;  // [slot][position][client]: the key of `slot` for every ciphertext of a batch
-    if (!Grid<Ops>::kClientMajor && galois_keys != nullptr) {
-        tiled.resize(key_stride * most_positions * Q);
-        for (size_t slot = 0; slot < key_stride; ++slot)
-            for (size_t v = 0; v < most_positions * Q; ++v)
-                tiled[slot * most_positions * Q + v] = galois_keys[(v % Q) * key_stride + slot];
-    }
-    Grid<Ops> grid{ctx, R, Q, ct, L, galois_keys, key_stride, &tiled, most_positions * Q, s};
+    // [slot][position][client]: the key of `slot` for every ciphertext of a batch (several rows need the swap: there are keys)
+    std::vector<const W*> tiled(key_stride * most_positions * Q);
+    for (size_t slot = 0; slot < key_stride; ++slot)
+        for (size_t v = 0; v < most_positions * Q; ++v)
+            tiled[slot * most_positions * Q + v] = galois_keys[(v % Q) * key_stride + slot];
+    Grid<Ops> grid{ctx, Q, ct, L, &tiled, most_positions * Q, s};
 
     Scratch rows_mem(stream);
     HEAMD_HIP_TRY(rows_mem.allocate(V * ct_bytes));
@@ -711,8 +668,6 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
         heamd::PnnsExtractLayout layout{};
         layout.clients = Q;
         layout.query_ciphertexts = K;
-        layout.row_stride = Grid<Ops>::kClientMajor ? 1 : Q;
-        layout.client_stride = Grid<Ops>::kClientMajor ? R : 1;
         const heamd::DeviceContext dc = q_ctx->device_context(L);
         for (size_t k = 0; k < K; ++k) {
             const size_t first = k * query.rows_per_ciphertext;
@@ -735,32 +690,24 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
         for (uint32_t step = 0; step < most; ++step) {
             while (query.rows[row_of[live - 1]].rotate_count <= step) --live;
             HEAMD_TRY_STATUS(grid.rotate(running, ahead, element_columns, 3, 0, live));
-            HEAMD_TRY_STATUS(grid.add(ring, extracted, 0, ahead, R, 0, live));
+            HEAMD_TRY_STATUS(grid.add(ring, extracted, 0, ahead, 0, live));
             running = ahead;
             std::swap(ahead, behind);
         }
         HEAMD_TRY_STATUS(grid.rotate(extracted, ahead, element_swap, 2, 0, R));
-        HEAMD_TRY_STATUS(grid.add(ring, extracted, 0, ahead, R, 0, R));
+        HEAMD_TRY_STATUS(grid.add(ring, extracted, 0, ahead, 0, R));
     }
 
     // 4) mulTranspose(vector:) of every row: the rows share the passes over the matrix
-    std::vector<const W*> pairs;
-    if (!Grid<Ops>::kClientMajor && galois_keys != nullptr) {
-        pairs.resize(2 * V);
-        for (size_t v = 0; v < V; ++v) {
-            pairs[2 * v] = galois_keys[(v % Q) * key_stride];
-            pairs[2 * v + 1] = galois_keys[(v % Q) * key_stride + 1];
-        }
+    std::vector<const W*> pairs(2 * V);
+    for (size_t v = 0; v < V; ++v) {
+        pairs[2 * v] = galois_keys[(v % Q) * key_stride];
+        pairs[2 * v + 1] = galois_keys[(v % Q) * key_stride + 1];
     }
     Scratch results_mem(stream), single_mem(stream), levels_mem(stream);
     HEAMD_HIP_TRY(results_mem.allocate(V * C * ct_bytes));
     W* results = static_cast<W*>(results_mem.get());  // the grid of [C] results
-    if (Grid<Ops>::kClientMajor) {
-        HEAMD_TRY_STATUS(bsgs_product<Ops>(ctx, plan, matrix, extracted, galois_keys, key_stride, Q, R, results, false, s));
-    } else {
-        HEAMD_TRY_STATUS(bsgs_product<Ops>(ctx, plan, matrix, extracted, galois_keys != nullptr ? pairs.data() : nullptr, 2, V, 1,
-                                           results, false, s));
-    }
+    HEAMD_TRY_STATUS(bsgs_product<Ops>(ctx, plan, matrix, extracted, pairs.data(), 2, V, results, false, s));
     const size_t out_ct = to_single ? 2 * n : ct;
     auto allocate_levels = [&](size_t batch) -> hipError_t {
         const size_t words = to_single ? Ops::to_single_scratch_words(L, batch, n) : 0;
@@ -776,7 +723,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
             source = static_cast<const W*>(single_mem.get());
         }
         for (size_t r = 0; r < R; ++r)
-            HEAMD_HIP_TRY(to_client_major<Ops>(out, R, r, source, R, position_of[r], Q, C * out_ct, stream));
+            HEAMD_HIP_TRY(to_client_major(out, R, r, source, position_of[r], Q, C * out_ct, stream));
         return HE_OK;
     }
 
@@ -786,7 +733,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
     const size_t last_parity = (halves - 1) & 1, before = last_parity == 1 ? (halves + 1) / 2 : halves / 2;
     auto half_position = [&](size_t j) { return ((j & 1) == last_parity ? before : 0) + (j >> 1); };
     const size_t last_length = R - (halves - 1) * cps;
-    Grid<Ops> sums{ctx, halves, Q, ct, L, galois_keys, key_stride, &tiled, most_positions * Q, s};
+    Grid<Ops> sums{ctx, Q, ct, L, &tiled, most_positions * Q, s};
     Scratch sums_mem(stream);
     HEAMD_HIP_TRY(sums_mem.allocate(2 * halves * Q * ct_bytes));
     W* current = static_cast<W*>(sums_mem.get());
@@ -796,7 +743,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
         HEAMD_TRY_STATUS(he_galois_element_rotating_columns(pack_steps[i].step, n, &elements[i]));
     for (size_t j = 0; j < halves; ++j) {  // the accumulator is the half's last element (HeScheme.swift:118)
         const size_t length = j + 1 < halves ? cps : last_length;
-        HEAMD_HIP_TRY(sums.copy(current, half_position(j), results, R, position_of[j * cps + length - 1], 1));
+        HEAMD_HIP_TRY(sums.copy(current, half_position(j), results, position_of[j * cps + length - 1], 1));
     }
     size_t live = halves;
     W* short_half = nullptr;  // where the short half's sum was when it ran out of elements
@@ -814,10 +761,10 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
         for (size_t j = 0; j < halves; ++j) {
             if (half_position(j) >= live) continue;
             const size_t length = j + 1 < halves ? cps : last_length;
-            HEAMD_TRY_STATUS(sums.add(ring, current, half_position(j), results, R, position_of[j * cps + length - 2 - step], 1));
+            HEAMD_TRY_STATUS(sums.add(ring, current, half_position(j), results, position_of[j * cps + length - 2 - step], 1));
         }
     }
-    if (short_half != nullptr && short_half != current) HEAMD_HIP_TRY(sums.copy(current, halves - 1, short_half, halves, halves - 1, 1));
+    if (short_half != nullptr && short_half != current) HEAMD_HIP_TRY(sums.copy(current, halves - 1, short_half, halves - 1, 1));
     // swapRowsAndAdd (:281-286, HeScheme.swift:143-151): the second half's sum is swapped, the first half's added to it
     const size_t seconds = halves / 2;
     const size_t second_first = half_position(1 < halves ? 1 : 0), first_first = half_position(0);
@@ -825,7 +772,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
         uint64_t element_swap = 0;
         HEAMD_TRY_STATUS(he_galois_element_swapping_rows(n, &element_swap));
         HEAMD_TRY_STATUS(sums.rotate(current, other, element_swap, 2, second_first, seconds));
-        HEAMD_TRY_STATUS(sums.add(ring, other, second_first, current, halves, first_first, seconds));
+        HEAMD_TRY_STATUS(sums.add(ring, other, second_first, current, first_first, seconds));
     }
     // 6) the M packed ciphertexts of every client, through modSwitchDownToSingle for the response
     W* packed = out;
@@ -835,8 +782,8 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
     }
     for (size_t m = 0; m < M; ++m) {
         const bool whole = m < seconds;
-        HEAMD_HIP_TRY(to_client_major<Ops>(packed, M, m, whole ? other : current, halves, (whole ? second_first : first_first) + m,
-                                           Q, ct, stream));
+        HEAMD_HIP_TRY(to_client_major(packed, M, m, whole ? other : current, (whole ? second_first : first_first) + m, Q, ct,
+                                      stream));
     }
     if (to_single) {
         HEAMD_HIP_TRY(allocate_levels(Q * M));

@@ -550,7 +550,6 @@ struct ExtractBatch {
     uint32_t count, first_row;               // the rows of this launch: masks first_row + i
     uint32_t ciphertext, query_ciphertexts;
     size_t poly_words;                       // L N
-    size_t row_stride, client_stride;        // in ciphertexts
 };
 
 // A lane owns 16 bytes of one polynomial of one client's query ciphertext (blockIdx.y: polynomial, blockIdx.z: client): it
@@ -589,7 +588,7 @@ __global__ __launch_bounds__(kRowThreads) void pnns_extract_rows_kernel(const W*
         } else {
             packed = Words4{lo32(product[0]), lo32(product[1]), lo32(product[2]), lo32(product[3])};
         }
-        const size_t target = batch.positions[i] * batch.row_stride + client * batch.client_stride;
+        const size_t target = static_cast<size_t>(batch.positions[i]) * gridDim.z + client;  // position-major over clients
         __builtin_nontemporal_store(packed, reinterpret_cast<Words4*>(out + (target * 2 + polynomial) * batch.poly_words + word));
     }
 }
@@ -638,8 +637,6 @@ hipError_t launch_pnns_extract_rows(const W* queries, const W* masks, W* out, co
         batch.ciphertext = ciphertext;
         batch.query_ciphertexts = static_cast<uint32_t>(layout.query_ciphertexts);
         batch.poly_words = poly_words;
-        batch.row_stride = layout.row_stride;
-        batch.client_stride = layout.client_stride;
         const dim3 grid(static_cast<unsigned>(blocks), 2, static_cast<unsigned>(layout.clients));
         if (uniform) {
             hipLaunchKernelGGL((pnns_extract_rows_kernel<W, true>), grid, dim3(kRowThreads), 0, stream, queries, masks, out, ctx,

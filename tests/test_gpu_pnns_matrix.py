@@ -56,9 +56,10 @@ def setup_for(oracle, degree, L, word32=False):
 
 class Case:
     """Inputs of one call: the matrix, Q clients' queries and keys (a key per Galois element, so two slots of one element hold
-    the same words, as a real evaluation key does)."""
+    the same words, as a real evaluation key does).  shared: {client: the client whose keys it is handed, words and device
+    tensors alike}."""
 
-    def __init__(self, s, rows, cols, row_count, clients, plan, seed, baby_step=None):
+    def __init__(self, s, rows, cols, row_count, clients, plan, seed, baby_step=None, shared=None):
         import torch
 
         self.s, self.rows, self.cols, self.row_count, self.clients, self.plan = s, rows, cols, row_count, clients, list(plan)
@@ -79,16 +80,20 @@ class Case:
         elements = sorted({element_of(step) for step, needed in zip(self.slot_steps, self.slot_needed) if needed})
         # per client: element -> words, drawn in the order of the elements, so a plan's order does not change a key
         self.keys = [{element: uniform_words(rng, ks_moduli, (L, 2), n) for element in elements} for _ in range(clients)]
+        for client, other in (shared or {}).items():
+            self.keys[client] = self.keys[other]
 
     def device_keys(self, drop=None):
         """Per client the list of 4 + len(plan) device tensors, None where the shape does not need the slot (or slot `drop`)."""
         element_of = element_of_for(self.s.degree)
-        out = []
+        rows = {}  # one row of tensors per distinct key set
         for by_element in self.keys:
+            if id(by_element) in rows:
+                continue
             cache = {element: to_device(self.s, words) for element, words in by_element.items()}
-            out.append([cache[element_of(step)] if needed and slot != drop else None
-                        for slot, (step, needed) in enumerate(zip(self.slot_steps, self.slot_needed))])
-        return out
+            rows[id(by_element)] = [cache[element_of(step)] if needed and slot != drop else None
+                                    for slot, (step, needed) in enumerate(zip(self.slot_steps, self.slot_needed))]
+        return [rows[id(by_element)] for by_element in self.keys]
 
     def expected(self):
         """-> (mulTranspose [Q][M][2][L][N], response [Q][M][2][1][N])"""
@@ -181,6 +186,22 @@ def test_words_u32(oracle, index):
     degree, _, rows, cols, row_count, clients = TABLE[index]
     s = get_setup(oracle, degree, word32=True)
     check(Case(s, rows, cols, row_count, clients, default_plan(degree, rows, cols, row_count), 32 * degree + row_count))
+
+
+@pytest.mark.parametrize("word32", [False, True])
+def test_two_clients_share_keys_next_to_a_third(oracle, word32):
+    """TABLE[1] (R = 5: all five slots) with a third client, clients 0 and 1 handed the same device key tensors in every slot and client
+    2 its own: in each Galois batch a run of two equal keys lies next to a run of one.  Queries are distinct per client, the
+    expected words come per client from the restatement with that client's keys."""
+    s = get_setup(oracle, 64, word32=word32)
+    assert s.ref.L == 3
+    case = Case(s, 10, 4, 5, 3, [(10, 1)], 64 * 5 + 3, shared={1: 0})
+    keys = case.device_keys()
+    for slot, needed in enumerate(case.slot_needed):
+        assert needed and keys[0][slot] is keys[1][slot]
+        assert keys[2][slot].data_ptr() != keys[0][slot].data_ptr()
+    assert not np.array_equal(case.query[0], case.query[1])
+    check(case)
 
 
 def test_missing_keys_leave_out_untouched(oracle):

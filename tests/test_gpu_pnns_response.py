@@ -145,6 +145,32 @@ def test_words_u32(oracle, degree):
     check(s, degree + 1, 100 if degree > 64 else 30, 16 if degree > 64 else 8, 5, degree + 5)  # Q = 5: two passes
 
 
+def test_u32_two_queries_share_keys_next_to_a_third(oracle):
+    """Q = 3 at N = 64 on 4-byte words, queries 0 and 1 under the same device key tensors and query 2 under its own: a run of
+    two equal keys next to a run of one inside each Galois batch.  1 x 3 is the smallest shape with baby_step > 1 and
+    giant_step > 1 (P = 4: 2 x 2), so both the rotations by -1 and the sum's rotation by -baby_step see the runs."""
+    rows, cols, queries = 1, 3, 3
+    s = get_setup(oracle, 64, word32=True)
+    rng = np.random.default_rng(643)
+    values, query, keys = random_inputs(s, rng, rows, cols, queries)
+    keys[1] = keys[0]
+    baby_step, giant_step = pnns.baby_step_giant_step(cols)
+    assert baby_step > 1 and giant_step > 1
+    assert not np.array_equal(query[0], query[1])
+    matrix, flag = s.pnns.diagonal_matrix(values)
+    assert int(flag.item()) == 0
+    own = device_keys(s, [keys[0], keys[2]], baby_step, giant_step)
+    galois = [own[0], own[0], own[1]]
+    device_query = to_device(s, query)
+    got_full = s.to_host(s.pnns.mul_transpose(matrix, rows, cols, device_query, galois))
+    got_single = s.to_host(s.pnns.compute_response(matrix, rows, cols, device_query, galois))
+    full, single = expected_words(s, s.to_host(matrix), rows, cols, baby_step, query, keys)
+    assert got_full.shape == full.shape and got_single.shape == single.shape
+    assert full.any() and single.any()
+    assert np.array_equal(got_full, full)
+    assert np.array_equal(got_single, single)
+
+
 # (degree, rows, cols, baby_step, queries)
 CASES = [
     (256, 300, 100, 12, 1),      # L = 2 below; P = 128, G = 11, the last giant step sums 8: ragged
