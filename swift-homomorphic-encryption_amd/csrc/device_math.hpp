@@ -854,4 +854,32 @@ __device__ __forceinline__ uint64_t barrett_reduce128(U128 x, uint64_t p, uint64
     return csub63(x.lo - q_lo * p, 0 - p);
 }
 
+// ---- 4-byte words (word32_kernels.hip: moduli <= 2^30 - 1) ------------------------------------------------------------
+__device__ __forceinline__ uint32_t csub32(uint32_t x, uint32_t m) { return x >= m ? x - m : x; }
+// x w mod p in [0, 2p) for any 32-bit x: Shoup with wf = floor(w 2^32 / p)
+__device__ __forceinline__ uint32_t shoup32_lazy(uint32_t x, uint32_t w, uint32_t wf, uint32_t p) {
+    return x * w - __umulhi(x, wf) * p;
+}
+// The same product on the full-width multiplier for the register passes: q = high word of x wf, then the low word of
+// x w + q (2^32 - p) -- three v_mad_u64_u32 (two issue slots each) against v_mul_hi_u32 (three to four), two
+// v_mul_lo_u32 (two each) and a subtract.  UNIFORM: the twiddle is wave-uniform and read from SGPRs (one scalar operand
+// per instruction); neg_p = 2^32 - p always is.
+template <bool UNIFORM>
+__device__ __forceinline__ uint32_t shoup32_lazy_mad(uint32_t x, uint32_t w, uint32_t wf, uint32_t neg_p) {
+    uint64_t q, t, carry;
+    if constexpr (UNIFORM) {
+        asm("v_mad_u64_u32 %0, %2, %3, %4, 0\n\t"
+            "v_mad_u64_u32 %1, %2, %3, %5, 0"
+            : "=&v"(q), "=&v"(t), "=&s"(carry)
+            : "v"(x), "s"(wf), "s"(w));
+    } else {
+        asm("v_mad_u64_u32 %0, %2, %3, %4, 0\n\t"
+            "v_mad_u64_u32 %1, %2, %3, %5, 0"
+            : "=&v"(q), "=&v"(t), "=&s"(carry)
+            : "v"(x), "v"(wf), "v"(w));
+    }
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %0" : "+v"(t), "=&s"(carry) : "v"(static_cast<uint32_t>(q >> 32)), "s"(neg_p));
+    return static_cast<uint32_t>(t);
+}
+
 }  // namespace heamd
