@@ -16,6 +16,7 @@
 #include "device_context.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_grid.hpp"
 
 namespace heamd {
 
@@ -23,21 +24,13 @@ namespace {
 
 constexpr unsigned kThreads = 256;
 
-constexpr size_t kGridCap = (size_t(1) << 31) - 1;
 // One workgroup per kThreads work items, up to the grid limit: the kernels keep their grid-stride loops for what lies beyond it,
 // but a lane that walks many items serialises its loads -- divideAndRoundQLast at N = 16384, L = 6 ran at 0.66 of 8 TB/s on
 // 256 x 8 workgroups and at 0.79 with one item per lane (profiles/r06y_exact_grids.txt)
-inline unsigned grid_for(size_t work_items) {
-    const size_t blocks = (work_items + kThreads - 1) / kThreads;
-    const size_t cap = kGridCap;
-    return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-}
+inline unsigned grid_for(size_t work_items) { return launch_grid::grid_for(work_items, kThreads); }
 // ... except the gathers that measured faster on a few workgroups per CU walking their items (the Coeff-form automorphism:
 // 0.67 against 0.57 of 8 TB/s; the plaintext unlift)
-inline unsigned grid_capped(size_t work_items) {
-    const unsigned blocks = grid_for(work_items);
-    return blocks < 256u * 8u ? blocks : 256u * 8u;
-}
+inline unsigned grid_capped(size_t work_items) { return launch_grid::grid_for(work_items, kThreads, 256u * 8u); }
 
 // Output word j of a row takes input word src (sign flipped when `negate`): shared by the automorphism and by the
 // multiplication by a power of x, which differ only in how the doubled index i in [0, 2N) is derived from j.
@@ -209,7 +202,7 @@ hipError_t launch_expand_move(const uint64_t* src, uint64_t* dst, const uint32_t
     if (words == 0) return hipSuccess;
     const size_t ct_words = (size_t(2) * ctx.moduli_count) << ctx.log_degree, blocks = words / (2 * kThreads);
     if (kExpandMovePairs && ctx.degree >= 2 * kThreads && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0 &&
-        blocks < (size_t(1) << 31) && queries * count < (size_t(1) << 31)) {
+        launch_grid::launch_fits(blocks, kThreads)) {  // (queries * count <= blocks: the kernel's 32-bit item and count fit too)
         hipLaunchKernelGGL(expand_move_pairs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, src, dst, table, ctx,
                            static_cast<uint32_t>(count), src_stride, dst_stride, static_cast<uint32_t>(ct_words / (2 * kThreads)));
         return hipGetLastError();
@@ -577,7 +570,7 @@ hipError_t launch_pack_rows(const uint64_t* slab, uint64_t* packed, const Packed
                             size_t polys, hipStream_t stream) {
     const size_t rows = polys * layout.rows;
     if (rows == 0) return hipSuccess;
-    if (log_degree < 6 || rows > 0x7fffffffull) return hipErrorInvalidValue;
+    if (log_degree < 6 || !launch_grid::launch_fits(rows, kTileWaves * 64)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pack_rows_kernel, dim3(static_cast<unsigned>(rows)), dim3(kTileWaves * 64), 0, stream, slab, packed,
                        layout, log_degree);
     return hipGetLastError();
@@ -587,7 +580,7 @@ hipError_t launch_serialize(const uint64_t* slab, uint8_t* bytes, const Serializ
                             uint32_t skip_lsbs, size_t batch, hipStream_t stream) {
     const size_t total = batch * layout.byte_offset[layout.rows];
     if (total == 0) return hipSuccess;
-    if (tile_aligned(layout, bytes, slab, log_degree) && batch * layout.rows <= 0x7fffffffull) {
+    if (tile_aligned(layout, bytes, slab, log_degree) && launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64)) {
         hipLaunchKernelGGL(serialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)), dim3(kTileWaves * 64), 0,
                            stream, slab, bytes, layout, log_degree, skip_lsbs);
         return hipGetLastError();
@@ -606,7 +599,7 @@ hipError_t launch_deserialize(const uint8_t* bytes, uint64_t* slab, const Serial
                               uint32_t skip_lsbs, size_t bytes_per_poly, size_t batch, hipStream_t stream) {
     const size_t total = (batch * layout.rows) << log_degree;
     if (total == 0) return hipSuccess;
-    if (tile_aligned(layout, bytes, slab, log_degree) && (bytes_per_poly & 15) == 0 && batch * layout.rows <= 0x7fffffffull) {
+    if (tile_aligned(layout, bytes, slab, log_degree) && (bytes_per_poly & 15) == 0 && launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64)) {
         hipLaunchKernelGGL(deserialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)), dim3(kTileWaves * 64),
                            0, stream, bytes, slab, layout, log_degree, skip_lsbs, bytes_per_poly);
         return hipGetLastError();

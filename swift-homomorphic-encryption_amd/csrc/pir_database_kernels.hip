@@ -4,6 +4,7 @@
 // into N coefficients of floor(log2 t) bits (CoefficientPacking.bytesToCoefficients, CoefficientPacking.swift:59-136) and
 // writes the slot's present byte.  The centred lift and forward NTT that follow are the existing Plaintext.convertToEvalFormat
 // kernels (pir_database.cpp).
+#include "launch_grid.hpp"
 #include "pir_database.hpp"
 
 namespace heamd {
@@ -11,7 +12,7 @@ namespace heamd {
 namespace {
 
 constexpr unsigned kUnpackThreads = 256;
-// one workgroup per slot up to this many, grid-stride beyond: a launch stays far below 2^31 lanes for any database size
+// one workgroup per slot up to this many, grid-stride beyond: a launch stays far below the lane limit for any database size
 constexpr size_t kUnpackGridCap = size_t(1) << 20;
 
 // byte q of prefix(e) || entry_e || zeros (q < encoded): the prefix is the entry's size, little-endian (IndexPirProtocol.swift:
@@ -88,7 +89,7 @@ template <typename W>
 hipError_t launch_pir_database_unpack(const PirDatabaseLayout& layout, size_t first_slot, size_t slots, W* staging,
                                       uint8_t* present, hipStream_t stream) {
     if (slots == 0) return hipSuccess;
-    const unsigned grid = static_cast<unsigned>(slots < kUnpackGridCap ? slots : kUnpackGridCap);
+    const unsigned grid = launch_grid::grid_for_blocks(slots, kUnpackThreads, kUnpackGridCap);
     hipLaunchKernelGGL(pir_database_unpack_kernel<W>, dim3(grid), dim3(kUnpackThreads), 0, stream, layout, first_slot, slots,
                        staging, present);
     return hipGetLastError();

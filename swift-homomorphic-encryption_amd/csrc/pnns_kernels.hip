@@ -7,6 +7,7 @@
 // And CiphertextMatrix.extractDenseRow (CiphertextMatrix.swift:252-370) for query matrices of several rows: the masks, and the
 // product of every query ciphertext with the masks of all the rows packed in it.
 #include "kernels.hpp"
+#include "launch_grid.hpp"
 
 namespace heamd {
 
@@ -386,7 +387,7 @@ hipError_t launch_pnns_quantize_rows(const float* vectors, size_t rows, size_t c
     if (rows == 0 || cols == 0) return hipSuccess;
     const size_t rows_per_block = kQuantizeThreads / kQuantizeLanesPerRow;
     const size_t blocks = (rows + rows_per_block - 1) / rows_per_block;
-    const unsigned grid = static_cast<unsigned>(blocks < kQuantizeGridCap ? blocks : kQuantizeGridCap);
+    const unsigned grid = launch_grid::grid_for_blocks(blocks, kQuantizeThreads, kQuantizeGridCap);
     hipLaunchKernelGGL(pnns_quantize_rows_kernel, dim3(grid), dim3(kQuantizeThreads), 0, stream, vectors, rows, cols,
                        scaling_factor, reinterpret_cast<long long*>(out));
     return hipGetLastError();
@@ -420,7 +421,7 @@ hipError_t launch_pnns_diagonal_pack(const int64_t* values, const uint32_t* slot
     shape.first_run = static_cast<uint32_t>(first_run);
     const size_t tiles = (n + kPackWords - 1) / kPackWords;
     const size_t blocks = tiles * layout.plaintexts_per_column;
-    if (blocks >= (size_t(1) << 31) || last_run - first_run >= 65535) return hipErrorInvalidValue;
+    if (!launch_grid::launch_fits(blocks, kPackThreads) || last_run - first_run >= 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pnns_diagonal_pack_kernel<W>, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(last_run - first_run + 1)),
                        dim3(kPackThreads), 0, stream, reinterpret_cast<const long long*>(values), slot_of_word, shape, staging,
                        out_of_range);
@@ -448,7 +449,7 @@ hipError_t launch_bsgs(const W* rot, const W* matrix, W* out, const DeviceContex
     const size_t useful = (items + kWaves - 1) / kWaves;
     if (splits > useful) splits = useful;
     if (splits == 0) splits = 1;
-    if (word_blocks >= (size_t(1) << 31) || splits > 65535) return hipErrorInvalidValue;
+    if (!launch_grid::launch_fits(word_blocks, kThreads) || splits > 65535) return hipErrorInvalidValue;
     if (FAST && tile_bytes > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_bytes));
@@ -485,7 +486,7 @@ hipError_t launch_pnns_bsgs_inner_product(const W* rot, const W* matrix, W* out,
     shape.group_columns = layout.group_columns;
     shape.out_queries = layout.out_queries;
     if (shape.plaintext_words % kVector != 0 || ctx.moduli_count != layout.moduli_count) return hipErrorInvalidValue;
-    if (static_cast<size_t>(layout.giant_step) * layout.group_columns >= (size_t(1) << 31)) return hipErrorInvalidValue;
+    if (static_cast<size_t>(layout.giant_step) * layout.group_columns > INT32_MAX) return hipErrorInvalidValue;  // (no launch guard: the kernel counts its (g, c) items in 32 bits)
     const size_t tile_bytes = size_t(layout.baby_step) * 2 * queries * 1024;
     const bool fast = shape.plaintext_words % (64 * kVector) == 0 && (size_t(1) << layout.log_degree) >= 64 * kVector &&
                       tile_bytes <= kPnnsBsgsTileLimit;
@@ -626,7 +627,7 @@ hipError_t launch_pnns_extract_rows(const W* queries, const W* masks, W* out, co
     const size_t n = size_t(1) << ctx.log_degree;
     const size_t poly_words = static_cast<size_t>(ctx.moduli_count) * n;
     const size_t blocks = (poly_words / kVector + kRowThreads - 1) / kRowThreads;
-    if (poly_words % kVector != 0 || blocks >= (size_t(1) << 31) || layout.clients > 65535) return hipErrorInvalidValue;
+    if (poly_words % kVector != 0 || !launch_grid::launch_fits(blocks, kRowThreads) || layout.clients > 65535) return hipErrorInvalidValue;
     const bool uniform = n >= 64 * kVector;
     for (size_t first = 0; first < count; first += kPnnsRowsPerLaunch) {
         const unsigned now = static_cast<unsigned>(count - first < kPnnsRowsPerLaunch ? count - first : kPnnsRowsPerLaunch);

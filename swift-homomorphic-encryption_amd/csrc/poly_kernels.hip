@@ -12,6 +12,7 @@
 #include "device_context.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_grid.hpp"
 #include "placement.hpp"
 
 namespace heamd {
@@ -20,15 +21,10 @@ namespace {
 
 constexpr unsigned kThreads = 256;
 
-constexpr size_t kGridCap = (size_t(1) << 31) - 1;
 // One workgroup per kThreads work items, up to the grid limit: the kernels keep their grid-stride loops for what lies beyond it,
 // but a lane that walks many items serialises its loads -- divideAndRoundQLast at N = 16384, L = 6 ran at 0.66 of 8 TB/s on
 // 256 x 8 workgroups and at 0.79 with one item per lane (profiles/r06y_exact_grids.txt)
-inline unsigned grid_for(size_t work_items) {
-    const size_t blocks = (work_items + kThreads - 1) / kThreads;
-    const size_t cap = kGridCap;
-    return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-}
+inline unsigned grid_for(size_t work_items) { return launch_grid::grid_for(work_items, kThreads); }
 
 template <ElementwiseOp OP>
 __device__ __forceinline__ uint64_t apply(uint64_t a, uint64_t b, const DeviceModulus& m, U64x2 scalar) {
@@ -769,7 +765,7 @@ hipError_t launch_inner_product_plain_polys(const W* cts, const W* pts, const ui
         // several queries side by side: ciphertext words through LDS, four column sets per workgroup
         const size_t column_groups = (columns + COLS * kTileWavefronts - 1) / (COLS * kTileWavefronts);
         const size_t blocks = column_groups * (words_per_poly / kTileWords);
-        if (ctx.degree >= kThreads && cadence != 0 && blocks < (size_t(1) << 31)) {
+        if (ctx.degree >= kThreads && cadence != 0 && launch_grid::launch_fits(blocks, kTileWords * kTileWavefronts)) {
             const dim3 tile_grid(static_cast<unsigned>(blocks)), tile_block(kTileWords * kTileWavefronts);
             if (present_device != nullptr)
                 hipLaunchKernelGGL((inner_product_plain_tile_kernel<POLYS, COLS, NARROW, true, W>), tile_grid, tile_block, 0,
@@ -782,7 +778,7 @@ hipError_t launch_inner_product_plain_polys(const W* cts, const W* pts, const ui
             return hipGetLastError();
         }
     }
-    if (ctx.degree >= kThreads && cadence != 0 && static_cast<size_t>(grid.x) * grid.y < (size_t(1) << 31)) {
+    if (ctx.degree >= kThreads && cadence != 0 && launch_grid::launch_fits(static_cast<size_t>(grid.x) * grid.y, kThreads)) {
         // one-dimensional grid: the kernel places the column groups of a word block on one XCD itself
         if (present_device != nullptr)
             hipLaunchKernelGGL((inner_product_plain_rows_kernel<POLYS, COLS, NARROW, true, false, W>),
@@ -839,7 +835,7 @@ hipError_t launch_packed_polys(const uint64_t* cts, const uint64_t* packed_pts, 
     constexpr int kCols = 4;
     const size_t words_per_poly = static_cast<size_t>(ctx.moduli_count) * ctx.degree;
     const size_t column_groups = (columns + kCols - 1) / kCols, blocks = column_groups * (words_per_poly / kThreads);
-    if (blocks >= (size_t(1) << 31)) return hipErrorInvalidValue;
+    if (!launch_grid::launch_fits(blocks, kThreads)) return hipErrorInvalidValue;
     const dim3 grid(static_cast<unsigned>(blocks));
     if (present_device != nullptr)
         hipLaunchKernelGGL((inner_product_plain_rows_kernel<POLYS, kCols, NARROW, true, true, uint64_t>), grid,

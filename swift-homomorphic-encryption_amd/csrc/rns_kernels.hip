@@ -13,6 +13,7 @@
 
 #include "bfv_context.hpp"
 #include "device_math.hpp"
+#include "launch_grid.hpp"
 #include "rns_kernels.hpp"
 
 namespace heamd {
@@ -22,21 +23,13 @@ namespace {
 constexpr unsigned kThreads = 256;
 constexpr int kMaxL = 16;  // compile-time specialisations for L = 1..kMaxL (16 x 55 bits = the N = 32768 security cap)
 
-constexpr size_t kGridCap = (size_t(1) << 31) - 1;
 // One workgroup per kThreads work items, up to the grid limit: the kernels keep their grid-stride loops for what lies beyond it,
 // but a lane that walks many items serialises its loads -- divideAndRoundQLast at N = 16384, L = 6 ran at 0.66 of 8 TB/s on
 // 256 x 8 workgroups and at 0.79 with one item per lane (profiles/r06y_exact_grids.txt)
-inline unsigned grid_for(size_t work_items) {
-    const size_t blocks = (work_items + kThreads - 1) / kThreads;
-    const size_t cap = kGridCap;
-    return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-}
+inline unsigned grid_for(size_t work_items) { return launch_grid::grid_for(work_items, kThreads); }
 
 // one lane per work item, no striding (kernels that keep many table constants live)
-inline unsigned exact_grid(size_t work_items) {
-    const size_t blocks = (work_items + kThreads - 1) / kThreads;
-    return static_cast<unsigned>(blocks ? blocks : 1);
-}
+inline unsigned exact_grid(size_t work_items) { return launch_grid::exact_grid(work_items, kThreads); }
 
 __device__ __forceinline__ uint64_t reduce128(U128 x, const DeviceModulus& m) {
     return barrett_reduce128(x, m.p, m.barrett128_lo, m.barrett128_hi);
@@ -825,7 +818,7 @@ struct LiftLauncher {
     template <typename W>
     static hipError_t run(const W* in, W* out, const RnsToolDevice& tool, size_t polys, const LiftLayout& layout,
                           hipStream_t s) {
-        if (((polys << tool.log_degree) + kThreads - 1) / kThreads > 0x7fffffffull) return hipErrorInvalidValue;
+        if (!launch_grid::launch_fits(exact_grid(polys << tool.log_degree), kThreads)) return hipErrorInvalidValue;
         bool launched = false;
         if constexpr (sizeof(W) == 8) {
             if (tool.wide_reduce_ok != 0) {
@@ -862,7 +855,7 @@ template <int L>
 struct FloorLauncher {
     template <typename W>
     static hipError_t run(const W* in, W* out, const RnsToolDevice& tool, size_t polys, hipStream_t s) {
-        if (((polys << tool.log_degree) + kThreads - 1) / kThreads > 0x7fffffffull) return hipErrorInvalidValue;
+        if (!launch_grid::launch_fits(exact_grid(polys << tool.log_degree), kThreads)) return hipErrorInvalidValue;
         bool launched = false;
         if constexpr (sizeof(W) == 8) {
             if (tool.wide_reduce_ok != 0) {
@@ -890,7 +883,7 @@ struct PlaintextTranslateLauncher {
     template <typename W>
     static hipError_t run(W* ct, const W* plaintexts, const RnsToolDevice& tool, size_t ct_words, bool subtract, size_t batch,
                           hipStream_t s) {
-        if (((batch << tool.log_degree) + kThreads - 1) / kThreads > 0x7fffffffull) return hipErrorInvalidValue;
+        if (!launch_grid::launch_fits(exact_grid(batch << tool.log_degree), kThreads)) return hipErrorInvalidValue;
         const dim3 grid(exact_grid(batch << tool.log_degree));
         if (subtract)
             hipLaunchKernelGGL((plaintext_translate_kernel<L, W, true>), grid, dim3(kThreads), 0, s, ct, plaintexts, tool,
@@ -907,7 +900,7 @@ struct ScaleAndRoundLauncher {
     template <typename W>
     static hipError_t run(const W* in, W* out, const RnsToolDevice& tool, U64x2 final_scale, size_t polys,
                           hipStream_t s) {
-        if (((polys << tool.log_degree) + kThreads - 1) / kThreads > 0x7fffffffull) return hipErrorInvalidValue;
+        if (!launch_grid::launch_fits(exact_grid(polys << tool.log_degree), kThreads)) return hipErrorInvalidValue;
         hipLaunchKernelGGL((scale_and_round_kernel<L, W>), dim3(exact_grid(polys << tool.log_degree)), dim3(kThreads), 0,
                            s, in, out, tool, final_scale, polys);
         return hipGetLastError();
@@ -1012,7 +1005,7 @@ hipError_t launch_tensor_accumulate_shared_sums(const uint64_t* lhs, const uint6
                                                 uint64_t cadence, hipStream_t stream) {
     if (items == 0) return hipSuccess;
     const size_t total = size_t(qbsk.moduli_count) << qbsk.log_degree;
-    if (cadence == 0 || qbsk.degree < kThreads || total / kThreads >= (size_t(1) << 31)) return hipErrorNotSupported;
+    if (cadence == 0 || qbsk.degree < kThreads || !launch_grid::launch_fits(total / kThreads, kThreads)) return hipErrorNotSupported;
     const size_t right = rhs_q != nullptr ? size_t(q_rows) << qbsk.log_degree : 0;
     for (size_t done = 0; done < items; done += 65535) {  // grid.y carries the item
         const size_t now = items - done < 65535 ? items - done : 65535;
@@ -1031,10 +1024,9 @@ hipError_t launch_tensor_accumulate_shared(const W* lhs, const W* rhs, W* out, c
                                            size_t items, uint64_t max_lazy, hipStream_t stream) {
     if (items == 0) return hipSuccess;
     const size_t total = size_t(qbsk.moduli_count) << qbsk.log_degree;
-    const size_t blocks = (total + kThreads - 1) / kThreads;
     for (size_t done = 0; done < items; done += 65535) {  // grid.y carries the item
         const size_t now = items - done < 65535 ? items - done : 65535;
-        hipLaunchKernelGGL(tensor_accumulate_shared_kernel<W>, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(now)),
+        hipLaunchKernelGGL(tensor_accumulate_shared_kernel<W>, dim3(grid_for(total), static_cast<unsigned>(now)),
                            dim3(kThreads), 0, stream, lhs, rhs + done * count * 2 * total, out + done * 3 * total, qbsk,
                            count, max_lazy);
         hipError_t e = hipGetLastError();

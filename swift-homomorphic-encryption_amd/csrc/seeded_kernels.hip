@@ -23,6 +23,7 @@
 #include "device_context.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_grid.hpp"
 
 namespace heamd {
 
@@ -310,14 +311,14 @@ hipError_t launch_seeded_uniform(const uint8_t* seeds, uint64_t* out, const Devi
     const size_t words = static_cast<size_t>(ctx.moduli_count) << ctx.log_degree;
     const size_t chunks = (words + kChunkBlocks - 1) / kChunkBlocks;
     const size_t chain_blocks = (batch + kChainSeedsPerWave - 1) / kChainSeedsPerWave, total_chunks = batch * chunks;
-    if (chain_blocks > 0x7fffffffull || chunks > 0xffffffffull) return hipErrorInvalidValue;
+    if (!launch_grid::launch_fits(chain_blocks, 64) || chunks > 0xffffffffull) return hipErrorInvalidValue;
     uint32_t* chain = static_cast<uint32_t*>(scratch);
     hipLaunchKernelGGL(seeded_chain_kernel, dim3(static_cast<unsigned>(chain_blocks)), dim3(64), 0, stream, seeds, chain,
                        batch, static_cast<uint32_t>(chunks));
     hipError_t status = hipGetLastError();
     if (status != hipSuccess) return status;
-    const size_t stream_blocks = (total_chunks + kStreamWaves - 1) / kStreamWaves, cap = 256 * 16;
-    hipLaunchKernelGGL(seeded_stream_kernel, dim3(static_cast<unsigned>(stream_blocks < cap ? stream_blocks : cap)),
+    const size_t stream_blocks = (total_chunks + kStreamWaves - 1) / kStreamWaves;
+    hipLaunchKernelGGL(seeded_stream_kernel, dim3(launch_grid::grid_for_blocks(stream_blocks, 64 * kStreamWaves, 256 * 16)),
                        dim3(64 * kStreamWaves), 0, stream, chain, out, ctx, static_cast<uint32_t>(chunks), total_chunks);
     return hipGetLastError();
 }

@@ -11,18 +11,15 @@
 //   simple_pir_response_kernel   computeResponse (SimplePir+Server.swift:31-38, SimplePir+Precompute.swift:51-114)
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_grid.hpp"
 
 namespace heamd {
 
 namespace {
 
 constexpr unsigned kFlatThreads = 256;
-constexpr size_t kFlatGridCap = size_t(1) << 20;  // grid-stride beyond: no launch nears 2^31 lanes
-
-inline unsigned flat_grid(size_t items) {
-    const size_t blocks = (items + kFlatThreads - 1) / kFlatThreads;
-    return static_cast<unsigned>(blocks < kFlatGridCap ? blocks : kFlatGridCap);
-}
+// at most 2^20 workgroups, grid-stride beyond: no launch nears the lane limit
+inline unsigned flat_grid(size_t items) { return launch_grid::grid_for(items, kFlatThreads, size_t(1) << 20); }
 
 // element (r, c) of the transposed database: flat index f = c * column_size + r of the reference's untransposed array, which
 // holds entry e = f / padded at offset o = f % padded; coefficient o of an entry is bits [o b, (o + 1) b) of its bytes read
@@ -242,7 +239,7 @@ template <typename W, typename E, unsigned QT>
 hipError_t response_pass(const E* database, size_t rows, size_t columns, const W* requests, unsigned live, W* responses,
                          W mask, hipStream_t stream) {
     const size_t blocks = (rows + kBlockRows - 1) / kBlockRows;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (!launch_grid::launch_fits(blocks, kResponseThreads)) return hipErrorInvalidValue;
     hipLaunchKernelGGL((simple_pir_response_kernel<W, E, QT>), dim3(static_cast<unsigned>(blocks)), dim3(kResponseThreads), 0,
                        stream, database, rows, columns, requests, live, responses, mask);
     return hipGetLastError();

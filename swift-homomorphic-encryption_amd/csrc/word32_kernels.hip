@@ -14,6 +14,7 @@
 #include "device_context.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_grid.hpp"
 #include "ntt_common.hpp"
 #include "placement.hpp"
 
@@ -23,15 +24,10 @@ namespace {
 
 constexpr unsigned kThreads = 256;
 
-constexpr size_t kGridCap = (size_t(1) << 31) - 1;
 // One workgroup per kThreads work items, up to the grid limit: the kernels keep their grid-stride loops for what lies beyond it,
 // but a lane that walks many items serialises its loads -- divideAndRoundQLast at N = 16384, L = 6 ran at 0.66 of 8 TB/s on
 // 256 x 8 workgroups and at 0.79 with one item per lane (profiles/r06y_exact_grids.txt)
-inline unsigned grid_for(size_t work_items) {
-    const size_t blocks = (work_items + kThreads - 1) / kThreads;
-    const size_t cap = kGridCap;
-    return static_cast<unsigned>(blocks < cap ? (blocks ? blocks : 1) : cap);
-}
+inline unsigned grid_for(size_t work_items) { return launch_grid::grid_for(work_items, kThreads); }
 
 // +1 word per 32: de-conflicts the power-of-two strides of the late forward / early inverse stages
 __device__ __forceinline__ uint32_t slot32(uint32_t idx) { return idx + (idx >> 5); }
@@ -762,7 +758,7 @@ hipError_t launch_copy_records(const uint64_t* in, size_t src_stride, uint64_t* 
     if (records == 0 || record_words == 0) return hipSuccess;
     constexpr size_t block_words = 2 * size_t(kThreads) * kCopyRecordVectors;
     const size_t blocks_per_record = record_words / block_words;
-    if (record_words % block_words != 0 || (src_stride | dst_stride) % 2 != 0 || blocks_per_record * records >= (size_t(1) << 31) ||
+    if (record_words % block_words != 0 || (src_stride | dst_stride) % 2 != 0 || !launch_grid::launch_fits(blocks_per_record * records, kThreads) ||
         ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(copy_records_kernel, dim3(static_cast<unsigned>(blocks_per_record * records)), dim3(kThreads), 0, stream, in,

@@ -1313,6 +1313,15 @@ class BfvContext32(BfvContext):
                                                               0, _stream(stream)))
         return out
 
+    def inner_product_shared(self, lhs, rhs, moduli_count=None, stream=None):
+        L = self._L(moduli_count)
+        count = lhs.numel() // (2 * L * self.degree)
+        items = rhs.numel() // (count * 2 * L * self.degree)
+        out = self._empty32((items, 3, L, self.degree), lhs)
+        _check(load_library().he_bfv_inner_product_shared_device_u32(self.h, L, _ptr32(lhs), _ptr32(rhs), count, items,
+                                                                     _ptr32(out), _stream(stream)))
+        return out
+
     def pir_compute_response(self, dimensions, dim0_query_eval, remaining_query, database, chunk_count,
                              present_device=None, relinearization_key=None, stream=None):
         """he_pir_compute_response_device_u32: everything in packed UInt32 words -> [chunks][2][1][N] (int32)."""
