@@ -831,6 +831,40 @@ int he_simple_pir_compute_response_device_u32(uint32_t plaintext_bits, uint32_t 
                                               size_t column_size, size_t database_columns, const uint32_t* requests,
                                               size_t query_count, uint32_t* responses, he_stream s);
 
+/* computeResponse for LARGE request batches, on the int8 matrix cores (v_mfma_i32_16x16x64_i8).  Layouts, argument checks,
+ * error codes and results are those of he_simple_pir_compute_response_device(_u32): the words are identical.  The modulus
+ * is a power of two, so the product splits exactly into 7-bit limbs; one read of the database answers
+ * `requests_per_pass` requests (32, or 16 above 4 / 6 shift classes at 4- / 8-byte words) instead of eight.
+ * The matrix kernel covers 1-byte elements with plaintext_bits <= 7 and 2-byte elements with plaintext_bits <= 14, at both
+ * word sizes and every ciphertext_bits the entry above accepts; for plaintext_bits 8, 15, 16 and the 4- and 8-byte
+ * elements the call runs the existing reply kernel.  he_simple_pir_batch_response_plan says which, without a device.
+ * PRECONDITION on the matrix path: every element is below 2^plaintext_bits, as process and pack produce them -- a stray
+ * high bit would be read as a sign (the entry above multiplies whatever the element holds).  Request words may hold
+ * anything: bits at and above ciphertext_bits fall out under the final mask, as there.
+ * Enqueue-only on `s`, no scratch.
+ * When to call it: measured on one MI355X over 32768 x 32768 elements, this entry is the faster one from
+ * query_count 4 at 7 / 28 bits in 4-byte words and from 8 at 14 / 42 bits in 8-byte words (9 - 10 x at 32 and more); for a
+ * single request the entry above is faster (0.20 against 0.27 ms, 0.35 against 0.70 ms). */
+int he_simple_pir_compute_response_batch_device(uint32_t plaintext_bits, uint32_t ciphertext_bits, const void* database,
+                                                size_t column_size, size_t database_columns, const uint64_t* requests,
+                                                size_t query_count, uint64_t* responses, he_stream s);
+int he_simple_pir_compute_response_batch_device_u32(uint32_t plaintext_bits, uint32_t ciphertext_bits, const void* database,
+                                                    size_t column_size, size_t database_columns, const uint32_t* requests,
+                                                    size_t query_count, uint32_t* responses, he_stream s);
+/* What the batch entries do for a shape.  Host only: callable without a GPU.  Any out pointer may be NULL.
+ * HE_ERR_INVALID_ARGUMENT: word_bits not 32 / 64, ciphertext_bits <= plaintext_bits or above the word.
+ * HEAMD_SIMPLE_PIR_FOLD_COLUMNS=<columns> lowers the fold cadence (to a multiple of 64, never below 64) and never raises
+ * it; the plan reports the cadence in force.  Off the matrix path database_limbs and fold_columns are 0 and
+ * requests_per_pass is the existing kernel's 8. */
+int he_simple_pir_batch_response_plan(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t word_bits,
+                                      size_t database_columns, size_t query_count,
+                                      uint32_t* out_matrix_path,       /* 1: int8 matrix kernel, 0: the existing reply kernel */
+                                      uint32_t* out_database_limbs,    /* 1 (plaintext_bits <= 7) or 2 (9 .. 14) */
+                                      uint32_t* out_request_limbs,     /* ceil(ciphertext_bits / 7) = shift classes kept */
+                                      uint32_t* out_requests_per_pass, /* requests answered by one read of the database */
+                                      size_t* out_fold_columns,        /* columns after which the i32 accumulators are folded */
+                                      size_t* out_workspace_bytes);    /* scratch from the stream-ordered cache: 0 */
+
 /* PirUtil.expand(ciphertexts:outputCount:using:) (PrivateInformationRetrieval/IndexPir/PirUtil.swift:196-355):
  * oblivious expansion of `ciphertext_count` query ciphertexts [..][2][L][N] (Coeff, top level) into `output_count`
  * ciphertexts, in the reference's output order.  The evaluation key is given as parallel host arrays:

@@ -269,6 +269,15 @@ hipError_t launch_simple_pir_response(const void* database, uint32_t element_byt
                                       const W* requests, size_t query_count, W* responses, uint32_t ciphertext_bits,
                                       hipStream_t stream);
 
+// ---- simple_pir_matrix_kernels.hip: computeResponse for large batches on the int8 matrix cores ----------------------------
+// The same product for 1-byte elements below 2^7 (database_limbs 1) or 2-byte elements below 2^14 (database_limbs 2), in
+// passes of simple_pir_batch::requests_per_pass_of(classes) requests per read of the database.  fold_columns: the cadence at
+// which the i32 accumulators are folded into words (0 or anything above the bound: the bound of simple_pir_batch_plan.hpp).
+template <typename W>
+hipError_t launch_simple_pir_matrix_response(const void* database, uint32_t database_limbs, size_t rows, size_t columns,
+                                             const W* requests, size_t query_count, W* responses, uint32_t ciphertext_bits,
+                                             size_t fold_columns, hipStream_t stream);
+
 // ---- pnns_kernels.hip: the PNNS server database (PrivateNearestNeighborSearch/) ------------------------------------------
 // normalizedScaledAndRounded (Util.swift:74-89), bit-exact: vectors [rows][cols] float32 -> out [rows][cols] int64
 hipError_t launch_pnns_quantize_rows(const float* vectors, size_t rows, size_t cols, float scaling_factor, int64_t* out,

@@ -1,5 +1,6 @@
 // simple_pir_api.cpp -- SimplePirServer (reference Sources/PrivateInformationRetrieval/SimplePir/) behind the C ABI: the
-// plan (computingParams), process (database and hint) and computeResponse.  Kernels: simple_pir_kernels.hip.
+// plan (computingParams), process (database and hint) and computeResponse.  Kernels: simple_pir_kernels.hip, and
+// simple_pir_matrix_kernels.hip for the batch entries (path and tile: simple_pir_batch_plan.hpp).
 //
 // The hint, database x A mod p with A the concatenated transposed negacyclic matrices of the seeded polynomials a_k
 // (SimplePir+Database.swift:178-206,252-290), is never formed from a materialised A.  Row i of negacyclicMatrix() is
@@ -13,6 +14,7 @@
 
 #include "api_internal.hpp"
 #include "kernels.hpp"
+#include "simple_pir_batch_plan.hpp"
 
 using heamd::as_stream;
 using heamd::invalid_argument;
@@ -218,6 +220,36 @@ int compute_response(uint32_t plaintext_bits, uint32_t ciphertext_bits, const vo
     return HE_OK;
 }
 
+// The checks shared by computeResponse's entries and the batch plan, in the order of compute_response above
+int check_response_bits(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t word_bits) {
+    if (plaintext_bits == 0 || ciphertext_bits <= plaintext_bits) return invalid_argument("ciphertext_bits must be > plaintext_bits");
+    if (ciphertext_bits > word_bits) return invalid_argument("ciphertext_bits does not fit the word");
+    return HE_OK;
+}
+
+// computeResponse for large batches: the int8 matrix kernel where the plan has one, the existing launcher elsewhere
+template <typename W>
+int compute_response_batch(uint32_t plaintext_bits, uint32_t ciphertext_bits, const void* database, size_t column_size,
+                           size_t database_columns, const W* requests, size_t query_count, W* responses, he_stream s) {
+    const int status = check_response_bits(plaintext_bits, ciphertext_bits, 8 * sizeof(W));
+    if (status != HE_OK) return status;
+    if (column_size == 0 || database_columns == 0 || query_count == 0) return HE_OK;
+    if (database == nullptr || requests == nullptr || responses == nullptr) return invalid_argument("null buffer");
+    if ((reinterpret_cast<uintptr_t>(database) & (element_bytes_of(plaintext_bits) - 1)) != 0)
+        return invalid_argument("database must be aligned to element_bytes");
+    const heamd::simple_pir_batch::Plan plan = heamd::simple_pir_batch::plan_for(plaintext_bits, ciphertext_bits, 8 * sizeof(W));
+    if (plan.matrix_path) {
+        HEAMD_HIP_TRY(heamd::launch_simple_pir_matrix_response<W>(database, plan.database_limbs, column_size, database_columns,
+                                                                  requests, query_count, responses, ciphertext_bits,
+                                                                  plan.fold_columns, as_stream(s)));
+    } else {
+        HEAMD_HIP_TRY(heamd::launch_simple_pir_response<W>(database, element_bytes_of(plaintext_bits), column_size,
+                                                           database_columns, requests, query_count, responses,
+                                                           ciphertext_bits, as_stream(s)));
+    }
+    return HE_OK;
+}
+
 }  // namespace
 
 extern "C" int he_simple_pir_shape(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t lattice_dimension,
@@ -320,4 +352,42 @@ extern "C" int he_simple_pir_compute_response_device_u32(uint32_t plaintext_bits
                                                          he_stream s) {
     return compute_response(plaintext_bits, ciphertext_bits, database, column_size, database_columns, requests, query_count,
                             responses, s);
+}
+
+extern "C" int he_simple_pir_compute_response_batch_device(uint32_t plaintext_bits, uint32_t ciphertext_bits,
+                                                           const void* database, size_t column_size, size_t database_columns,
+                                                           const uint64_t* requests, size_t query_count, uint64_t* responses,
+                                                           he_stream s) {
+    return compute_response_batch(plaintext_bits, ciphertext_bits, database, column_size, database_columns, requests,
+                                  query_count, responses, s);
+}
+
+extern "C" int he_simple_pir_compute_response_batch_device_u32(uint32_t plaintext_bits, uint32_t ciphertext_bits,
+                                                               const void* database, size_t column_size,
+                                                               size_t database_columns, const uint32_t* requests,
+                                                               size_t query_count, uint32_t* responses, he_stream s) {
+    return compute_response_batch(plaintext_bits, ciphertext_bits, database, column_size, database_columns, requests,
+                                  query_count, responses, s);
+}
+
+extern "C" int he_simple_pir_batch_response_plan(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t word_bits,
+                                                 size_t database_columns, size_t query_count, uint32_t* out_matrix_path,
+                                                 uint32_t* out_database_limbs, uint32_t* out_request_limbs,
+                                                 uint32_t* out_requests_per_pass, size_t* out_fold_columns,
+                                                 size_t* out_workspace_bytes) {
+    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    const int status = check_response_bits(plaintext_bits, ciphertext_bits, word_bits);
+    if (status != HE_OK) return status;
+    // the tile depends on the widths alone today; the shape is part of the question so that a later split over the columns
+    // or a pre-split of the requests into scratch can answer it without another entry
+    (void)database_columns;
+    (void)query_count;
+    const heamd::simple_pir_batch::Plan plan = heamd::simple_pir_batch::plan_for(plaintext_bits, ciphertext_bits, word_bits);
+    if (out_matrix_path != nullptr) *out_matrix_path = plan.matrix_path;
+    if (out_database_limbs != nullptr) *out_database_limbs = plan.database_limbs;
+    if (out_request_limbs != nullptr) *out_request_limbs = plan.request_limbs;
+    if (out_requests_per_pass != nullptr) *out_requests_per_pass = plan.requests_per_pass;
+    if (out_fold_columns != nullptr) *out_fold_columns = plan.fold_columns;
+    if (out_workspace_bytes != nullptr) *out_workspace_bytes = plan.workspace_bytes;
+    return HE_OK;
 }

@@ -27,6 +27,7 @@ from .binding import (  # noqa: F401
     set_device,
     scratch_cached_bytes,
     shard_bounds,
+    simple_pir_batch_plan,
     simple_pir_shape,
     set_scratch_cache,
     stream_copy,

@@ -220,6 +220,12 @@ SIGNATURES = [
     ("he_simple_pir_unpack_database_device_u32", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
     ("he_simple_pir_compute_response_device", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
     ("he_simple_pir_compute_response_device_u32", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
+    ("he_simple_pir_compute_response_batch_device", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
+    ("he_simple_pir_compute_response_batch_device_u32", ctypes.c_int,
+     [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
+    ("he_simple_pir_batch_response_plan", ctypes.c_int,
+     [c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32),
+      ctypes.POINTER(c_u32), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
     ("he_pnns_context_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
     ("he_pnns_context_create_u32", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
     ("he_pnns_context_destroy", None, [vp]),
@@ -1420,6 +1426,17 @@ def simple_pir_shape(plaintext_bits, ciphertext_bits, lattice_dimension, entry_c
     return out
 
 
+def simple_pir_batch_plan(plaintext_bits, ciphertext_bits, database_columns, query_count, word_bits=64):
+    """he_simple_pir_batch_response_plan: what SimplePirServer.compute_response_batch does for a shape -> dict.  Host only."""
+    words = [c_u32(0) for _ in range(4)]
+    sizes = [c_size(0) for _ in range(2)]
+    _check(load_library().he_simple_pir_batch_response_plan(int(plaintext_bits), int(ciphertext_bits), int(word_bits),
+                                                            int(database_columns), int(query_count),
+                                                            *[ctypes.byref(v) for v in words + sizes]))
+    names = ("matrix_path", "database_limbs", "request_limbs", "requests_per_pass", "fold_columns", "workspace_bytes")
+    return {name: v.value for name, v in zip(names, words + sizes)}
+
+
 _SIMPLE_PIR_ELEMENT_DTYPES = {1: "uint8", 2: "int16", 4: "int32", 8: "int64"}
 
 
@@ -1525,6 +1542,22 @@ class SimplePirServer:
             self.params["column_size"], self.params["database_columns"], self._word_ptr(requests), requests.shape[0],
             vp(responses.data_ptr()), _stream(stream)))
         return responses
+
+    def compute_response_batch(self, requests, stream=None):
+        """computeResponse(to:) for large batches: the words of compute_response, formed on the int8 matrix cores where
+        simple_pir_batch_plan says so (elements must be below 2^plaintext_bits, as process and from_wide leave them)."""
+        if requests.dim() != 2 or requests.shape[1] != self.params["database_columns"]:
+            raise ValueError("expected requests [query_count][database_columns]")
+        responses = self._words((requests.shape[0], self.params["column_size"]), requests.device)
+        _check(self._entry("he_simple_pir_compute_response_batch_device")(
+            self.params["plaintext_bits"], self.params["ciphertext_bits"], vp(self.database.data_ptr()),
+            self.params["column_size"], self.params["database_columns"], self._word_ptr(requests), requests.shape[0],
+            vp(responses.data_ptr()), _stream(stream)))
+        return responses
+
+    def batch_plan(self, query_count):
+        return simple_pir_batch_plan(self.params["plaintext_bits"], self.params["ciphertext_bits"],
+                                     self.params["database_columns"], query_count, self.word_bits)
 
 
 class SimplePirServer32(SimplePirServer):
