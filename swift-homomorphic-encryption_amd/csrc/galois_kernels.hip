@@ -17,6 +17,7 @@
 #include "device_math.hpp"
 #include "kernels.hpp"
 #include "launch_grid.hpp"
+#include "serialize_form.hpp"
 
 namespace heamd {
 
@@ -546,26 +547,6 @@ __global__ void __launch_bounds__(kTileWaves * 64)
 
 }  // namespace
 
-namespace {
-// every row and the record itself start on an 8-byte boundary of an 8-byte aligned buffer
-bool word_aligned(const SerializeLayout& layout, const void* bytes) {
-    if ((reinterpret_cast<uintptr_t>(bytes) & 7) != 0) return false;
-    for (uint32_t r = 0; r <= layout.rows; ++r)
-        if ((layout.byte_offset[r] & 7) != 0) return false;
-    return true;
-}
-// whole 128-coefficient tiles, every row, the record and both buffers on 16-byte boundaries
-bool tile_aligned(const SerializeLayout& layout, const void* bytes, const void* slab, uint32_t log_degree) {
-    if (log_degree < 7) return false;
-    if (((reinterpret_cast<uintptr_t>(bytes) | reinterpret_cast<uintptr_t>(slab)) & 15) != 0) return false;
-    for (uint32_t r = 0; r <= layout.rows; ++r)
-        if ((layout.byte_offset[r] & 15) != 0) return false;
-    for (uint32_t r = 0; r < layout.rows; ++r)
-        if (layout.width[r] == 0 || layout.width[r] > 64) return false;
-    return true;
-}
-}  // namespace
-
 hipError_t launch_pack_rows(const uint64_t* slab, uint64_t* packed, const PackedLayout& layout, uint32_t log_degree,
                             size_t polys, hipStream_t stream) {
     const size_t rows = polys * layout.rows;
@@ -580,12 +561,18 @@ hipError_t launch_serialize(const uint64_t* slab, uint8_t* bytes, const Serializ
                             uint32_t skip_lsbs, size_t batch, hipStream_t stream) {
     const size_t total = batch * layout.byte_offset[layout.rows];
     if (total == 0) return hipSuccess;
-    if (tile_aligned(layout, bytes, slab, log_degree) && launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64)) {
+    // a tile-aligned call is word-aligned too (serialize_form.hpp): a tile grid that does not fit a launch takes the word form
+    serialize_form::Form form = serialize_form::for_serialize(layout.rows, layout.width, layout.byte_offset,
+                                                              reinterpret_cast<uintptr_t>(bytes),
+                                                              reinterpret_cast<uintptr_t>(slab), log_degree);
+    if (form == serialize_form::Form::kTile && !launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64))
+        form = serialize_form::Form::kWord;
+    if (form == serialize_form::Form::kTile) {
         hipLaunchKernelGGL(serialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)), dim3(kTileWaves * 64), 0,
                            stream, slab, bytes, layout, log_degree, skip_lsbs);
         return hipGetLastError();
     }
-    if (word_aligned(layout, bytes)) {
+    if (form == serialize_form::Form::kWord) {
         hipLaunchKernelGGL(serialize_words_kernel, dim3(grid_for(total >> 3)), dim3(256), 0, stream, slab,
                            reinterpret_cast<uint64_t*>(bytes), layout, log_degree, skip_lsbs, total >> 3);
         return hipGetLastError();
@@ -599,12 +586,18 @@ hipError_t launch_deserialize(const uint8_t* bytes, uint64_t* slab, const Serial
                               uint32_t skip_lsbs, size_t bytes_per_poly, size_t batch, hipStream_t stream) {
     const size_t total = (batch * layout.rows) << log_degree;
     if (total == 0) return hipSuccess;
-    if (tile_aligned(layout, bytes, slab, log_degree) && (bytes_per_poly & 15) == 0 && launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64)) {
+    // the record stride counts as well: records may be longer than the polynomial needs
+    serialize_form::Form form = serialize_form::for_deserialize(layout.rows, layout.width, layout.byte_offset,
+                                                                reinterpret_cast<uintptr_t>(bytes),
+                                                                reinterpret_cast<uintptr_t>(slab), log_degree, bytes_per_poly);
+    if (form == serialize_form::Form::kTile && !launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64))
+        form = serialize_form::Form::kWord;
+    if (form == serialize_form::Form::kTile) {
         hipLaunchKernelGGL(deserialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)), dim3(kTileWaves * 64),
                            0, stream, bytes, slab, layout, log_degree, skip_lsbs, bytes_per_poly);
         return hipGetLastError();
     }
-    if (word_aligned(layout, bytes) && (bytes_per_poly & 7) == 0) {
+    if (form == serialize_form::Form::kWord) {
         hipLaunchKernelGGL(deserialize_words_kernel, dim3(grid_for(total)), dim3(256), 0, stream,
                            reinterpret_cast<const uint64_t*>(bytes), slab, layout, log_degree, skip_lsbs,
                            bytes_per_poly >> 3, total);
