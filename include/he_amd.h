@@ -222,6 +222,74 @@ int he_poly_mul_scalar_device_u32(const he_poly_context* ctx, uint32_t* data, co
 int he_poly_divide_and_round_q_last_device_u32(const he_poly_context* ctx, const uint32_t* device_in,
                                                uint32_t* device_out, size_t batch, he_stream s);
 
+/* The wire entries above on slabs of 4-byte words: the same contracts, widths at most 30 (HE_ERR_INVALID_MODULUS for a larger
+ * modulus).  4-byte slabs take the 8-bytes-per-lane and the byte kernels (he_ciphertexts_wire_plan with poly_count 0 says which). */
+int he_poly_serialize_device_u32(const he_poly_context* ctx, const uint32_t* device_slab, size_t batch, int skip_lsbs,
+                                 uint8_t* device_bytes, he_stream s);
+int he_poly_deserialize_device_u32(const he_poly_context* ctx, const uint8_t* device_bytes, size_t bytes_per_poly,
+                                   size_t batch, int skip_lsbs, uint32_t* device_slab, he_stream s);
+int he_poly_random_from_seeds_device_u32(const he_poly_context* ctx, const uint8_t* device_seeds, size_t batch,
+                                         uint32_t* device_slab, he_stream s);
+
+/* ---- wire format of whole ciphertexts: seeded in, forDecryption out, `count` per call ----
+ * A record is the `polys` bytes of the reference's SerializedCiphertext.full: the polynomial count as a little-endian UInt16,
+ * then PolyRq.serialize(skipLSBs[p]) of each polynomial (Serialize.swift:31-94, SerializedCiphertext.swift:126-147).  Record i
+ * lies at records + i * record_stride (any stride >= the byte count, any address); its ciphertext is cts[i] of
+ * [count][poly_count][L][N].  ctx is the he_poly_context of the ciphertext's level (keys: the key-switching context and its
+ * L + 1 moduli); the _u32 forms take packed 4-byte slabs over a context whose moduli fit UInt32.  skip_lsbs is a HOST array
+ * of poly_count entries, NULL = zeros.  Errors: HE_ERR_UNSUPPORTED for poly_count outside 1..3 (no reference ciphertext has
+ * more), HE_ERR_INVALID_COEFFICIENT_PACKING per polynomial as he_poly_serialize_device reports it,
+ * HE_ERR_SERIALIZED_BUFFER_SIZE_MISMATCH for a stride below the byte count.  All enqueue-only on `s`. */
+
+/* Bfv.skipLSBsForDecryption (Bfv/Bfv+Decrypt.swift:51-109): the skips of a reply's two polynomials, from the degree, the first
+ * coefficient modulus, the plaintext modulus and the ciphertext's modulus count ({0, 0} unless that is 1).  Host only. */
+int he_bfv_skip_lsbs_for_decryption(uint32_t degree, uint64_t q0, uint64_t plaintext_modulus, uint32_t moduli_count,
+                                    int out_skip_lsbs[2]);
+/* Serialize.serializePolysBufferSize: 2 + the sum of serializationByteCount(skipLSBs[p]); 0 on invalid arguments.  Host only. */
+size_t he_ciphertexts_serialization_byte_count(const he_poly_context* ctx, uint32_t poly_count, const int* skip_lsbs);
+/* Which kernel form a wire call takes, without a device (csrc/ciphertext_wire_form.hpp, csrc/serialize_form.hpp).
+ * direction 0 = serialize, 1 = deserialize; word_bits 32 or 64; the addresses are the two buffers' as integers.
+ * poly_count 1..3: the ciphertext entries below -- form 3 ("chunk": a lane owns an aligned 8-byte chunk of the records
+ * buffer, byte stores where a chunk holds a record's first or last bytes) for serialize, 4 ("field": a lane owns a
+ * coefficient and reads the aligned 8-byte words around its field) for deserialize; items_per_record is the lanes' index
+ * space per record and edge_free says that the record pointer and stride are multiples of 8.
+ * poly_count 0: the polynomial-level entries (skip_lsbs[0]; record_stride = bytes_per_poly, ignored for serialize) -- form
+ * 0 byte, 1 word, 2 tile.  Any out pointer may be NULL.  Errors as the calls themselves report them. */
+int he_ciphertexts_wire_plan(int direction, uint32_t word_bits, const he_poly_context* ctx, uint32_t poly_count,
+                             const int* skip_lsbs, size_t record_stride, uint64_t records_address, uint64_t slab_address,
+                             uint32_t* out_form, size_t* out_record_bytes, size_t* out_items_per_record,
+                             uint32_t* out_edge_free);
+/* Ciphertext.serialize(forDecryption:) per ciphertext.  Bytes between a record's byte count and the stride, and everything
+ * outside the records, are not written (nor read). */
+int he_ciphertexts_serialize_device(const he_poly_context* ctx, const uint64_t* cts, size_t count, uint32_t poly_count,
+                                    const int* skip_lsbs, uint8_t* records, size_t record_stride, he_stream s);
+int he_ciphertexts_serialize_device_u32(const he_poly_context* ctx, const uint32_t* cts, size_t count, uint32_t poly_count,
+                                        const int* skip_lsbs, uint8_t* records, size_t record_stride, he_stream s);
+/* Ciphertext(deserialize: .full) per record.  Nothing outside [records, records + (count - 1) * record_stride + byte count)
+ * is read; fields are not validated (as he_poly_deserialize_device).  The reference takes the polynomial count from the
+ * buffer and throws on a mismatch; a kernel cannot, so device_header_mismatch (optional, a DEVICE word the caller has zeroed)
+ * is set to 1 when some record's header differs from poly_count -- every record is still decoded as poly_count polynomials. */
+int he_ciphertexts_deserialize_device(const he_poly_context* ctx, const uint8_t* records, size_t record_stride, size_t count,
+                                      uint32_t poly_count, const int* skip_lsbs, uint64_t* cts,
+                                      uint32_t* device_header_mismatch, he_stream s);
+int he_ciphertexts_deserialize_device_u32(const he_poly_context* ctx, const uint8_t* records, size_t record_stride,
+                                          size_t count, uint32_t poly_count, const int* skip_lsbs, uint32_t* cts,
+                                          uint32_t* device_header_mismatch, he_stream s);
+/* Ciphertext(deserialize: .seeded(poly0:seed:)) (SerializedCiphertext.swift:53-60) into cts [count][2][L][N]: slot 0 =
+ * PolyRq(deserialize:) of poly0_bytes + i * record_stride (bare polynomial records, no header, stride >=
+ * he_poly_serialization_byte_count(ctx, 0)); slot 1 = PolyRq<_, Eval>.random(NistAes128Ctr(seed: seeds[i])), seeds
+ * [count][32], inverse-transformed when coeff_format != 0 (queries; key-switching keys are Eval).  Both kernels write at
+ * ciphertext stride: no staging slab, no copy.  poly0_bytes == NULL leaves every slot 0 untouched, seeds == NULL every slot 1.
+ * coeff_format != 0 enqueues one inverse transform per ciphertext after the two launches; a context with a modulus that is no
+ * NTT modulus (HE_ERR_INVALID_NTT_MODULUS) or, on 4-byte words, a degree above 32768 (HE_ERR_UNSUPPORTED) is refused before
+ * anything is enqueued. */
+int he_ciphertexts_deserialize_seeded_device(const he_poly_context* ctx, const uint8_t* poly0_bytes, size_t record_stride,
+                                             const uint8_t* seeds, size_t count, int coeff_format, uint64_t* cts,
+                                             he_stream s);
+int he_ciphertexts_deserialize_seeded_device_u32(const he_poly_context* ctx, const uint8_t* poly0_bytes, size_t record_stride,
+                                                 const uint8_t* seeds, size_t count, int coeff_format, uint32_t* cts,
+                                                 he_stream s);
+
 /* =====================================================================================================
  * B3: Context<Bfv<UInt64>> and the HeScheme operations on the hot path
  * =================================================================================================== */

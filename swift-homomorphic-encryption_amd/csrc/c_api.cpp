@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -10,8 +11,10 @@
 #include <vector>
 
 #include "api_internal.hpp"
+#include "ciphertext_wire_form.hpp"
 #include "kernels.hpp"
 #include "poly_context.hpp"
+#include "serialize_form.hpp"
 
 using heamd::as_stream;
 using heamd::invalid_argument;
@@ -707,17 +710,29 @@ int serialize_layout(const PolyContext& pc, int skip_lsbs, heamd::SerializeLayou
 }
 }  // namespace
 
-size_t he_poly_serialization_byte_count(const he_poly_context* ctx, int skip_lsbs) {
-    if (ctx == nullptr) return 0;
-    heamd::SerializeLayout layout{};
-    if (serialize_layout(*ctx->impl, skip_lsbs, layout) != HE_OK) return 0;
-    return static_cast<size_t>(layout.byte_offset[layout.rows]);
+extern "C++" {  // (templates)
+namespace {
+int check_moduli_fit_u32(const PolyContext& pc) {
+    for (uint32_t i = 0; i < pc.moduli_count(); ++i)
+        if (pc.moduli()[i] > ((uint64_t(1) << 30) - 1)) {
+            heamd::set_last_error("modulus " + std::to_string(pc.moduli()[i]) + " does not fit UInt32 (max 2^30 - 1)");
+            return HE_ERR_INVALID_MODULUS;
+        }
+    return HE_OK;
 }
 
-int he_poly_serialize_device(const he_poly_context* ctx, const uint64_t* device_slab, size_t batch, int skip_lsbs,
-                             uint8_t* device_bytes, he_stream s) {
+uint32_t log2_of_degree(const PolyContext& pc) { return static_cast<uint32_t>(__builtin_ctz(pc.degree())); }
+
+// the polynomial-level wire entries, one body for 8- and 4-byte slabs (4-byte: every modulus must fit UInt32)
+template <typename W>
+int poly_serialize(const he_poly_context* ctx, const W* device_slab, size_t batch, int skip_lsbs, uint8_t* device_bytes,
+                   he_stream s) {
     if (ctx == nullptr) return invalid_argument("null context");
     const PolyContext& pc = *ctx->impl;
+    if (sizeof(W) == 4) {
+        const int fits = check_moduli_fit_u32(pc);
+        if (fits != HE_OK) return fits;
+    }
     heamd::SerializeLayout layout{};
     int status = serialize_layout(pc, skip_lsbs, layout);
     if (status != HE_OK) return status;
@@ -725,15 +740,20 @@ int he_poly_serialize_device(const he_poly_context* ctx, const uint64_t* device_
     if (device_slab == nullptr || device_bytes == nullptr) return invalid_argument("null buffer");
     status = pc.check_device();
     if (status != HE_OK) return status;
-    HEAMD_HIP_TRY(heamd::launch_serialize(device_slab, device_bytes, layout, pc.device_context().log_degree,
+    HEAMD_HIP_TRY(heamd::launch_serialize(device_slab, device_bytes, layout, log2_of_degree(pc),
                                           static_cast<uint32_t>(skip_lsbs), batch, as_stream(s)));
     return HE_OK;
 }
 
-int he_poly_deserialize_device(const he_poly_context* ctx, const uint8_t* device_bytes, size_t bytes_per_poly,
-                               size_t batch, int skip_lsbs, uint64_t* device_slab, he_stream s) {
+template <typename W>
+int poly_deserialize(const he_poly_context* ctx, const uint8_t* device_bytes, size_t bytes_per_poly, size_t batch,
+                     int skip_lsbs, W* device_slab, he_stream s) {
     if (ctx == nullptr) return invalid_argument("null context");
     const PolyContext& pc = *ctx->impl;
+    if (sizeof(W) == 4) {
+        const int fits = check_moduli_fit_u32(pc);
+        if (fits != HE_OK) return fits;
+    }
     heamd::SerializeLayout layout{};
     int status = serialize_layout(pc, skip_lsbs, layout);
     if (status != HE_OK) return status;
@@ -746,9 +766,51 @@ int he_poly_deserialize_device(const he_poly_context* ctx, const uint8_t* device
     if (device_slab == nullptr || device_bytes == nullptr) return invalid_argument("null buffer");
     status = pc.check_device();
     if (status != HE_OK) return status;
-    HEAMD_HIP_TRY(heamd::launch_deserialize(device_bytes, device_slab, layout, pc.device_context().log_degree,
+    HEAMD_HIP_TRY(heamd::launch_deserialize(device_bytes, device_slab, layout, log2_of_degree(pc),
                                             static_cast<uint32_t>(skip_lsbs), bytes_per_poly, batch, as_stream(s)));
     return HE_OK;
+}
+
+template <typename W>
+int poly_random_from_seeds(const he_poly_context* ctx, const uint8_t* device_seeds, size_t batch, W* device_slab,
+                           he_stream s) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    const PolyContext& pc = *ctx->impl;
+    if (sizeof(W) == 4) {
+        const int fits = check_moduli_fit_u32(pc);
+        if (fits != HE_OK) return fits;
+    }
+    if (batch == 0) return HE_OK;
+    if (device_seeds == nullptr || device_slab == nullptr) return invalid_argument("null buffer");
+    int status = pc.check_device();
+    if (status != HE_OK) return status;
+    heamd::Scratch chain(as_stream(s));
+    HEAMD_HIP_TRY(chain.allocate(heamd::seeded_uniform_scratch_bytes(pc.device_context(), batch)));
+    HEAMD_HIP_TRY(heamd::launch_seeded_uniform(device_seeds, device_slab, size_t(pc.moduli_count()) * pc.degree(),
+                                               pc.device_context(), batch, chain.get(), as_stream(s)));
+    return HE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t he_poly_serialization_byte_count(const he_poly_context* ctx, int skip_lsbs) {
+    if (ctx == nullptr) return 0;
+    heamd::SerializeLayout layout{};
+    if (serialize_layout(*ctx->impl, skip_lsbs, layout) != HE_OK) return 0;
+    return static_cast<size_t>(layout.byte_offset[layout.rows]);
+}
+
+int he_poly_serialize_device(const he_poly_context* ctx, const uint64_t* device_slab, size_t batch, int skip_lsbs,
+                             uint8_t* device_bytes, he_stream s) {
+    return poly_serialize(ctx, device_slab, batch, skip_lsbs, device_bytes, s);
+}
+int he_poly_deserialize_device(const he_poly_context* ctx, const uint8_t* device_bytes, size_t bytes_per_poly,
+                               size_t batch, int skip_lsbs, uint64_t* device_slab, he_stream s) {
+    return poly_deserialize(ctx, device_bytes, bytes_per_poly, batch, skip_lsbs, device_slab, s);
+}
+int he_poly_random_from_seeds_device(const he_poly_context* ctx, const uint8_t* device_seeds, size_t batch,
+                                     uint64_t* device_slab, he_stream s) {
+    return poly_random_from_seeds(ctx, device_seeds, batch, device_slab, s);
 }
 
 // ------------------------------------------------------------------------------------------ PolyRq<UInt32>
@@ -868,19 +930,278 @@ int he_poly_divide_and_round_q_last_device_u32(const he_poly_context* ctx, const
     return HE_OK;
 }
 
-int he_poly_random_from_seeds_device(const he_poly_context* ctx, const uint8_t* device_seeds, size_t batch,
-                                     uint64_t* device_slab, he_stream s) {
+// ------------------------------------------------------------------- wire format of whole ciphertexts, and on 4-byte slabs
+extern "C++" {  // (templates)
+namespace {
+// the record of `poly_count` polynomials behind a header of header_bytes: serialize_layout per polynomial, one after another
+int ciphertext_wire_layout(const PolyContext& pc, uint32_t poly_count, const int* skip_lsbs, uint32_t header_bytes,
+                           heamd::CiphertextWireLayout& out) {
+    if (poly_count < 1 || poly_count > heamd::kMaxWirePolys) {
+        heamd::set_last_error("a ciphertext record holds 1 to 3 polynomials, not " + std::to_string(poly_count));
+        return HE_ERR_UNSUPPORTED;
+    }
+    out.polys = poly_count;
+    out.rows = pc.moduli_count();
+    out.byte_offset[0] = header_bytes;
+    for (uint32_t p = 0; p < poly_count; ++p) {
+        const int skip = skip_lsbs == nullptr ? 0 : skip_lsbs[p];
+        heamd::SerializeLayout poly{};
+        const int status = serialize_layout(pc, skip, poly);
+        if (status != HE_OK) return status;
+        out.skip[p] = static_cast<uint8_t>(skip);
+        for (uint32_t r = 0; r < poly.rows; ++r) {
+            const uint32_t f = p * poly.rows + r;
+            out.width[f] = static_cast<uint8_t>(poly.width[r]);
+            out.byte_offset[f + 1] = out.byte_offset[f] + (poly.byte_offset[r + 1] - poly.byte_offset[r]);
+        }
+    }
+    return HE_OK;
+}
+
+int short_stride(size_t stride, uint64_t need) {
+    heamd::set_last_error("record stride " + std::to_string(stride) + " is below the record's " + std::to_string(need) +
+                          " bytes");
+    return HE_ERR_SERIALIZED_BUFFER_SIZE_MISMATCH;
+}
+
+template <typename W>
+int ciphertexts_serialize(const he_poly_context* ctx, const W* cts, size_t count, uint32_t poly_count, const int* skip_lsbs,
+                          uint8_t* records, size_t record_stride, he_stream s) {
     if (ctx == nullptr) return invalid_argument("null context");
     const PolyContext& pc = *ctx->impl;
-    if (batch == 0) return HE_OK;
-    if (device_seeds == nullptr || device_slab == nullptr) return invalid_argument("null buffer");
-    int status = pc.check_device();
+    if (sizeof(W) == 4) {
+        const int fits = check_moduli_fit_u32(pc);
+        if (fits != HE_OK) return fits;
+    }
+    heamd::CiphertextWireLayout layout{};
+    int status = ciphertext_wire_layout(pc, poly_count, skip_lsbs, 2, layout);
     if (status != HE_OK) return status;
-    heamd::Scratch chain(as_stream(s));
-    HEAMD_HIP_TRY(chain.allocate(heamd::seeded_uniform_scratch_bytes(pc.device_context(), batch)));
-    HEAMD_HIP_TRY(heamd::launch_seeded_uniform(device_seeds, device_slab, pc.device_context(), batch, chain.get(),
-                                               as_stream(s)));
+    const uint64_t record_bytes = layout.byte_offset[layout.polys * layout.rows];
+    if (record_stride < record_bytes) return short_stride(record_stride, record_bytes);
+    if (count == 0) return HE_OK;
+    if (cts == nullptr || records == nullptr) return invalid_argument("null buffer");
+    status = pc.check_device();
+    if (status != HE_OK) return status;
+    HEAMD_HIP_TRY(heamd::launch_ciphertexts_serialize(cts, size_t(poly_count) * pc.moduli_count() * pc.degree(), records,
+                                                      record_stride, layout, log2_of_degree(pc), count, as_stream(s)));
     return HE_OK;
+}
+
+template <typename W>
+int ciphertexts_deserialize(const he_poly_context* ctx, const uint8_t* records, size_t record_stride, size_t count,
+                            uint32_t poly_count, const int* skip_lsbs, W* cts, uint32_t* device_header_mismatch, he_stream s) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    const PolyContext& pc = *ctx->impl;
+    if (sizeof(W) == 4) {
+        const int fits = check_moduli_fit_u32(pc);
+        if (fits != HE_OK) return fits;
+    }
+    heamd::CiphertextWireLayout layout{};
+    int status = ciphertext_wire_layout(pc, poly_count, skip_lsbs, 2, layout);
+    if (status != HE_OK) return status;
+    const uint64_t record_bytes = layout.byte_offset[layout.polys * layout.rows];
+    if (record_stride < record_bytes) return short_stride(record_stride, record_bytes);
+    if (count == 0) return HE_OK;
+    if (cts == nullptr || records == nullptr) return invalid_argument("null buffer");
+    status = pc.check_device();
+    if (status != HE_OK) return status;
+    HEAMD_HIP_TRY(heamd::launch_ciphertexts_deserialize(records, record_stride, cts,
+                                                        size_t(poly_count) * pc.moduli_count() * pc.degree(), layout,
+                                                        log2_of_degree(pc), count, device_header_mismatch, as_stream(s)));
+    return HE_OK;
+}
+
+hipError_t inverse_ntt_rows(const PolyContext& pc, uint64_t* rows, hipStream_t stream) {
+    return heamd::launch_ntt(true, rows, pc.device_context(), 0, pc.moduli_count(), pc.moduli_count(), stream);
+}
+hipError_t inverse_ntt_rows(const PolyContext& pc, uint32_t* rows, hipStream_t stream) {
+    heamd::DeviceContext32 dc{};
+    if (pc.device_context32(pc.moduli_count(), dc) != HE_OK) return hipErrorInvalidValue;
+    return heamd::launch_ntt32(true, rows, dc, 0, pc.moduli_count(), pc.moduli_count(), stream);
+}
+
+template <typename W>
+int ciphertexts_deserialize_seeded(const he_poly_context* ctx, const uint8_t* poly0_bytes, size_t record_stride,
+                                   const uint8_t* seeds, size_t count, int coeff_format, W* cts, he_stream s) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    const PolyContext& pc = *ctx->impl;
+    if (sizeof(W) == 4) {
+        const int fits = check_moduli_fit_u32(pc);
+        if (fits != HE_OK) return fits;
+    }
+    heamd::CiphertextWireLayout layout{};
+    int status = ciphertext_wire_layout(pc, 1, nullptr, 0, layout);  // poly0 is a bare PolyRq record, skipLSBs 0
+    if (status != HE_OK) return status;
+    const uint64_t record_bytes = layout.byte_offset[layout.rows];
+    if (poly0_bytes != nullptr && record_stride < record_bytes) return short_stride(record_stride, record_bytes);
+    if (coeff_format != 0 && seeds != nullptr) {
+        if (!pc.all_ntt(pc.moduli_count())) {  // validateNttModuli (PolyContext.swift:175-181), as he_ntt_inverse_device
+            heamd::set_last_error("a modulus of this context is not an NTT modulus for degree " + std::to_string(pc.degree()));
+            return HE_ERR_INVALID_NTT_MODULUS;
+        }
+        // nothing is enqueued for a transform that does not exist: launch_ntt32 holds a row in the LDS, up to N = 32768
+        if (sizeof(W) == 4 && pc.degree() > 32768) {
+            heamd::set_last_error("UInt32 transform supports degrees up to 32768");
+            return HE_ERR_UNSUPPORTED;
+        }
+    }
+    if (count == 0) return HE_OK;
+    if (cts == nullptr) return invalid_argument("null ciphertexts");
+    status = pc.check_device();
+    if (status != HE_OK) return status;
+    hipStream_t stream = as_stream(s);
+    const size_t poly_words = size_t(pc.moduli_count()) * pc.degree();
+    if (poly0_bytes != nullptr)
+        HEAMD_HIP_TRY(heamd::launch_ciphertexts_deserialize(poly0_bytes, record_stride, cts, 2 * poly_words, layout,
+                                                            log2_of_degree(pc), count, nullptr, stream));
+    if (seeds != nullptr) {
+        heamd::Scratch chain(stream);
+        HEAMD_HIP_TRY(chain.allocate(heamd::seeded_uniform_scratch_bytes(pc.device_context(), count)));
+        HEAMD_HIP_TRY(heamd::launch_seeded_uniform(seeds, cts + poly_words, 2 * poly_words, pc.device_context(), count,
+                                                   chain.get(), stream));
+        // a Coeff ciphertext takes the inverse transform of its `a` (Bfv+Encrypt.swift:155-156): the rows of slot 1 are not
+        // contiguous across ciphertexts, so one transform per ciphertext -- a query is a handful of ciphertexts, and the keys,
+        // which come by the dozen, are Eval and take none
+        if (coeff_format != 0)
+            for (size_t i = 0; i < count; ++i) {
+                HEAMD_HIP_TRY(inverse_ntt_rows(pc, cts + (2 * i + 1) * poly_words, stream));
+            }
+    }
+    return HE_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int he_bfv_skip_lsbs_for_decryption(uint32_t degree, uint64_t q0, uint64_t plaintext_modulus, uint32_t moduli_count,
+                                    int out_skip_lsbs[2]) {
+    if (out_skip_lsbs == nullptr) return invalid_argument("null output");
+    if (degree == 0 || q0 == 0 || plaintext_modulus == 0 || moduli_count == 0) return invalid_argument("zero parameter");
+    out_skip_lsbs[0] = out_skip_lsbs[1] = 0;
+    if (moduli_count != 1) return HE_OK;  // Bfv+Decrypt.swift:52-54
+    const uint64_t t = plaintext_modulus;
+    // floor(log2(q0 / t)) - 3, one bit kept for the rounding and two for the ciphertext's own error (:59-74)
+    const int l_prime = q0 / 2 >= t ? (63 - __builtin_clzll(q0 / t)) - 3 : 0;
+    // Int(8 sqrt(2 N / 9)): z-score 8 on the error that the dropped bits of `a` add (:100-103)
+    const long long tmp = static_cast<long long>(8.0 * std::sqrt(2.0 * static_cast<double>(degree) / 9.0));
+    int ceil_log2 = 0;
+    if (tmp > 1) ceil_log2 = 64 - __builtin_clzll(static_cast<unsigned long long>(tmp - 1));
+    const int poly1 = l_prime - ceil_log2;
+    if (poly1 <= 1) {  // at most one bit off `a`: take it off `b`, whose effect is deterministic (:104-107)
+        out_skip_lsbs[0] = l_prime + 1 > 0 ? l_prime + 1 : 0;
+        out_skip_lsbs[1] = 0;
+    } else {
+        out_skip_lsbs[0] = l_prime > 0 ? l_prime : 0;
+        out_skip_lsbs[1] = poly1;
+    }
+    return HE_OK;
+}
+
+size_t he_ciphertexts_serialization_byte_count(const he_poly_context* ctx, uint32_t poly_count, const int* skip_lsbs) {
+    if (ctx == nullptr) return 0;
+    heamd::CiphertextWireLayout layout{};
+    if (ciphertext_wire_layout(*ctx->impl, poly_count, skip_lsbs, 2, layout) != HE_OK) return 0;
+    return static_cast<size_t>(layout.byte_offset[layout.polys * layout.rows]);
+}
+
+int he_ciphertexts_wire_plan(int direction, uint32_t word_bits, const he_poly_context* ctx, uint32_t poly_count,
+                             const int* skip_lsbs, size_t record_stride, uint64_t records_address, uint64_t slab_address,
+                             uint32_t* out_form, size_t* out_record_bytes, size_t* out_items_per_record,
+                             uint32_t* out_edge_free) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    if (direction != 0 && direction != 1) return invalid_argument("direction must be 0 (serialize) or 1 (deserialize)");
+    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    const PolyContext& pc = *ctx->impl;
+    if (word_bits == 32) {
+        const int fits = check_moduli_fit_u32(pc);
+        if (fits != HE_OK) return fits;
+    }
+    uint32_t form = 0, edge_free = 0;
+    uint64_t record_bytes = 0, items = 0;
+    if (poly_count == 0) {  // the polynomial-level entries: serialize_form.hpp
+        heamd::SerializeLayout layout{};
+        const int status = serialize_layout(pc, skip_lsbs == nullptr ? 0 : skip_lsbs[0], layout);
+        if (status != HE_OK) return status;
+        record_bytes = layout.byte_offset[layout.rows];
+        if (direction == 1 && record_stride < record_bytes) return short_stride(record_stride, record_bytes);
+        namespace sf = heamd::serialize_form;
+        const uintptr_t bytes = static_cast<uintptr_t>(records_address), slab = static_cast<uintptr_t>(slab_address);
+        const uint32_t logn = log2_of_degree(pc);
+        sf::Form f;
+        if (word_bits == 64)
+            f = direction == 0 ? sf::for_serialize(layout.rows, layout.width, layout.byte_offset, bytes, slab, logn)
+                               : sf::for_deserialize(layout.rows, layout.width, layout.byte_offset, bytes, slab, logn,
+                                                     record_stride);
+        else
+            f = direction == 0 ? sf::for_serialize_narrow(layout.rows, layout.byte_offset, bytes)
+                               : sf::for_deserialize_narrow(layout.rows, layout.byte_offset, bytes, record_stride);
+        form = static_cast<uint32_t>(f);
+        const uint64_t coefficients = uint64_t(layout.rows) << log2_of_degree(pc);
+        items = direction == 1 ? (f == sf::Form::kTile ? layout.rows : coefficients)
+                               : (f == sf::Form::kTile ? layout.rows : f == sf::Form::kWord ? record_bytes >> 3 : record_bytes);
+        edge_free = f != sf::Form::kByte;
+    } else {
+        heamd::CiphertextWireLayout layout{};
+        const int status = ciphertext_wire_layout(pc, poly_count, skip_lsbs, 2, layout);
+        if (status != HE_OK) return status;
+        record_bytes = layout.byte_offset[layout.polys * layout.rows];
+        if (record_stride < record_bytes) return short_stride(record_stride, record_bytes);
+        namespace cf = heamd::ciphertext_wire_form;
+        const cf::Plan plan = direction == 0 ? cf::for_serialize(record_bytes, record_stride,
+                                                                 static_cast<uintptr_t>(records_address))
+                                             : cf::for_deserialize(layout.polys, layout.rows, log2_of_degree(pc), record_stride,
+                                                                   static_cast<uintptr_t>(records_address));
+        form = static_cast<uint32_t>(plan.form);
+        items = plan.items_per_record;
+        edge_free = plan.edge_free ? 1 : 0;
+    }
+    if (out_form != nullptr) *out_form = form;
+    if (out_record_bytes != nullptr) *out_record_bytes = static_cast<size_t>(record_bytes);
+    if (out_items_per_record != nullptr) *out_items_per_record = static_cast<size_t>(items);
+    if (out_edge_free != nullptr) *out_edge_free = edge_free;
+    return HE_OK;
+}
+
+int he_ciphertexts_serialize_device(const he_poly_context* ctx, const uint64_t* cts, size_t count, uint32_t poly_count,
+                                    const int* skip_lsbs, uint8_t* records, size_t record_stride, he_stream s) {
+    return ciphertexts_serialize(ctx, cts, count, poly_count, skip_lsbs, records, record_stride, s);
+}
+int he_ciphertexts_serialize_device_u32(const he_poly_context* ctx, const uint32_t* cts, size_t count, uint32_t poly_count,
+                                        const int* skip_lsbs, uint8_t* records, size_t record_stride, he_stream s) {
+    return ciphertexts_serialize(ctx, cts, count, poly_count, skip_lsbs, records, record_stride, s);
+}
+int he_ciphertexts_deserialize_device(const he_poly_context* ctx, const uint8_t* records, size_t record_stride, size_t count,
+                                      uint32_t poly_count, const int* skip_lsbs, uint64_t* cts,
+                                      uint32_t* device_header_mismatch, he_stream s) {
+    return ciphertexts_deserialize(ctx, records, record_stride, count, poly_count, skip_lsbs, cts, device_header_mismatch, s);
+}
+int he_ciphertexts_deserialize_device_u32(const he_poly_context* ctx, const uint8_t* records, size_t record_stride,
+                                          size_t count, uint32_t poly_count, const int* skip_lsbs, uint32_t* cts,
+                                          uint32_t* device_header_mismatch, he_stream s) {
+    return ciphertexts_deserialize(ctx, records, record_stride, count, poly_count, skip_lsbs, cts, device_header_mismatch, s);
+}
+int he_ciphertexts_deserialize_seeded_device(const he_poly_context* ctx, const uint8_t* poly0_bytes, size_t record_stride,
+                                             const uint8_t* seeds, size_t count, int coeff_format, uint64_t* cts,
+                                             he_stream s) {
+    return ciphertexts_deserialize_seeded(ctx, poly0_bytes, record_stride, seeds, count, coeff_format, cts, s);
+}
+int he_ciphertexts_deserialize_seeded_device_u32(const he_poly_context* ctx, const uint8_t* poly0_bytes, size_t record_stride,
+                                                 const uint8_t* seeds, size_t count, int coeff_format, uint32_t* cts,
+                                                 he_stream s) {
+    return ciphertexts_deserialize_seeded(ctx, poly0_bytes, record_stride, seeds, count, coeff_format, cts, s);
+}
+
+int he_poly_serialize_device_u32(const he_poly_context* ctx, const uint32_t* device_slab, size_t batch, int skip_lsbs,
+                                 uint8_t* device_bytes, he_stream s) {
+    return poly_serialize(ctx, device_slab, batch, skip_lsbs, device_bytes, s);
+}
+int he_poly_deserialize_device_u32(const he_poly_context* ctx, const uint8_t* device_bytes, size_t bytes_per_poly,
+                                   size_t batch, int skip_lsbs, uint32_t* device_slab, he_stream s) {
+    return poly_deserialize(ctx, device_bytes, bytes_per_poly, batch, skip_lsbs, device_slab, s);
+}
+int he_poly_random_from_seeds_device_u32(const he_poly_context* ctx, const uint8_t* device_seeds, size_t batch,
+                                         uint32_t* device_slab, he_stream s) {
+    return poly_random_from_seeds(ctx, device_seeds, batch, device_slab, s);
 }
 
 int he_poly_mul_scalar_device(const he_poly_context* ctx, uint64_t* data, const uint64_t* scalar_residues,

@@ -294,9 +294,10 @@ __device__ __forceinline__ uint32_t row_of_byte(const SerializeLayout& layout, u
     return r;
 }
 
-// one lane = one output byte
+// one lane = one output byte (W: uint64_t or uint32_t slabs)
+template <typename W>
 __global__ void __launch_bounds__(256)
-    serialize_kernel(const uint64_t* __restrict__ slab, uint8_t* __restrict__ bytes, const SerializeLayout layout,
+    serialize_kernel(const W* __restrict__ slab, uint8_t* __restrict__ bytes, const SerializeLayout layout,
                      uint32_t logn, uint32_t skip, size_t total_bytes) {
     const uint64_t per_poly = layout.byte_offset[layout.rows];
     const uint32_t n = 1u << logn;
@@ -307,12 +308,12 @@ __global__ void __launch_bounds__(256)
         const uint32_t w = layout.width[r];
         const uint64_t bit = (in_poly - layout.byte_offset[r]) * 8;
         uint32_t k = static_cast<uint32_t>(bit / w), offset = static_cast<uint32_t>(bit - uint64_t(k) * w);
-        const uint64_t* row = slab + ((poly * layout.rows + r) << logn);
+        const W* row = slab + ((poly * layout.rows + r) << logn);
         uint32_t byte = 0, needed = 8;
         while (needed > 0 && k < n) {
             const uint32_t available = w - offset;
             const uint32_t take = available < needed ? available : needed;
-            const uint64_t value = row[k] >> skip;
+            const uint64_t value = static_cast<uint64_t>(row[k]) >> skip;
             byte = (byte << take) | static_cast<uint32_t>((value >> (available - take)) & ((1u << take) - 1u));
             needed -= take;
             offset += take;
@@ -326,8 +327,9 @@ __global__ void __launch_bounds__(256)
 }
 
 // one lane = one coefficient; bytes past the row's end read as zero (CoefficientPacking.swift:128-133)
+template <typename W>
 __global__ void __launch_bounds__(256)
-    deserialize_kernel(const uint8_t* __restrict__ bytes, uint64_t* __restrict__ slab, const SerializeLayout layout,
+    deserialize_kernel(const uint8_t* __restrict__ bytes, W* __restrict__ slab, const SerializeLayout layout,
                        uint32_t logn, uint32_t skip, size_t bytes_per_poly, size_t total_words) {
     const uint32_t n = 1u << logn;
     for (size_t idx = blockIdx.x * size_t(256) + threadIdx.x; idx < total_words; idx += size_t(gridDim.x) * 256) {
@@ -346,7 +348,7 @@ __global__ void __launch_bounds__(256)
         for (int b = 0; b < 8; ++b) window = (window << 8) | (first + b < row_bytes ? row[first + b] : 0);
         const uint64_t ninth = first + 8 < row_bytes ? row[first + 8] : 0;
         const uint64_t aligned = offset == 0 ? window : ((window << offset) | (ninth >> (8 - offset)));
-        slab[idx] = (aligned >> (64 - w)) << skip;
+        slab[idx] = static_cast<W>((aligned >> (64 - w)) << skip);
     }
 }
 
@@ -358,8 +360,9 @@ __device__ __forceinline__ uint64_t byte_swap64(uint64_t v) {
 }
 
 // one lane = 8 output bytes = stream bits [64 c, 64 c + 64) of one row
+template <typename W>
 __global__ void __launch_bounds__(256)
-    serialize_words_kernel(const uint64_t* __restrict__ slab, uint64_t* __restrict__ words, const SerializeLayout layout,
+    serialize_words_kernel(const W* __restrict__ slab, uint64_t* __restrict__ words, const SerializeLayout layout,
                            uint32_t logn, uint32_t skip, size_t total_words) {
     const uint64_t words_per_poly = layout.byte_offset[layout.rows] >> 3;
     const uint32_t n = 1u << logn;
@@ -370,14 +373,14 @@ __global__ void __launch_bounds__(256)
         const uint32_t w = layout.width[r];
         const uint64_t bit = ((word_in_poly << 3) - layout.byte_offset[r]) << 3;
         uint32_t k = static_cast<uint32_t>(bit / w), offset = static_cast<uint32_t>(bit - uint64_t(k) * w);
-        const uint64_t* row = slab + ((poly * layout.rows + r) << logn);
+        const W* row = slab + ((poly * layout.rows + r) << logn);
         const uint64_t field_mask = w == 64 ? ~uint64_t(0) : ((uint64_t(1) << w) - 1);
         uint64_t out = 0;
         uint32_t needed = 64;
         while (needed > 0 && k < n) {
             const uint32_t available = w - offset;
             const uint32_t take = available < needed ? available : needed;
-            const uint64_t value = (row[k] >> skip) & field_mask;
+            const uint64_t value = (static_cast<uint64_t>(row[k]) >> skip) & field_mask;
             const uint64_t piece = (value >> (available - take)) & (take == 64 ? ~uint64_t(0) : ((uint64_t(1) << take) - 1));
             out = (take == 64 ? 0 : (out << take)) | piece;
             needed -= take;
@@ -393,8 +396,9 @@ __global__ void __launch_bounds__(256)
 }
 
 // one lane = one coefficient, read from the two aligned 8-byte words that hold its field
+template <typename W>
 __global__ void __launch_bounds__(256)
-    deserialize_words_kernel(const uint64_t* __restrict__ words, uint64_t* __restrict__ slab, const SerializeLayout layout,
+    deserialize_words_kernel(const uint64_t* __restrict__ words, W* __restrict__ slab, const SerializeLayout layout,
                              uint32_t logn, uint32_t skip, size_t words_per_poly, size_t total_coefficients) {
     const uint32_t n = 1u << logn;
     for (size_t idx = blockIdx.x * size_t(256) + threadIdx.x; idx < total_coefficients;
@@ -412,7 +416,7 @@ __global__ void __launch_bounds__(256)
         const uint64_t high = byte_swap64(row[first]);
         const uint64_t low = first + 1 < row_words ? byte_swap64(row[first + 1]) : 0;  // past the row: zero bits
         const uint64_t aligned = offset == 0 ? high : ((high << offset) | (low >> (64 - offset)));
-        slab[idx] = (aligned >> (64 - w)) << skip;
+        slab[idx] = static_cast<W>((aligned >> (64 - w)) << skip);
     }
 }
 
@@ -557,55 +561,76 @@ hipError_t launch_pack_rows(const uint64_t* slab, uint64_t* packed, const Packed
     return hipGetLastError();
 }
 
-hipError_t launch_serialize(const uint64_t* slab, uint8_t* bytes, const SerializeLayout& layout, uint32_t log_degree,
+template <typename W>
+hipError_t launch_serialize(const W* slab, uint8_t* bytes, const SerializeLayout& layout, uint32_t log_degree,
                             uint32_t skip_lsbs, size_t batch, hipStream_t stream) {
     const size_t total = batch * layout.byte_offset[layout.rows];
     if (total == 0) return hipSuccess;
     // a tile-aligned call is word-aligned too (serialize_form.hpp): a tile grid that does not fit a launch takes the word form
-    serialize_form::Form form = serialize_form::for_serialize(layout.rows, layout.width, layout.byte_offset,
-                                                              reinterpret_cast<uintptr_t>(bytes),
-                                                              reinterpret_cast<uintptr_t>(slab), log_degree);
+    serialize_form::Form form =
+        sizeof(W) == 8 ? serialize_form::for_serialize(layout.rows, layout.width, layout.byte_offset,
+                                                       reinterpret_cast<uintptr_t>(bytes), reinterpret_cast<uintptr_t>(slab),
+                                                       log_degree)
+                       : serialize_form::for_serialize_narrow(layout.rows, layout.byte_offset,
+                                                              reinterpret_cast<uintptr_t>(bytes));
     if (form == serialize_form::Form::kTile && !launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64))
         form = serialize_form::Form::kWord;
-    if (form == serialize_form::Form::kTile) {
-        hipLaunchKernelGGL(serialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)), dim3(kTileWaves * 64), 0,
-                           stream, slab, bytes, layout, log_degree, skip_lsbs);
-        return hipGetLastError();
+    if constexpr (sizeof(W) == 8) {  // the tile form is the 8-byte slabs' (serialize_form.hpp)
+        if (form == serialize_form::Form::kTile) {
+            hipLaunchKernelGGL(serialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)), dim3(kTileWaves * 64),
+                               0, stream, slab, bytes, layout, log_degree, skip_lsbs);
+            return hipGetLastError();
+        }
     }
     if (form == serialize_form::Form::kWord) {
-        hipLaunchKernelGGL(serialize_words_kernel, dim3(grid_for(total >> 3)), dim3(256), 0, stream, slab,
+        hipLaunchKernelGGL(serialize_words_kernel<W>, dim3(grid_for(total >> 3)), dim3(256), 0, stream, slab,
                            reinterpret_cast<uint64_t*>(bytes), layout, log_degree, skip_lsbs, total >> 3);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(serialize_kernel, dim3(grid_for(total)), dim3(256), 0, stream, slab, bytes, layout, log_degree,
+    hipLaunchKernelGGL(serialize_kernel<W>, dim3(grid_for(total)), dim3(256), 0, stream, slab, bytes, layout, log_degree,
                        skip_lsbs, total);
     return hipGetLastError();
 }
 
-hipError_t launch_deserialize(const uint8_t* bytes, uint64_t* slab, const SerializeLayout& layout, uint32_t log_degree,
+template <typename W>
+hipError_t launch_deserialize(const uint8_t* bytes, W* slab, const SerializeLayout& layout, uint32_t log_degree,
                               uint32_t skip_lsbs, size_t bytes_per_poly, size_t batch, hipStream_t stream) {
     const size_t total = (batch * layout.rows) << log_degree;
     if (total == 0) return hipSuccess;
     // the record stride counts as well: records may be longer than the polynomial needs
-    serialize_form::Form form = serialize_form::for_deserialize(layout.rows, layout.width, layout.byte_offset,
-                                                                reinterpret_cast<uintptr_t>(bytes),
-                                                                reinterpret_cast<uintptr_t>(slab), log_degree, bytes_per_poly);
+    serialize_form::Form form =
+        sizeof(W) == 8 ? serialize_form::for_deserialize(layout.rows, layout.width, layout.byte_offset,
+                                                         reinterpret_cast<uintptr_t>(bytes), reinterpret_cast<uintptr_t>(slab),
+                                                         log_degree, bytes_per_poly)
+                       : serialize_form::for_deserialize_narrow(layout.rows, layout.byte_offset,
+                                                                reinterpret_cast<uintptr_t>(bytes), bytes_per_poly);
     if (form == serialize_form::Form::kTile && !launch_grid::launch_fits(batch * layout.rows, kTileWaves * 64))
         form = serialize_form::Form::kWord;
-    if (form == serialize_form::Form::kTile) {
-        hipLaunchKernelGGL(deserialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)), dim3(kTileWaves * 64),
-                           0, stream, bytes, slab, layout, log_degree, skip_lsbs, bytes_per_poly);
-        return hipGetLastError();
+    if constexpr (sizeof(W) == 8) {
+        if (form == serialize_form::Form::kTile) {
+            hipLaunchKernelGGL(deserialize_tiles_kernel, dim3(static_cast<unsigned>(batch * layout.rows)),
+                               dim3(kTileWaves * 64), 0, stream, bytes, slab, layout, log_degree, skip_lsbs, bytes_per_poly);
+            return hipGetLastError();
+        }
     }
     if (form == serialize_form::Form::kWord) {
-        hipLaunchKernelGGL(deserialize_words_kernel, dim3(grid_for(total)), dim3(256), 0, stream,
+        hipLaunchKernelGGL(deserialize_words_kernel<W>, dim3(grid_for(total)), dim3(256), 0, stream,
                            reinterpret_cast<const uint64_t*>(bytes), slab, layout, log_degree, skip_lsbs,
                            bytes_per_poly >> 3, total);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(deserialize_kernel, dim3(grid_for(total)), dim3(256), 0, stream, bytes, slab, layout, log_degree,
+    hipLaunchKernelGGL(deserialize_kernel<W>, dim3(grid_for(total)), dim3(256), 0, stream, bytes, slab, layout, log_degree,
                        skip_lsbs, bytes_per_poly, total);
     return hipGetLastError();
 }
+
+#define HEAMD_INSTANTIATE_WIRE(W)                                                                                       \
+    template hipError_t launch_serialize<W>(const W*, uint8_t*, const SerializeLayout&, uint32_t, uint32_t, size_t,     \
+                                            hipStream_t);                                                               \
+    template hipError_t launch_deserialize<W>(const uint8_t*, W*, const SerializeLayout&, uint32_t, uint32_t, size_t,   \
+                                              size_t, hipStream_t);
+HEAMD_INSTANTIATE_WIRE(uint64_t)
+HEAMD_INSTANTIATE_WIRE(uint32_t)
+#undef HEAMD_INSTANTIATE_WIRE
 
 }  // namespace heamd

@@ -190,8 +190,10 @@ hipError_t launch_divide_and_round_q_last32(const uint32_t* in, uint32_t* out, c
 
 // seeded_kernels.hip: out[b] = PolyRq.random(context, NistAes128Ctr(seed: seeds[b])), seeds [batch][32] bytes
 // scratch: seeded_uniform_scratch_bytes(ctx, batch) bytes (the per-chunk round keys of every seed's re-key chain)
+// polynomial b starts at out + b * poly_stride words (W: uint64_t or uint32_t slabs; the reduction is the same, the store narrows)
 size_t seeded_uniform_scratch_bytes(const DeviceContext& ctx, size_t batch);
-hipError_t launch_seeded_uniform(const uint8_t* seeds, uint64_t* out, const DeviceContext& ctx, size_t batch,
+template <typename W>
+hipError_t launch_seeded_uniform(const uint8_t* seeds, W* out, size_t poly_stride, const DeviceContext& ctx, size_t batch,
                                  void* scratch, hipStream_t stream);
 
 // wire format of a polynomial: per residue row, the serialized bit width and the byte offset of the row
@@ -201,10 +203,35 @@ struct SerializeLayout {
     uint32_t width[kMaxSerializedRows];            // ceilLog2(q_r) - skipLSBs
     uint64_t byte_offset[kMaxSerializedRows + 1];  // prefix sums of ceil(N width / 8); [rows] = bytes per polynomial
 };
-hipError_t launch_serialize(const uint64_t* slab, uint8_t* bytes, const SerializeLayout& layout, uint32_t log_degree,
+// (W: uint64_t or uint32_t slabs; 4-byte slabs take the word and byte forms, serialize_form.hpp)
+template <typename W>
+hipError_t launch_serialize(const W* slab, uint8_t* bytes, const SerializeLayout& layout, uint32_t log_degree,
                             uint32_t skip_lsbs, size_t batch, hipStream_t stream);
-hipError_t launch_deserialize(const uint8_t* bytes, uint64_t* slab, const SerializeLayout& layout, uint32_t log_degree,
+template <typename W>
+hipError_t launch_deserialize(const uint8_t* bytes, W* slab, const SerializeLayout& layout, uint32_t log_degree,
                               uint32_t skip_lsbs, size_t bytes_per_poly, size_t batch, hipStream_t stream);
+
+// ciphertext_wire_kernels.hip -- whole ciphertexts <-> the reference's wire records in one launch.
+// Record i lies at records + i * record_stride and holds `header` bytes (2: the polynomial count as a little-endian UInt16;
+// 0: a bare polynomial record) followed by the rows of its `polys` polynomials, each row bit-packed at its own width.
+// Its words lie at slab + i * ct_words: [polys][rows][N].
+constexpr uint32_t kMaxWirePolys = 3;
+constexpr uint32_t kMaxWireRows = kMaxWirePolys * kMaxSerializedRows;
+struct CiphertextWireLayout {
+    uint32_t polys, rows;                   // rows per polynomial
+    uint8_t skip[4];                        // skipLSBs per polynomial
+    uint8_t width[kMaxWireRows];            // per (polynomial, row): ceilLog2(q_r) - skip[polynomial]
+    uint64_t byte_offset[kMaxWireRows + 1];  // of each (polynomial, row) in the record; [0] = header, [polys rows] = record bytes
+};
+template <typename W>
+hipError_t launch_ciphertexts_serialize(const W* slab, size_t ct_words, uint8_t* records, size_t record_stride,
+                                        const CiphertextWireLayout& layout, uint32_t log_degree, size_t count,
+                                        hipStream_t stream);
+// mismatch (may be nullptr): set to 1 when a record's header differs from layout.polys (layouts with a header only)
+template <typename W>
+hipError_t launch_ciphertexts_deserialize(const uint8_t* records, size_t record_stride, W* slab, size_t ct_words,
+                                          const CiphertextWireLayout& layout, uint32_t log_degree, size_t count,
+                                          uint32_t* mismatch, hipStream_t stream);
 
 // ---- galois_kernels.hip (in and out must not alias) ------------------------------------------------------------
 // f(x) -> f(x^g) on Coeff rows; `inverse_element` = g^-1 mod 2N

@@ -257,8 +257,9 @@ constexpr int kTableCopies = 16;  // interleaved copies of the AES T-table in LD
 constexpr int kStreamWaves = 4;
 
 // the 256 counter blocks of one (seed, chunk) per wavefront, 4 per lane
+template <typename W>
 __global__ void __launch_bounds__(64 * kStreamWaves)
-    seeded_stream_kernel(const uint32_t* __restrict__ chain, uint64_t* __restrict__ out, const DeviceContext ctx,
+    seeded_stream_kernel(const uint32_t* __restrict__ chain, W* __restrict__ out, size_t poly_stride, const DeviceContext ctx,
                          uint32_t chunks, size_t total_chunks) {
     __shared__ uint32_t table[256 * kTableCopies];
     fill_table<kTableCopies, 64 * kStreamWaves>(table);
@@ -275,7 +276,7 @@ __global__ void __launch_bounds__(64 * kStreamWaves)
 #pragma unroll
         for (int i = 0; i < 44; ++i) rk[i] = record[i];
         const Block v{{record[44], record[45], record[46], record[47]}};
-        uint64_t* poly = out + seed_index * words;
+        W* poly = out + seed_index * poly_stride;
         const size_t first = static_cast<size_t>(chunk) * kChunkBlocks + 4 * lane;
         Block stream[4];
 #pragma unroll
@@ -291,7 +292,7 @@ __global__ void __launch_bounds__(64 * kStreamWaves)
                 value.hi = static_cast<uint64_t>(__builtin_bswap32(stream[j].w[2])) |
                            (static_cast<uint64_t>(__builtin_bswap32(stream[j].w[3])) << 32);
                 const DeviceModulus m = ctx.moduli[word >> ctx.log_degree];
-                poly[word] = barrett_reduce128(value, m.p, m.barrett128_lo, m.barrett128_hi);
+                poly[word] = static_cast<W>(barrett_reduce128(value, m.p, m.barrett128_lo, m.barrett128_hi));
             }
         }
     }
@@ -305,7 +306,8 @@ size_t seeded_uniform_scratch_bytes(const DeviceContext& ctx, size_t batch) {
     return batch * chunks * kRecordWords * sizeof(uint32_t);
 }
 
-hipError_t launch_seeded_uniform(const uint8_t* seeds, uint64_t* out, const DeviceContext& ctx, size_t batch,
+template <typename W>
+hipError_t launch_seeded_uniform(const uint8_t* seeds, W* out, size_t poly_stride, const DeviceContext& ctx, size_t batch,
                                  void* scratch, hipStream_t stream) {
     if (batch == 0) return hipSuccess;
     const size_t words = static_cast<size_t>(ctx.moduli_count) << ctx.log_degree;
@@ -318,9 +320,15 @@ hipError_t launch_seeded_uniform(const uint8_t* seeds, uint64_t* out, const Devi
     hipError_t status = hipGetLastError();
     if (status != hipSuccess) return status;
     const size_t stream_blocks = (total_chunks + kStreamWaves - 1) / kStreamWaves;
-    hipLaunchKernelGGL(seeded_stream_kernel, dim3(launch_grid::grid_for_blocks(stream_blocks, 64 * kStreamWaves, 256 * 16)),
-                       dim3(64 * kStreamWaves), 0, stream, chain, out, ctx, static_cast<uint32_t>(chunks), total_chunks);
+    hipLaunchKernelGGL(seeded_stream_kernel<W>, dim3(launch_grid::grid_for_blocks(stream_blocks, 64 * kStreamWaves, 256 * 16)),
+                       dim3(64 * kStreamWaves), 0, stream, chain, out, poly_stride, ctx, static_cast<uint32_t>(chunks),
+                       total_chunks);
     return hipGetLastError();
 }
+
+template hipError_t launch_seeded_uniform<uint64_t>(const uint8_t*, uint64_t*, size_t, const DeviceContext&, size_t, void*,
+                                                    hipStream_t);
+template hipError_t launch_seeded_uniform<uint32_t>(const uint8_t*, uint32_t*, size_t, const DeviceContext&, size_t, void*,
+                                                    hipStream_t);
 
 }  // namespace heamd

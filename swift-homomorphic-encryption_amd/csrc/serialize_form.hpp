@@ -54,5 +54,15 @@ inline Form for_deserialize(uint32_t rows, const uint32_t* width, const uint64_t
     return Form::kByte;
 }
 
+// Slabs of 4-byte words (PolyRq<UInt32>, widths <= 30) take the word and byte forms: a 128-coefficient tile of such a slab is
+// 32 lanes of 16 bytes, not the tile kernels' 64.  Neither form asks anything of the slab's address.
+inline Form for_serialize_narrow(uint32_t rows, const uint64_t* byte_offset, uintptr_t bytes) {
+    return word_aligned(rows, byte_offset, bytes) ? Form::kWord : Form::kByte;
+}
+
+inline Form for_deserialize_narrow(uint32_t rows, const uint64_t* byte_offset, uintptr_t bytes, size_t bytes_per_poly) {
+    return word_aligned(rows, byte_offset, bytes) && (bytes_per_poly & 7) == 0 ? Form::kWord : Form::kByte;
+}
+
 }  // namespace serialize_form
 }  // namespace heamd

@@ -170,7 +170,7 @@ int process_database(const he_simple_pir_context* ctx, const uint8_t* entries, c
     HEAMD_HIP_TRY(a_eval_mem.allocate(blocks * n * sizeof(uint64_t)));
     uint64_t* a = static_cast<uint64_t*>(a_mem.get());
     uint64_t* a_eval = static_cast<uint64_t*>(a_eval_mem.get());
-    HEAMD_HIP_TRY(heamd::launch_seeded_uniform(seed, a, stream_ctx, 1, chain_mem.get(), stream));
+    HEAMD_HIP_TRY(heamd::launch_seeded_uniform(seed, a, size_t(0), stream_ctx, 1, chain_mem.get(), stream));
     // sigma(a_k) = a_k(x^(2N-1)); 2N - 1 is its own inverse mod 2N
     HEAMD_HIP_TRY(heamd::launch_galois_coeff<uint64_t>(a, a_eval, dc, static_cast<uint32_t>(2 * n - 1), blocks, stream));
     HEAMD_HIP_TRY(heamd::launch_ntt(false, a_eval, dc, 0, 1, blocks, stream));

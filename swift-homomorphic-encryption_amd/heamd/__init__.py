@@ -28,6 +28,7 @@ from .binding import (  # noqa: F401
     scratch_cached_bytes,
     shard_bounds,
     simple_pir_batch_plan,
+    skip_lsbs_for_decryption,
     simple_pir_shape,
     set_scratch_cache,
     stream_copy,

@@ -119,6 +119,24 @@ SIGNATURES = [
     ("he_poly_serialization_byte_count", c_size, [vp, ctypes.c_int]),
     ("he_poly_serialize_device", ctypes.c_int, [vp, vp, c_size, ctypes.c_int, vp, vp]),
     ("he_poly_deserialize_device", ctypes.c_int, [vp, vp, c_size, c_size, ctypes.c_int, vp, vp]),
+    ("he_poly_serialize_device_u32", ctypes.c_int, [vp, vp, c_size, ctypes.c_int, vp, vp]),
+    ("he_poly_deserialize_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, ctypes.c_int, vp, vp]),
+    ("he_poly_random_from_seeds_device_u32", ctypes.c_int, [vp, vp, c_size, vp, vp]),
+    ("he_bfv_skip_lsbs_for_decryption", ctypes.c_int, [c_u32, c_u64, c_u64, c_u32, ctypes.POINTER(ctypes.c_int)]),
+    ("he_ciphertexts_serialization_byte_count", c_size, [vp, c_u32, ctypes.POINTER(ctypes.c_int)]),
+    ("he_ciphertexts_wire_plan", ctypes.c_int,
+     [ctypes.c_int, c_u32, vp, c_u32, ctypes.POINTER(ctypes.c_int), c_size, c_u64, c_u64, ctypes.POINTER(c_u32),
+      ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_u32)]),
+    ("he_ciphertexts_serialize_device", ctypes.c_int,
+     [vp, vp, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, c_size, vp]),
+    ("he_ciphertexts_serialize_device_u32", ctypes.c_int,
+     [vp, vp, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, c_size, vp]),
+    ("he_ciphertexts_deserialize_device", ctypes.c_int,
+     [vp, vp, c_size, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, vp, vp]),
+    ("he_ciphertexts_deserialize_device_u32", ctypes.c_int,
+     [vp, vp, c_size, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, vp, vp]),
+    ("he_ciphertexts_deserialize_seeded_device", ctypes.c_int, [vp, vp, c_size, vp, c_size, ctypes.c_int, vp, vp]),
+    ("he_ciphertexts_deserialize_seeded_device_u32", ctypes.c_int, [vp, vp, c_size, vp, c_size, ctypes.c_int, vp, vp]),
     ("he_poly_multiply_power_of_x_device", ctypes.c_int, [vp, vp, vp, c_size, ctypes.c_int64, vp]),
     ("he_bfv_context_create", ctypes.c_int, [c_u32, c_u64, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_bfv_context_create_u32", ctypes.c_int, [c_u32, c_u64, U64P, c_u32, ctypes.POINTER(vp)]),
@@ -742,6 +760,106 @@ class PolyContext:
         out = torch.empty((batch, len(self.moduli), self.degree), dtype=torch.int64, device=data.device)
         _check(load_library().he_poly_deserialize_device(self.h, vp(data.data_ptr()), per, batch, skip_lsbs,
                                                          vp(out.data_ptr()), _stream(stream)))
+        return out
+
+    # ---- the wire format on 4-byte slabs, and of whole ciphertexts ----
+    def random_from_seeds_u32(self, seeds, stream=None):
+        import torch
+
+        batch = seeds.numel() // 32
+        out = torch.empty((batch, len(self.moduli), self.degree), dtype=torch.int32, device=seeds.device)
+        _check(load_library().he_poly_random_from_seeds_device_u32(self.h, vp(seeds.data_ptr()), batch,
+                                                                   vp(out.data_ptr()), _stream(stream)))
+        return out
+
+    def serialize_u32(self, slab, skip_lsbs=0, stream=None):
+        import torch
+
+        batch = self._batch32(slab)
+        out = torch.empty((batch, self.serialization_byte_count(skip_lsbs)), dtype=torch.uint8, device=slab.device)
+        _check(load_library().he_poly_serialize_device_u32(self.h, vp(slab.data_ptr()), batch, skip_lsbs,
+                                                           vp(out.data_ptr()), _stream(stream)))
+        return out
+
+    def deserialize_u32(self, data, skip_lsbs=0, stream=None):
+        import torch
+
+        batch, per = data.shape[0], data.shape[1]
+        out = torch.empty((batch, len(self.moduli), self.degree), dtype=torch.int32, device=data.device)
+        _check(load_library().he_poly_deserialize_device_u32(self.h, vp(data.data_ptr()), per, batch, skip_lsbs,
+                                                             vp(out.data_ptr()), _stream(stream)))
+        return out
+
+    @staticmethod
+    def _skips(skip_lsbs, poly_count):
+        if skip_lsbs is None:
+            return None
+        assert len(skip_lsbs) >= max(poly_count, 1)
+        return (ctypes.c_int * len(skip_lsbs))(*[int(v) for v in skip_lsbs])
+
+    def ciphertexts_serialization_byte_count(self, poly_count, skip_lsbs=None):
+        return int(load_library().he_ciphertexts_serialization_byte_count(self.h, poly_count,
+                                                                          self._skips(skip_lsbs, poly_count)))
+
+    def ciphertexts_wire_plan(self, direction, poly_count, skip_lsbs=None, record_stride=0, records_address=0,
+                              slab_address=0, word_bits=64):
+        """he_ciphertexts_wire_plan -> dict(form, record_bytes, items_per_record, edge_free).  Host only."""
+        form, edge = c_u32(0), c_u32(0)
+        record_bytes, items = c_size(0), c_size(0)
+        _check(load_library().he_ciphertexts_wire_plan(
+            {"serialize": 0, "deserialize": 1}[direction], word_bits, self.h, poly_count, self._skips(skip_lsbs, poly_count),
+            record_stride, records_address, slab_address, ctypes.byref(form), ctypes.byref(record_bytes), ctypes.byref(items),
+            ctypes.byref(edge)))
+        names = {0: "byte", 1: "word", 2: "tile", 3: "chunk", 4: "field"}
+        return {"form": names[form.value], "record_bytes": record_bytes.value, "items_per_record": items.value,
+                "edge_free": bool(edge.value)}
+
+    def ciphertexts_serialize(self, cts, skip_lsbs=None, record_stride=None, out=None, stream=None):
+        """Ciphertext.serialize(forDecryption:) per ciphertext: [count][polys][L][N] (int64, or int32 for the _u32 entry) ->
+        uint8 records `record_stride` bytes apart, written into `out` from its first byte when given."""
+        import torch
+
+        count, polys = cts.shape[0], cts.shape[1]
+        need = self.ciphertexts_serialization_byte_count(polys, skip_lsbs)
+        stride = need if record_stride is None else record_stride
+        if out is None:
+            out = torch.empty((count, stride), dtype=torch.uint8, device=cts.device)
+        lib = load_library()
+        fn = lib.he_ciphertexts_serialize_device_u32 if cts.dtype == torch.int32 else lib.he_ciphertexts_serialize_device
+        _check(fn(self.h, vp(cts.data_ptr()), count, polys, self._skips(skip_lsbs, polys), vp(out.data_ptr()), stride,
+                  _stream(stream)))
+        return out
+
+    def ciphertexts_deserialize(self, records, count, poly_count, skip_lsbs=None, record_stride=None, word_bits=64, out=None,
+                                mismatch=None, stream=None):
+        """Ciphertext(deserialize: .full) per record -> [count][polys][L][N]; mismatch: a zeroed int32 device tensor."""
+        import torch
+
+        stride = self.ciphertexts_serialization_byte_count(poly_count, skip_lsbs) if record_stride is None else record_stride
+        if out is None:
+            out = torch.empty((count, poly_count, len(self.moduli), self.degree),
+                              dtype=torch.int32 if word_bits == 32 else torch.int64, device=records.device)
+        lib = load_library()
+        fn = lib.he_ciphertexts_deserialize_device_u32 if word_bits == 32 else lib.he_ciphertexts_deserialize_device
+        _check(fn(self.h, vp(records.data_ptr()), stride, count, poly_count, self._skips(skip_lsbs, poly_count),
+                  vp(out.data_ptr()), None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
+        return out
+
+    def ciphertexts_deserialize_seeded(self, poly0_bytes, seeds, count, coeff_format, record_stride=None, word_bits=64,
+                                       out=None, stream=None):
+        """Ciphertext(deserialize: .seeded(poly0:seed:)) per ciphertext -> [count][2][L][N]; either input may be None."""
+        import torch
+
+        stride = self.serialization_byte_count(0) if record_stride is None else record_stride
+        if out is None:
+            device = (poly0_bytes if poly0_bytes is not None else seeds).device
+            out = torch.empty((count, 2, len(self.moduli), self.degree),
+                              dtype=torch.int32 if word_bits == 32 else torch.int64, device=device)
+        lib = load_library()
+        fn = lib.he_ciphertexts_deserialize_seeded_device_u32 if word_bits == 32 else lib.he_ciphertexts_deserialize_seeded_device
+        _check(fn(self.h, None if poly0_bytes is None else vp(poly0_bytes.data_ptr()), stride,
+                  None if seeds is None else vp(seeds.data_ptr()), count, int(bool(coeff_format)), vp(out.data_ptr()),
+                  _stream(stream)))
         return out
 
     def apply_galois(self, slab, element, eval_format=False, stream=None):
@@ -1408,6 +1526,14 @@ class BfvContext32(BfvContext):
         _check(load_library().he_bfv_plaintext_to_coeff_device_u32(self.h, L, _ptr32(plaintext_eval), _ptr32(out), batch,
                                                                    _stream(stream)))
         return out
+
+
+def skip_lsbs_for_decryption(degree, q0, plaintext_modulus, moduli_count=1):
+    """Bfv.skipLSBsForDecryption -> [poly0, poly1].  Host only."""
+    out = (ctypes.c_int * 2)()
+    _check(load_library().he_bfv_skip_lsbs_for_decryption(int(degree), int(q0), int(plaintext_modulus), int(moduli_count),
+                                                          out))
+    return [out[0], out[1]]
 
 
 def simple_pir_shape(plaintext_bits, ciphertext_bits, lattice_dimension, entry_count, entry_size_in_bytes, word_bits=64):
