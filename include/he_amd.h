@@ -56,7 +56,10 @@ enum he_status {
     HE_ERR_MISSING_GALOIS_KEY = 19, /* missingGaloisKey / missingGaloisElement  Bfv/Bfv.swift:184-189 */
     HE_ERR_SERIALIZED_BUFFER_SIZE_MISMATCH = 20, /* serializedBufferSizeMismatch  PolyRq/PolyRq+Serialize.swift:41-51 */
     HE_ERR_INVALID_COEFFICIENT_PACKING = 21,     /* invalidCoefficientPacking     CoefficientPacking.swift:27-31 */
-    HE_ERR_SIMD_ENCODING_NOT_SUPPORTED = 22      /* simdEncodingNotSupported      Encoding.swift:225 */
+    HE_ERR_SIMD_ENCODING_NOT_SUPPORTED = 22,     /* simdEncodingNotSupported      Encoding.swift:225 */
+    /* PirError cases of ProcessedDatabase.init(from:context:) (PrivateInformationRetrieval/Util/Error.swift:32-33) */
+    HE_ERR_INVALID_DATABASE_SERIALIZATION_VERSION = 23,      /* IndexPir/IndexPirProtocol.swift:307-311 */
+    HE_ERR_INVALID_DATABASE_SERIALIZATION_PLAINTEXT_TAG = 24 /* IndexPir/IndexPirProtocol.swift:329-330 */
 };
 
 typedef struct he_poly_context he_poly_context; /* PolyContext<UInt64>   PolyRq/PolyContext.swift:19-35 */
@@ -659,6 +662,66 @@ int he_pir_process_database_device_u32(const he_bfv_context* ctx, const uint32_t
                                        const uint8_t* entries, const uint64_t* entry_sizes, size_t entry_count,
                                        size_t entry_size_in_bytes, int encoding_entry_size, uint32_t* database,
                                        uint8_t* present, he_stream s);
+
+/* ---- processed-database files: ProcessedDatabase.serialize() / init(from:context:) ----------------------
+ * The file PIRProcessDatabase writes and every index- and keyword-PIR server loads (PrivateInformationRetrieval/IndexPir/
+ * IndexPirProtocol.swift:248-379):
+ *   [version: 1 byte = 1 (:253-255)][plaintext count: UInt32 little-endian (:313-315, :367)], then per plaintext in array order
+ *   tag 0 (serializedZeroPlaintextTag, :258-260) and nothing else, or tag 1 (serializedPlaintextTag, :263-265) followed by
+ *   Plaintext<Eval>.serialize().poly: a bare PolyRq.serialize record over the top-level ciphertext context with skipLSBs 0,
+ *   S = he_poly_serialization_byte_count(he_bfv_ciphertext_context(ctx, L), 0) bytes (:317-328, :369-376).
+ * Array order is the order MulPirServer.process returns (MulPir.swift:487-503, :542-555): the flat [chunk_count][prod(
+ * dimensions)] order of he_pir_process_database_device's database and present mask -- file index p is device slot p.  So the
+ * tag of plaintext i lies at byte 5 + i + S rank(i), rank(i) the number of present plaintexts before i, and the file has
+ * 5 + count + S popcount(present) bytes (:338-349).
+ *
+ * The three host entries need no device and work on host-only contexts. */
+
+/* The walk along the tags, which is sequential by nature (where tag i lies depends on tags 0 .. i - 1): over `bytes`, the HOST
+ * image of a file from its first byte.  present_out (HOST, `capacity` bytes; may be NULL) gets one byte per plaintext, 0 or 1.
+ * Errors: a version other than 1 HE_ERR_INVALID_DATABASE_SERIALIZATION_VERSION; a tag other than 0 or 1
+ * HE_ERR_INVALID_DATABASE_SERIALIZATION_PLAINTEXT_TAG; a buffer that ends inside the header, before a tag or inside a payload
+ * HE_ERR_INVALID_ARGUMENT (the reference traps); present_out given with capacity below the file's count
+ * HE_ERR_INVALID_ARGUMENT, nothing written.  Bytes after the last plaintext are ignored, as the reference ignores them:
+ * out_bytes_consumed says where the file ended.  The out values (any may be NULL) are written on success only; after a tag or
+ * truncation error present_out holds the plaintexts before it. */
+int he_pir_database_file_scan(const he_bfv_context* ctx, const uint8_t* bytes, size_t byte_count, uint8_t* present_out,
+                              size_t capacity, size_t* out_count, size_t* out_present_count, size_t* out_bytes_consumed);
+/* ProcessedDatabase.serializationByteCount (:338-349) of a whole file with this HOST mask (a byte != 0: present): 5 + count +
+ * S popcount; 5 for count 0.  count + S popcount of a range of the mask is the byte count of that segment of the body. */
+int he_pir_database_file_byte_count(const he_bfv_context* ctx, const uint8_t* present, size_t count, size_t* out);
+/* The version byte and the count (:366-367).  HE_ERR_INVALID_ARGUMENT for a count above UInt32.max. */
+int he_pir_database_file_header(size_t count, uint8_t out[5]);
+
+/* The body of a file, or any segment of it cut at a plaintext boundary, into the database: `records` (DEVICE, any address)
+ * points at the TAG of the range's first plaintext, not at the file's first byte; present (DEVICE, [count]) and database
+ * (DEVICE, [count][L][N] at the top level) are the range's.  A 30 GB file goes through a staging buffer in pieces this way,
+ * and a keyword-PIR server loads its sub-tables one by one.  Every word of `database` is written: a present plaintext
+ * (mask byte != 0) gets exactly the words he_poly_deserialize_device gives for its payload bytes -- fields are not validated,
+ * fields at or above the modulus and set pad bits included -- a nil plaintext all zeros, which is what
+ * he_pir_process_database_device produces.  Nothing outside [records, records + records_bytes) is read; bytes the range would
+ * need past records_bytes read as zero.  Whether records_bytes covers count + S popcount cannot be known on the host without
+ * the mask, and a kernel cannot throw: device_mismatch (optional, a DEVICE word the caller has zeroed) gets bit 0 when the
+ * range needs more than records_bytes and bit 1 when a tag byte is not the one the mask implies.
+ * Errors, all before anything is enqueued: null pointers and `database` overlapping `records` HE_ERR_INVALID_ARGUMENT; a
+ * context of more than 64 moduli HE_ERR_UNSUPPORTED; a host-only context HE_ERR_DEVICE.  Enqueue-only: a prefix count of the
+ * mask into stream-ordered scratch (4 bytes per plaintext), then one launch. */
+int he_pir_database_load_device(const he_bfv_context* ctx, const uint8_t* records, size_t records_bytes,
+                                const uint8_t* present, size_t count, uint64_t* database, uint32_t* device_mismatch,
+                                he_stream s);
+/* The inverse: tags and payloads of the range into `records` (no 5-byte header: he_pir_database_file_header).  The slab of a
+ * plaintext whose mask byte is 0 is ignored and need not be zero.  Exactly the bytes [records, records + min(records_bytes,
+ * count + S popcount)) are written and no byte of the buffer is read: an aligned 8-byte chunk inside a payload is one store,
+ * a chunk that holds a payload's first or last bytes is byte stores.  device_mismatch bit 0 as above.  Same errors. */
+int he_pir_database_save_device(const he_bfv_context* ctx, const uint64_t* database, const uint8_t* present, size_t count,
+                                uint8_t* records, size_t records_bytes, uint32_t* device_mismatch, he_stream s);
+/* The same on the packed 4-byte slabs of a Bfv<UInt32> context (HE_ERR_INVALID_ARGUMENT on any other). */
+int he_pir_database_load_device_u32(const he_bfv_context* ctx, const uint8_t* records, size_t records_bytes,
+                                    const uint8_t* present, size_t count, uint32_t* database, uint32_t* device_mismatch,
+                                    he_stream s);
+int he_pir_database_save_device_u32(const he_bfv_context* ctx, const uint32_t* database, const uint8_t* present,
+                                    size_t count, uint8_t* records, size_t records_bytes, uint32_t* device_mismatch,
+                                    he_stream s);
 
 /* ---- PNNS server database (PrivateNearestNeighborSearch/) ------------------------------------------------------------------
  * Database.process (ProcessedDatabase.swift:194-229) for one context, on the device: the float vectors are normalised,

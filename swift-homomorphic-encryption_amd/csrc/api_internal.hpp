@@ -135,6 +135,11 @@ int pir_remaining_dimensions_chunks_eval(const he_bfv_context* ctx, const uint32
                                          size_t remaining_query_count, const uint64_t* relinearization_key, uint64_t* out,
                                          he_stream s);
 
+// c_api.cpp: a bare PolyRq.serialize record over `pc` with skipLSBs 0 as a one-polynomial wire layout without a header (the
+// payload of a processed-database file's plaintext); HE_OK or serialize_layout's errors (not exported)
+struct CiphertextWireLayout;
+int poly_wire_layout(const PolyContext& pc, CiphertextWireLayout& out);
+
 // Stream-ordered scratch buffer (scratch_allocate / scratch_release on the same stream).
 class Scratch {
   public:

@@ -328,6 +328,8 @@ const char* he_status_string(int status) {
         case HE_ERR_SERIALIZED_BUFFER_SIZE_MISMATCH: return "serializedBufferSizeMismatch";
         case HE_ERR_INVALID_COEFFICIENT_PACKING: return "invalidCoefficientPacking";
         case HE_ERR_SIMD_ENCODING_NOT_SUPPORTED: return "simdEncodingNotSupported";
+        case HE_ERR_INVALID_DATABASE_SERIALIZATION_VERSION: return "invalidDatabaseSerializationVersion";
+        case HE_ERR_INVALID_DATABASE_SERIALIZATION_PLAINTEXT_TAG: return "invalidDatabaseSerializationPlaintextTag";
         default: return "unknown";
     }
 }
@@ -1071,6 +1073,10 @@ int ciphertexts_deserialize_seeded(const he_poly_context* ctx, const uint8_t* po
 }
 
 }  // namespace
+
+int heamd::poly_wire_layout(const PolyContext& pc, heamd::CiphertextWireLayout& out) {
+    return ciphertext_wire_layout(pc, 1, nullptr, 0, out);
+}
 }  // extern "C++"
 
 int he_bfv_skip_lsbs_for_decryption(uint32_t degree, uint64_t q0, uint64_t plaintext_modulus, uint32_t moduli_count,

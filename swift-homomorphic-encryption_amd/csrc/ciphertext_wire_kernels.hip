@@ -19,39 +19,13 @@
 #include "ciphertext_wire_form.hpp"
 #include "kernels.hpp"
 #include "launch_grid.hpp"
+#include "wire_stream.hpp"
 
 namespace heamd {
 
 namespace {
 
-__device__ __forceinline__ uint64_t wire_byte_swap64(uint64_t v) {
-    return (static_cast<uint64_t>(__builtin_bswap32(static_cast<uint32_t>(v))) << 32) |
-           __builtin_bswap32(static_cast<uint32_t>(v >> 32));
-}
-
-// `bits` (8 .. 64) stream bits of a row of w-bit fields starting at stream bit `bit`, right-aligned; past the last field: zeros
-template <typename W>
-__device__ __forceinline__ uint64_t gather_row_bits(const W* __restrict__ row, uint32_t n, uint32_t w, uint32_t skip,
-                                                    uint64_t bit, uint32_t bits) {
-    uint32_t k = static_cast<uint32_t>(bit / w), offset = static_cast<uint32_t>(bit - uint64_t(k) * w);
-    const uint64_t field_mask = w == 64 ? ~uint64_t(0) : ((uint64_t(1) << w) - 1);
-    uint64_t out = 0;
-    uint32_t needed = bits;
-    while (needed > 0 && k < n) {
-        const uint32_t available = w - offset;
-        const uint32_t take = available < needed ? available : needed;
-        const uint64_t value = (static_cast<uint64_t>(row[k]) >> skip) & field_mask;
-        const uint64_t piece = (value >> (available - take)) & (take == 64 ? ~uint64_t(0) : ((uint64_t(1) << take) - 1));
-        out = (take == 64 ? 0 : (out << take)) | piece;
-        needed -= take;
-        offset += take;
-        if (offset == w) {
-            offset = 0;
-            ++k;
-        }
-    }
-    return needed >= 64 ? 0 : (out << needed);  // zero padding after the last coefficient
-}
+using namespace wire_stream;  // gather_row_bits, load_stream_field, wire_byte_swap64
 
 template <typename W>
 __global__ void __launch_bounds__(256)
@@ -93,14 +67,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// the aligned 8-byte word at `word` as a big-endian integer; bytes outside [lowest, end) read as zero and are not touched
-__device__ __forceinline__ uint64_t load_stream_word(const uint8_t* word, const uint8_t* lowest, const uint8_t* end) {
-    if (word >= lowest && word + 8 <= end) return wire_byte_swap64(*reinterpret_cast<const uint64_t*>(word));
-    uint64_t v = 0;
-    for (int b = 0; b < 8; ++b) v = (v << 8) | (word + b >= lowest && word + b < end ? word[b] : 0);
-    return v;
-}
-
 template <typename W>
 __global__ void __launch_bounds__(256)
     ciphertexts_deserialize_kernel(const uint8_t* __restrict__ records, size_t stride, W* __restrict__ slab, size_t ct_words,
@@ -122,15 +88,8 @@ __global__ void __launch_bounds__(256)
             if ((uint32_t(base[0]) | (uint32_t(base[1]) << 8)) != layout.polys) *mismatch = 1;
         }
         const uint32_t w = layout.width[f], skip = layout.skip[f / layout.rows];
-        const uint64_t bit = uint64_t(k) * w;
-        const uint8_t* first = base + layout.byte_offset[f] + (bit >> 3);
-        const uint8_t* word = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(first) & ~uintptr_t(7));
-        const uint32_t shift = static_cast<uint32_t>(first - word) * 8 + static_cast<uint32_t>(bit & 7);  // 0 .. 63
-        const uint64_t high = load_stream_word(word, records, buffer_end);
-        // the field ends in the next word only when shift + w > 64; otherwise that word is not read
-        const uint64_t low = shift + w > 64 ? load_stream_word(word + 8, records, buffer_end) : 0;
-        const uint64_t aligned = shift == 0 ? high : ((high << shift) | (low >> (64 - shift)));
-        slab[record * ct_words + (static_cast<size_t>(f) << logn) + k] = static_cast<W>((aligned >> (64 - w)) << skip);
+        const uint64_t field = load_stream_field(base + layout.byte_offset[f], k, w, records, buffer_end);
+        slab[record * ct_words + (static_cast<size_t>(f) << logn) + k] = static_cast<W>(field << skip);
     }
 }
 

@@ -233,6 +233,24 @@ hipError_t launch_ciphertexts_deserialize(const uint8_t* records, size_t record_
                                           const CiphertextWireLayout& layout, uint32_t log_degree, size_t count,
                                           uint32_t* mismatch, hipStream_t stream);
 
+// pir_database_file_kernels.hip -- the body of a ProcessedDatabase file (IndexPirProtocol.swift:302-378) <-> the database.
+// Plaintext p of the range has its tag at records + p + S ranks[p] and, when present[p] != 0, its S = layout.byte_offset[rows]
+// payload bytes behind it (layout: one polynomial, no header, skips 0); its words lie at database + p * rows * N.
+// ranks [count + 1]: the present plaintexts before p, and their total
+hipError_t launch_pir_database_file_ranks(const uint8_t* present, size_t count, uint32_t* ranks, hipStream_t stream);
+// every word of the database is written (nil plaintexts: zeros); nothing outside [records, records + records_bytes) is read.
+// mismatch (may be nullptr): bit 0 when the range needs more than records_bytes, bit 1 when a tag byte is not what present says
+template <typename W>
+hipError_t launch_pir_database_file_load(const uint8_t* records, uint64_t records_bytes, const uint8_t* present,
+                                         const uint32_t* ranks, size_t count, W* database,
+                                         const CiphertextWireLayout& layout, uint32_t log_degree, uint32_t* mismatch,
+                                         hipStream_t stream);
+// exactly the range's bytes below records_bytes are written, none is read; mismatch bit 0 as above
+template <typename W>
+hipError_t launch_pir_database_file_save(const W* database, const uint8_t* present, const uint32_t* ranks, size_t count,
+                                         uint8_t* records, uint64_t records_bytes, const CiphertextWireLayout& layout,
+                                         uint32_t log_degree, uint32_t* mismatch, hipStream_t stream);
+
 // ---- galois_kernels.hip (in and out must not alias) ------------------------------------------------------------
 // f(x) -> f(x^g) on Coeff rows; `inverse_element` = g^-1 mod 2N
 // (W: uint64_t or uint32_t slabs)

@@ -23,6 +23,7 @@ STATUS_NAMES = {
     12: "unequalContexts", 13: "notEnoughPrimes", 14: "notInvertible", 15: "invalidEncryptionParameters",
     16: "invalidArgument", 17: "deviceError", 18: "unsupportedHeOperation", 19: "missingGaloisKey",
     20: "serializedBufferSizeMismatch", 21: "invalidCoefficientPacking", 22: "simdEncodingNotSupported",
+    23: "invalidDatabaseSerializationVersion", 24: "invalidDatabaseSerializationPlaintextTag",
 }
 
 
@@ -225,6 +226,14 @@ SIGNATURES = [
      [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
     ("he_pir_process_database_device_u32", ctypes.c_int,
      [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
+    ("he_pir_database_file_scan", ctypes.c_int,
+     [vp, vp, c_size, vp, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
+    ("he_pir_database_file_byte_count", ctypes.c_int, [vp, vp, c_size, ctypes.POINTER(c_size)]),
+    ("he_pir_database_file_header", ctypes.c_int, [c_size, vp]),
+    ("he_pir_database_load_device", ctypes.c_int, [vp, vp, c_size, vp, c_size, vp, vp, vp]),
+    ("he_pir_database_load_device_u32", ctypes.c_int, [vp, vp, c_size, vp, c_size, vp, vp, vp]),
+    ("he_pir_database_save_device", ctypes.c_int, [vp, vp, vp, c_size, vp, c_size, vp, vp]),
+    ("he_pir_database_save_device_u32", ctypes.c_int, [vp, vp, vp, c_size, vp, c_size, vp, vp]),
     ("he_simple_pir_shape", ctypes.c_int,
      [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
       ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_u64), ctypes.POINTER(c_u32)]),
@@ -1273,6 +1282,89 @@ class BfvContext:
             int(bool(encoding_entry_size)), self._database_ptr(database), vp(present.data_ptr()), _stream(stream)))
         return database, present
 
+    # ---- processed-database files: ProcessedDatabase.serialize() / init(from:context:) ----
+    _database_file_suffix = ""
+
+    def database_file_payload_bytes(self):
+        """S: the bytes of a present plaintext behind its tag."""
+        return self.ciphertext_context().serialization_byte_count(0)
+
+    def database_file_byte_count(self, present):
+        """he_pir_database_file_byte_count of a whole file with this host mask."""
+        mask = np.ascontiguousarray(present, dtype=np.uint8).reshape(-1)
+        out = c_size()
+        _check(load_library().he_pir_database_file_byte_count(self.h, vp(mask.ctypes.data), mask.size, ctypes.byref(out)))
+        return int(out.value)
+
+    def scan_database_file(self, data):
+        """he_pir_database_file_scan over the host image of a file -> dict(count, present (uint8 array), present_count,
+        bytes_consumed).  Host only."""
+        image = np.frombuffer(data, dtype=np.uint8)
+        claimed = int.from_bytes(bytes(image[1:5]), "little") if image.size >= 5 else 0
+        present = np.zeros(min(claimed, max(image.size - 5, 0)), dtype=np.uint8)  # a plaintext takes a byte at the least
+        outs = [c_size() for _ in range(3)]
+        _check(load_library().he_pir_database_file_scan(self.h, vp(image.ctypes.data), image.size, vp(present.ctypes.data),
+                                                        present.size, *[ctypes.byref(o) for o in outs]))
+        return {"count": int(outs[0].value), "present": present[:int(outs[0].value)], "present_count": int(outs[1].value),
+                "bytes_consumed": int(outs[2].value)}
+
+    def load_database_segment(self, records, present, records_bytes=None, out=None, mismatch=None, stream=None):
+        """he_pir_database_load_device(_u32): records (uint8 device tensor, from the tag of the segment's first plaintext),
+        present (uint8 device tensor [count]) -> database [count][L][N]; mismatch: a zeroed int32 device tensor."""
+        count = present.numel()
+        if out is None:
+            out = self._database_tensor((count, self.L, self.degree), records.device)
+        elif out.numel() != count * self.L * self.degree:
+            raise ValueError("out does not hold the segment's plaintexts")
+        size = records.numel() if records_bytes is None else int(records_bytes)
+        fn = getattr(load_library(), "he_pir_database_load_device" + self._database_file_suffix)
+        _check(fn(self.h, vp(records.data_ptr()), size, vp(present.data_ptr()), count, self._database_ptr(out),
+                  None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
+        return out
+
+    def save_database_segment(self, database, present, records_bytes=None, out=None, mismatch=None, stream=None):
+        """he_pir_database_save_device(_u32): tags and payloads of database [count][L][N] under present (uint8 device tensor;
+        its host sum sizes `out` when that is not given) -> uint8 device tensor."""
+        import torch
+
+        count = present.numel()
+        if database.numel() != count * self.L * self.degree:
+            raise ValueError("database does not hold one plaintext per mask byte")
+        if out is None:
+            need = count + self.database_file_payload_bytes() * int((present != 0).sum().item())
+            out = torch.empty(need if records_bytes is None else int(records_bytes), dtype=torch.uint8, device=database.device)
+        size = out.numel() if records_bytes is None else int(records_bytes)
+        fn = getattr(load_library(), "he_pir_database_save_device" + self._database_file_suffix)
+        _check(fn(self.h, self._database_ptr(database), vp(present.data_ptr()), count, vp(out.data_ptr()), size,
+                  None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
+        return out
+
+    def load_database_file(self, data, device="cuda", stream=None):
+        """ProcessedDatabase.init(from:context:) on the device: scan on the host, upload, load -> (database [count][L][N],
+        present uint8 [count]).  Trailing bytes are ignored, as the reference ignores them."""
+        import torch
+
+        scan = self.scan_database_file(data)
+        image = np.frombuffer(data, dtype=np.uint8)[5:scan["bytes_consumed"]]
+        records = torch.from_numpy(image.copy()).to(device)
+        present = torch.from_numpy(scan["present"].copy()).to(device)
+        mismatch = torch.zeros(1, dtype=torch.int32, device=device)
+        database = self.load_database_segment(records, present, mismatch=mismatch, stream=stream)
+        if int(mismatch.item()) != 0:  # (cannot happen after a scan of the same bytes)
+            raise HeError(16, "the database file does not hold what its tags announce")
+        return database, present
+
+    def save_database_file(self, database, present, stream=None):
+        """ProcessedDatabase.serialize(): the header from the host entry, the body from the device -> bytes."""
+        header = (ctypes.c_uint8 * 5)()
+        _check(load_library().he_pir_database_file_header(present.numel(), header))
+        if present.numel() == 0:
+            return bytes(header)
+        body = self.save_database_segment(database.reshape(-1), present.reshape(-1), stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        return bytes(header) + body.cpu().numpy().tobytes()
+
     def packed_plaintext_words(self, moduli_count=None):
         return int(load_library().he_bfv_packed_plaintext_words(self.h, self._L(moduli_count)))
 
@@ -1502,6 +1594,7 @@ class BfvContext32(BfvContext):
         return out
 
     _process_entry = "he_pir_process_database_device_u32"
+    _database_file_suffix = "_u32"
 
     def _database_tensor(self, shape, device):
         import torch

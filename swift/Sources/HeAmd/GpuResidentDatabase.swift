@@ -83,6 +83,75 @@ public final class GpuResidentDatabase<Scheme: HeScheme>: @unchecked Sendable wh
         try withExtendedLifetime(entries) { try stream.synchronize() } // the raw entries are freed after the kernels
     }
 
+    /// ProcessedDatabase.init(from:context:) (IndexPirProtocol.swift:303-334) on the device: `buffer` is the file
+    /// PIRProcessDatabase wrote.  The host walks its tags (he_pir_database_file_scan: where a tag lies depends on the tags
+    /// before it), the body crosses PCIe as it is -- ceilLog2(q) bits per coefficient instead of 64 -- and
+    /// he_pir_database_load_device unpacks it into the Eval words and leaves nil plaintexts as zeros.  A wrong version or tag
+    /// throws with the reference's PirError text; bytes after the last plaintext are ignored, as the reference ignores them.
+    public init(from buffer: [UInt8], context: Scheme.Context) throws {
+        let handle = try context.gpu
+        var count = 0, consumed = 0
+        try buffer.withUnsafeBufferPointer { bytes in
+            try heAmdCheck(he_pir_database_file_scan(handle, bytes.baseAddress, bytes.count, nil, 0, &count, nil, &consumed))
+        }
+        var mask = [UInt8](repeating: 0, count: count)
+        try buffer.withUnsafeBufferPointer { bytes in
+            try mask.withUnsafeMutableBufferPointer { maskBytes in
+                try heAmdCheck(he_pir_database_file_scan(handle, bytes.baseAddress, bytes.count, maskBytes.baseAddress, count,
+                                                         nil, nil, nil))
+            }
+        }
+        let polyWords = context.ciphertextContext.moduli.count * context.degree
+        let stream = try HeAmdStream()
+        plaintextCount = count
+        plaintexts = try DeviceBuffer(count: count * polyWords)
+        present = try DeviceBuffer(count: (count + 7) / 8)
+        let bodyBytes = consumed - 5 // behind the version byte and the UInt32 count
+        let records = try DeviceBuffer(count: (bodyBytes + 7) / 8)
+        try mask.withUnsafeBufferPointer { bytes in
+            try present.upload(bytes: bytes, atByte: 0, on: stream)
+        }
+        try buffer.withUnsafeBufferPointer { bytes in
+            try records.upload(bytes: UnsafeBufferPointer(rebasing: bytes[5..<consumed]), atByte: 0, on: stream)
+        }
+        let maskBytes = UnsafeRawPointer(present.pointer).assumingMemoryBound(to: UInt8.self)
+        let recordBytes = UnsafeRawPointer(records.pointer).assumingMemoryBound(to: UInt8.self)
+        try heAmdCheck(he_pir_database_load_device(handle, recordBytes, bodyBytes, maskBytes, count, plaintexts.pointer, nil,
+                                                   stream.raw))
+        try withExtendedLifetime(records) { try stream.synchronize() } // the file's bytes are freed after the kernel
+    }
+
+    /// ProcessedDatabase.serialize() (IndexPirProtocol.swift:362-378) of the resident copy: the bytes the reference writes
+    /// for the same plaintexts, so a database built by `init(processing:with:using:)` can be handed to a reference server.
+    /// The header comes from the host entry, tags and payloads from he_pir_database_save_device.  `context` is the one the
+    /// database was built under (a resident database keeps none).
+    public func serialize(context: Scheme.Context) throws -> [UInt8] {
+        let handle = try context.gpu
+        let stream = try HeAmdStream()
+        var mask = [UInt8](repeating: 0, count: plaintextCount)
+        try mask.withUnsafeMutableBufferPointer { bytes in
+            try heAmdCheck(he_memcpy_d2h(bytes.baseAddress, present.pointer, plaintextCount, stream.raw))
+            try heAmdCheck(he_stream_synchronize(stream.raw))
+        }
+        var fileBytes = 0
+        try mask.withUnsafeBufferPointer { bytes in
+            try heAmdCheck(he_pir_database_file_byte_count(handle, bytes.baseAddress, plaintextCount, &fileBytes))
+        }
+        let bodyBytes = fileBytes - 5
+        let records = try DeviceBuffer(count: (bodyBytes + 7) / 8)
+        let recordBytes = UnsafeMutableRawPointer(records.pointer).assumingMemoryBound(to: UInt8.self)
+        try heAmdCheck(he_pir_database_save_device(handle, plaintexts.pointer, maskPointer, plaintextCount, recordBytes,
+                                                   bodyBytes, nil, stream.raw))
+        var buffer = [UInt8](repeating: 0, count: fileBytes)
+        try buffer.withUnsafeMutableBufferPointer { bytes in
+            guard let base = bytes.baseAddress else { return }
+            try heAmdCheck(he_pir_database_file_header(plaintextCount, base))
+            try heAmdCheck(he_memcpy_d2h(base + 5, records.pointer, bodyBytes, stream.raw))
+            try heAmdCheck(he_stream_synchronize(stream.raw))
+        }
+        return buffer
+    }
+
     /// Bytes of HBM the database occupies.
     public var byteCount: Int {
         (plaintexts.count + present.count) * MemoryLayout<UInt64>.stride
