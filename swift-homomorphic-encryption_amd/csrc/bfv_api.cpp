@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "rns_kernels.hpp"
 #include "side_lane.hpp"
+#include "word_layer.hpp"
 
 using heamd::as_stream;
 using heamd::BfvContext;
@@ -63,8 +64,9 @@ int bfv_create(uint32_t degree, uint64_t t, const uint64_t* q, uint32_t count, b
     return HE_OK;
 }
 
-// Common argument checks; returns the level's tool on success.
-int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolLevel** tool) {
+// Common argument checks; returns the level's tool on success.  word_bytes 4: the slabs are packed [UInt32], the same kernels
+// run on 4-byte words (widened in registers) and the context must come from he_bfv_context_create_u32.
+int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolLevel** tool, size_t word_bytes = 8) {
     if (ctx == nullptr) return invalid_argument("null context");
     if (!ctx->impl->valid(moduli_count)) return invalid_argument("moduli_count out of range");
     if (ctx->impl->host_only()) {
@@ -78,6 +80,7 @@ int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolL
         heamd::set_last_error("more than 16 ciphertext moduli are not supported by the BEHZ kernels");
         return HE_ERR_UNSUPPORTED;
     }
+    if (word_bytes == 4 && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     return HE_OK;
 }
 
@@ -93,21 +96,6 @@ int resolve_workspace(void* workspace, size_t workspace_bytes, size_t needed, Sc
     HEAMD_HIP_TRY(scratch.allocate(needed));
     *out = static_cast<uint64_t*>(scratch.get());
     return HE_OK;
-}
-
-// ---- transforms by slab word type: 8-byte words run the tiled kernels with fused loads (ntt_kernels.hip), 4-byte words
-// (Bfv<UInt32>: every modulus, Bsk primes included, is <= 2^30 - 1) the 4-byte kernels of word32_kernels.hip ------------
-hipError_t ntt_records(bool inverse, uint64_t* slab, const PolyContext& pc, const DeviceContext& dc, uint32_t record_rows,
-                       size_t records, hipStream_t stream) {
-    (void)pc;
-    return heamd::launch_ntt_mixed(inverse, slab, dc, record_rows, records, stream);
-}
-hipError_t ntt_records(bool inverse, uint32_t* slab, const PolyContext& pc, const DeviceContext& dc, uint32_t record_rows,
-                       size_t records, hipStream_t stream) {
-    heamd::DeviceContext32 dc32{};
-    if (pc.device_context32(record_rows, dc32) != HE_OK) return hipErrorInvalidValue;
-    dc32.moduli = dc.moduli;  // the caller may have substituted constants (t N^-1)
-    return heamd::launch_ntt32(inverse, slab, dc32, 0, record_rows, records * record_rows, stream);
 }
 
 // Eval form over [Q, Bsk] -> Coeff over Q: (x t) -> inverse NTT -> floorQBskToQ  (Bfv+Multiply.swift:31-48)
@@ -548,25 +536,38 @@ int he_bfv_copy_bsk_moduli(const he_bfv_context* ctx, uint64_t* out_bsk) {
     return HE_OK;
 }
 
-int he_rns_lift_q_to_qbsk_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in, uint64_t* out,
-                                 size_t batch, he_stream s) {
+extern "C++" {
+namespace {
+// RnsTool.liftQToQBsk (`lift`) / floorQBskToQ on whole polynomials
+template <typename W>
+int rns_base_change(const he_bfv_context* ctx, uint32_t moduli_count, bool lift, const W* in, W* out, size_t batch, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null slab");
-    HEAMD_HIP_TRY(heamd::launch_lift_q_to_qbsk(in, out, tool->device, batch, as_stream(s)));
+    if (lift) HEAMD_HIP_TRY(heamd::launch_lift_q_to_qbsk(in, out, tool->device, batch, as_stream(s)));
+    else HEAMD_HIP_TRY(heamd::launch_floor_qbsk_to_q(in, out, tool->device, batch, as_stream(s)));
     return HE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int he_rns_lift_q_to_qbsk_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in, uint64_t* out,
+                                 size_t batch, he_stream s) {
+    return rns_base_change(ctx, moduli_count, true, in, out, batch, s);
+}
+int he_rns_lift_q_to_qbsk_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* in, uint32_t* out,
+                                     size_t batch, he_stream s) {
+    return rns_base_change(ctx, moduli_count, true, in, out, batch, s);
 }
 int he_rns_floor_qbsk_to_q_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in, uint64_t* out,
                                   size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null slab");
-    HEAMD_HIP_TRY(heamd::launch_floor_qbsk_to_q(in, out, tool->device, batch, as_stream(s)));
-    return HE_OK;
+    return rns_base_change(ctx, moduli_count, false, in, out, batch, s);
+}
+int he_rns_floor_qbsk_to_q_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* in,
+                                      uint32_t* out, size_t batch, he_stream s) {
+    return rns_base_change(ctx, moduli_count, false, in, out, batch, s);
 }
 
 // ------------------------------------------------------------------------------------------ ct x ct
@@ -581,9 +582,8 @@ template <typename W>
 int mul_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, W* out, size_t batch,
               void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
-    if (sizeof(W) == 4 && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     if (batch == 0) return HE_OK;
     if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");
     {
@@ -624,9 +624,8 @@ template <typename W>
 int relinearize_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* ct3, const W* key, W* out, size_t batch,
                       void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
-    if (sizeof(W) == 4 && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     if (key == nullptr || !ctx->impl->has_key_switching()) {
         heamd::set_last_error("no relinearization key");
         return HE_ERR_MISSING_RELINEARIZATION_KEY;  // Bfv.swift:208-210
@@ -712,9 +711,8 @@ int bfv_apply_galois_grouped(const he_bfv_context* ctx, uint32_t L, const W* ct,
                              size_t groups, size_t group_size, W* out, void* workspace, size_t workspace_bytes,
                              hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, L, &tool);
+    int status = check_level(ctx, L, &tool, sizeof(W));
     if (status != HE_OK) return status;
-    if (sizeof(W) == 4 && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     bool missing = keys == nullptr || !ctx->impl->has_key_switching();
     for (size_t g = 0; !missing && g < groups; ++g) missing = keys[g] == nullptr;
     if (missing) {
@@ -779,10 +777,13 @@ int he_bfv_apply_galois_device_u32(const he_bfv_context* ctx, uint32_t moduli_co
 }
 
 // ------------------------------------------------------------------------------------------ scaleAndRound
-int he_rns_scale_and_round_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in,
-                                  uint64_t scaling_factor, uint64_t* out, size_t batch, he_stream s) {
+extern "C++" {
+namespace {
+template <typename W>
+int scale_and_round(const he_bfv_context* ctx, uint32_t moduli_count, const W* in, uint64_t scaling_factor, W* out, size_t batch,
+                    he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null polynomial");
@@ -794,35 +795,53 @@ int he_rns_scale_and_round_device(const he_bfv_context* ctx, uint32_t moduli_cou
     HEAMD_HIP_TRY(heamd::launch_scale_and_round(in, out, tool->device, final_scale, batch, as_stream(s)));
     return HE_OK;
 }
+}  // namespace
+}  // extern "C++"
+
+int he_rns_scale_and_round_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in,
+                                  uint64_t scaling_factor, uint64_t* out, size_t batch, he_stream s) {
+    return scale_and_round(ctx, moduli_count, in, scaling_factor, out, batch, s);
+}
+int he_rns_scale_and_round_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* in,
+                                      uint64_t scaling_factor, uint32_t* out, size_t batch, he_stream s) {
+    return scale_and_round(ctx, moduli_count, in, scaling_factor, out, batch, s);
+}
 
 // ------------------------------------------------------------------------------------------ plaintext <-> Eval
-int he_bfv_plaintext_to_eval_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* plaintext,
-                                    uint64_t* out, size_t batch, he_stream s) {
+extern "C++" {
+template <typename W>
+int heamd::bfv_plaintext_to_eval(const he_bfv_context* ctx, uint32_t moduli_count, const W* plaintext, W* out, size_t batch,
+                                 hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (plaintext == nullptr || out == nullptr) return invalid_argument("null plaintext");
-    hipStream_t stream = as_stream(s);
     const PolyContext* q_ctx = ctx->impl->ciphertext(moduli_count);
     const DeviceContext dc = q_ctx->device_context(moduli_count);
-    // Plaintext.convertToEvalFormat (Plaintext.swift:149-170): centered lift, then forwardNtt -- one kernel where the
-    // degree has a tiled NTT (the lift rides the transform's load), two launches otherwise
-    hipError_t fused = heamd::launch_ntt_lift(plaintext, ctx->impl->plaintext_modulus(), batch, out, dc, stream);
-    if (fused != hipErrorNotSupported) {
-        HEAMD_HIP_TRY(fused);
-        return HE_OK;
+    // Plaintext.convertToEvalFormat (Plaintext.swift:149-170): centered lift, then forwardNtt -- for 8-byte words one kernel
+    // where the degree has a tiled NTT (the lift rides the transform's load), two launches otherwise
+    if constexpr (sizeof(W) == 8) {
+        hipError_t fused = heamd::launch_ntt_lift(plaintext, ctx->impl->plaintext_modulus(), batch, out, dc, stream);
+        if (fused != hipErrorNotSupported) {
+            HEAMD_HIP_TRY(fused);
+            return HE_OK;
+        }
+        (void)hipGetLastError();
     }
-    (void)hipGetLastError();
     HEAMD_HIP_TRY(heamd::launch_plaintext_lift(plaintext, out, dc, ctx->impl->plaintext_modulus(), batch, stream));
-    HEAMD_HIP_TRY(heamd::launch_ntt(false, out, dc, 0, moduli_count, batch * moduli_count, stream));
+    HEAMD_HIP_TRY(ntt_rows(false, out, *q_ctx, dc, moduli_count, batch * moduli_count, stream));
     return HE_OK;
 }
+template int heamd::bfv_plaintext_to_eval(const he_bfv_context*, uint32_t, const uint64_t*, uint64_t*, size_t, hipStream_t);
+template int heamd::bfv_plaintext_to_eval(const he_bfv_context*, uint32_t, const uint32_t*, uint32_t*, size_t, hipStream_t);
 
-int he_bfv_plaintext_to_coeff_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* plaintext_eval,
-                                     uint64_t* out, size_t batch, he_stream s) {
+namespace {
+template <typename W>
+int plaintext_to_coeff(const he_bfv_context* ctx, uint32_t moduli_count, const W* plaintext_eval, W* out, size_t batch,
+                       he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (plaintext_eval == nullptr || out == nullptr) return invalid_argument("null plaintext");
@@ -833,105 +852,157 @@ int he_bfv_plaintext_to_coeff_device(const he_bfv_context* ctx, uint32_t moduli_
     // Plaintext.convertToCoeffFormat (Plaintext.swift:176-191) keeps residue row 0 only and rows are independent
     // under the inverse NTT, so only row 0 is transformed
     HEAMD_HIP_TRY(heamd::launch_first_rows(plaintext_eval, out, dc, batch, stream));
-    HEAMD_HIP_TRY(heamd::launch_ntt(true, out, dc, 0, 1, batch, stream));
+    HEAMD_HIP_TRY(ntt_rows(true, out, *q_ctx, dc, 1, batch, stream));  // (not ntt_records: its 8-byte schedule is the [Q, Bsk] one)
     HEAMD_HIP_TRY(heamd::launch_plaintext_unlift(out, q_ctx->moduli()[0], ctx->impl->plaintext_modulus(), batch * n,
                                                  stream));
-    return HE_OK;
-}
-
-// ------------------------------------------------------------------------------------------ mod switch, ct x pt
-int he_bfv_mod_switch_down_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
-                                  const uint64_t* in, uint64_t* out, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (moduli_count < 2) return HE_ERR_INVALID_POLY_CONTEXT;  // PolyRq.swift:366-368
-    if (batch == 0 || poly_count == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
-    HEAMD_HIP_TRY(heamd::launch_divide_and_round_q_last(in, out, pc->device_context(), moduli_count,
-                                                        batch * poly_count, as_stream(s)));
-    return HE_OK;
-}
-
-// Ciphertext.modSwitchDownToSingle (Bfv.swift:163-171): moduli_count -> 1 moduli, one kernel for 2..8 moduli
-int he_bfv_mod_switch_down_to_single_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
-                                            const uint64_t* in, uint64_t* out, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0 || poly_count == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    hipStream_t stream = as_stream(s);
-    const size_t polys = batch * poly_count, n = ctx->impl->degree();
-    if (moduli_count == 1) {  // already there
-        if (in != out) HEAMD_HIP_TRY(hipMemcpyAsync(out, in, polys * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-        return HE_OK;
-    }
-    const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
-    hipError_t e = heamd::launch_mod_switch_down_to_single(in, out, pc->device_context(), moduli_count, polys, stream);
-    if (e != hipErrorNotSupported) {
-        HEAMD_HIP_TRY(e);
-        return HE_OK;
-    }
-    (void)hipGetLastError();
-    // more than 8 moduli (or degree 1): step by step through two scratch slabs
-    Scratch level_mem(stream);
-    HEAMD_HIP_TRY(level_mem.allocate(2 * polys * size_t(moduli_count - 1) * n * sizeof(uint64_t)));
-    uint64_t* ping = static_cast<uint64_t*>(level_mem.get());
-    uint64_t* pong = ping + polys * size_t(moduli_count - 1) * n;
-    const uint64_t* current = in;
-    for (uint32_t level = moduli_count; level > 1; --level) {
-        uint64_t* target = level == 2 ? out : (current == ping ? pong : ping);
-        HEAMD_HIP_TRY(heamd::launch_divide_and_round_q_last(current, target, ctx->impl->ciphertext(level)->device_context(),
-                                                            level, polys, stream));
-        current = target;
-    }
-    return HE_OK;
-}
-
-int he_bfv_mul_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint64_t* ct,
-                            const uint64_t* pt, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0 || poly_count == 0) return HE_OK;
-    if (ct == nullptr || pt == nullptr) return invalid_argument("null operand");
-    const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
-    HEAMD_HIP_TRY(heamd::launch_mul_plain(ct, pt, pc->device_context(), poly_count, batch, as_stream(s)));
-    return HE_OK;
-}
-
-extern "C++" {
-namespace {
-// Bfv.addAssignCoeff / subAssignCoeff(_: inout CoeffCiphertext, _: CoeffPlaintext) (Bfv/Bfv.swift:110-117) =
-// plaintextTranslate (Bfv/Bfv+Encrypt.swift:75-140)
-template <typename W>
-int plaintext_translate(const he_bfv_context* ctx, const RnsToolLevel* tool, uint32_t poly_count, W* ct, const W* plaintexts,
-                        bool subtract, size_t batch, he_stream s) {
-    if (poly_count == 0) return invalid_argument("a ciphertext has at least one polynomial");
-    if (batch == 0) return HE_OK;
-    if (ct == nullptr || plaintexts == nullptr) return invalid_argument("null operand");
-    (void)ctx;
-    HEAMD_HIP_TRY(heamd::launch_plaintext_translate(ct, plaintexts, tool->device, poly_count, subtract, batch, as_stream(s)));
     return HE_OK;
 }
 }  // namespace
 }  // extern "C++"
 
+int he_bfv_plaintext_to_eval_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* plaintext,
+                                    uint64_t* out, size_t batch, he_stream s) {
+    return heamd::bfv_plaintext_to_eval(ctx, moduli_count, plaintext, out, batch, as_stream(s));
+}
+int he_bfv_plaintext_to_eval_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* plaintext,
+                                        uint32_t* out, size_t batch, he_stream s) {
+    return heamd::bfv_plaintext_to_eval(ctx, moduli_count, plaintext, out, batch, as_stream(s));
+}
+int he_bfv_plaintext_to_coeff_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* plaintext_eval,
+                                     uint64_t* out, size_t batch, he_stream s) {
+    return plaintext_to_coeff(ctx, moduli_count, plaintext_eval, out, batch, s);
+}
+int he_bfv_plaintext_to_coeff_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* plaintext_eval,
+                                         uint32_t* out, size_t batch, he_stream s) {
+    return plaintext_to_coeff(ctx, moduli_count, plaintext_eval, out, batch, s);
+}
+
+// ------------------------------------------------------------------------------------------ mod switch, ct x pt
+extern "C++" {
+namespace {
+template <typename W>
+int mod_switch_down(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* in, W* out, size_t batch,
+                    he_stream s) {
+    const RnsToolLevel* tool = nullptr;
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    if (status != HE_OK) return status;
+    if (moduli_count < 2) return HE_ERR_INVALID_POLY_CONTEXT;  // PolyRq.swift:366-368
+    if (batch == 0 || poly_count == 0) return HE_OK;
+    if (in == nullptr || out == nullptr) return invalid_argument("null ciphertext");
+    HEAMD_HIP_TRY(divide_and_round_q_last(in, out, *ctx->impl->ciphertext(moduli_count), moduli_count, batch * poly_count,
+                                          as_stream(s)));
+    return HE_OK;
+}
+
+template <typename W>
+int mul_plain_entry(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, W* ct, const W* pt, size_t batch,
+                    he_stream s) {
+    const RnsToolLevel* tool = nullptr;
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    if (status != HE_OK) return status;
+    if (batch == 0 || poly_count == 0) return HE_OK;
+    if (ct == nullptr || pt == nullptr) return invalid_argument("null operand");
+    const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
+    HEAMD_HIP_TRY(mul_plain(ct, pt, pc->device_context(), poly_count, batch, as_stream(s)));
+    return HE_OK;
+}
+
+// Bfv.addAssignCoeff / subAssignCoeff(_: inout CoeffCiphertext, _: CoeffPlaintext) (Bfv/Bfv.swift:110-117) =
+// plaintextTranslate (Bfv/Bfv+Encrypt.swift:75-140)
+template <typename W>
+int plaintext_translate(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, W* ct, const W* plaintexts,
+                        bool subtract, size_t batch, he_stream s) {
+    const RnsToolLevel* tool = nullptr;
+    const int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    if (status != HE_OK) return status;
+    if (poly_count == 0) return invalid_argument("a ciphertext has at least one polynomial");
+    if (batch == 0) return HE_OK;
+    if (ct == nullptr || plaintexts == nullptr) return invalid_argument("null operand");
+    HEAMD_HIP_TRY(heamd::launch_plaintext_translate(ct, plaintexts, tool->device, poly_count, subtract, batch, as_stream(s)));
+    return HE_OK;
+}
+}  // namespace
+
+// Ciphertext.modSwitchDownToSingle (Bfv.swift:163-171): moduli_count -> 1 moduli
+template <typename W>
+int heamd::bfv_mod_switch_down_to_single(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* in,
+                                         W* out, size_t batch, hipStream_t stream) {
+    const RnsToolLevel* tool = nullptr;
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    if (status != HE_OK) return status;
+    if (batch == 0 || poly_count == 0) return HE_OK;
+    if (in == nullptr || out == nullptr) return invalid_argument("null ciphertext");
+    const size_t polys = batch * poly_count, n = ctx->impl->degree();
+    if (moduli_count == 1) {  // already there
+        if (in != out) HEAMD_HIP_TRY(hipMemcpyAsync(out, in, polys * n * sizeof(W), hipMemcpyDeviceToDevice, stream));
+        return HE_OK;
+    }
+    if constexpr (sizeof(W) == 8) {  // one kernel for 2..8 moduli
+        const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
+        hipError_t e = heamd::launch_mod_switch_down_to_single(in, out, pc->device_context(), moduli_count, polys, stream);
+        if (e != hipErrorNotSupported) {
+            HEAMD_HIP_TRY(e);
+            return HE_OK;
+        }
+        (void)hipGetLastError();
+    }
+    // step by step; the levels between the first and the last alternate between two scratch slabs
+    Scratch level_mem(stream);
+    const size_t level_words = polys * size_t(moduli_count - 1) * n;
+    if (moduli_count > 2) HEAMD_HIP_TRY(level_mem.allocate(2 * level_words * sizeof(W)));
+    W* ping = static_cast<W*>(level_mem.get());
+    W* pong = ping != nullptr ? ping + level_words : nullptr;
+    const W* current = in;
+    for (uint32_t level = moduli_count; level > 1; --level) {
+        W* target = level == 2 ? out : (current == ping ? pong : ping);
+        HEAMD_HIP_TRY(divide_and_round_q_last(current, target, *ctx->impl->ciphertext(level), level, polys, stream));
+        current = target;
+    }
+    return HE_OK;
+}
+template int heamd::bfv_mod_switch_down_to_single(const he_bfv_context*, uint32_t, uint32_t, const uint64_t*, uint64_t*, size_t,
+                                                  hipStream_t);
+template int heamd::bfv_mod_switch_down_to_single(const he_bfv_context*, uint32_t, uint32_t, const uint32_t*, uint32_t*, size_t,
+                                                  hipStream_t);
+}  // extern "C++"
+
+int he_bfv_mod_switch_down_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
+                                  const uint64_t* in, uint64_t* out, size_t batch, he_stream s) {
+    return mod_switch_down(ctx, moduli_count, poly_count, in, out, batch, s);
+}
+int he_bfv_mod_switch_down_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
+                                      const uint32_t* in, uint32_t* out, size_t batch, he_stream s) {
+    return mod_switch_down(ctx, moduli_count, poly_count, in, out, batch, s);
+}
+// (there is no 4-byte twin in the C ABI: the 4-byte PNNS and PIR responses call the body)
+int he_bfv_mod_switch_down_to_single_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
+                                            const uint64_t* in, uint64_t* out, size_t batch, he_stream s) {
+    return heamd::bfv_mod_switch_down_to_single(ctx, moduli_count, poly_count, in, out, batch, as_stream(s));
+}
+
+int he_bfv_mul_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint64_t* ct,
+                            const uint64_t* pt, size_t batch, he_stream s) {
+    return mul_plain_entry(ctx, moduli_count, poly_count, ct, pt, batch, s);
+}
+int he_bfv_mul_plain_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint32_t* ct,
+                                const uint32_t* pt, size_t batch, he_stream s) {
+    return mul_plain_entry(ctx, moduli_count, poly_count, ct, pt, batch, s);
+}
 int he_bfv_add_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint64_t* ct,
                             const uint64_t* plaintexts, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    const int status = check_level(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    return plaintext_translate(ctx, tool, poly_count, ct, plaintexts, false, batch, s);
+    return plaintext_translate(ctx, moduli_count, poly_count, ct, plaintexts, false, batch, s);
+}
+int he_bfv_add_plain_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint32_t* ct,
+                                const uint32_t* plaintexts, size_t batch, he_stream s) {
+    return plaintext_translate(ctx, moduli_count, poly_count, ct, plaintexts, false, batch, s);
 }
 int he_bfv_sub_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint64_t* ct,
                             const uint64_t* plaintexts, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    const int status = check_level(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    return plaintext_translate(ctx, tool, poly_count, ct, plaintexts, true, batch, s);
+    return plaintext_translate(ctx, moduli_count, poly_count, ct, plaintexts, true, batch, s);
+}
+int he_bfv_sub_plain_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint32_t* ct,
+                                const uint32_t* plaintexts, size_t batch, he_stream s) {
+    return plaintext_translate(ctx, moduli_count, poly_count, ct, plaintexts, true, batch, s);
 }
 
 extern "C++" {
@@ -941,25 +1012,18 @@ template <typename W>
 int inner_product_plain(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* cts, const W* pts,
                         const uint8_t* present_device, size_t count, size_t columns, W* out, hipStream_t stream) {
     const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
-    const uint64_t max_lazy = pc->max_lazy_product_accumulation_count(moduli_count);
-    // the carry-counting accumulator's reduction wants sums below 2^127: at most 2^127 / (p_max - 1)^2 products
-    uint64_t cadence = max_lazy;
-    bool narrow_moduli = true;  // every modulus below 2^56
-    for (uint32_t i = 0; i < moduli_count; ++i) {
-        narrow_moduli = narrow_moduli && (pc->moduli()[i] >> 56) == 0;
-        const unsigned __int128 below = pc->moduli()[i] - 1;
-        if (below == 0) continue;
-        // a window starts from the previous window's folded residue (< p), so cadence (p - 1)^2 + p - 1 must stay
-        // below 2^127
-        const unsigned __int128 limit = ((static_cast<unsigned __int128>(1) << 127) - pc->moduli()[i]) / (below * below);
-        if (limit < cadence) cadence = static_cast<uint64_t>(limit);
-    }
+    const heamd::AccumulatorCadence lazy = heamd::accumulator_cadence(*pc, moduli_count);
     HEAMD_HIP_TRY(heamd::launch_inner_product_plain(cts, pts, present_device, out, pc->device_context(), poly_count,
-                                                    count, columns, max_lazy, cadence, narrow_moduli, stream));
+                                                    count, columns, lazy.max_lazy, lazy.cadence, lazy.narrow_moduli, stream));
     return HE_OK;
 }
+// (the resident entry looks at the word size before the level, unlike every other 4-byte entry;
+// tests/test_word_twin_status.py pins the order)
 int check_inner_product_plain(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const void* cts,
-                              const void* pts, size_t count, size_t columns, const void* out, bool* nothing_to_do) {
+                              const void* pts, size_t count, size_t columns, const void* out, bool* nothing_to_do,
+                              size_t word_bytes = 8) {
+    if (word_bytes == 4 && ctx != nullptr && ctx->impl->word_bits() != 32)
+        return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     const RnsToolLevel* tool = nullptr;
     int status = check_level(ctx, moduli_count, &tool);
     if (status != HE_OK) return status;
@@ -974,7 +1038,31 @@ int check_inner_product_plain(const he_bfv_context* ctx, uint32_t moduli_count, 
         return invalid_argument("poly_count must be 1, 2, 3, 4, 6 or 8");
     return HE_OK;
 }
+template <typename W>
+int inner_product_plain_resident(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* cts,
+                                 const W* pts, const uint8_t* present_device, size_t count, size_t columns, W* out, he_stream s) {
+    bool nothing = false;
+    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, count, columns, out, &nothing, sizeof(W));
+    if (status != HE_OK || nothing) return status;
+    return inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, as_stream(s));
+}
 }  // namespace
+
+heamd::AccumulatorCadence heamd::accumulator_cadence(const PolyContext& pc, uint32_t level) {
+    AccumulatorCadence lazy{pc.max_lazy_product_accumulation_count(level), 0, true};
+    // the carry-counting accumulator's reduction wants sums below 2^127: at most 2^127 / (p_max - 1)^2 products
+    lazy.cadence = lazy.max_lazy;
+    for (uint32_t i = 0; i < level; ++i) {
+        lazy.narrow_moduli = lazy.narrow_moduli && (pc.moduli()[i] >> 56) == 0;
+        const unsigned __int128 below = pc.moduli()[i] - 1;
+        if (below == 0) continue;
+        // a window starts from the previous window's folded residue (< p), so cadence (p - 1)^2 + p - 1 must stay
+        // below 2^127
+        const unsigned __int128 limit = ((static_cast<unsigned __int128>(1) << 127) - pc.moduli()[i]) / (below * below);
+        if (limit < lazy.cadence) lazy.cadence = static_cast<uint64_t>(limit);
+    }
+    return lazy;
+}
 }  // extern "C++"
 
 int he_bfv_inner_product_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
@@ -998,10 +1086,13 @@ int he_bfv_inner_product_plain_device(const he_bfv_context* ctx, uint32_t moduli
 int he_bfv_inner_product_plain_resident_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
                                                const uint64_t* cts, const uint64_t* pts, const uint8_t* present_device,
                                                size_t count, size_t columns, uint64_t* out, he_stream s) {
-    bool nothing = false;
-    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, count, columns, out, &nothing);
-    if (status != HE_OK || nothing) return status;
-    return inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, as_stream(s));
+    return inner_product_plain_resident(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, s);
+}
+int he_bfv_inner_product_plain_resident_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
+                                                   const uint32_t* cts, const uint32_t* pts,
+                                                   const uint8_t* present_device, size_t count, size_t columns,
+                                                   uint32_t* out, he_stream s) {
+    return inner_product_plain_resident(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, s);
 }
 
 // ------------------------------------------------------------------------------------------ packed plaintexts
@@ -1058,22 +1149,14 @@ int he_bfv_inner_product_plain_packed_device(const he_bfv_context* ctx, uint32_t
     status = packed_layout(ctx, moduli_count, layout);
     if (status != HE_OK) return status;
     const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
-    uint64_t cadence = pc->max_lazy_product_accumulation_count(moduli_count);
-    bool narrow_moduli = true;
-    for (uint32_t i = 0; i < moduli_count; ++i) {  // as in inner_product_plain above
-        narrow_moduli = narrow_moduli && (pc->moduli()[i] >> 56) == 0;
-        const unsigned __int128 below = pc->moduli()[i] - 1;
-        if (below == 0) continue;
-        const unsigned __int128 limit = ((static_cast<unsigned __int128>(1) << 127) - pc->moduli()[i]) / (below * below);
-        if (limit < cadence) cadence = static_cast<uint64_t>(limit);
-    }
-    if (cadence == 0) {
+    const heamd::AccumulatorCadence lazy = heamd::accumulator_cadence(*pc, moduli_count);
+    if (lazy.cadence == 0) {
         heamd::set_last_error("moduli too wide for the packed inner product");
         return HE_ERR_UNSUPPORTED;
     }
     HEAMD_HIP_TRY(heamd::launch_inner_product_plain_packed(cts, packed_pts, layout, present_device, out,
-                                                           pc->device_context(), poly_count, count, columns, cadence,
-                                                           narrow_moduli, as_stream(s)));
+                                                           pc->device_context(), poly_count, count, columns, lazy.cadence,
+                                                           lazy.narrow_moduli, as_stream(s)));
     return HE_OK;
 }
 
@@ -1183,183 +1266,49 @@ int bfv_inner_product_shared_eval_rhs(const he_bfv_context* ctx, uint32_t L, con
 }  // namespace heamd
 }  // extern "C++"
 
-int he_bfv_inner_product_shared_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
-                                       const uint64_t* rhs, size_t count, size_t items, uint64_t* out, he_stream s) {
+extern "C++" {
+namespace {
+template <typename W>
+int inner_product_shared_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count,
+                               size_t items, W* out, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
     if (count == 0) return invalid_argument("empty ciphertext vector");
     if (items == 0) return HE_OK;
     if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");
     return inner_product_shared_pipeline(ctx, tool, moduli_count, lhs, rhs, count, items, out, as_stream(s));
 }
-
-int he_bfv_inner_product_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
-                                const uint64_t* rhs, size_t count, uint64_t* out, void* workspace,
-                                size_t workspace_bytes, he_stream s) {
+template <typename W>
+int inner_product_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count, W* out,
+                        void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
     if (status != HE_OK) return status;
     if (count == 0) return invalid_argument("empty ciphertext vector");
     if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");
     return inner_product_pipeline(ctx, tool, moduli_count, lhs, rhs, count, out, workspace, workspace_bytes, as_stream(s));
-}
-
-// ------------------------------------------------------------------------------------------ Bfv<UInt32> on 4-byte slabs
-// The remaining entry points of this file on packed [UInt32] slabs: the same kernels instantiated on 4-byte words
-// (widened in registers), the transforms through word32_kernels.hip.  The context must come from
-// he_bfv_context_create_u32.
-extern "C++" {
-namespace {
-int check_level_u32(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolLevel** tool) {
-    const int status = check_level(ctx, moduli_count, tool);
-    if (status != HE_OK) return status;
-    if (ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
-    return HE_OK;
 }
 }  // namespace
 }  // extern "C++"
 
-int he_rns_lift_q_to_qbsk_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* in, uint32_t* out,
-                                     size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null slab");
-    HEAMD_HIP_TRY(heamd::launch_lift_q_to_qbsk(in, out, tool->device, batch, as_stream(s)));
-    return HE_OK;
+int he_bfv_inner_product_shared_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
+                                       const uint64_t* rhs, size_t count, size_t items, uint64_t* out, he_stream s) {
+    return inner_product_shared_entry(ctx, moduli_count, lhs, rhs, count, items, out, s);
 }
-int he_rns_floor_qbsk_to_q_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* in,
-                                      uint32_t* out, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null slab");
-    HEAMD_HIP_TRY(heamd::launch_floor_qbsk_to_q(in, out, tool->device, batch, as_stream(s)));
-    return HE_OK;
+int he_bfv_inner_product_shared_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* lhs,
+                                           const uint32_t* rhs, size_t count, size_t items, uint32_t* out, he_stream s) {
+    return inner_product_shared_entry(ctx, moduli_count, lhs, rhs, count, items, out, s);
 }
-int he_rns_scale_and_round_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* in,
-                                      uint64_t scaling_factor, uint32_t* out, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null polynomial");
-    const uint64_t t = ctx->impl->plaintext_modulus();
-    if (scaling_factor >= t) return invalid_argument("scaling factor not reduced mod t");
-    const uint64_t scaled = heamd::mul_mod(tool->device.inv_gamma_mod_t, scaling_factor, t);
-    const heamd::U64x2 final_scale{scaled, heamd::shoup_factor(scaled, t)};
-    HEAMD_HIP_TRY(heamd::launch_scale_and_round(in, out, tool->device, final_scale, batch, as_stream(s)));
-    return HE_OK;
+int he_bfv_inner_product_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
+                                const uint64_t* rhs, size_t count, uint64_t* out, void* workspace,
+                                size_t workspace_bytes, he_stream s) {
+    return inner_product_entry(ctx, moduli_count, lhs, rhs, count, out, workspace, workspace_bytes, s);
 }
-
-int he_bfv_plaintext_to_eval_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* plaintext,
-                                        uint32_t* out, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (plaintext == nullptr || out == nullptr) return invalid_argument("null plaintext");
-    hipStream_t stream = as_stream(s);
-    const PolyContext* q_ctx = ctx->impl->ciphertext(moduli_count);
-    const DeviceContext dc = q_ctx->device_context(moduli_count);
-    HEAMD_HIP_TRY(heamd::launch_plaintext_lift(plaintext, out, dc, ctx->impl->plaintext_modulus(), batch, stream));
-    HEAMD_HIP_TRY(ntt_records(false, out, *q_ctx, dc, moduli_count, batch, stream));
-    return HE_OK;
-}
-int he_bfv_plaintext_to_coeff_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* plaintext_eval,
-                                         uint32_t* out, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (plaintext_eval == nullptr || out == nullptr) return invalid_argument("null plaintext");
-    hipStream_t stream = as_stream(s);
-    const PolyContext* q_ctx = ctx->impl->ciphertext(moduli_count);
-    const DeviceContext dc = q_ctx->device_context(moduli_count);
-    HEAMD_HIP_TRY(heamd::launch_first_rows(plaintext_eval, out, dc, batch, stream));
-    HEAMD_HIP_TRY(ntt_records(true, out, *q_ctx, dc, 1, batch, stream));  // row 0 only (Plaintext.swift:176-191)
-    HEAMD_HIP_TRY(heamd::launch_plaintext_unlift(out, q_ctx->moduli()[0], ctx->impl->plaintext_modulus(),
-                                                 batch * ctx->impl->degree(), stream));
-    return HE_OK;
-}
-
-int he_bfv_mod_switch_down_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
-                                      const uint32_t* in, uint32_t* out, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (moduli_count < 2) return HE_ERR_INVALID_POLY_CONTEXT;  // PolyRq.swift:366-368
-    if (batch == 0 || poly_count == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
-    heamd::DeviceContext32 dc32{};
-    status = pc->device_context32(moduli_count, dc32);
-    if (status != HE_OK) return status;
-    HEAMD_HIP_TRY(heamd::launch_divide_and_round_q_last32(in, out, dc32, moduli_count, batch * poly_count, as_stream(s)));
-    return HE_OK;
-}
-
-int he_bfv_mul_plain_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint32_t* ct,
-                                const uint32_t* pt, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (batch == 0 || poly_count == 0) return HE_OK;
-    if (ct == nullptr || pt == nullptr) return invalid_argument("null operand");
-    const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
-    HEAMD_HIP_TRY(heamd::launch_mul_plain32(ct, pt, pc->device_context(), poly_count, batch, as_stream(s)));
-    return HE_OK;
-}
-
-int he_bfv_add_plain_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint32_t* ct,
-                                const uint32_t* plaintexts, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    const int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    return plaintext_translate(ctx, tool, poly_count, ct, plaintexts, false, batch, s);
-}
-int he_bfv_sub_plain_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint32_t* ct,
-                                const uint32_t* plaintexts, size_t batch, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    const int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    return plaintext_translate(ctx, tool, poly_count, ct, plaintexts, true, batch, s);
-}
-
-int he_bfv_inner_product_plain_resident_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
-                                                   const uint32_t* cts, const uint32_t* pts,
-                                                   const uint8_t* present_device, size_t count, size_t columns,
-                                                   uint32_t* out, he_stream s) {
-    if (ctx != nullptr && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
-    bool nothing = false;
-    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, count, columns, out, &nothing);
-    if (status != HE_OK || nothing) return status;
-    return inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, as_stream(s));
-}
-
 int he_bfv_inner_product_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* lhs,
                                     const uint32_t* rhs, size_t count, uint32_t* out, void* workspace,
                                     size_t workspace_bytes, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (count == 0) return invalid_argument("empty ciphertext vector");
-    if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    return inner_product_pipeline(ctx, tool, moduli_count, lhs, rhs, count, out, workspace, workspace_bytes, as_stream(s));
-}
-
-int he_bfv_inner_product_shared_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* lhs,
-                                           const uint32_t* rhs, size_t count, size_t items, uint32_t* out, he_stream s) {
-    const RnsToolLevel* tool = nullptr;
-    int status = check_level_u32(ctx, moduli_count, &tool);
-    if (status != HE_OK) return status;
-    if (count == 0) return invalid_argument("empty ciphertext vector");
-    if (items == 0) return HE_OK;
-    if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    return inner_product_shared_pipeline(ctx, tool, moduli_count, lhs, rhs, count, items, out, as_stream(s));
+    return inner_product_entry(ctx, moduli_count, lhs, rhs, count, out, workspace, workspace_bytes, s);
 }
 
 }  // extern "C"

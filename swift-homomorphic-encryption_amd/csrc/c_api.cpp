@@ -15,9 +15,12 @@
 #include "kernels.hpp"
 #include "poly_context.hpp"
 #include "serialize_form.hpp"
+#include "word_layer.hpp"
 
 using heamd::as_stream;
+using heamd::check_word_device;
 using heamd::invalid_argument;
+using heamd::kChecksDeviceFirst;
 using heamd::PolyContext;
 using heamd::Scratch;
 
@@ -39,23 +42,6 @@ int with_device_copy(uint64_t* host, size_t words, Body body) {
     (void)hipFree(device);
     if (status != HE_OK) return status;
     if (e != hipSuccess) return heamd::device_failure(e, "host-pointer round trip");
-    return HE_OK;
-}
-
-int ntt_device(const he_poly_context* ctx, uint64_t* slab, size_t batch, bool inverse, hipStream_t stream) {
-    if (ctx == nullptr) return invalid_argument("null context");
-    const PolyContext& pc = *ctx->impl;
-    // validateNttModuli (PolyContext.swift:175-181) comes first in forwardNtt(poly:) / inverseNtt(poly:)
-    if (!pc.all_ntt(pc.moduli_count())) {
-        heamd::set_last_error("a modulus of this context is not an NTT modulus for degree " + std::to_string(pc.degree()));
-        return HE_ERR_INVALID_NTT_MODULUS;
-    }
-    if (batch == 0) return HE_OK;
-    if (slab == nullptr) return invalid_argument("null slab");
-    int status = pc.check_device();
-    if (status != HE_OK) return status;
-    HEAMD_HIP_TRY(heamd::launch_ntt(inverse, slab, pc.device_context(), 0, pc.moduli_count(),
-                                    batch * pc.moduli_count(), stream));
     return HE_OK;
 }
 
@@ -81,18 +67,90 @@ int ntt_rows_device(const he_poly_context* ctx, uint64_t modulus, uint64_t* rows
     return HE_OK;
 }
 
-int elementwise(const he_poly_context* ctx, heamd::ElementwiseOp op, uint64_t* lhs, const uint64_t* rhs, size_t batch,
-                he_stream s) {
+}  // namespace
+
+// forwardNtt(poly:) / inverseNtt(poly:) on slabs of either word
+template <typename W>
+int heamd::poly_ntt(const he_poly_context* ctx, W* slab, size_t batch, bool inverse, hipStream_t stream) {
     if (ctx == nullptr) return invalid_argument("null context");
     const PolyContext& pc = *ctx->impl;
+    // validateNttModuli (PolyContext.swift:175-181) comes first in forwardNtt(poly:) / inverseNtt(poly:)
+    if (!pc.all_ntt(pc.moduli_count())) {
+        if (sizeof(W) == 8)  // (the 4-byte entries return the status alone)
+            set_last_error("a modulus of this context is not an NTT modulus for degree " + std::to_string(pc.degree()));
+        return HE_ERR_INVALID_NTT_MODULUS;
+    }
+    if (kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
     if (batch == 0) return HE_OK;
-    if (lhs == nullptr || (rhs == nullptr && op != heamd::ElementwiseOp::Neg)) return invalid_argument("null slab");
-    int status = pc.check_device();
-    if (status != HE_OK) return status;
-    HEAMD_HIP_TRY(heamd::launch_elementwise(op, lhs, rhs, pc.device_context(), batch * pc.moduli_count(), as_stream(s)));
+    if (slab == nullptr) return invalid_argument("null slab");
+    if (!kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
+    const hipError_t e = ntt_rows(inverse, slab, pc, pc.device_context(), pc.moduli_count(), batch * pc.moduli_count(), stream);
+    if (sizeof(W) == 4 && e == hipErrorNotSupported) {  // launch_ntt32 holds a row in the LDS
+        set_last_error("UInt32 transform supports degrees up to 32768");
+        return HE_ERR_UNSUPPORTED;
+    }
+    HEAMD_HIP_TRY(e);
+    return HE_OK;
+}
+template int heamd::poly_ntt(const he_poly_context*, uint64_t*, size_t, bool, hipStream_t);
+template int heamd::poly_ntt(const he_poly_context*, uint32_t*, size_t, bool, hipStream_t);
+
+template <typename W>
+int heamd::poly_elementwise(const he_poly_context* ctx, ElementwiseOp op, W* lhs, const W* rhs, size_t batch,
+                            hipStream_t stream) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    const PolyContext& pc = *ctx->impl;
+    if (kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
+    if (batch == 0) return HE_OK;
+    if (lhs == nullptr || (rhs == nullptr && op != ElementwiseOp::Neg)) return invalid_argument("null slab");
+    if (!kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
+    HEAMD_HIP_TRY(elementwise_rows(op, lhs, rhs, nullptr, pc, batch * pc.moduli_count(), stream));
+    return HE_OK;
+}
+template int heamd::poly_elementwise(const he_poly_context*, heamd::ElementwiseOp, uint64_t*, const uint64_t*, size_t,
+                                     hipStream_t);
+template int heamd::poly_elementwise(const he_poly_context*, heamd::ElementwiseOp, uint32_t*, const uint32_t*, size_t,
+                                     hipStream_t);
+
+namespace {
+// MultiplyConstantModulus(multiplicand:divisionModulus:) per row (PolyRq.swift:235-238)
+template <typename W>
+int poly_mul_scalar(const he_poly_context* ctx, W* data, const W* scalar_residues, size_t batch, he_stream s) {
+    if (ctx == nullptr || scalar_residues == nullptr) return invalid_argument("null pointer");
+    const PolyContext& pc = *ctx->impl;
+    if (kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
+    if (batch == 0) return HE_OK;
+    if (sizeof(W) == 4 && data == nullptr) return invalid_argument("null slab");  // (the 8-byte entry takes its slab unchecked)
+    if (!kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
+    std::vector<heamd::U64x2> pairs(pc.moduli_count());
+    for (uint32_t i = 0; i < pc.moduli_count(); ++i) {
+        const uint64_t p = pc.moduli()[i];
+        if (scalar_residues[i] >= p) return invalid_argument("scalar residue not reduced");
+        pairs[i] = heamd::U64x2{scalar_residues[i], heamd::shoup_factor(scalar_residues[i], p)};
+    }
+    hipStream_t stream = as_stream(s);
+    Scratch scratch(stream);
+    HEAMD_HIP_TRY(scratch.allocate(pairs.size() * sizeof(heamd::U64x2)));
+    HEAMD_HIP_TRY(hipMemcpyAsync(scratch.get(), pairs.data(), pairs.size() * sizeof(heamd::U64x2),
+                                 hipMemcpyHostToDevice, stream));
+    HEAMD_HIP_TRY(hipStreamSynchronize(stream));  // the pageable host vector must outlive the async copy
+    HEAMD_HIP_TRY(elementwise_rows(heamd::ElementwiseOp::MulScalar, data, nullptr, static_cast<const uint64_t*>(scratch.get()),
+                                   pc, batch * pc.moduli_count(), stream));
     return HE_OK;
 }
 
+template <typename W>
+int poly_divide_and_round_q_last(const he_poly_context* ctx, const W* in, W* out, size_t batch, he_stream s) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    const PolyContext& pc = *ctx->impl;
+    if (pc.moduli_count() < 2) return HE_ERR_INVALID_POLY_CONTEXT;  // no next context (PolyRq.swift:366-368)
+    if (kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
+    if (batch == 0) return HE_OK;
+    if (in == nullptr || out == nullptr) return invalid_argument("null slab");
+    if (!kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
+    HEAMD_HIP_TRY(divide_and_round_q_last(in, out, pc, pc.moduli_count(), batch, as_stream(s)));
+    return HE_OK;
+}
 }  // namespace
 
 // ---- scratch (api_internal.hpp scratch_allocate / scratch_release) ----------------------------------------------------
@@ -576,10 +634,10 @@ int he_generate_primes(const int32_t* significant_bit_counts, uint32_t count, in
 
 // ------------------------------------------------------------------------------------------ NTT
 int he_ntt_forward_device(const he_poly_context* ctx, uint64_t* device_slab, size_t batch, he_stream stream) {
-    return ntt_device(ctx, device_slab, batch, false, as_stream(stream));
+    return heamd::poly_ntt(ctx, device_slab, batch, false, as_stream(stream));
 }
 int he_ntt_inverse_device(const he_poly_context* ctx, uint64_t* device_slab, size_t batch, he_stream stream) {
-    return ntt_device(ctx, device_slab, batch, true, as_stream(stream));
+    return heamd::poly_ntt(ctx, device_slab, batch, true, as_stream(stream));
 }
 int he_ntt_forward_rows_device(const he_poly_context* ctx, uint64_t modulus, uint64_t* device_rows, size_t rows,
                                he_stream stream) {
@@ -603,7 +661,7 @@ static int ntt_host(const he_poly_context* ctx, uint64_t* host_slab, size_t batc
     // costs more than the overlap gains) -- profiles/r05d_host_seam_pipelined_vs_blocking.txt.
     const size_t words = batch * pc.moduli_count() * pc.degree();
     return with_device_copy(host_slab, words, [&](uint64_t* device, hipStream_t stream) {
-        return ntt_device(ctx, device, batch, inverse, stream);
+        return heamd::poly_ntt(ctx, device, batch, inverse, stream);
     });
 }
 int he_ntt_forward(const he_poly_context* ctx, uint64_t* host_slab, size_t batch) {
@@ -635,16 +693,16 @@ int he_ntt_device_variant(const he_poly_context* ctx, uint64_t* device_slab, siz
 
 // ------------------------------------------------------------------------------------------ element-wise
 int he_poly_add_device(const he_poly_context* ctx, uint64_t* lhs, const uint64_t* rhs, size_t batch, he_stream s) {
-    return elementwise(ctx, heamd::ElementwiseOp::Add, lhs, rhs, batch, s);
+    return heamd::poly_elementwise(ctx, heamd::ElementwiseOp::Add, lhs, rhs, batch, as_stream(s));
 }
 int he_poly_sub_device(const he_poly_context* ctx, uint64_t* lhs, const uint64_t* rhs, size_t batch, he_stream s) {
-    return elementwise(ctx, heamd::ElementwiseOp::Sub, lhs, rhs, batch, s);
+    return heamd::poly_elementwise(ctx, heamd::ElementwiseOp::Sub, lhs, rhs, batch, as_stream(s));
 }
 int he_poly_neg_device(const he_poly_context* ctx, uint64_t* data, size_t batch, he_stream s) {
-    return elementwise(ctx, heamd::ElementwiseOp::Neg, data, nullptr, batch, s);
+    return heamd::poly_elementwise<uint64_t>(ctx, heamd::ElementwiseOp::Neg, data, nullptr, batch, as_stream(s));
 }
 int he_poly_mul_device(const he_poly_context* ctx, uint64_t* lhs, const uint64_t* rhs, size_t batch, he_stream s) {
-    return elementwise(ctx, heamd::ElementwiseOp::Mul, lhs, rhs, batch, s);
+    return heamd::poly_elementwise(ctx, heamd::ElementwiseOp::Mul, lhs, rhs, batch, as_stream(s));
 }
 int he_poly_apply_galois_device(const he_poly_context* ctx, const uint64_t* in, uint64_t* out, size_t batch,
                                 uint64_t element, int eval_format, he_stream s) {
@@ -816,46 +874,14 @@ int he_poly_random_from_seeds_device(const he_poly_context* ctx, const uint8_t* 
 }
 
 // ------------------------------------------------------------------------------------------ PolyRq<UInt32>
-namespace {
-int ntt32(const he_poly_context* ctx, uint32_t* slab, size_t batch, bool inverse, he_stream s) {
-    if (ctx == nullptr) return invalid_argument("null context");
-    const PolyContext& pc = *ctx->impl;
-    if (!pc.all_ntt(pc.moduli_count())) return HE_ERR_INVALID_NTT_MODULUS;
-    heamd::DeviceContext32 dc{};
-    int status = pc.device_context32(pc.moduli_count(), dc);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (slab == nullptr) return invalid_argument("null slab");
-    hipError_t e = heamd::launch_ntt32(inverse, slab, dc, 0, pc.moduli_count(), batch * pc.moduli_count(), as_stream(s));
-    if (e == hipErrorNotSupported) {
-        heamd::set_last_error("UInt32 transform supports degrees up to 32768");
-        return HE_ERR_UNSUPPORTED;
-    }
-    HEAMD_HIP_TRY(e);
-    return HE_OK;
-}
-int elementwise32(const he_poly_context* ctx, heamd::ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, size_t batch,
-                  he_stream s) {
-    if (ctx == nullptr) return invalid_argument("null context");
-    const PolyContext& pc = *ctx->impl;
-    heamd::DeviceContext32 dc{};
-    int status = pc.device_context32(pc.moduli_count(), dc);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (lhs == nullptr || (rhs == nullptr && op != heamd::ElementwiseOp::Neg)) return invalid_argument("null slab");
-    HEAMD_HIP_TRY(heamd::launch_elementwise32(op, lhs, rhs, nullptr, dc, batch * pc.moduli_count(), as_stream(s)));
-    return HE_OK;
-}
-}  // namespace
-
 int he_ntt_forward_device_u32(const he_poly_context* ctx, uint32_t* device_slab, size_t batch, he_stream s) {
-    return ntt32(ctx, device_slab, batch, false, s);
+    return heamd::poly_ntt(ctx, device_slab, batch, false, as_stream(s));
 }
 int he_ntt_inverse_device_u32(const he_poly_context* ctx, uint32_t* device_slab, size_t batch, he_stream s) {
-    return ntt32(ctx, device_slab, batch, true, s);
+    return heamd::poly_ntt(ctx, device_slab, batch, true, as_stream(s));
 }
 int he_poly_add_device_u32(const he_poly_context* ctx, uint32_t* lhs, const uint32_t* rhs, size_t batch, he_stream s) {
-    return elementwise32(ctx, heamd::ElementwiseOp::Add, lhs, rhs, batch, s);
+    return heamd::poly_elementwise(ctx, heamd::ElementwiseOp::Add, lhs, rhs, batch, as_stream(s));
 }
 // ---- word-size bridge for Bfv<UInt32> callers
 int he_words_widen_u32_device(const uint32_t* in, uint64_t* out, size_t words, he_stream s) {
@@ -882,54 +908,21 @@ int he_words_narrow_u64_device(const uint64_t* in, uint32_t* out, size_t words, 
 }
 
 int he_poly_sub_device_u32(const he_poly_context* ctx, uint32_t* lhs, const uint32_t* rhs, size_t batch, he_stream s) {
-    return elementwise32(ctx, heamd::ElementwiseOp::Sub, lhs, rhs, batch, s);
+    return heamd::poly_elementwise(ctx, heamd::ElementwiseOp::Sub, lhs, rhs, batch, as_stream(s));
 }
 int he_poly_neg_device_u32(const he_poly_context* ctx, uint32_t* data, size_t batch, he_stream s) {
-    return elementwise32(ctx, heamd::ElementwiseOp::Neg, data, nullptr, batch, s);
+    return heamd::poly_elementwise<uint32_t>(ctx, heamd::ElementwiseOp::Neg, data, nullptr, batch, as_stream(s));
 }
 int he_poly_mul_device_u32(const he_poly_context* ctx, uint32_t* lhs, const uint32_t* rhs, size_t batch, he_stream s) {
-    return elementwise32(ctx, heamd::ElementwiseOp::Mul, lhs, rhs, batch, s);
+    return heamd::poly_elementwise(ctx, heamd::ElementwiseOp::Mul, lhs, rhs, batch, as_stream(s));
 }
 int he_poly_mul_scalar_device_u32(const he_poly_context* ctx, uint32_t* data, const uint32_t* scalar_residues,
                                   size_t batch, he_stream s) {
-    if (ctx == nullptr || scalar_residues == nullptr) return invalid_argument("null pointer");
-    const PolyContext& pc = *ctx->impl;
-    heamd::DeviceContext32 dc{};
-    int status = pc.device_context32(pc.moduli_count(), dc);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (data == nullptr) return invalid_argument("null slab");
-    std::vector<uint64_t> pairs(2 * pc.moduli_count());
-    for (uint32_t i = 0; i < pc.moduli_count(); ++i) {
-        const uint64_t p = pc.moduli()[i];
-        if (scalar_residues[i] >= p) return invalid_argument("scalar residue not reduced");
-        pairs[2 * i] = scalar_residues[i];
-        pairs[2 * i + 1] = heamd::shoup_factor(scalar_residues[i], p);
-    }
-    hipStream_t stream = as_stream(s);
-    Scratch scratch(stream);
-    HEAMD_HIP_TRY(scratch.allocate(pairs.size() * sizeof(uint64_t)));
-    HEAMD_HIP_TRY(hipMemcpyAsync(scratch.get(), pairs.data(), pairs.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                 stream));
-    HEAMD_HIP_TRY(hipStreamSynchronize(stream));  // the pageable host vector must outlive the async copy
-    HEAMD_HIP_TRY(heamd::launch_elementwise32(heamd::ElementwiseOp::MulScalar, data, nullptr,
-                                              static_cast<const uint64_t*>(scratch.get()), dc,
-                                              batch * pc.moduli_count(), stream));
-    return HE_OK;
+    return poly_mul_scalar(ctx, data, scalar_residues, batch, s);
 }
 int he_poly_divide_and_round_q_last_device_u32(const he_poly_context* ctx, const uint32_t* device_in,
                                                uint32_t* device_out, size_t batch, he_stream s) {
-    if (ctx == nullptr) return invalid_argument("null context");
-    const PolyContext& pc = *ctx->impl;
-    if (pc.moduli_count() < 2) return HE_ERR_INVALID_POLY_CONTEXT;  // PolyRq.swift:366-368
-    heamd::DeviceContext32 dc{};
-    int status = pc.device_context32(pc.moduli_count(), dc);
-    if (status != HE_OK) return status;
-    if (batch == 0) return HE_OK;
-    if (device_in == nullptr || device_out == nullptr) return invalid_argument("null slab");
-    HEAMD_HIP_TRY(heamd::launch_divide_and_round_q_last32(device_in, device_out, dc, pc.moduli_count(), batch,
-                                                          as_stream(s)));
-    return HE_OK;
+    return poly_divide_and_round_q_last(ctx, device_in, device_out, batch, s);
 }
 
 // ------------------------------------------------------------------- wire format of whole ciphertexts, and on 4-byte slabs
@@ -1013,15 +1006,6 @@ int ciphertexts_deserialize(const he_poly_context* ctx, const uint8_t* records, 
     return HE_OK;
 }
 
-hipError_t inverse_ntt_rows(const PolyContext& pc, uint64_t* rows, hipStream_t stream) {
-    return heamd::launch_ntt(true, rows, pc.device_context(), 0, pc.moduli_count(), pc.moduli_count(), stream);
-}
-hipError_t inverse_ntt_rows(const PolyContext& pc, uint32_t* rows, hipStream_t stream) {
-    heamd::DeviceContext32 dc{};
-    if (pc.device_context32(pc.moduli_count(), dc) != HE_OK) return hipErrorInvalidValue;
-    return heamd::launch_ntt32(true, rows, dc, 0, pc.moduli_count(), pc.moduli_count(), stream);
-}
-
 template <typename W>
 int ciphertexts_deserialize_seeded(const he_poly_context* ctx, const uint8_t* poly0_bytes, size_t record_stride,
                                    const uint8_t* seeds, size_t count, int coeff_format, W* cts, he_stream s) {
@@ -1066,7 +1050,8 @@ int ciphertexts_deserialize_seeded(const he_poly_context* ctx, const uint8_t* po
         // which come by the dozen, are Eval and take none
         if (coeff_format != 0)
             for (size_t i = 0; i < count; ++i) {
-                HEAMD_HIP_TRY(inverse_ntt_rows(pc, cts + (2 * i + 1) * poly_words, stream));
+                HEAMD_HIP_TRY(ntt_rows(true, cts + (2 * i + 1) * poly_words, pc, pc.device_context(), pc.moduli_count(),
+                                       pc.moduli_count(), stream));
             }
     }
     return HE_OK;
@@ -1212,43 +1197,11 @@ int he_poly_random_from_seeds_device_u32(const he_poly_context* ctx, const uint8
 
 int he_poly_mul_scalar_device(const he_poly_context* ctx, uint64_t* data, const uint64_t* scalar_residues,
                               size_t batch, he_stream s) {
-    if (ctx == nullptr || scalar_residues == nullptr) return invalid_argument("null pointer");
-    const PolyContext& pc = *ctx->impl;
-    if (batch == 0) return HE_OK;
-    int status = pc.check_device();
-    if (status != HE_OK) return status;
-    // MultiplyConstantModulus(multiplicand:divisionModulus:) per row (PolyRq.swift:235-238)
-    std::vector<heamd::U64x2> pairs(pc.moduli_count());
-    for (uint32_t i = 0; i < pc.moduli_count(); ++i) {
-        const uint64_t p = pc.moduli()[i];
-        if (scalar_residues[i] >= p) return invalid_argument("scalar residue not reduced");
-        pairs[i] = heamd::U64x2{scalar_residues[i], heamd::shoup_factor(scalar_residues[i], p)};
-    }
-    hipStream_t stream = as_stream(s);
-    Scratch scratch(stream);
-    HEAMD_HIP_TRY(scratch.allocate(pairs.size() * sizeof(heamd::U64x2)));
-    HEAMD_HIP_TRY(hipMemcpyAsync(scratch.get(), pairs.data(), pairs.size() * sizeof(heamd::U64x2),
-                                 hipMemcpyHostToDevice, stream));
-    // the pageable host vector must outlive the async copy
-    HEAMD_HIP_TRY(hipStreamSynchronize(stream));
-    HEAMD_HIP_TRY(heamd::launch_elementwise(heamd::ElementwiseOp::MulScalar, data,
-                                            static_cast<const uint64_t*>(scratch.get()), pc.device_context(),
-                                            batch * pc.moduli_count(), stream));
-    return HE_OK;
+    return poly_mul_scalar(ctx, data, scalar_residues, batch, s);
 }
-
 int he_poly_divide_and_round_q_last_device(const he_poly_context* ctx, const uint64_t* in, uint64_t* out,
                                            size_t batch, he_stream s) {
-    if (ctx == nullptr) return invalid_argument("null context");
-    const PolyContext& pc = *ctx->impl;
-    if (pc.moduli_count() < 2) return HE_ERR_INVALID_POLY_CONTEXT;  // no next context (PolyRq.swift:366-368)
-    if (batch == 0) return HE_OK;
-    if (in == nullptr || out == nullptr) return invalid_argument("null slab");
-    int status = pc.check_device();
-    if (status != HE_OK) return status;
-    HEAMD_HIP_TRY(heamd::launch_divide_and_round_q_last(in, out, pc.device_context(), pc.moduli_count(), batch,
-                                                        as_stream(s)));
-    return HE_OK;
+    return poly_divide_and_round_q_last(ctx, in, out, batch, s);
 }
 int he_poly_divide_and_round_q_last(const he_poly_context* ctx, const uint64_t* host_in, uint64_t* host_out,
                                     size_t batch) {

@@ -16,17 +16,12 @@
 #include "api_internal.hpp"
 #include "kernels.hpp"
 #include "side_lane.hpp"
+#include "word_layer.hpp"
 
 using heamd::as_stream;
 using heamd::invalid_argument;
 using heamd::Scratch;
 using heamd::SideLane;
-
-#define HEAMD_TRY_STATUS(expr)            \
-    do {                                  \
-        const int status_ = (expr);       \
-        if (status_ != HE_OK) return status_; \
-    } while (0)
 
 namespace {
 
@@ -350,18 +345,15 @@ extern "C" int he_pir_compute_response_packed_device(const he_bfv_context* ctx, 
 namespace {
 // scratch of the 4-byte remaining-dimension stages for up to `group` chunks at a time
 struct Word32Stages {
-    Scratch next_mem, products_mem, level_mem;
-    uint32_t *next = nullptr, *products = nullptr, *ping = nullptr, *pong = nullptr;
-    explicit Word32Stages(hipStream_t stream) : next_mem(stream), products_mem(stream), level_mem(stream) {}
+    Scratch next_mem, products_mem;
+    uint32_t *next = nullptr, *products = nullptr;
+    explicit Word32Stages(hipStream_t stream) : next_mem(stream), products_mem(stream) {}
     hipError_t allocate(const ChunkShape& shape, size_t group) {
         const size_t ct2 = 2 * size_t(shape.L) * shape.n, ct3 = 3 * size_t(shape.L) * shape.n, widest = group * shape.columns;
         if (hipError_t e = next_mem.allocate(widest * ct2 * sizeof(uint32_t)); e != hipSuccess) return e;
         if (hipError_t e = products_mem.allocate(widest * ct3 * sizeof(uint32_t)); e != hipSuccess) return e;
-        if (hipError_t e = level_mem.allocate(2 * group * ct2 * sizeof(uint32_t)); e != hipSuccess) return e;
         next = static_cast<uint32_t*>(next_mem.get());
         products = static_cast<uint32_t*>(products_mem.get());
-        ping = static_cast<uint32_t*>(level_mem.get());
-        pong = ping + group * ct2;
         return hipSuccess;
     }
 };
@@ -372,9 +364,8 @@ int remaining_dimensions_u32(const he_bfv_context* ctx, const uint32_t* dimensio
                              const ChunkShape& shape, size_t chunks, uint32_t* results, Word32Stages& stages,
                              const uint32_t* remaining_query, const uint32_t* relinearization_key, uint32_t* target,
                              he_stream s) {
-    hipStream_t stream = as_stream(s);
     const uint32_t L = shape.L;
-    const size_t ct2 = 2 * size_t(L) * shape.n, out_words = 2 * shape.n;
+    const size_t ct2 = 2 * size_t(L) * shape.n;
     uint32_t* current = results;
     uint32_t* other = stages.next;
     size_t count = shape.columns, cursor = 0;
@@ -393,17 +384,7 @@ int remaining_dimensions_u32(const he_bfv_context* ctx, const uint32_t* dimensio
     }
     if (count != 1) return invalid_argument("dimensions leave more than one ciphertext");  // PirUtil.swift:481-482
     // modSwitchDownToSingle (:483)
-    if (L == 1) {
-        HEAMD_HIP_TRY(hipMemcpyAsync(target, current, chunks * out_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-        return HE_OK;
-    }
-    const uint32_t* source = current;
-    for (uint32_t level = L; level > 1; --level) {
-        uint32_t* step = level == 2 ? target : (source == stages.ping ? stages.pong : stages.ping);
-        HEAMD_TRY_STATUS(he_bfv_mod_switch_down_device_u32(ctx, level, 2, source, step, chunks, s));
-        source = step;
-    }
-    return HE_OK;
+    return heamd::bfv_mod_switch_down_to_single(ctx, L, 2, current, target, chunks, as_stream(s));
 }
 }  // namespace
 

@@ -9,8 +9,9 @@
 //
 // And the server's answer, Server.computeResponse (Server.swift:61-88) for one-row query vectors: PlaintextMatrix.mulTranspose(
 // vector:using:) (MatrixMultiplication.swift:131-226) over Q independent queries, then modSwitchDownToSingle.  Rotations, the
-// transforms, additions and the mod-switch are the library's own entry points, batched over the queries; the one kernel of its
-// own is the pass over the matrix (pnns_kernels.hip, pnns_bsgs_inner_product_kernel).
+// transforms, additions and the mod-switch are the bodies of the library's own entry points for either word (word_layer.hpp),
+// batched over the queries; the one kernel of its own is the pass over the matrix (pnns_kernels.hip,
+// pnns_bsgs_inner_product_kernel).
 //
 // And PlaintextMatrix.mulTranspose(matrix:using:) (MatrixMultiplication.swift:236-298) for query matrices of several rows:
 // CiphertextMatrix.extractDenseRow per row (masks and masked products: pnns_row_mask_kernel, pnns_extract_rows_kernel), the
@@ -24,16 +25,11 @@
 #include "api_internal.hpp"
 #include "bfv_context.hpp"
 #include "kernels.hpp"
+#include "word_layer.hpp"
 
 using heamd::as_stream;
 using heamd::invalid_argument;
 using heamd::Scratch;
-
-#define HEAMD_TRY_STATUS(expr)                \
-    do {                                      \
-        const int status_ = (expr);           \
-        if (status_ != HE_OK) return status_; \
-    } while (0)
 
 // Opaque handle of include/he_amd.h
 struct he_pnns_context {
@@ -166,24 +162,6 @@ size_t group_plaintexts(size_t n, uint32_t L, size_t word_bytes) {
     return group ? group : 1;
 }
 
-int inverse_ntt(const heamd::PolyContext& ring, uint64_t* slabs, size_t count, hipStream_t stream) {
-    HEAMD_HIP_TRY(heamd::launch_ntt(true, slabs, ring.device_context(), 0, 1, count, stream));
-    return HE_OK;
-}
-int inverse_ntt(const heamd::PolyContext& ring, uint32_t* slabs, size_t count, hipStream_t stream) {
-    heamd::DeviceContext32 dc{};
-    const int status = ring.device_context32(1, dc);
-    if (status != HE_OK) return status;
-    HEAMD_HIP_TRY(heamd::launch_ntt32(true, slabs, dc, 0, 1, count, stream));
-    return HE_OK;
-}
-int to_eval(const he_bfv_context* ctx, uint32_t L, const uint64_t* staging, uint64_t* out, size_t batch, he_stream s) {
-    return he_bfv_plaintext_to_eval_device(ctx, L, staging, out, batch, s);
-}
-int to_eval(const he_bfv_context* ctx, uint32_t L, const uint32_t* staging, uint32_t* out, size_t batch, he_stream s) {
-    return he_bfv_plaintext_to_eval_device_u32(ctx, L, staging, out, batch, s);
-}
-
 template <typename W>
 int diagonal_matrix(const he_pnns_context* ctx, const int64_t* values, size_t rows, size_t cols, uint32_t baby_step,
                     int reduce, uint32_t moduli_count, W* out, uint32_t* out_of_range, he_stream s) {
@@ -193,8 +171,7 @@ int diagonal_matrix(const he_pnns_context* ctx, const int64_t* values, size_t ro
     const heamd::BfvContext& bfv = heamd::bfv_impl(ctx->bfv);
     if (bfv.word_bits() != 8 * sizeof(W)) return invalid_argument("context of the other word size");
     // the level checks of Plaintext.convertToEvalFormat (host-only context: HE_ERR_DEVICE) before anything is enqueued
-    const int ready = to_eval(ctx->bfv, moduli_count, static_cast<const W*>(nullptr), static_cast<W*>(nullptr), 0, s);
-    if (ready != HE_OK) return ready;
+    HEAMD_TRY_STATUS(heamd::bfv_plaintext_to_eval<W>(ctx->bfv, moduli_count, nullptr, nullptr, 0, as_stream(s)));
     if (values == nullptr || out == nullptr) return invalid_argument("null buffer");
     const heamd::PolyContext& ring = *ctx->plaintext;
     const int on_device = ring.check_device();
@@ -219,10 +196,9 @@ int diagonal_matrix(const he_pnns_context* ctx, const int64_t* values, size_t ro
         const size_t count = total - first < group ? total - first : group;
         HEAMD_HIP_TRY(heamd::launch_pnns_diagonal_pack<W>(values, ctx->slot_of_word_device, layout, first, count, staging,
                                                            out_of_range, stream));
-        const int inverted = inverse_ntt(ring, staging, count, stream);
-        if (inverted != HE_OK) return inverted;
-        const int converted = to_eval(ctx->bfv, moduli_count, staging, out + first * moduli_count * n, count, s);
-        if (converted != HE_OK) return converted;
+        HEAMD_HIP_TRY(ntt_rows(true, staging, ring, ring.device_context(), 1, count, stream));
+        HEAMD_TRY_STATUS(heamd::bfv_plaintext_to_eval(ctx->bfv, moduli_count, staging, out + first * moduli_count * n, count,
+                                                      stream));
     }
     return HE_OK;
 }
@@ -237,58 +213,6 @@ int apply_galois(const he_bfv_context* ctx, uint32_t L, const W* in, uint64_t el
     return heamd::bfv_apply_galois_grouped(ctx, L, in, element, per_group.data(), groups, group_size, out, nullptr, 0,
                                            as_stream(s));
 }
-
-// The library's entry points by word size
-struct Ops64 {
-    using Word = uint64_t;
-    static int forward_ntt(const he_poly_context* ring, Word* slab, size_t polys, he_stream s) {
-        return he_ntt_forward_device(ring, slab, polys, s);
-    }
-    static int inverse_ntt(const he_poly_context* ring, Word* slab, size_t polys, he_stream s) {
-        return he_ntt_inverse_device(ring, slab, polys, s);
-    }
-    static int add(const he_poly_context* ring, Word* lhs, const Word* rhs, size_t polys, he_stream s) {
-        return he_poly_add_device(ring, lhs, rhs, polys, s);
-    }
-    static int to_single(const he_bfv_context* ctx, uint32_t L, const Word* in, Word* out, size_t batch, Word*, he_stream s) {
-        return he_bfv_mod_switch_down_to_single_device(ctx, L, 2, in, out, batch, s);
-    }
-    static size_t to_single_scratch_words(uint32_t, size_t, size_t) { return 0; }
-};
-struct Ops32 {
-    using Word = uint32_t;
-    static int forward_ntt(const he_poly_context* ring, Word* slab, size_t polys, he_stream s) {
-        return he_ntt_forward_device_u32(ring, slab, polys, s);
-    }
-    static int inverse_ntt(const he_poly_context* ring, Word* slab, size_t polys, he_stream s) {
-        return he_ntt_inverse_device_u32(ring, slab, polys, s);
-    }
-    static int add(const he_poly_context* ring, Word* lhs, const Word* rhs, size_t polys, he_stream s) {
-        return he_poly_add_device_u32(ring, lhs, rhs, polys, s);
-    }
-    // the chain of he_bfv_mod_switch_down_device_u32 through two slabs of `level_words` words
-    static int to_single(const he_bfv_context* ctx, uint32_t L, const Word* in, Word* out, size_t batch, Word* levels,
-                         he_stream s) {
-        const size_t n = heamd::bfv_impl(ctx).degree();
-        if (L == 1) {
-            HEAMD_HIP_TRY(hipMemcpyAsync(out, in, batch * 2 * n * sizeof(Word), hipMemcpyDeviceToDevice, as_stream(s)));
-            return HE_OK;
-        }
-        Word* ping = levels;
-        Word* pong = levels + batch * 2 * size_t(L - 1) * n;
-        const Word* source = in;
-        for (uint32_t level = L; level > 1; --level) {
-            Word* step = level == 2 ? out : (source == ping ? pong : ping);
-            const int status = he_bfv_mod_switch_down_device_u32(ctx, level, 2, source, step, batch, s);
-            if (status != HE_OK) return status;
-            source = step;
-        }
-        return HE_OK;
-    }
-    static size_t to_single_scratch_words(uint32_t L, size_t batch, size_t n) {
-        return L > 2 ? 2 * batch * 2 * size_t(L - 1) * n : 0;
-    }
-};
 
 // Result ciphertexts per group: the inner products of a group ([G][Q][group][2][L][N]) stay near 2 GiB.
 // HEAMD_PNNS_RESPONSE_GROUP=<result ciphertexts> forces smaller groups (the tests: many groups must give the words of one).
@@ -305,11 +229,9 @@ size_t response_group(size_t result_count, size_t queries, size_t giant_step, si
 // mulTranspose(vector:using:) (MatrixMultiplication.swift:131-226) for `vectors` one-row vectors already on the device:
 // vector v under the keys keys[v * key_stride] (rotatingColumns(by: -1)) and keys[v * key_stride + 1] ((by: -babyStep)).
 // Everything has been validated.  out [vectors][C][2][L][N], or [..][2][1][N] through modSwitchDownToSingle.
-template <typename Ops>
-int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typename Ops::Word* matrix,
-                 const typename Ops::Word* queries, const typename Ops::Word* const* galois_keys, size_t key_stride,
-                 size_t vectors, typename Ops::Word* out, bool to_single, he_stream s) {
-    using W = typename Ops::Word;
+template <typename W>
+int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const W* matrix, const W* queries,
+                 const W* const* galois_keys, size_t key_stride, size_t vectors, W* out, bool to_single, he_stream s) {
     const heamd::BfvContext& bfv = heamd::bfv_impl(ctx->bfv);
     const uint32_t b = plan.baby_step, G = plan.giant_step, L = bfv.top_level();
     const size_t n = bfv.degree(), C = plan.plaintexts_per_column, Q = vectors;
@@ -331,7 +253,7 @@ int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typen
     for (uint32_t j = 1; j < b; ++j)
         HEAMD_TRY_STATUS(apply_galois(ctx->bfv, L, rot + size_t(j - 1) * Q * ct, element_one, galois_keys, key_stride, Q, 1,
                                       rot + size_t(j) * Q * ct, s));
-    HEAMD_TRY_STATUS(Ops::forward_ntt(ring, rot, size_t(b) * Q * 2, s));
+    HEAMD_TRY_STATUS(heamd::poly_ntt(ring, rot, size_t(b) * Q * 2, false, stream));
 
     heamd::PnnsBsgsLayout layout{};
     layout.rot_step_words = Q * ct;
@@ -342,26 +264,18 @@ int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typen
     layout.padded_cols = static_cast<uint32_t>(plan.padded_cols);
     layout.columns = static_cast<uint32_t>(C);
     layout.out_queries = static_cast<uint32_t>(Q);
-    layout.max_lazy = q_ctx->max_lazy_product_accumulation_count(L);
-    layout.cadence = layout.max_lazy;
-    layout.narrow_moduli = true;
-    for (uint32_t i = 0; i < L; ++i) {  // as he_bfv_inner_product_plain_device: sums of the carry-counting accumulator below 2^127
-        layout.narrow_moduli = layout.narrow_moduli && (q_ctx->moduli()[i] >> 56) == 0;
-        const unsigned __int128 below = q_ctx->moduli()[i] - 1;
-        if (below == 0) continue;
-        const unsigned __int128 limit = ((static_cast<unsigned __int128>(1) << 127) - q_ctx->moduli()[i]) / (below * below);
-        if (limit < layout.cadence) layout.cadence = static_cast<uint64_t>(limit);
-    }
+    const heamd::AccumulatorCadence lazy = heamd::accumulator_cadence(*q_ctx, L);
+    layout.max_lazy = lazy.max_lazy;
+    layout.cadence = lazy.cadence;
+    layout.narrow_moduli = lazy.narrow_moduli;
     const unsigned per_pass = heamd::pnns_bsgs_queries_per_pass(layout, sizeof(W), Q);
     const heamd::DeviceContext dc = q_ctx->device_context(L);
 
     const size_t group = response_group(C, Q, G, ct_bytes);
     const size_t out_ct = to_single ? 2 * n : ct;  // words of a result ciphertext in `out`
-    Scratch products_mem(stream), sums_mem(stream), levels_mem(stream);
+    Scratch products_mem(stream), sums_mem(stream);
     HEAMD_HIP_TRY(products_mem.allocate(Q * G * group * ct_bytes));
     HEAMD_HIP_TRY(sums_mem.allocate(2 * Q * group * ct_bytes));
-    const size_t level_words = to_single ? Ops::to_single_scratch_words(L, Q * group, n) : 0;
-    if (level_words != 0) HEAMD_HIP_TRY(levels_mem.allocate(level_words * sizeof(W)));
     W* products = static_cast<W*>(products_mem.get());  // [G][Q][now][2][L][N]
     W* sums = static_cast<W*>(sums_mem.get());          // two of [Q][now][2][L][N]
     for (size_t first = 0; first < C; first += group) {
@@ -374,7 +288,7 @@ int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typen
             HEAMD_HIP_TRY(heamd::launch_pnns_bsgs_inner_product<W>(rot + q * ct, matrix, products + q * now * ct, dc, layout,
                                                                    taken, stream));
         }
-        HEAMD_TRY_STATUS(Ops::inverse_ntt(ring, products, Q * G * now * 2, s));
+        HEAMD_TRY_STATUS(heamd::poly_ntt(ring, products, Q * G * now * 2, true, stream));
         // 3) rotateColumnsAndSum (HeScheme.swift:113-133): the last giant step's product, then per earlier one rotate by
         //    -babyStep and add it; every step one key switch and one addition over the Q x now accumulators.  The products are
         //    giant-step major, so the last step's slab is the first accumulator where it lies.
@@ -382,15 +296,16 @@ int bsgs_product(const he_pnns_context* ctx, const MatrixPlan& plan, const typen
         W* other = sums;
         for (uint32_t g = G - 1; g-- > 0;) {
             HEAMD_TRY_STATUS(apply_galois(ctx->bfv, L, current, element_baby, galois_keys + 1, key_stride, Q, now, other, s));
-            HEAMD_TRY_STATUS(Ops::add(ring, other, products + size_t(g) * Q * now * ct, Q * now * 2, s));
+            HEAMD_TRY_STATUS(heamd::poly_elementwise(ring, heamd::ElementwiseOp::Add, other, products + size_t(g) * Q * now * ct,
+                                                     Q * now * 2, stream));
             current = other;
             other = current == sums ? sums + Q * now * ct : sums;
         }
         // 4) the group's results to their places in out [Q][C]; computeResponse: through modSwitchDownToSingle (Server.swift:84)
         if (to_single && now == C) {
-            HEAMD_TRY_STATUS(Ops::to_single(ctx->bfv, L, current, out, Q * C, static_cast<W*>(levels_mem.get()), s));
+            HEAMD_TRY_STATUS(heamd::bfv_mod_switch_down_to_single(ctx->bfv, L, 2, current, out, Q * C, stream));
         } else if (to_single) {
-            HEAMD_TRY_STATUS(Ops::to_single(ctx->bfv, L, current, other, Q * now, static_cast<W*>(levels_mem.get()), s));
+            HEAMD_TRY_STATUS(heamd::bfv_mod_switch_down_to_single(ctx->bfv, L, 2, current, other, Q * now, stream));
             HEAMD_HIP_TRY(hipMemcpy2DAsync(out + first * out_ct, C * out_ct * sizeof(W), other, now * out_ct * sizeof(W),
                                            now * out_ct * sizeof(W), Q, hipMemcpyDeviceToDevice, stream));
         } else {
@@ -424,11 +339,10 @@ int response_buffers(const he_pnns_context* ctx, const W* matrix, const W* queri
     return bfv.ciphertext(bfv.top_level())->check_device();
 }
 
-template <typename Ops>
-int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, size_t matrix_plaintext_count, size_t rows,
-                  size_t cols, uint32_t baby_step, const typename Ops::Word* queries, size_t query_count,
-                  const typename Ops::Word* const* galois_keys, typename Ops::Word* out, bool to_single, he_stream s) {
-    using W = typename Ops::Word;
+template <typename W>
+int mul_transpose(const he_pnns_context* ctx, const W* matrix, size_t matrix_plaintext_count, size_t rows, size_t cols,
+                  uint32_t baby_step, const W* queries, size_t query_count, const W* const* galois_keys, W* out,
+                  bool to_single, he_stream s) {
     MatrixPlan plan;
     HEAMD_TRY_STATUS(response_plan<W>(ctx, matrix_plaintext_count, rows, cols, baby_step, plan));
     if (query_count == 0) return HE_OK;
@@ -447,7 +361,7 @@ int mul_transpose(const he_pnns_context* ctx, const typename Ops::Word* matrix, 
         }
     }
     HEAMD_TRY_STATUS(response_buffers<W>(ctx, matrix, queries, out));
-    return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, 2, Q, out, to_single, s);
+    return bsgs_product(ctx, plan, matrix, queries, galois_keys, 2, Q, out, to_single, s);
 }
 
 // ---- mulTranspose(matrix:using:): query matrices of several rows ------------------------------------------------------------
@@ -532,9 +446,8 @@ int query_plan(const he_pnns_context* ctx, size_t matrix_rows, size_t cols, size
 
 // Ciphertexts of (position, client): the rows of the clients' queries, later the half-chunks of their results.  A Galois call
 // takes a key per ciphertext, so positions are the outer index and a run of positions over all clients is one contiguous batch.
-template <typename Ops>
+template <typename W>
 struct Grid {
-    using W = typename Ops::Word;
     const he_pnns_context* ctx;
     size_t clients, ct;  // ct: words of a ciphertext
     uint32_t L;
@@ -551,7 +464,8 @@ struct Grid {
     // lhs positions [first, first + count) += rhs positions [rhs_first, ..)
     int add(const he_poly_context* ring, W* lhs, size_t first, const W* rhs, size_t rhs_first, size_t count) const {
         if (count == 0) return HE_OK;
-        return Ops::add(ring, lhs + first * clients * ct, rhs + rhs_first * clients * ct, count * clients * 2, s);
+        return heamd::poly_elementwise(ring, heamd::ElementwiseOp::Add, lhs + first * clients * ct, rhs + rhs_first * clients * ct,
+                                       count * clients * 2, as_stream(s));
     }
     // dst positions [first, first + count) = src positions [src_first, ..)
     hipError_t copy(W* dst, size_t first, const W* src, size_t src_first, size_t count) const {
@@ -570,12 +484,11 @@ hipError_t to_client_major(W* dst, size_t dst_positions, size_t to, const W* src
                             unit * sizeof(W), clients, hipMemcpyDeviceToDevice, stream);
 }
 
-template <typename Ops>
-int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* matrix, size_t matrix_plaintext_count,
-                         size_t rows, size_t cols, uint32_t baby_step, const typename Ops::Word* queries, size_t query_rows,
-                         size_t query_count, const he_pnns_pack_step* pack_steps, size_t pack_step_count,
-                         const typename Ops::Word* const* galois_keys, typename Ops::Word* out, bool to_single, he_stream s) {
-    using W = typename Ops::Word;
+template <typename W>
+int mul_transpose_matrix(const he_pnns_context* ctx, const W* matrix, size_t matrix_plaintext_count, size_t rows, size_t cols,
+                         uint32_t baby_step, const W* queries, size_t query_rows, size_t query_count,
+                         const he_pnns_pack_step* pack_steps, size_t pack_step_count, const W* const* galois_keys, W* out,
+                         bool to_single, he_stream s) {
     MatrixPlan plan;
     HEAMD_TRY_STATUS(response_plan<W>(ctx, matrix_plaintext_count, rows, cols, baby_step, plan));
     QueryPlan query;
@@ -620,7 +533,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
     }
     HEAMD_TRY_STATUS(response_buffers<W>(ctx, matrix, queries, out));
     if (R == 1)  // one row: the vector's own ciphertext, and rotateColumnsAndSum of one element
-        return bsgs_product<Ops>(ctx, plan, matrix, queries, galois_keys, key_stride, Q, out, to_single, s);
+        return bsgs_product(ctx, plan, matrix, queries, galois_keys, key_stride, Q, out, to_single, s);
     if (reinterpret_cast<uintptr_t>(queries) % 16 != 0) return invalid_argument("the queries must be 16-byte aligned");
     HEAMD_TRY_STATUS(ctx->plaintext->check_device());
     const heamd::PolyContext* q_ctx = bfv.ciphertext(L);
@@ -642,7 +555,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
     for (size_t slot = 0; slot < key_stride; ++slot)
         for (size_t v = 0; v < most_positions * Q; ++v)
             tiled[slot * most_positions * Q + v] = galois_keys[(v % Q) * key_stride + slot];
-    Grid<Ops> grid{ctx, Q, ct, L, &tiled, most_positions * Q, s};
+    Grid<W> grid{ctx, Q, ct, L, &tiled, most_positions * Q, s};
 
     Scratch rows_mem(stream);
     HEAMD_HIP_TRY(rows_mem.allocate(V * ct_bytes));
@@ -658,13 +571,13 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
         for (size_t r = 0; r < R; ++r) patterns[r] = heamd::PnnsRowMask{query.rows[r].lower, query.rows[r].period, query.rows[r].copies};
         HEAMD_HIP_TRY(heamd::launch_pnns_row_masks<W>(ctx->slot_of_word_device, patterns.data(), R, static_cast<uint32_t>(P),
                                                        ctx->plaintext->log_degree(), staging, stream));
-        HEAMD_TRY_STATUS(inverse_ntt(*ctx->plaintext, staging, R, stream));
-        HEAMD_TRY_STATUS(to_eval(ctx->bfv, L, staging, masks, R, s));
+        HEAMD_HIP_TRY(ntt_rows(true, staging, *ctx->plaintext, ctx->plaintext->device_context(), 1, R, stream));
+        HEAMD_TRY_STATUS(heamd::bfv_plaintext_to_eval(ctx->bfv, L, staging, masks, R, stream));
         // 2) every query ciphertext to Eval once; each is read once for all the rows packed in it (:340-342)
         HEAMD_HIP_TRY(eval_mem.allocate(Q * K * ct_bytes));
         W* eval = static_cast<W*>(eval_mem.get());
         HEAMD_HIP_TRY(hipMemcpyAsync(eval, queries, Q * K * ct_bytes, hipMemcpyDeviceToDevice, stream));
-        HEAMD_TRY_STATUS(Ops::forward_ntt(ring, eval, Q * K * 2, s));
+        HEAMD_TRY_STATUS(heamd::poly_ntt(ring, eval, Q * K * 2, false, stream));
         heamd::PnnsExtractLayout layout{};
         layout.clients = Q;
         layout.query_ciphertexts = K;
@@ -676,7 +589,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
                                                               static_cast<uint32_t>(first), position_of.data() + first, count,
                                                               stream));
         }
-        HEAMD_TRY_STATUS(Ops::inverse_ntt(ring, extracted, V * 2, s));
+        HEAMD_TRY_STATUS(heamd::poly_ntt(ring, extracted, V * 2, true, stream));
         // 3) replication over a SIMD row (:347-353), then both SIMD rows (:358-361)
         HEAMD_HIP_TRY(copies_mem.allocate(2 * V * ct_bytes));
         W* ahead = static_cast<W*>(copies_mem.get());
@@ -704,22 +617,17 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
         pairs[2 * v] = galois_keys[(v % Q) * key_stride];
         pairs[2 * v + 1] = galois_keys[(v % Q) * key_stride + 1];
     }
-    Scratch results_mem(stream), single_mem(stream), levels_mem(stream);
+    Scratch results_mem(stream), single_mem(stream);
     HEAMD_HIP_TRY(results_mem.allocate(V * C * ct_bytes));
     W* results = static_cast<W*>(results_mem.get());  // the grid of [C] results
-    HEAMD_TRY_STATUS(bsgs_product<Ops>(ctx, plan, matrix, extracted, pairs.data(), 2, V, results, false, s));
+    HEAMD_TRY_STATUS(bsgs_product<W>(ctx, plan, matrix, extracted, pairs.data(), 2, V, results, false, s));
     const size_t out_ct = to_single ? 2 * n : ct;
-    auto allocate_levels = [&](size_t batch) -> hipError_t {
-        const size_t words = to_single ? Ops::to_single_scratch_words(L, batch, n) : 0;
-        return words != 0 ? levels_mem.allocate(words * sizeof(W)) : hipSuccess;
-    };
     if (cps == 0) {  // no packing: innerProducts is every row's C results, in row order (:265)
         const W* source = results;
         if (to_single) {
             HEAMD_HIP_TRY(single_mem.allocate(V * C * out_ct * sizeof(W)));
-            HEAMD_HIP_TRY(allocate_levels(V * C));
-            HEAMD_TRY_STATUS(Ops::to_single(ctx->bfv, L, results, static_cast<W*>(single_mem.get()), V * C,
-                                            static_cast<W*>(levels_mem.get()), s));
+            HEAMD_TRY_STATUS(heamd::bfv_mod_switch_down_to_single(ctx->bfv, L, 2, results,
+                                                                  static_cast<W*>(single_mem.get()), V * C, stream));
             source = static_cast<const W*>(single_mem.get());
         }
         for (size_t r = 0; r < R; ++r)
@@ -733,7 +641,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
     const size_t last_parity = (halves - 1) & 1, before = last_parity == 1 ? (halves + 1) / 2 : halves / 2;
     auto half_position = [&](size_t j) { return ((j & 1) == last_parity ? before : 0) + (j >> 1); };
     const size_t last_length = R - (halves - 1) * cps;
-    Grid<Ops> sums{ctx, Q, ct, L, &tiled, most_positions * Q, s};
+    Grid<W> sums{ctx, Q, ct, L, &tiled, most_positions * Q, s};
     Scratch sums_mem(stream);
     HEAMD_HIP_TRY(sums_mem.allocate(2 * halves * Q * ct_bytes));
     W* current = static_cast<W*>(sums_mem.get());
@@ -786,8 +694,7 @@ int mul_transpose_matrix(const he_pnns_context* ctx, const typename Ops::Word* m
                                       stream));
     }
     if (to_single) {
-        HEAMD_HIP_TRY(allocate_levels(Q * M));
-        HEAMD_TRY_STATUS(Ops::to_single(ctx->bfv, L, packed, out, Q * M, static_cast<W*>(levels_mem.get()), s));
+        HEAMD_TRY_STATUS(heamd::bfv_mod_switch_down_to_single(ctx->bfv, L, 2, packed, out, Q * M, stream));
     }
     return HE_OK;
 }
@@ -842,7 +749,7 @@ extern "C" int he_pnns_mul_transpose_device(const he_pnns_context* ctx, const ui
                                             size_t rows, size_t cols, uint32_t baby_step, const uint64_t* queries,
                                             size_t query_count, const uint64_t* const* galois_keys, uint64_t* out,
                                             he_stream s) {
-    return mul_transpose<Ops64>(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
+    return mul_transpose(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
                                 out, false, s);
 }
 
@@ -850,7 +757,7 @@ extern "C" int he_pnns_mul_transpose_device_u32(const he_pnns_context* ctx, cons
                                                 size_t matrix_plaintext_count, size_t rows, size_t cols, uint32_t baby_step,
                                                 const uint32_t* queries, size_t query_count,
                                                 const uint32_t* const* galois_keys, uint32_t* out, he_stream s) {
-    return mul_transpose<Ops32>(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
+    return mul_transpose(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
                                 out, false, s);
 }
 
@@ -858,7 +765,7 @@ extern "C" int he_pnns_compute_response_device(const he_pnns_context* ctx, const
                                                size_t matrix_plaintext_count, size_t rows, size_t cols, uint32_t baby_step,
                                                const uint64_t* queries, size_t query_count,
                                                const uint64_t* const* galois_keys, uint64_t* out, he_stream s) {
-    return mul_transpose<Ops64>(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
+    return mul_transpose(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
                                 out, true, s);
 }
 
@@ -866,7 +773,7 @@ extern "C" int he_pnns_compute_response_device_u32(const he_pnns_context* ctx, c
                                                    size_t matrix_plaintext_count, size_t rows, size_t cols, uint32_t baby_step,
                                                    const uint32_t* queries, size_t query_count,
                                                    const uint32_t* const* galois_keys, uint32_t* out, he_stream s) {
-    return mul_transpose<Ops32>(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
+    return mul_transpose(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_count, galois_keys,
                                 out, true, s);
 }
 
@@ -885,16 +792,16 @@ extern "C" int he_pnns_query_matrix_shape(const he_pnns_context* ctx, size_t mat
     return HE_OK;
 }
 
-#define HEAMD_PNNS_MATRIX_ENTRY(NAME, OPS, WORD, TO_SINGLE)                                                                   \
+#define HEAMD_PNNS_MATRIX_ENTRY(NAME, WORD, TO_SINGLE)                                                                        \
     extern "C" int NAME(const he_pnns_context* ctx, const WORD* matrix, size_t matrix_plaintext_count, size_t rows, size_t cols, \
                         uint32_t baby_step, const WORD* queries, size_t query_rows, size_t query_count,                        \
                         const he_pnns_pack_step* pack_steps, size_t pack_step_count, const WORD* const* galois_keys, WORD* out, \
                         he_stream s) {                                                                                         \
-        return mul_transpose_matrix<OPS>(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_rows,      \
-                                         query_count, pack_steps, pack_step_count, galois_keys, out, TO_SINGLE, s);            \
+        return mul_transpose_matrix(ctx, matrix, matrix_plaintext_count, rows, cols, baby_step, queries, query_rows,           \
+                                    query_count, pack_steps, pack_step_count, galois_keys, out, TO_SINGLE, s);                 \
     }
-HEAMD_PNNS_MATRIX_ENTRY(he_pnns_mul_transpose_matrix_device, Ops64, uint64_t, false)
-HEAMD_PNNS_MATRIX_ENTRY(he_pnns_mul_transpose_matrix_device_u32, Ops32, uint32_t, false)
-HEAMD_PNNS_MATRIX_ENTRY(he_pnns_compute_response_matrix_device, Ops64, uint64_t, true)
-HEAMD_PNNS_MATRIX_ENTRY(he_pnns_compute_response_matrix_device_u32, Ops32, uint32_t, true)
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_mul_transpose_matrix_device, uint64_t, false)
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_mul_transpose_matrix_device_u32, uint32_t, false)
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_compute_response_matrix_device, uint64_t, true)
+HEAMD_PNNS_MATRIX_ENTRY(he_pnns_compute_response_matrix_device_u32, uint32_t, true)
 #undef HEAMD_PNNS_MATRIX_ENTRY

@@ -1,0 +1,111 @@
+// word_layer.hpp -- the host layer under the C ABI written once for both slab words (not exported): W = uint64_t for
+// Bfv<UInt64>, W = uint32_t for Bfv<UInt32> on packed 4-byte slabs (every modulus, Bsk primes included, <= 2^30 - 1).
+// Most launchers are templates on W already; the few that come as a pair of names are overloaded by word here, and the
+// operations that c_api.cpp, bfv_api.cpp, pnns_api.cpp and pir_api.cpp share are declared here, each defined once in the
+// translation unit that owns it.  An extern "C" entry point and its `_u32` twin are one-line wrappers of such a body.
+#pragma once
+
+#include "api_internal.hpp"
+#include "kernels.hpp"
+
+#define HEAMD_TRY_STATUS(expr)                \
+    do {                                      \
+        const int status_ = (expr);           \
+        if (status_ != HE_OK) return status_; \
+    } while (0)
+
+namespace heamd {
+
+// ---- launchers by slab word.  `dc` is the 8-byte image the caller chose (a level of the context, constants it may have
+// substituted); the 4-byte image is built from `pc` over the moduli the launch walks, with dc's constants.
+// Transform of `rows` rows, row r under modulus r % period: ntt_kernels.hip / word32_kernels.hip
+inline hipError_t ntt_rows(bool inverse, uint64_t* slab, const PolyContext&, const DeviceContext& dc, uint32_t period,
+                           size_t rows, hipStream_t stream) {
+    return launch_ntt(inverse, slab, dc, 0, period, rows, stream);
+}
+inline hipError_t ntt_rows(bool inverse, uint32_t* slab, const PolyContext& pc, const DeviceContext& dc, uint32_t period,
+                           size_t rows, hipStream_t stream) {
+    DeviceContext32 dc32{};
+    if (pc.device_context32(period, dc32) != HE_OK) return hipErrorInvalidValue;
+    dc32.moduli = dc.moduli;  // the caller may have substituted constants (t N^-1)
+    return launch_ntt32(inverse, slab, dc32, 0, period, rows, stream);
+}
+// Transform of `records` records of record_rows rows: 8-byte words take the mixed schedule of the [Q, Bsk] slabs
+inline hipError_t ntt_records(bool inverse, uint64_t* slab, const PolyContext&, const DeviceContext& dc, uint32_t record_rows,
+                              size_t records, hipStream_t stream) {
+    return launch_ntt_mixed(inverse, slab, dc, record_rows, records, stream);
+}
+inline hipError_t ntt_records(bool inverse, uint32_t* slab, const PolyContext& pc, const DeviceContext& dc,
+                              uint32_t record_rows, size_t records, hipStream_t stream) {
+    return ntt_rows(inverse, slab, pc, dc, record_rows, records * record_rows, stream);
+}
+// lhs = op(lhs, rhs) over `rows` rows of every modulus of pc; MulScalar reads `scalars`, (scalar, Shoup factor) pairs
+inline hipError_t elementwise_rows(ElementwiseOp op, uint64_t* lhs, const uint64_t* rhs, const uint64_t* scalars,
+                                   const PolyContext& pc, size_t rows, hipStream_t stream) {
+    return launch_elementwise(op, lhs, op == ElementwiseOp::MulScalar ? scalars : rhs, pc.device_context(), rows, stream);
+}
+inline hipError_t elementwise_rows(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
+                                   const PolyContext& pc, size_t rows, hipStream_t stream) {
+    DeviceContext32 dc32{};
+    if (pc.device_context32(pc.moduli_count(), dc32) != HE_OK) return hipErrorInvalidValue;
+    return launch_elementwise32(op, lhs, rhs, scalars, dc32, rows, stream);
+}
+// divideAndRoundQLast of `polys` polynomials over the first moduli_count moduli of pc
+inline hipError_t divide_and_round_q_last(const uint64_t* in, uint64_t* out, const PolyContext& pc, uint32_t moduli_count,
+                                          size_t polys, hipStream_t stream) {
+    return launch_divide_and_round_q_last(in, out, pc.device_context(), moduli_count, polys, stream);
+}
+inline hipError_t divide_and_round_q_last(const uint32_t* in, uint32_t* out, const PolyContext& pc, uint32_t moduli_count,
+                                          size_t polys, hipStream_t stream) {
+    DeviceContext32 dc32{};
+    if (pc.device_context32(moduli_count, dc32) != HE_OK) return hipErrorInvalidValue;
+    return launch_divide_and_round_q_last32(in, out, dc32, moduli_count, polys, stream);
+}
+inline hipError_t mul_plain(uint64_t* ct, const uint64_t* pt, const DeviceContext& dc, uint32_t poly_count, size_t batch,
+                            hipStream_t stream) {
+    return launch_mul_plain(ct, pt, dc, poly_count, batch, stream);
+}
+inline hipError_t mul_plain(uint32_t* ct, const uint32_t* pt, const DeviceContext& dc, uint32_t poly_count, size_t batch,
+                            hipStream_t stream) {
+    return launch_mul_plain32(ct, pt, dc, poly_count, batch, stream);
+}
+
+// What an entry point needs of pc before it launches on slabs of W: its tables on the current device, and for 4-byte
+// words every modulus within 2^30 - 1 (HE_ERR_INVALID_MODULUS) and the 4-byte tables, built on first use.
+template <typename W>
+int check_word_device(const PolyContext& pc) {
+    if constexpr (sizeof(W) == 8) return pc.check_device();
+    DeviceContext32 dc32{};
+    return pc.device_context32(pc.moduli_count(), dc32);
+}
+// The 4-byte polynomial entries make that check before they look at the batch, the 8-byte ones behind their argument checks.
+template <typename W>
+constexpr bool kChecksDeviceFirst = sizeof(W) == 4;
+
+// ---- c_api.cpp: he_ntt_forward/inverse_device and he_poly_add/sub/neg/mul_device, with their checks
+template <typename W>
+int poly_ntt(const he_poly_context* ctx, W* slab, size_t batch, bool inverse, hipStream_t stream);
+template <typename W>
+int poly_elementwise(const he_poly_context* ctx, ElementwiseOp op, W* lhs, const W* rhs, size_t batch, hipStream_t stream);
+
+// ---- bfv_api.cpp
+// Plaintext.convertToEvalFormat, with the checks of he_bfv_plaintext_to_eval_device (a batch of 0 with null slabs checks
+// the level and nothing else)
+template <typename W>
+int bfv_plaintext_to_eval(const he_bfv_context* ctx, uint32_t moduli_count, const W* plaintext, W* out, size_t batch,
+                          hipStream_t stream);
+// Ciphertext.modSwitchDownToSingle, with the checks of he_bfv_mod_switch_down_to_single_device: one kernel where 8-byte words
+// have it (2..8 moduli), else divideAndRoundQLast level by level through scratch of its own
+template <typename W>
+int bfv_mod_switch_down_to_single(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* in, W* out,
+                                  size_t batch, hipStream_t stream);
+// How often the carry-counting accumulator of a plaintext inner product over the first `level` moduli of pc reduces:
+// max_lazy is the reference's cadence, cadence (<= max_lazy) keeps the sums below 2^127, narrow_moduli says that every
+// modulus is below 2^56 (kernels.hpp, launch_inner_product_plain)
+struct AccumulatorCadence {
+    uint64_t max_lazy, cadence;
+    bool narrow_moduli;
+};
+AccumulatorCadence accumulator_cadence(const PolyContext& pc, uint32_t level);
+
+}  // namespace heamd

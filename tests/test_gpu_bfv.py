@@ -378,15 +378,18 @@ def test_inner_product_plain_queries_side_by_side(oracle, small, config3, querie
         assert np.array_equal(got[:, q], single.reshape(columns, 2, big.L, big.degree)), q
 
 
-@pytest.mark.parametrize("bits", [[50, 55], [55, 40, 62, 48], [45] * 6, [60, 61, 62, 55, 50, 45, 40, 58, 59]])
+@pytest.mark.parametrize("bits", [[50, 55], [55, 40, 62, 48], [45] * 6, [60, 61, 62, 55, 50, 45, 40, 58, 59],
+                                  [60, 61, 62, 55, 50, 45, 40, 58, 59, 57]])
 def test_mod_switch_down_to_single(oracle, bits):
     """Ciphertext.modSwitchDownToSingle (Bfv.swift:163-171) in one kernel: word for word the chain of modSwitchDown steps
-    (the oracle's and the step entry point's), from every level of contexts with 1 to 8 ciphertext moduli; words at 0
-    and q - 1 included."""
+    (the oracle's and the step entry point's), from every level of contexts with 1 to 9 ciphertext moduli; words at 0
+    and q - 1 included.  Ten primes: level 9 is past the one kernel's 2..8 moduli and goes step by step through scratch."""
     degree = 64
     t = oracle.generate_primes([17], True, degree)[0]
     q = oracle.generate_primes(bits, False, degree)
+    assert len(set(q)) == len(bits)
     ours, ref = heamd.BfvContext(degree, t, q), oracle.BfvContext(degree, t, q)
+    assert ours.L == len(bits) - 1
     rng = np.random.default_rng(len(bits))
     for level in range(ours.L, 0, -1):
         moduli = q[:level]

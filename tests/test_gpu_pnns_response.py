@@ -171,6 +171,17 @@ def test_u32_two_queries_share_keys_next_to_a_third(oracle):
     assert np.array_equal(got_single, single)
 
 
+def test_u32_words_at_four_moduli(oracle):
+    """Five 27..29-bit primes at N = 64: L = 4, the smallest level at which modSwitchDownToSingle's step-by-step chain (all a
+    4-byte response has) reads back from both of its scratch slabs -- at L = 3 it writes the first one only.  rows > N: C = 2."""
+    degree = 64
+    q = oracle.generate_primes([27, 28, 28, 29, 29], False, degree, word_bits=32)
+    assert len(set(q)) == 5
+    s = Setup(oracle, degree, word32=True, q=q)
+    assert s.ref.L == s.bfv.L == 4
+    check(s, 65, 5, None, 2, 6504)
+
+
 # (degree, rows, cols, baby_step, queries)
 CASES = [
     (256, 300, 100, 12, 1),      # L = 2 below; P = 128, G = 11, the last giant step sums 8: ragged
