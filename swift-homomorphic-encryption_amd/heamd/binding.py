@@ -1,4 +1,5 @@
 """ctypes binding of include/he_amd.h (no compute happens in Python)."""
+import collections
 import ctypes
 import os
 
@@ -15,6 +16,20 @@ HOST_CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
 c_u64 = ctypes.c_uint64
 c_u32 = ctypes.c_uint32
 c_size = ctypes.c_size_t
+
+
+class Word(collections.namedtuple("Word", "bits suffix dtype")):
+    """The word of a device slab: its bit count, the suffix of the C entries that take it and its torch dtype's name."""
+
+    __slots__ = ()
+
+
+WORD64 = Word(64, "", "int64")
+WORD32 = Word(32, "_u32", "int32")  # packed [UInt32]: int32 tensors
+
+
+def _word_of(word_bits):
+    return WORD32 if word_bits == 32 else WORD64
 
 STATUS_NAMES = {
     0: "ok", 1: "invalidDegree", 2: "invalidModulus", 3: "coprimeModuli", 4: "emptyModulus",
@@ -36,7 +51,8 @@ class HeError(RuntimeError):
         super().__init__(f"HeError.{self.name} ({code}) {detail}".strip())
 
 
-# Every symbol include/he_amd.h declares: (name, restype, argtypes)
+# Every symbol include/he_amd.h declares: (name, restype, argtypes).  The 4-byte twin of an entry in _TWINNED is not spelled
+# out: it has the name with WORD32's suffix and the same types.
 SIGNATURES = [
     ("he_status_string", ctypes.c_char_p, [ctypes.c_int]),
     ("he_last_error_message", ctypes.c_char_p, []),
@@ -107,22 +123,12 @@ SIGNATURES = [
     ("he_poly_reduce_accumulator_device", ctypes.c_int, [vp, vp, vp, vp]),
     ("he_poly_apply_galois_device", ctypes.c_int, [vp, vp, vp, c_size, c_u64, ctypes.c_int, vp]),
     ("he_poly_random_from_seeds_device", ctypes.c_int, [vp, vp, c_size, vp, vp]),
-    ("he_ntt_forward_device_u32", ctypes.c_int, [vp, vp, c_size, vp]),
-    ("he_ntt_inverse_device_u32", ctypes.c_int, [vp, vp, c_size, vp]),
-    ("he_poly_add_device_u32", ctypes.c_int, [vp, vp, vp, c_size, vp]),
-    ("he_poly_sub_device_u32", ctypes.c_int, [vp, vp, vp, c_size, vp]),
-    ("he_poly_neg_device_u32", ctypes.c_int, [vp, vp, c_size, vp]),
-    ("he_poly_mul_device_u32", ctypes.c_int, [vp, vp, vp, c_size, vp]),
     ("he_poly_mul_scalar_device_u32", ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_uint32), c_size, vp]),
-    ("he_poly_divide_and_round_q_last_device_u32", ctypes.c_int, [vp, vp, vp, c_size, vp]),
     ("he_words_widen_u32_device", ctypes.c_int, [vp, vp, c_size, vp]),
     ("he_words_narrow_u64_device", ctypes.c_int, [vp, vp, c_size, vp]),
     ("he_poly_serialization_byte_count", c_size, [vp, ctypes.c_int]),
     ("he_poly_serialize_device", ctypes.c_int, [vp, vp, c_size, ctypes.c_int, vp, vp]),
     ("he_poly_deserialize_device", ctypes.c_int, [vp, vp, c_size, c_size, ctypes.c_int, vp, vp]),
-    ("he_poly_serialize_device_u32", ctypes.c_int, [vp, vp, c_size, ctypes.c_int, vp, vp]),
-    ("he_poly_deserialize_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, ctypes.c_int, vp, vp]),
-    ("he_poly_random_from_seeds_device_u32", ctypes.c_int, [vp, vp, c_size, vp, vp]),
     ("he_bfv_skip_lsbs_for_decryption", ctypes.c_int, [c_u32, c_u64, c_u64, c_u32, ctypes.POINTER(ctypes.c_int)]),
     ("he_ciphertexts_serialization_byte_count", c_size, [vp, c_u32, ctypes.POINTER(ctypes.c_int)]),
     ("he_ciphertexts_wire_plan", ctypes.c_int,
@@ -130,17 +136,11 @@ SIGNATURES = [
       ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_u32)]),
     ("he_ciphertexts_serialize_device", ctypes.c_int,
      [vp, vp, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, c_size, vp]),
-    ("he_ciphertexts_serialize_device_u32", ctypes.c_int,
-     [vp, vp, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, c_size, vp]),
     ("he_ciphertexts_deserialize_device", ctypes.c_int,
      [vp, vp, c_size, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, vp, vp]),
-    ("he_ciphertexts_deserialize_device_u32", ctypes.c_int,
-     [vp, vp, c_size, c_size, c_u32, ctypes.POINTER(ctypes.c_int), vp, vp, vp]),
     ("he_ciphertexts_deserialize_seeded_device", ctypes.c_int, [vp, vp, c_size, vp, c_size, ctypes.c_int, vp, vp]),
-    ("he_ciphertexts_deserialize_seeded_device_u32", ctypes.c_int, [vp, vp, c_size, vp, c_size, ctypes.c_int, vp, vp]),
     ("he_poly_multiply_power_of_x_device", ctypes.c_int, [vp, vp, vp, c_size, ctypes.c_int64, vp]),
     ("he_bfv_context_create", ctypes.c_int, [c_u32, c_u64, U64P, c_u32, ctypes.POINTER(vp)]),
-    ("he_bfv_context_create_u32", ctypes.c_int, [c_u32, c_u64, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_bfv_context_destroy", None, [vp]),
     ("he_bfv_ciphertext_moduli_count", c_u32, [vp]),
     ("he_bfv_ciphertext_context", vp, [vp, c_u32]),
@@ -173,30 +173,6 @@ SIGNATURES = [
       ctypes.POINTER(vp), c_size, c_size, vp, vp]),
     ("he_pir_compute_response_packed_device", ctypes.c_int,
      [vp, ctypes.POINTER(c_u32), c_u32, vp, vp, c_size, vp, vp, c_size, vp, vp, vp]),
-    # Bfv<UInt32> on packed 4-byte slabs
-    ("he_rns_lift_q_to_qbsk_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp]),
-    ("he_rns_floor_qbsk_to_q_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp]),
-    ("he_rns_scale_and_round_device_u32", ctypes.c_int, [vp, c_u32, vp, c_u64, vp, c_size, vp]),
-    ("he_bfv_mul_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, vp, c_size, vp, c_size, vp]),
-    ("he_bfv_relinearize_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, vp, c_size, vp, c_size, vp]),
-    ("he_bfv_apply_galois_device_u32", ctypes.c_int, [vp, c_u32, vp, c_u64, vp, vp, c_size, vp, c_size, vp]),
-    ("he_bfv_mod_switch_down_device_u32", ctypes.c_int, [vp, c_u32, c_u32, vp, vp, c_size, vp]),
-    ("he_bfv_mul_plain_device_u32", ctypes.c_int, [vp, c_u32, c_u32, vp, vp, c_size, vp]),
-    ("he_bfv_add_plain_device_u32", ctypes.c_int, [vp, c_u32, c_u32, vp, vp, c_size, vp]),
-    ("he_bfv_sub_plain_device_u32", ctypes.c_int, [vp, c_u32, c_u32, vp, vp, c_size, vp]),
-    ("he_bfv_inner_product_plain_resident_device_u32", ctypes.c_int,
-     [vp, c_u32, c_u32, vp, vp, vp, c_size, c_size, vp, vp]),
-    ("he_bfv_inner_product_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp, vp, c_size, vp]),
-    ("he_bfv_inner_product_shared_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, c_size, c_size, vp, vp]),
-    ("he_pir_compute_response_device_u32", ctypes.c_int,
-     [vp, ctypes.POINTER(c_u32), c_u32, vp, vp, c_size, vp, vp, c_size, vp, vp, vp]),
-    ("he_pir_compute_response_queries_device_u32", ctypes.c_int,
-     [vp, ctypes.POINTER(c_u32), c_u32, c_size, vp, vp, c_size, vp, vp, c_size, ctypes.POINTER(vp), vp, vp]),
-    ("he_pir_compute_response_to_query_device_u32", ctypes.c_int,
-     [vp, ctypes.POINTER(c_u32), c_u32, vp, c_size, c_size, U64P, ctypes.POINTER(vp), c_size, vp, ctypes.POINTER(vp),
-      ctypes.POINTER(vp), c_size, c_size, vp, vp]),
-    ("he_bfv_plaintext_to_eval_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp]),
-    ("he_bfv_plaintext_to_coeff_device_u32", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp]),
     ("he_galois_element_swapping_rows", ctypes.c_int, [c_u64, U64P]),
     ("he_galois_element_rotating_columns", ctypes.c_int, [ctypes.c_int64, c_u64, U64P]),
     ("he_bfv_apply_galois_workspace_bytes", c_size, [vp, c_u32, c_size]),
@@ -224,55 +200,37 @@ SIGNATURES = [
       ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
     ("he_pir_process_database_device", ctypes.c_int,
      [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
-    ("he_pir_process_database_device_u32", ctypes.c_int,
-     [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
     ("he_pir_database_file_scan", ctypes.c_int,
      [vp, vp, c_size, vp, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
     ("he_pir_database_file_byte_count", ctypes.c_int, [vp, vp, c_size, ctypes.POINTER(c_size)]),
     ("he_pir_database_file_header", ctypes.c_int, [c_size, vp]),
     ("he_pir_database_load_device", ctypes.c_int, [vp, vp, c_size, vp, c_size, vp, vp, vp]),
-    ("he_pir_database_load_device_u32", ctypes.c_int, [vp, vp, c_size, vp, c_size, vp, vp, vp]),
     ("he_pir_database_save_device", ctypes.c_int, [vp, vp, vp, c_size, vp, c_size, vp, vp]),
-    ("he_pir_database_save_device_u32", ctypes.c_int, [vp, vp, vp, c_size, vp, c_size, vp, vp]),
     ("he_simple_pir_shape", ctypes.c_int,
      [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
       ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_u64), ctypes.POINTER(c_u32)]),
     ("he_simple_pir_context_create", ctypes.c_int, [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(vp)]),
     ("he_simple_pir_context_destroy", None, [vp]),
     ("he_simple_pir_process_database_device", ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
-    ("he_simple_pir_process_database_device_u32", ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
     ("he_simple_pir_pack_database_device", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
-    ("he_simple_pir_pack_database_device_u32", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
     ("he_simple_pir_unpack_database_device", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
-    ("he_simple_pir_unpack_database_device_u32", ctypes.c_int, [c_u32, vp, vp, c_size, vp]),
     ("he_simple_pir_compute_response_device", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
-    ("he_simple_pir_compute_response_device_u32", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
     ("he_simple_pir_compute_response_batch_device", ctypes.c_int, [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
-    ("he_simple_pir_compute_response_batch_device_u32", ctypes.c_int,
-     [c_u32, c_u32, vp, c_size, c_size, vp, c_size, vp, vp]),
     ("he_simple_pir_batch_response_plan", ctypes.c_int,
      [c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32),
       ctypes.POINTER(c_u32), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
     ("he_pnns_context_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
-    ("he_pnns_context_create_u32", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
     ("he_pnns_context_destroy", None, [vp]),
     ("he_pnns_matrix_shape", ctypes.c_int,
      [vp, c_size, c_size, ctypes.c_int, c_u32, ctypes.POINTER(c_size), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     ("he_pnns_quantize_rows_device", ctypes.c_int, [vp, c_size, c_size, ctypes.c_float, vp, vp]),
     ("he_pnns_diagonal_matrix_device", ctypes.c_int, [vp, vp, c_size, c_size, c_u32, ctypes.c_int, c_u32, vp, vp, vp]),
-    ("he_pnns_diagonal_matrix_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_u32, ctypes.c_int, c_u32, vp, vp, vp]),
     ("he_pnns_mul_transpose_device", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
-    ("he_pnns_mul_transpose_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
     ("he_pnns_compute_response_device", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
-    ("he_pnns_compute_response_device_u32", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, vp, vp, vp]),
     ("he_pnns_query_matrix_shape", ctypes.c_int, [vp, c_size, c_size, c_size, vp, vp, vp]),
     ("he_pnns_mul_transpose_matrix_device", ctypes.c_int,
      [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
-    ("he_pnns_mul_transpose_matrix_device_u32", ctypes.c_int,
-     [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
     ("he_pnns_compute_response_matrix_device", ctypes.c_int,
-     [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
-    ("he_pnns_compute_response_matrix_device_u32", ctypes.c_int,
      [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
     # diagnostics / test hooks
     ("he_poly_context_create_host_only", ctypes.c_int, [c_u32, U64P, c_u32, ctypes.POINTER(vp)]),
@@ -281,6 +239,27 @@ SIGNATURES = [
     ("he_bfv_context_create_host_only", ctypes.c_int, [c_u32, c_u64, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_bfv_copy_bsk_moduli", ctypes.c_int, [vp, U64P]),
 ]
+_TWINNED = (
+    "he_ntt_forward_device", "he_ntt_inverse_device", "he_poly_add_device", "he_poly_sub_device", "he_poly_neg_device",
+    "he_poly_mul_device", "he_poly_divide_and_round_q_last_device", "he_poly_serialize_device",
+    "he_poly_deserialize_device", "he_poly_random_from_seeds_device", "he_ciphertexts_serialize_device",
+    "he_ciphertexts_deserialize_device", "he_ciphertexts_deserialize_seeded_device", "he_bfv_context_create",
+    "he_rns_lift_q_to_qbsk_device", "he_rns_floor_qbsk_to_q_device", "he_rns_scale_and_round_device",
+    "he_bfv_mul_device", "he_bfv_relinearize_device", "he_bfv_apply_galois_device", "he_bfv_mod_switch_down_device",
+    "he_bfv_mul_plain_device", "he_bfv_add_plain_device", "he_bfv_sub_plain_device",
+    "he_bfv_inner_product_plain_resident_device", "he_bfv_inner_product_device", "he_bfv_inner_product_shared_device",
+    "he_pir_compute_response_device", "he_pir_compute_response_queries_device",
+    "he_pir_compute_response_to_query_device", "he_bfv_plaintext_to_eval_device", "he_bfv_plaintext_to_coeff_device",
+    "he_pir_process_database_device", "he_pir_database_load_device", "he_pir_database_save_device",
+    "he_simple_pir_process_database_device", "he_simple_pir_pack_database_device",
+    "he_simple_pir_unpack_database_device", "he_simple_pir_compute_response_device",
+    "he_simple_pir_compute_response_batch_device", "he_pnns_context_create", "he_pnns_diagonal_matrix_device",
+    "he_pnns_mul_transpose_device", "he_pnns_compute_response_device", "he_pnns_mul_transpose_matrix_device",
+    "he_pnns_compute_response_matrix_device",
+)
+_rows = {name: (restype, argtypes) for name, restype, argtypes in SIGNATURES}
+SIGNATURES += [(name + WORD32.suffix,) + _rows[name] for name in _TWINNED]
+del _rows
 
 _lib = None
 
@@ -534,20 +513,35 @@ def to_host32(tensor):
     return tensor.detach().cpu().contiguous().numpy().view(np.uint32).astype(np.uint64)
 
 
-def _ptr32(tensor):
-    if not tensor.is_cuda or not tensor.is_contiguous() or tensor.element_size() != 4:
-        raise ValueError("expected a contiguous CUDA tensor of 32-bit words (int32 storage)")
-    return vp(tensor.data_ptr())
+def _entry(name, word=WORD64):
+    """The C entry `name` for slabs of `word`."""
+    return getattr(load_library(), name + word.suffix)
 
 
-def _ptr(tensor):
+def _ptr(tensor, word=WORD64):
     if not tensor.is_cuda:
         raise ValueError("expected a CUDA (HIP) tensor")
     if not tensor.is_contiguous():
         raise ValueError("expected a contiguous tensor")
-    if tensor.element_size() != 8:
-        raise ValueError("expected 64-bit words (int64 storage)")
+    if tensor.element_size() * 8 != word.bits:
+        raise ValueError(f"expected {word.bits}-bit words ({word.dtype} storage)")
     return vp(tensor.data_ptr())
+
+
+def _opt_ptr(tensor, word=WORD64):
+    return vp() if tensor is None else _ptr(tensor, word)
+
+
+def _empty(shape, word, device):
+    import torch
+
+    return torch.empty(shape, dtype=getattr(torch, word.dtype), device=device)
+
+
+def _workspace(workspace):
+    if workspace is None:
+        return vp(), 0
+    return vp(workspace.data_ptr()), workspace.numel() * workspace.element_size()
 
 
 def _stream(stream):
@@ -608,14 +602,23 @@ class PolyContext:
             raise ValueError(f"slab of {tensor.numel()} words is not [batch][{per // self.degree}][{self.degree}]")
         return tensor.numel() // per
 
-    # ---- PolyRq.forwardNtt / inverseNtt (in place, device tensors)
-    def forward_ntt_(self, slab, stream=None):
-        _check(load_library().he_ntt_forward_device(self.h, _ptr(slab), self._batch(slab), _stream(stream)))
+    # ---- PolyRq.forwardNtt / inverseNtt (in place, device tensors).  One body per operation takes the slab's word; the `_u32`
+    # names are PolyRq<UInt32> on int32 tensors [batch][L][N] of packed UInt32 words.
+    def _ntt(self, name, slab, word, stream):
+        _check(_entry(name, word)(self.h, _ptr(slab, word), self._batch(slab), _stream(stream)))
         return slab
 
+    def forward_ntt_(self, slab, stream=None):
+        return self._ntt("he_ntt_forward_device", slab, WORD64, stream)
+
     def inverse_ntt_(self, slab, stream=None):
-        _check(load_library().he_ntt_inverse_device(self.h, _ptr(slab), self._batch(slab), _stream(stream)))
-        return slab
+        return self._ntt("he_ntt_inverse_device", slab, WORD64, stream)
+
+    def forward_ntt_u32_(self, slab, stream=None):
+        return self._ntt("he_ntt_forward_device", slab, WORD32, stream)
+
+    def inverse_ntt_u32_(self, slab, stream=None):
+        return self._ntt("he_ntt_inverse_device", slab, WORD32, stream)
 
     def ntt_variant_(self, slab, inverse, variant, stream=None):
         _check(load_library().he_ntt_device_variant(self.h, _ptr(slab), self._batch(slab), int(inverse), variant,
@@ -661,36 +664,60 @@ class PolyContext:
         return array.size // per
 
     # ---- element-wise (in place on lhs)
-    def add_(self, lhs, rhs, stream=None):
-        _check(load_library().he_poly_add_device(self.h, _ptr(lhs), _ptr(rhs), self._batch(lhs), _stream(stream)))
+    def _binary(self, name, lhs, rhs, word, stream):
+        _check(_entry(name, word)(self.h, _ptr(lhs, word), _ptr(rhs, word), self._batch(lhs), _stream(stream)))
         return lhs
+
+    def _neg(self, data, word, stream):
+        _check(_entry("he_poly_neg_device", word)(self.h, _ptr(data, word), self._batch(data), _stream(stream)))
+        return data
+
+    def _mul_scalar(self, data, scalar_residues, word, stream):
+        if word is WORD32:  # the one entry whose twin differs: it takes uint32 residues
+            residues = (c_u32 * len(self.moduli))(*[int(v) for v in scalar_residues])
+        else:
+            array = _u64(list(scalar_residues))
+            residues = array.ctypes.data_as(U64P)
+        _check(_entry("he_poly_mul_scalar_device", word)(self.h, _ptr(data, word), residues, self._batch(data),
+                                                         _stream(stream)))
+        return data
+
+    def _divide_and_round_q_last(self, slab, word, stream):
+        batch = self._batch(slab)
+        out = _empty((batch, max(len(self.moduli) - 1, 0), self.degree), word, slab.device)
+        _check(_entry("he_poly_divide_and_round_q_last_device", word)(self.h, _ptr(slab, word), vp(out.data_ptr()), batch,
+                                                                      _stream(stream)))
+        return out
+
+    def add_(self, lhs, rhs, stream=None):
+        return self._binary("he_poly_add_device", lhs, rhs, WORD64, stream)
 
     def sub_(self, lhs, rhs, stream=None):
-        _check(load_library().he_poly_sub_device(self.h, _ptr(lhs), _ptr(rhs), self._batch(lhs), _stream(stream)))
-        return lhs
+        return self._binary("he_poly_sub_device", lhs, rhs, WORD64, stream)
 
     def neg_(self, data, stream=None):
-        _check(load_library().he_poly_neg_device(self.h, _ptr(data), self._batch(data), _stream(stream)))
-        return data
+        return self._neg(data, WORD64, stream)
 
     def mul_(self, lhs, rhs, stream=None):
-        _check(load_library().he_poly_mul_device(self.h, _ptr(lhs), _ptr(rhs), self._batch(lhs), _stream(stream)))
-        return lhs
+        return self._binary("he_poly_mul_device", lhs, rhs, WORD64, stream)
+
+    def elementwise_u32_(self, op, lhs, rhs=None, stream=None):
+        if op == "neg":
+            return self._neg(lhs, WORD32, stream)
+        name = {"add": "he_poly_add_device", "sub": "he_poly_sub_device", "mul": "he_poly_mul_device"}[op]
+        return self._binary(name, lhs, rhs, WORD32, stream)
 
     def mul_scalar_(self, data, scalar_residues, stream=None):
-        s = _u64(list(scalar_residues))
-        _check(load_library().he_poly_mul_scalar_device(self.h, _ptr(data), s.ctypes.data_as(U64P), self._batch(data),
-                                                        _stream(stream)))
-        return data
+        return self._mul_scalar(data, scalar_residues, WORD64, stream)
+
+    def mul_scalar_u32_(self, data, scalar_residues, stream=None):
+        return self._mul_scalar(data, scalar_residues, WORD32, stream)
 
     def divide_and_round_q_last(self, slab, stream=None):
-        import torch
+        return self._divide_and_round_q_last(slab, WORD64, stream)
 
-        batch = self._batch(slab)
-        out = torch.empty((batch, max(len(self.moduli) - 1, 0), self.degree), dtype=torch.int64, device=slab.device)
-        _check(load_library().he_poly_divide_and_round_q_last_device(self.h, _ptr(slab), vp(out.data_ptr()), batch,
-                                                                     _stream(stream)))
-        return out
+    def divide_and_round_q_last_u32(self, slab, stream=None):
+        return self._divide_and_round_q_last(slab, WORD32, stream)
 
     def divide_and_round_q_last_host(self, array):
         a = _u64(array)
@@ -700,104 +727,53 @@ class PolyContext:
                                                               out.ctypes.data_as(U64P), batch))
         return out
 
-    # ---- PolyRq<UInt32>: int32 tensors [batch][L][N] holding UInt32 words ----
-    def _batch32(self, slab):
-        return slab.numel() // (len(self.moduli) * self.degree)
+    # ---- the wire format of polynomials, on either word, and of whole ciphertexts ----
+    def _random_from_seeds(self, seeds, word, stream):
+        batch = seeds.numel() // 32
+        out = _empty((batch, len(self.moduli), self.degree), word, seeds.device)
+        _check(_entry("he_poly_random_from_seeds_device", word)(self.h, vp(seeds.data_ptr()), batch, vp(out.data_ptr()),
+                                                                _stream(stream)))
+        return out
 
-    def forward_ntt_u32_(self, slab, stream=None):
-        _check(load_library().he_ntt_forward_device_u32(self.h, vp(slab.data_ptr()), self._batch32(slab), _stream(stream)))
-        return slab
-
-    def inverse_ntt_u32_(self, slab, stream=None):
-        _check(load_library().he_ntt_inverse_device_u32(self.h, vp(slab.data_ptr()), self._batch32(slab), _stream(stream)))
-        return slab
-
-    def elementwise_u32_(self, op, lhs, rhs=None, stream=None):
-        lib = load_library()
-        batch = self._batch32(lhs)
-        if op == "neg":
-            _check(lib.he_poly_neg_device_u32(self.h, vp(lhs.data_ptr()), batch, _stream(stream)))
-        else:
-            fn = {"add": lib.he_poly_add_device_u32, "sub": lib.he_poly_sub_device_u32,
-                  "mul": lib.he_poly_mul_device_u32}[op]
-            _check(fn(self.h, vp(lhs.data_ptr()), vp(rhs.data_ptr()), batch, _stream(stream)))
-        return lhs
-
-    def mul_scalar_u32_(self, data, scalar_residues, stream=None):
-        arr = (ctypes.c_uint32 * len(self.moduli))(*[int(v) for v in scalar_residues])
-        _check(load_library().he_poly_mul_scalar_device_u32(self.h, vp(data.data_ptr()), arr, self._batch32(data),
-                                                            _stream(stream)))
-        return data
-
-    def divide_and_round_q_last_u32(self, slab, stream=None):
+    def _serialize(self, slab, skip_lsbs, word, stream):
         import torch
 
-        batch = self._batch32(slab)
-        out = torch.empty((batch, len(self.moduli) - 1, self.degree), dtype=torch.int32, device=slab.device)
-        _check(load_library().he_poly_divide_and_round_q_last_device_u32(self.h, vp(slab.data_ptr()),
-                                                                         vp(out.data_ptr()), batch, _stream(stream)))
+        batch = self._batch(slab)
+        out = torch.empty((batch, self.serialization_byte_count(skip_lsbs)), dtype=torch.uint8, device=slab.device)
+        _check(_entry("he_poly_serialize_device", word)(self.h, _ptr(slab, word), batch, skip_lsbs, vp(out.data_ptr()),
+                                                        _stream(stream)))
+        return out
+
+    def _deserialize(self, data, skip_lsbs, word, stream):
+        batch, per = data.shape[0], data.shape[1]
+        out = _empty((batch, len(self.moduli), self.degree), word, data.device)
+        _check(_entry("he_poly_deserialize_device", word)(self.h, vp(data.data_ptr()), per, batch, skip_lsbs,
+                                                          vp(out.data_ptr()), _stream(stream)))
         return out
 
     def random_from_seeds(self, seeds, stream=None):
         """PolyRq.random(context:using: NistAes128Ctr(seed:)) per seed: uint8 tensor [batch][32] -> [batch][L][N]."""
-        import torch
+        return self._random_from_seeds(seeds, WORD64, stream)
 
-        batch = seeds.numel() // 32
-        out = torch.empty((batch, len(self.moduli), self.degree), dtype=torch.int64, device=seeds.device)
-        _check(load_library().he_poly_random_from_seeds_device(self.h, vp(seeds.data_ptr()), batch,
-                                                               vp(out.data_ptr()), _stream(stream)))
-        return out
+    def random_from_seeds_u32(self, seeds, stream=None):
+        return self._random_from_seeds(seeds, WORD32, stream)
 
     def serialization_byte_count(self, skip_lsbs=0):
         return int(load_library().he_poly_serialization_byte_count(self.h, skip_lsbs))
 
     def serialize(self, slab, skip_lsbs=0, stream=None):
         """PolyRq.serialize per polynomial: [batch][L][N] -> uint8 tensor [batch][byte count]."""
-        import torch
+        return self._serialize(slab, skip_lsbs, WORD64, stream)
 
-        batch = self._batch(slab)
-        out = torch.empty((batch, self.serialization_byte_count(skip_lsbs)), dtype=torch.uint8, device=slab.device)
-        _check(load_library().he_poly_serialize_device(self.h, _ptr(slab), batch, skip_lsbs, vp(out.data_ptr()),
-                                                       _stream(stream)))
-        return out
+    def serialize_u32(self, slab, skip_lsbs=0, stream=None):
+        return self._serialize(slab, skip_lsbs, WORD32, stream)
 
     def deserialize(self, data, skip_lsbs=0, stream=None):
         """PolyRq(deserialize:context:skipLSBs:) per record: uint8 tensor [batch][bytes] -> [batch][L][N]."""
-        import torch
-
-        batch, per = data.shape[0], data.shape[1]
-        out = torch.empty((batch, len(self.moduli), self.degree), dtype=torch.int64, device=data.device)
-        _check(load_library().he_poly_deserialize_device(self.h, vp(data.data_ptr()), per, batch, skip_lsbs,
-                                                         vp(out.data_ptr()), _stream(stream)))
-        return out
-
-    # ---- the wire format on 4-byte slabs, and of whole ciphertexts (DESIGN.md 4.10) ----
-    def random_from_seeds_u32(self, seeds, stream=None):
-        import torch
-
-        batch = seeds.numel() // 32
-        out = torch.empty((batch, len(self.moduli), self.degree), dtype=torch.int32, device=seeds.device)
-        _check(load_library().he_poly_random_from_seeds_device_u32(self.h, vp(seeds.data_ptr()), batch,
-                                                                   vp(out.data_ptr()), _stream(stream)))
-        return out
-
-    def serialize_u32(self, slab, skip_lsbs=0, stream=None):
-        import torch
-
-        batch = self._batch32(slab)
-        out = torch.empty((batch, self.serialization_byte_count(skip_lsbs)), dtype=torch.uint8, device=slab.device)
-        _check(load_library().he_poly_serialize_device_u32(self.h, vp(slab.data_ptr()), batch, skip_lsbs,
-                                                           vp(out.data_ptr()), _stream(stream)))
-        return out
+        return self._deserialize(data, skip_lsbs, WORD64, stream)
 
     def deserialize_u32(self, data, skip_lsbs=0, stream=None):
-        import torch
-
-        batch, per = data.shape[0], data.shape[1]
-        out = torch.empty((batch, len(self.moduli), self.degree), dtype=torch.int32, device=data.device)
-        _check(load_library().he_poly_deserialize_device_u32(self.h, vp(data.data_ptr()), per, batch, skip_lsbs,
-                                                             vp(out.data_ptr()), _stream(stream)))
-        return out
+        return self._deserialize(data, skip_lsbs, WORD32, stream)
 
     @staticmethod
     def _skips(skip_lsbs, poly_count):
@@ -833,8 +809,7 @@ class PolyContext:
         stride = need if record_stride is None else record_stride
         if out is None:
             out = torch.empty((count, stride), dtype=torch.uint8, device=cts.device)
-        lib = load_library()
-        fn = lib.he_ciphertexts_serialize_device_u32 if cts.dtype == torch.int32 else lib.he_ciphertexts_serialize_device
+        fn = _entry("he_ciphertexts_serialize_device", WORD32 if cts.dtype == torch.int32 else WORD64)
         _check(fn(self.h, vp(cts.data_ptr()), count, polys, self._skips(skip_lsbs, polys), vp(out.data_ptr()), stride,
                   _stream(stream)))
         return out
@@ -842,33 +817,27 @@ class PolyContext:
     def ciphertexts_deserialize(self, records, count, poly_count, skip_lsbs=None, record_stride=None, word_bits=64, out=None,
                                 mismatch=None, stream=None):
         """Ciphertext(deserialize: .full) per record -> [count][polys][L][N]; mismatch: a zeroed int32 device tensor."""
-        import torch
-
+        word = _word_of(word_bits)
         stride = self.ciphertexts_serialization_byte_count(poly_count, skip_lsbs) if record_stride is None else record_stride
         if out is None:
-            out = torch.empty((count, poly_count, len(self.moduli), self.degree),
-                              dtype=torch.int32 if word_bits == 32 else torch.int64, device=records.device)
-        lib = load_library()
-        fn = lib.he_ciphertexts_deserialize_device_u32 if word_bits == 32 else lib.he_ciphertexts_deserialize_device
-        _check(fn(self.h, vp(records.data_ptr()), stride, count, poly_count, self._skips(skip_lsbs, poly_count),
-                  vp(out.data_ptr()), None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
+            out = _empty((count, poly_count, len(self.moduli), self.degree), word, records.device)
+        _check(_entry("he_ciphertexts_deserialize_device", word)(
+            self.h, vp(records.data_ptr()), stride, count, poly_count, self._skips(skip_lsbs, poly_count),
+            vp(out.data_ptr()), None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
         return out
 
     def ciphertexts_deserialize_seeded(self, poly0_bytes, seeds, count, coeff_format, record_stride=None, word_bits=64,
                                        out=None, stream=None):
         """Ciphertext(deserialize: .seeded(poly0:seed:)) per ciphertext -> [count][2][L][N]; either input may be None."""
-        import torch
-
+        word = _word_of(word_bits)
         stride = self.serialization_byte_count(0) if record_stride is None else record_stride
         if out is None:
             device = (poly0_bytes if poly0_bytes is not None else seeds).device
-            out = torch.empty((count, 2, len(self.moduli), self.degree),
-                              dtype=torch.int32 if word_bits == 32 else torch.int64, device=device)
-        lib = load_library()
-        fn = lib.he_ciphertexts_deserialize_seeded_device_u32 if word_bits == 32 else lib.he_ciphertexts_deserialize_seeded_device
-        _check(fn(self.h, None if poly0_bytes is None else vp(poly0_bytes.data_ptr()), stride,
-                  None if seeds is None else vp(seeds.data_ptr()), count, int(bool(coeff_format)), vp(out.data_ptr()),
-                  _stream(stream)))
+            out = _empty((count, 2, len(self.moduli), self.degree), word, device)
+        _check(_entry("he_ciphertexts_deserialize_seeded_device", word)(
+            self.h, None if poly0_bytes is None else vp(poly0_bytes.data_ptr()), stride,
+            None if seeds is None else vp(seeds.data_ptr()), count, int(bool(coeff_format)), vp(out.data_ptr()),
+            _stream(stream)))
         return out
 
     def apply_galois(self, slab, element, eval_format=False, stream=None):
@@ -903,16 +872,20 @@ class PolyContext:
 
 
 class BfvContext:
-    """Context<Bfv<UInt64>> (reference Context.swift:94-159) plus the Bfv operations on the hot path."""
+    """Context<Bfv<UInt64>> (reference Context.swift:94-159) plus the Bfv operations on the hot path.  Each method resolves
+    its entry, checks its slabs and allocates its result through the class's slab word; a method whose entry has no 4-byte
+    twin names WORD64 and works on 8-byte slabs in BfvContext32 too."""
+
+    _word = WORD64  # of the class, not of word_bits: BfvContext(word_bits=32) holds Bfv<UInt32> constants on 8-byte slabs
 
     def __init__(self, degree, plaintext_modulus, coefficient_moduli, host_only=False, word_bits=64):
         """word_bits=32: Context<Bfv<UInt32>> constants on 8-byte words (he_bfv_context_create_u32)."""
         lib = load_library()
         arr = _u64(list(coefficient_moduli))
         h = vp()
-        create = lib.he_bfv_context_create_host_only if host_only else lib.he_bfv_context_create
-        if word_bits == 32:
-            create = lib.he_bfv_context_create_u32
+        word = _word_of(word_bits)  # of the constants; the slabs' word is the class's
+        host = host_only and word is WORD64
+        create = lib.he_bfv_context_create_host_only if host else _entry("he_bfv_context_create", word)
         _check(create(degree, plaintext_modulus, arr.ctypes.data_as(U64P), len(arr), ctypes.byref(h)))
         self.h = h
         self.degree = degree
@@ -949,33 +922,30 @@ class BfvContext:
         _check(load_library().he_bfv_copy_bsk_moduli(self.h, out.ctypes.data_as(U64P)))
         return [int(v) for v in out]
 
-    def _empty(self, shape, like):
-        import torch
-
-        return torch.empty(shape, dtype=torch.int64, device=like.device)
-
     def lift_q_to_qbsk(self, polys, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = polys.numel() // (L * self.degree)
-        out = self._empty((batch, 2 * L + 1, self.degree), polys)
-        _check(load_library().he_rns_lift_q_to_qbsk_device(self.h, L, _ptr(polys), _ptr(out), batch, _stream(stream)))
+        out = _empty((batch, 2 * L + 1, self.degree), w, polys.device)
+        _check(_entry("he_rns_lift_q_to_qbsk_device", w)(
+            self.h, L, _ptr(polys, w), _ptr(out, w), batch, _stream(stream)))
         return out
 
     def floor_qbsk_to_q(self, polys, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = polys.numel() // ((2 * L + 1) * self.degree)
-        out = self._empty((batch, L, self.degree), polys)
-        _check(load_library().he_rns_floor_qbsk_to_q_device(self.h, L, _ptr(polys), _ptr(out), batch, _stream(stream)))
+        out = _empty((batch, L, self.degree), w, polys.device)
+        _check(_entry("he_rns_floor_qbsk_to_q_device", w)(
+            self.h, L, _ptr(polys, w), _ptr(out, w), batch, _stream(stream)))
         return out
 
     def mul(self, lhs, rhs, moduli_count=None, stream=None, workspace=None):
         """Bfv.mulAssign(ct, ct): [batch][2][L][N] x [batch][2][L][N] -> [batch][3][L][N] (Coeff)."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = lhs.numel() // (2 * L * self.degree)
-        out = self._empty((batch, 3, L, self.degree), lhs)
-        ws_ptr, ws_bytes = (vp(workspace.data_ptr()), workspace.numel() * workspace.element_size()) if workspace is not None else (vp(), 0)
-        _check(load_library().he_bfv_mul_device(self.h, L, _ptr(lhs), _ptr(rhs), _ptr(out), batch, ws_ptr, ws_bytes,
-                                                _stream(stream)))
+        out = _empty((batch, 3, L, self.degree), w, lhs.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(_entry("he_bfv_mul_device", w)(
+            self.h, L, _ptr(lhs, w), _ptr(rhs, w), _ptr(out, w), batch, ws_ptr, ws_bytes, _stream(stream)))
         return out
 
     def mul_workspace_bytes(self, batch, moduli_count=None):
@@ -986,13 +956,13 @@ class BfvContext:
 
     def relinearize(self, ct3, key, moduli_count=None, stream=None, workspace=None):
         """Bfv.relinearize: [batch][3][L][N] + key [L_top][2][L_top+1][N] -> [batch][2][L][N]."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = ct3.numel() // (3 * L * self.degree)
-        out = self._empty((batch, 2, L, self.degree), ct3)
-        key_ptr = vp() if key is None else _ptr(key)
-        ws_ptr, ws_bytes = (vp(workspace.data_ptr()), workspace.numel() * workspace.element_size()) if workspace is not None else (vp(), 0)
-        _check(load_library().he_bfv_relinearize_device(self.h, L, _ptr(ct3), key_ptr, _ptr(out), batch, ws_ptr,
-                                                        ws_bytes, _stream(stream)))
+        out = _empty((batch, 2, L, self.degree), w, ct3.device)
+        key_ptr = _opt_ptr(key, w)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(_entry("he_bfv_relinearize_device", w)(
+            self.h, L, _ptr(ct3, w), key_ptr, _ptr(out, w), batch, ws_ptr, ws_bytes, _stream(stream)))
         return out
 
     def apply_galois_workspace_bytes(self, batch, moduli_count=None):
@@ -1000,46 +970,46 @@ class BfvContext:
 
     def apply_galois(self, ct, element, key, moduli_count=None, stream=None, workspace=None):
         """Bfv.applyGalois: [batch][2][L][N] Coeff + the element's Galois key -> [batch][2][L][N]."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = ct.numel() // (2 * L * self.degree)
-        out = self._empty((batch, 2, L, self.degree), ct)
-        key_ptr = vp() if key is None else _ptr(key)
-        ws_ptr, ws_bytes = (vp(workspace.data_ptr()), workspace.numel() * workspace.element_size()) if workspace is not None else (vp(), 0)
-        _check(load_library().he_bfv_apply_galois_device(self.h, L, _ptr(ct), int(element), key_ptr, _ptr(out), batch,
-                                                         ws_ptr, ws_bytes, _stream(stream)))
+        out = _empty((batch, 2, L, self.degree), w, ct.device)
+        key_ptr = _opt_ptr(key, w)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(_entry("he_bfv_apply_galois_device", w)(
+            self.h, L, _ptr(ct, w), int(element), key_ptr, _ptr(out, w), batch, ws_ptr, ws_bytes, _stream(stream)))
         return out
 
     def scale_and_round(self, poly, scaling_factor=1, moduli_count=None, stream=None):
         """_RnsTool.scaleAndRound: [batch][L][N] Coeff -> [batch][N] mod t."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = poly.numel() // (L * self.degree)
-        out = self._empty((batch, self.degree), poly)
-        _check(load_library().he_rns_scale_and_round_device(self.h, L, _ptr(poly), int(scaling_factor), _ptr(out),
-                                                            batch, _stream(stream)))
+        out = _empty((batch, self.degree), w, poly.device)
+        _check(_entry("he_rns_scale_and_round_device", w)(
+            self.h, L, _ptr(poly, w), int(scaling_factor), _ptr(out, w), batch, _stream(stream)))
         return out
 
     def plaintext_to_eval(self, plaintext, moduli_count=None, stream=None):
         """Plaintext.convertToEvalFormat: [batch][N] (values < t) -> [batch][L][N] Eval."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = plaintext.numel() // self.degree
-        out = self._empty((batch, L, self.degree), plaintext)
-        _check(load_library().he_bfv_plaintext_to_eval_device(self.h, L, _ptr(plaintext), _ptr(out), batch,
-                                                              _stream(stream)))
+        out = _empty((batch, L, self.degree), w, plaintext.device)
+        _check(_entry("he_bfv_plaintext_to_eval_device", w)(
+            self.h, L, _ptr(plaintext, w), _ptr(out, w), batch, _stream(stream)))
         return out
 
     def plaintext_to_coeff(self, plaintext_eval, moduli_count=None, stream=None):
         """Plaintext.convertToCoeffFormat: [batch][L][N] Eval -> [batch][N] (values < t)."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = plaintext_eval.numel() // (L * self.degree)
-        out = self._empty((batch, self.degree), plaintext_eval)
-        _check(load_library().he_bfv_plaintext_to_coeff_device(self.h, L, _ptr(plaintext_eval), _ptr(out), batch,
-                                                               _stream(stream)))
+        out = _empty((batch, self.degree), w, plaintext_eval.device)
+        _check(_entry("he_bfv_plaintext_to_coeff_device", w)(
+            self.h, L, _ptr(plaintext_eval, w), _ptr(out, w), batch, _stream(stream)))
         return out
 
     def pir_expand(self, ciphertexts, output_count, galois_keys, stream=None):
         """PirUtil.expand: [count][2][L][N] Coeff + {element: key tensor} -> [output_count][2][L][N]."""
         count = ciphertexts.numel() // (2 * self.L * self.degree)
-        out = self._empty((output_count, 2, self.L, self.degree), ciphertexts)
+        out = _empty((output_count, 2, self.L, self.degree), WORD64, ciphertexts.device)
         elements = sorted(galois_keys)
         element_array = _u64(elements)
         key_array = (vp * max(len(elements), 1))(*[vp(galois_keys[e].data_ptr()) for e in elements])
@@ -1053,7 +1023,7 @@ class BfvContext:
         {element: key tensor} dict per query (the same elements in each) -> [queries][output_count][2][L][N]."""
         queries = len(galois_keys_per_query)
         count = ciphertexts.numel() // (queries * 2 * self.L * self.degree)
-        out = self._empty((queries, output_count, 2, self.L, self.degree), ciphertexts)
+        out = _empty((queries, output_count, 2, self.L, self.degree), WORD64, ciphertexts.device)
         elements = sorted(galois_keys_per_query[0])
         element_array = _u64(elements)
         pointers = [vp(keys[e].data_ptr()) for keys in galois_keys_per_query for e in elements]
@@ -1067,14 +1037,14 @@ class BfvContext:
                                    relinearization_key=None, stream=None):
         """PirUtilProtocol.computeResponseForOneChunk -> response ciphertext [2][1][N] (Coeff, one modulus)."""
         dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
-        out = self._empty((2, 1, self.degree), dim0_query_eval)
+        out = _empty((2, 1, self.degree), WORD64, dim0_query_eval.device)
         pres = None
         if present is not None:
             pres_arr = np.ascontiguousarray(present, dtype=np.uint8)
             pres = pres_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
-        rest = vp() if remaining_query is None else _ptr(remaining_query)
+        rest = _opt_ptr(remaining_query)
         rest_count = 0 if remaining_query is None else remaining_query.numel() // (2 * self.L * self.degree)
-        key = vp() if relinearization_key is None else _ptr(relinearization_key)
+        key = _opt_ptr(relinearization_key)
         _check(load_library().he_pir_compute_response_chunk_device(self.h, dims, len(dimensions),
                                                                    _ptr(dim0_query_eval), rest, rest_count,
                                                                    _ptr(database), pres, key, _ptr(out),
@@ -1086,7 +1056,7 @@ class BfvContext:
         present_device: uint8 device tensor [columns][d0] or None.  Enqueue-only."""
         d0 = dim0_query_eval.numel() // (2 * self.L * self.degree)
         columns = database.numel() // (d0 * self.L * self.degree)
-        out = self._empty((columns, 2, self.L, self.degree), dim0_query_eval)
+        out = _empty((columns, 2, self.L, self.degree), WORD64, dim0_query_eval.device)
         mask = vp() if present_device is None else vp(present_device.data_ptr())
         _check(load_library().he_pir_dim0_columns_device(self.h, _ptr(dim0_query_eval), d0, _ptr(database), mask,
                                                          columns, _ptr(out), _stream(stream)))
@@ -1095,10 +1065,10 @@ class BfvContext:
     def pir_remaining_dimensions(self, dimensions, intermediate, remaining_query, relinearization_key=None, stream=None):
         """PirUtil.swift:448-485 on all columns' dim-0 results ([columns][2][L][N] Coeff, consumed) -> [2][1][N]."""
         dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
-        out = self._empty((2, 1, self.degree), intermediate)
-        rest = vp() if remaining_query is None else _ptr(remaining_query)
+        out = _empty((2, 1, self.degree), WORD64, intermediate.device)
+        rest = _opt_ptr(remaining_query)
         rest_count = 0 if remaining_query is None else remaining_query.numel() // (2 * self.L * self.degree)
-        key = vp() if relinearization_key is None else _ptr(relinearization_key)
+        key = _opt_ptr(relinearization_key)
         _check(load_library().he_pir_remaining_dimensions_device(self.h, dims, len(dimensions), _ptr(intermediate), rest,
                                                                  rest_count, key, _ptr(out), _stream(stream)))
         return out
@@ -1106,39 +1076,42 @@ class BfvContext:
     def pir_compute_response(self, dimensions, dim0_query_eval, remaining_query, database, chunk_count,
                              present_device=None, relinearization_key=None, stream=None):
         """PirUtil.computeResponse's chunk loop for one query: database [chunks][prod(dims)][L][N] -> [chunks][2][1][N]."""
+        w = self._word
         dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
-        out = self._empty((chunk_count, 2, 1, self.degree), dim0_query_eval)
-        rest = vp() if remaining_query is None else _ptr(remaining_query)
+        out = _empty((chunk_count, 2, 1, self.degree), w, dim0_query_eval.device)
+        rest = _opt_ptr(remaining_query, w)
         rest_count = 0 if remaining_query is None else remaining_query.numel() // (2 * self.L * self.degree)
-        key = vp() if relinearization_key is None else _ptr(relinearization_key)
+        key = _opt_ptr(relinearization_key, w)
         mask = vp() if present_device is None else vp(present_device.data_ptr())
-        _check(load_library().he_pir_compute_response_device(self.h, dims, len(dimensions), _ptr(dim0_query_eval), rest,
-                                                             rest_count, _ptr(database), mask, chunk_count, key,
-                                                             _ptr(out), _stream(stream)))
+        _check(_entry("he_pir_compute_response_device", w)(
+            self.h, dims, len(dimensions), _ptr(dim0_query_eval, w), rest, rest_count, _ptr(database, w), mask,
+            chunk_count, key, _ptr(out, w), _stream(stream)))
         return out
 
     def pir_compute_response_to_query(self, dimensions, query_ciphertexts, indices_count, galois_keys, relinearization_key,
                                       databases, chunk_count, present_devices=None, stream=None):
         """PirUtil.computeResponse: Query.ciphertexts [count][2][L][N] Coeff + the evaluation key ({element: Galois key
         tensor}, relinearization key tensor or None) + one database tensor (shared by all indices) or a list of one per
-        index (present_devices likewise: None, one mask or a list) -> [indices][chunks][2][1][N]."""
+        index (present_devices likewise: None, one mask or a list) -> [indices][chunks][2][1][N].  The Galois keys are 8-byte
+        (widened) tensors on either slab word."""
+        w = self._word
         dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
         count = query_ciphertexts.numel() // (2 * self.L * self.degree)
-        out = self._empty((indices_count, chunk_count, 2, 1, self.degree), query_ciphertexts)
+        out = _empty((indices_count, chunk_count, 2, 1, self.degree), w, query_ciphertexts.device)
         elements = sorted(galois_keys)
         element_array = _u64(elements)
         key_array = (vp * max(len(elements), 1))(*[vp(galois_keys[e].data_ptr()) for e in elements])
-        relin = vp() if relinearization_key is None else _ptr(relinearization_key)
+        relin = _opt_ptr(relinearization_key, w)
         database_list = list(databases) if isinstance(databases, (list, tuple)) else [databases]
         database_array = (vp * len(database_list))(*[vp(d.data_ptr()) for d in database_list])
         mask_array = None
         if present_devices is not None:
             mask_list = list(present_devices) if isinstance(present_devices, (list, tuple)) else [present_devices]
             mask_array = (vp * len(mask_list))(*[vp() if m is None else vp(m.data_ptr()) for m in mask_list])
-        _check(load_library().he_pir_compute_response_to_query_device(
-            self.h, dims, len(dimensions), _ptr(query_ciphertexts), count, indices_count,
+        _check(_entry("he_pir_compute_response_to_query_device", w)(
+            self.h, dims, len(dimensions), _ptr(query_ciphertexts, w), count, indices_count,
             element_array.ctypes.data_as(U64P), key_array, len(elements), relin, database_array, mask_array,
-            len(database_list), chunk_count, _ptr(out), _stream(stream)))
+            len(database_list), chunk_count, _ptr(out, w), _stream(stream)))
         return out
 
     def pir_compute_response_queries(self, dimensions, dim0_queries_eval, remaining_queries, database, chunk_count,
@@ -1146,58 +1119,59 @@ class BfvContext:
         """`queries` queries over one database in one call: dim0_queries_eval [d0][queries][2][L][N] Eval,
         remaining_queries [queries][rest][2][L][N] (or None), relinearization_keys: one tensor per query (or None)
         -> [queries][chunks][2][1][N]."""
+        w = self._word
         dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
         queries = dim0_queries_eval.numel() // (int(dimensions[0]) * 2 * self.L * self.degree)
-        out = self._empty((queries, chunk_count, 2, 1, self.degree), dim0_queries_eval)
-        rest = vp() if remaining_queries is None else _ptr(remaining_queries)
+        out = _empty((queries, chunk_count, 2, 1, self.degree), w, dim0_queries_eval.device)
+        rest = _opt_ptr(remaining_queries, w)
         rest_count = 0 if remaining_queries is None else remaining_queries.numel() // (queries * 2 * self.L * self.degree)
         keys = None
         if relinearization_keys is not None:
             keys = (vp * queries)(*[vp(k.data_ptr()) for k in relinearization_keys])
         mask = vp() if present_device is None else vp(present_device.data_ptr())
-        _check(load_library().he_pir_compute_response_queries_device(
-            self.h, dims, len(dimensions), queries, _ptr(dim0_queries_eval), rest, rest_count, _ptr(database), mask,
-            chunk_count, keys, _ptr(out), _stream(stream)))
+        _check(_entry("he_pir_compute_response_queries_device", w)(
+            self.h, dims, len(dimensions), queries, _ptr(dim0_queries_eval, w), rest, rest_count, _ptr(database, w),
+            mask, chunk_count, keys, _ptr(out, w), _stream(stream)))
         return out
 
     def mod_switch_down(self, ct, poly_count, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = ct.numel() // (poly_count * L * self.degree)
-        out = self._empty((batch, poly_count, L - 1, self.degree), ct)
-        _check(load_library().he_bfv_mod_switch_down_device(self.h, L, poly_count, _ptr(ct), _ptr(out), batch,
-                                                            _stream(stream)))
+        out = _empty((batch, poly_count, L - 1, self.degree), w, ct.device)
+        _check(_entry("he_bfv_mod_switch_down_device", w)(
+            self.h, L, poly_count, _ptr(ct, w), _ptr(out, w), batch, _stream(stream)))
         return out
 
     def mod_switch_down_to_single(self, ct, poly_count, moduli_count=None, stream=None):
         """Ciphertext.modSwitchDownToSingle: [batch][polys][L][N] -> [batch][polys][1][N]."""
         L = self._L(moduli_count)
         batch = ct.numel() // (poly_count * L * self.degree)
-        out = self._empty((batch, poly_count, 1, self.degree), ct)
+        out = _empty((batch, poly_count, 1, self.degree), WORD64, ct.device)
         _check(load_library().he_bfv_mod_switch_down_to_single_device(self.h, L, poly_count, _ptr(ct), _ptr(out), batch,
                                                                       _stream(stream)))
         return out
 
     def mul_plain_(self, ct, pt, poly_count, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = pt.numel() // (L * self.degree)
-        _check(load_library().he_bfv_mul_plain_device(self.h, L, poly_count, _ptr(ct), _ptr(pt), batch,
-                                                      _stream(stream)))
+        _check(_entry("he_bfv_mul_plain_device", w)(
+            self.h, L, poly_count, _ptr(ct, w), _ptr(pt, w), batch, _stream(stream)))
         return ct
 
     def add_plain_(self, ct, plaintexts, poly_count=2, subtract=False, moduli_count=None, stream=None):
         """Bfv.addAssignCoeff / subAssignCoeff(ciphertext, plaintext): ct [batch][polys][L][N] Coeff in place,
         plaintexts [batch][N] mod t."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         batch = plaintexts.numel() // self.degree
-        fn = load_library().he_bfv_sub_plain_device if subtract else load_library().he_bfv_add_plain_device
-        _check(fn(self.h, L, poly_count, _ptr(ct), _ptr(plaintexts), batch, _stream(stream)))
+        fn = _entry("he_bfv_sub_plain_device", w) if subtract else _entry("he_bfv_add_plain_device", w)
+        _check(fn(self.h, L, poly_count, _ptr(ct, w), _ptr(plaintexts, w), batch, _stream(stream)))
         return ct
 
     def inner_product_plain(self, cts, pts, present=None, poly_count=2, columns=1, moduli_count=None, stream=None):
         """cts [count][polys][L][N]; pts [columns][count][L][N]; present: host bytes [columns][count] or None."""
         L = self._L(moduli_count)
         count = cts.numel() // (poly_count * L * self.degree)
-        out = self._empty((columns, poly_count, L, self.degree), cts)
+        out = _empty((columns, poly_count, L, self.degree), WORD64, cts.device)
         pres = None
         if present is not None:
             pres_arr = np.ascontiguousarray(present, dtype=np.uint8)
@@ -1209,13 +1183,12 @@ class BfvContext:
     def inner_product_plain_resident(self, cts, pts, present_device=None, poly_count=2, columns=1, moduli_count=None,
                                      stream=None):
         """inner_product_plain with the nil-plaintext mask as a uint8 DEVICE tensor [columns][count]: enqueue-only."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         count = cts.numel() // (poly_count * L * self.degree)
-        out = self._empty((columns, poly_count, L, self.degree), cts)
+        out = _empty((columns, poly_count, L, self.degree), w, cts.device)
         mask = vp() if present_device is None else vp(present_device.data_ptr())
-        _check(load_library().he_bfv_inner_product_plain_resident_device(self.h, L, poly_count, _ptr(cts), _ptr(pts),
-                                                                         mask, count, columns, _ptr(out),
-                                                                         _stream(stream)))
+        _check(_entry("he_bfv_inner_product_plain_resident_device", w)(
+            self.h, L, poly_count, _ptr(cts, w), _ptr(pts, w), mask, count, columns, _ptr(out, w), _stream(stream)))
         return out
 
     def pir_database_shape(self, dimensions, entry_count, entry_size_in_bytes, encoding_entry_size=False):
@@ -1228,16 +1201,6 @@ class BfvContext:
         names = ("chunk_count", "plaintexts_per_chunk", "bytes_per_plaintext", "entries_per_plaintext",
                  "entry_size_encoding_width")
         return {name: int(o.value) for name, o in zip(names, outs)}
-
-    _process_entry = "he_pir_process_database_device"
-
-    def _database_tensor(self, shape, device):
-        import torch
-
-        return torch.empty(shape, dtype=torch.int64, device=device)
-
-    def _database_ptr(self, database):
-        return _ptr(database)
 
     def pir_process_database(self, entries, dimensions, entry_size_in_bytes, encoding_entry_size=False, entry_sizes=None,
                              entry_count=None, out=None, device="cuda", stream=None):
@@ -1269,7 +1232,7 @@ class BfvContext:
         if entries.dtype != torch.uint8 or not entries.is_cuda or not entries.is_contiguous():
             raise ValueError("entries must be a contiguous uint8 device tensor")
         if out is None:
-            database = self._database_tensor((chunks, per_chunk, self.L, self.degree), entries.device)
+            database = _empty((chunks, per_chunk, self.L, self.degree), self._word, entries.device)
             present = torch.empty((chunks, per_chunk), dtype=torch.uint8, device=entries.device)
         else:
             database, present = out
@@ -1277,14 +1240,12 @@ class BfvContext:
                 raise ValueError("out tensors do not hold the database's shape")
         dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
         size_ptr = sizes.ctypes.data_as(U64P) if sizes is not None else None
-        _check(getattr(load_library(), self._process_entry)(
+        _check(_entry("he_pir_process_database_device", self._word)(
             self.h, dims, len(dimensions), vp(entries.data_ptr()), size_ptr, count, int(entry_size_in_bytes),
-            int(bool(encoding_entry_size)), self._database_ptr(database), vp(present.data_ptr()), _stream(stream)))
+            int(bool(encoding_entry_size)), _ptr(database, self._word), vp(present.data_ptr()), _stream(stream)))
         return database, present
 
     # ---- processed-database files: ProcessedDatabase.serialize() / init(from:context:) ----
-    _database_file_suffix = ""
-
     def database_file_payload_bytes(self):
         """S: the bytes of a present plaintext behind its tag."""
         return self.ciphertext_context().serialization_byte_count(0)
@@ -1313,13 +1274,13 @@ class BfvContext:
         present (uint8 device tensor [count]) -> database [count][L][N]; mismatch: a zeroed int32 device tensor."""
         count = present.numel()
         if out is None:
-            out = self._database_tensor((count, self.L, self.degree), records.device)
+            out = _empty((count, self.L, self.degree), self._word, records.device)
         elif out.numel() != count * self.L * self.degree:
             raise ValueError("out does not hold the segment's plaintexts")
         size = records.numel() if records_bytes is None else int(records_bytes)
-        fn = getattr(load_library(), "he_pir_database_load_device" + self._database_file_suffix)
-        _check(fn(self.h, vp(records.data_ptr()), size, vp(present.data_ptr()), count, self._database_ptr(out),
-                  None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
+        _check(_entry("he_pir_database_load_device", self._word)(
+            self.h, vp(records.data_ptr()), size, vp(present.data_ptr()), count, _ptr(out, self._word),
+            None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
         return out
 
     def save_database_segment(self, database, present, records_bytes=None, out=None, mismatch=None, stream=None):
@@ -1334,9 +1295,9 @@ class BfvContext:
             need = count + self.database_file_payload_bytes() * int((present != 0).sum().item())
             out = torch.empty(need if records_bytes is None else int(records_bytes), dtype=torch.uint8, device=database.device)
         size = out.numel() if records_bytes is None else int(records_bytes)
-        fn = getattr(load_library(), "he_pir_database_save_device" + self._database_file_suffix)
-        _check(fn(self.h, self._database_ptr(database), vp(present.data_ptr()), count, vp(out.data_ptr()), size,
-                  None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
+        _check(_entry("he_pir_database_save_device", self._word)(
+            self.h, _ptr(database, self._word), vp(present.data_ptr()), count, vp(out.data_ptr()), size,
+            None if mismatch is None else vp(mismatch.data_ptr()), _stream(stream)))
         return out
 
     def load_database_file(self, data, device="cuda", stream=None):
@@ -1385,7 +1346,7 @@ class BfvContext:
                                    stream=None):
         L = self._L(moduli_count)
         count = cts.numel() // (poly_count * L * self.degree)
-        out = self._empty((columns, poly_count, L, self.degree), cts)
+        out = _empty((columns, poly_count, L, self.degree), WORD64, cts.device)
         mask = vp() if present_device is None else vp(present_device.data_ptr())
         _check(load_library().he_bfv_inner_product_plain_packed_device(self.h, L, poly_count, _ptr(cts), _ptr(packed_pts),
                                                                        mask, count, columns, _ptr(out), _stream(stream)))
@@ -1394,10 +1355,10 @@ class BfvContext:
     def pir_compute_response_packed(self, dimensions, dim0_query_eval, remaining_query, packed_database, chunk_count,
                                     present_device=None, relinearization_key=None, stream=None):
         dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
-        out = self._empty((chunk_count, 2, 1, self.degree), dim0_query_eval)
-        rest = vp() if remaining_query is None else _ptr(remaining_query)
+        out = _empty((chunk_count, 2, 1, self.degree), WORD64, dim0_query_eval.device)
+        rest = _opt_ptr(remaining_query)
         rest_count = 0 if remaining_query is None else remaining_query.numel() // (2 * self.L * self.degree)
-        key = vp() if relinearization_key is None else _ptr(relinearization_key)
+        key = _opt_ptr(relinearization_key)
         mask = vp() if present_device is None else vp(present_device.data_ptr())
         _check(load_library().he_pir_compute_response_packed_device(self.h, dims, len(dimensions), _ptr(dim0_query_eval),
                                                                     rest, rest_count, _ptr(packed_database), mask,
@@ -1405,21 +1366,21 @@ class BfvContext:
         return out
 
     def inner_product(self, lhs, rhs, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         count = lhs.numel() // (2 * L * self.degree)
-        out = self._empty((3, L, self.degree), lhs)
-        _check(load_library().he_bfv_inner_product_device(self.h, L, _ptr(lhs), _ptr(rhs), count, _ptr(out), vp(), 0,
-                                                          _stream(stream)))
+        out = _empty((3, L, self.degree), w, lhs.device)
+        _check(_entry("he_bfv_inner_product_device", w)(
+            self.h, L, _ptr(lhs, w), _ptr(rhs, w), count, _ptr(out, w), vp(), 0, _stream(stream)))
         return out
 
     def inner_product_shared(self, lhs, rhs, moduli_count=None, stream=None):
         """rhs [items][count][2][L][N]: `items` inner products with the same left vector -> [items][3][L][N]."""
-        L = self._L(moduli_count)
+        L, w = self._L(moduli_count), self._word
         count = lhs.numel() // (2 * L * self.degree)
         items = rhs.numel() // (count * 2 * L * self.degree)
-        out = self._empty((items, 3, L, self.degree), lhs)
-        _check(load_library().he_bfv_inner_product_shared_device(self.h, L, _ptr(lhs), _ptr(rhs), count, items, _ptr(out),
-                                                                 _stream(stream)))
+        out = _empty((items, 3, L, self.degree), w, lhs.device)
+        _check(_entry("he_bfv_inner_product_shared_device", w)(
+            self.h, L, _ptr(lhs, w), _ptr(rhs, w), count, items, _ptr(out, w), _stream(stream)))
         return out
 
 
@@ -1430,195 +1391,7 @@ class BfvContext32(BfvContext):
     def __init__(self, degree, plaintext_modulus, coefficient_moduli, host_only=False):
         super().__init__(degree, plaintext_modulus, coefficient_moduli, host_only=host_only, word_bits=32)
 
-    def _empty32(self, shape, like):
-        import torch
-
-        return torch.empty(shape, dtype=torch.int32, device=like.device)
-
-    @staticmethod
-    def _ws(workspace):
-        return (vp(workspace.data_ptr()), workspace.numel() * workspace.element_size()) if workspace is not None else (vp(), 0)
-
-    def lift_q_to_qbsk(self, polys, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = polys.numel() // (L * self.degree)
-        out = self._empty32((batch, 2 * L + 1, self.degree), polys)
-        _check(load_library().he_rns_lift_q_to_qbsk_device_u32(self.h, L, _ptr32(polys), _ptr32(out), batch, _stream(stream)))
-        return out
-
-    def floor_qbsk_to_q(self, polys, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = polys.numel() // ((2 * L + 1) * self.degree)
-        out = self._empty32((batch, L, self.degree), polys)
-        _check(load_library().he_rns_floor_qbsk_to_q_device_u32(self.h, L, _ptr32(polys), _ptr32(out), batch, _stream(stream)))
-        return out
-
-    def scale_and_round(self, poly, scaling_factor=1, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = poly.numel() // (L * self.degree)
-        out = self._empty32((batch, self.degree), poly)
-        _check(load_library().he_rns_scale_and_round_device_u32(self.h, L, _ptr32(poly), int(scaling_factor), _ptr32(out),
-                                                                batch, _stream(stream)))
-        return out
-
-    def mul(self, lhs, rhs, moduli_count=None, stream=None, workspace=None):
-        L = self._L(moduli_count)
-        batch = lhs.numel() // (2 * L * self.degree)
-        out = self._empty32((batch, 3, L, self.degree), lhs)
-        ws_ptr, ws_bytes = self._ws(workspace)
-        _check(load_library().he_bfv_mul_device_u32(self.h, L, _ptr32(lhs), _ptr32(rhs), _ptr32(out), batch, ws_ptr,
-                                                    ws_bytes, _stream(stream)))
-        return out
-
-    def relinearize(self, ct3, key, moduli_count=None, stream=None, workspace=None):
-        L = self._L(moduli_count)
-        batch = ct3.numel() // (3 * L * self.degree)
-        out = self._empty32((batch, 2, L, self.degree), ct3)
-        ws_ptr, ws_bytes = self._ws(workspace)
-        _check(load_library().he_bfv_relinearize_device_u32(self.h, L, _ptr32(ct3), _ptr32(key), _ptr32(out), batch,
-                                                            ws_ptr, ws_bytes, _stream(stream)))
-        return out
-
-    def apply_galois(self, ct, element, key, moduli_count=None, stream=None, workspace=None):
-        L = self._L(moduli_count)
-        batch = ct.numel() // (2 * L * self.degree)
-        out = self._empty32((batch, 2, L, self.degree), ct)
-        ws_ptr, ws_bytes = self._ws(workspace)
-        _check(load_library().he_bfv_apply_galois_device_u32(self.h, L, _ptr32(ct), int(element), _ptr32(key), _ptr32(out),
-                                                             batch, ws_ptr, ws_bytes, _stream(stream)))
-        return out
-
-    def mod_switch_down(self, ct, poly_count, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = ct.numel() // (poly_count * L * self.degree)
-        out = self._empty32((batch, poly_count, L - 1, self.degree), ct)
-        _check(load_library().he_bfv_mod_switch_down_device_u32(self.h, L, poly_count, _ptr32(ct), _ptr32(out), batch,
-                                                                _stream(stream)))
-        return out
-
-    def mul_plain_(self, ct, pt, poly_count, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = pt.numel() // (L * self.degree)
-        _check(load_library().he_bfv_mul_plain_device_u32(self.h, L, poly_count, _ptr32(ct), _ptr32(pt), batch,
-                                                          _stream(stream)))
-        return ct
-
-    def add_plain_(self, ct, plaintexts, poly_count=2, subtract=False, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = plaintexts.numel() // self.degree
-        fn = load_library().he_bfv_sub_plain_device_u32 if subtract else load_library().he_bfv_add_plain_device_u32
-        _check(fn(self.h, L, poly_count, _ptr32(ct), _ptr32(plaintexts), batch, _stream(stream)))
-        return ct
-
-    def inner_product_plain_resident(self, cts, pts, present_device=None, poly_count=2, columns=1, moduli_count=None,
-                                     stream=None):
-        L = self._L(moduli_count)
-        count = cts.numel() // (poly_count * L * self.degree)
-        out = self._empty32((columns, poly_count, L, self.degree), cts)
-        mask = vp() if present_device is None else vp(present_device.data_ptr())
-        _check(load_library().he_bfv_inner_product_plain_resident_device_u32(self.h, L, poly_count, _ptr32(cts),
-                                                                             _ptr32(pts), mask, count, columns,
-                                                                             _ptr32(out), _stream(stream)))
-        return out
-
-    def inner_product(self, lhs, rhs, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        count = lhs.numel() // (2 * L * self.degree)
-        out = self._empty32((3, L, self.degree), lhs)
-        _check(load_library().he_bfv_inner_product_device_u32(self.h, L, _ptr32(lhs), _ptr32(rhs), count, _ptr32(out), vp(),
-                                                              0, _stream(stream)))
-        return out
-
-    def inner_product_shared(self, lhs, rhs, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        count = lhs.numel() // (2 * L * self.degree)
-        items = rhs.numel() // (count * 2 * L * self.degree)
-        out = self._empty32((items, 3, L, self.degree), lhs)
-        _check(load_library().he_bfv_inner_product_shared_device_u32(self.h, L, _ptr32(lhs), _ptr32(rhs), count, items,
-                                                                     _ptr32(out), _stream(stream)))
-        return out
-
-    def pir_compute_response(self, dimensions, dim0_query_eval, remaining_query, database, chunk_count,
-                             present_device=None, relinearization_key=None, stream=None):
-        """he_pir_compute_response_device_u32: everything in packed UInt32 words -> [chunks][2][1][N] (int32)."""
-        dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
-        out = self._empty32((chunk_count, 2, 1, self.degree), dim0_query_eval)
-        rest = vp() if remaining_query is None else _ptr32(remaining_query)
-        rest_count = 0 if remaining_query is None else remaining_query.numel() // (2 * self.L * self.degree)
-        key = vp() if relinearization_key is None else _ptr32(relinearization_key)
-        mask = vp() if present_device is None else vp(present_device.data_ptr())
-        _check(load_library().he_pir_compute_response_device_u32(self.h, dims, len(dimensions), _ptr32(dim0_query_eval),
-                                                                 rest, rest_count, _ptr32(database), mask, chunk_count,
-                                                                 key, _ptr32(out), _stream(stream)))
-        return out
-
-    def pir_compute_response_queries(self, dimensions, dim0_queries_eval, remaining_queries, database, chunk_count,
-                                     relinearization_keys, present_device=None, stream=None):
-        """he_pir_compute_response_queries_device_u32: dim0_queries_eval [d0][queries][2][L][N] Eval, remaining_queries
-        [queries][rest][2][L][N] (or None), one relinearization key per query (or None) -> [queries][chunks][2][1][N]."""
-        dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
-        queries = dim0_queries_eval.numel() // (int(dimensions[0]) * 2 * self.L * self.degree)
-        out = self._empty32((queries, chunk_count, 2, 1, self.degree), dim0_queries_eval)
-        rest = vp() if remaining_queries is None else _ptr32(remaining_queries)
-        rest_count = 0 if remaining_queries is None else remaining_queries.numel() // (queries * 2 * self.L * self.degree)
-        keys = None
-        if relinearization_keys is not None:
-            keys = (vp * queries)(*[vp(k.data_ptr()) for k in relinearization_keys])
-        mask = vp() if present_device is None else vp(present_device.data_ptr())
-        _check(load_library().he_pir_compute_response_queries_device_u32(
-            self.h, dims, len(dimensions), queries, _ptr32(dim0_queries_eval), rest, rest_count, _ptr32(database), mask,
-            chunk_count, keys, _ptr32(out), _stream(stream)))
-        return out
-
-    def pir_compute_response_to_query(self, dimensions, query_ciphertexts, indices_count, galois_keys_wide,
-                                      relinearization_key, databases, chunk_count, present_devices=None, stream=None):
-        """he_pir_compute_response_to_query_device_u32: int32 query / relinearization key / databases, Galois keys as
-        int64 (widened) tensors -> [indices][chunks][2][1][N] (int32)."""
-        dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
-        count = query_ciphertexts.numel() // (2 * self.L * self.degree)
-        out = self._empty32((indices_count, chunk_count, 2, 1, self.degree), query_ciphertexts)
-        elements = sorted(galois_keys_wide)
-        element_array = _u64(elements)
-        key_array = (vp * max(len(elements), 1))(*[vp(galois_keys_wide[e].data_ptr()) for e in elements])
-        relin = vp() if relinearization_key is None else _ptr32(relinearization_key)
-        database_list = list(databases) if isinstance(databases, (list, tuple)) else [databases]
-        database_array = (vp * len(database_list))(*[vp(d.data_ptr()) for d in database_list])
-        mask_array = None
-        if present_devices is not None:
-            mask_list = list(present_devices) if isinstance(present_devices, (list, tuple)) else [present_devices]
-            mask_array = (vp * len(mask_list))(*[vp() if m is None else vp(m.data_ptr()) for m in mask_list])
-        _check(load_library().he_pir_compute_response_to_query_device_u32(
-            self.h, dims, len(dimensions), _ptr32(query_ciphertexts), count, indices_count,
-            element_array.ctypes.data_as(U64P), key_array, len(elements), relin, database_array, mask_array,
-            len(database_list), chunk_count, _ptr32(out), _stream(stream)))
-        return out
-
-    _process_entry = "he_pir_process_database_device_u32"
-    _database_file_suffix = "_u32"
-
-    def _database_tensor(self, shape, device):
-        import torch
-
-        return torch.empty(shape, dtype=torch.int32, device=device)
-
-    def _database_ptr(self, database):
-        return _ptr32(database)
-
-    def plaintext_to_eval(self, plaintext, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = plaintext.numel() // self.degree
-        out = self._empty32((batch, L, self.degree), plaintext)
-        _check(load_library().he_bfv_plaintext_to_eval_device_u32(self.h, L, _ptr32(plaintext), _ptr32(out), batch,
-                                                                  _stream(stream)))
-        return out
-
-    def plaintext_to_coeff(self, plaintext_eval, moduli_count=None, stream=None):
-        L = self._L(moduli_count)
-        batch = plaintext_eval.numel() // (L * self.degree)
-        out = self._empty32((batch, self.degree), plaintext_eval)
-        _check(load_library().he_bfv_plaintext_to_coeff_device_u32(self.h, L, _ptr32(plaintext_eval), _ptr32(out), batch,
-                                                                   _stream(stream)))
-        return out
+    _word = WORD32
 
 
 def skip_lsbs_for_decryption(degree, q0, plaintext_modulus, moduli_count=1):
@@ -1664,8 +1437,8 @@ class SimplePirServer:
     torch tensor [column_size][database_columns] of element_bytes-wide elements, `hint` [column_size][lattice_dimension]
     words mod params["modulus"], requests and responses torch tensors of words (int64 storage; int32 in SimplePirServer32)."""
 
-    word_bits = 64
-    _suffix = ""
+    _word = WORD64
+    word_bits = _word.bits
 
     def __init__(self, database, hint, params, _handle=None):
         self.database, self.hint, self.params = database, hint, params
@@ -1675,16 +1448,6 @@ class SimplePirServer:
         if getattr(self, "h", None):
             load_library().he_simple_pir_context_destroy(self.h)
             self.h = None
-
-    @classmethod
-    def _words(cls, shape, device):
-        import torch
-
-        return torch.empty(shape, dtype=torch.int64 if cls.word_bits == 64 else torch.int32, device=device)
-
-    @classmethod
-    def _entry(cls, name):
-        return getattr(load_library(), name + cls._suffix)
 
     @classmethod
     def process(cls, entries, plaintext_bits, ciphertext_bits, lattice_dimension, seed, stream=None):
@@ -1720,12 +1483,11 @@ class SimplePirServer:
         if out is None:
             database = torch.empty((params["column_size"], params["database_columns"]), device=entries.device,
                                    dtype=getattr(torch, _SIMPLE_PIR_ELEMENT_DTYPES[params["element_bytes"]]))
-            hint = self._words((params["column_size"], params["lattice_dimension"]), entries.device)
+            hint = _empty((params["column_size"], params["lattice_dimension"]), self._word, entries.device)
         else:
             database, hint = out
-        _check(self._entry("he_simple_pir_process_database_device")(self.h, vp(entries.data_ptr()), vp(seed.data_ptr()),
-                                                                    vp(database.data_ptr()), vp(hint.data_ptr()),
-                                                                    _stream(stream)))
+        _check(_entry("he_simple_pir_process_database_device", self._word)(
+            self.h, vp(entries.data_ptr()), vp(seed.data_ptr()), vp(database.data_ptr()), vp(hint.data_ptr()), _stream(stream)))
         self.database, self.hint = database, hint
         return self
 
@@ -1736,29 +1498,25 @@ class SimplePirServer:
 
         database = torch.empty(tuple(wide.shape), device=wide.device,
                                dtype=getattr(torch, _SIMPLE_PIR_ELEMENT_DTYPES[params["element_bytes"]]))
-        _check(cls._entry("he_simple_pir_pack_database_device")(params["plaintext_bits"], cls._word_ptr(wide),
-                                                                vp(database.data_ptr()), wide.numel(), _stream(stream)))
+        _check(_entry("he_simple_pir_pack_database_device", cls._word)(
+            params["plaintext_bits"], _ptr(wide, cls._word), vp(database.data_ptr()), wide.numel(), _stream(stream)))
         return cls(database, hint, params)
-
-    @classmethod
-    def _word_ptr(cls, tensor):
-        return _ptr(tensor) if cls.word_bits == 64 else _ptr32(tensor)
 
     def wide_database(self, stream=None):
         """The database as the reference stores it: one word per element."""
-        wide = self._words(tuple(self.database.shape), self.database.device)
-        _check(self._entry("he_simple_pir_unpack_database_device")(self.params["plaintext_bits"], vp(self.database.data_ptr()),
-                                                                   vp(wide.data_ptr()), wide.numel(), _stream(stream)))
+        wide = _empty(tuple(self.database.shape), self._word, self.database.device)
+        _check(_entry("he_simple_pir_unpack_database_device", self._word)(
+            self.params["plaintext_bits"], vp(self.database.data_ptr()), vp(wide.data_ptr()), wide.numel(), _stream(stream)))
         return wide
 
     def compute_response(self, requests, stream=None):
         """computeResponse(to:): requests [query_count][database_columns] -> responses [query_count][column_size]."""
         if requests.dim() != 2 or requests.shape[1] != self.params["database_columns"]:
             raise ValueError("expected requests [query_count][database_columns]")
-        responses = self._words((requests.shape[0], self.params["column_size"]), requests.device)
-        _check(self._entry("he_simple_pir_compute_response_device")(
+        responses = _empty((requests.shape[0], self.params["column_size"]), self._word, requests.device)
+        _check(_entry("he_simple_pir_compute_response_device", self._word)(
             self.params["plaintext_bits"], self.params["ciphertext_bits"], vp(self.database.data_ptr()),
-            self.params["column_size"], self.params["database_columns"], self._word_ptr(requests), requests.shape[0],
+            self.params["column_size"], self.params["database_columns"], _ptr(requests, self._word), requests.shape[0],
             vp(responses.data_ptr()), _stream(stream)))
         return responses
 
@@ -1767,10 +1525,10 @@ class SimplePirServer:
         simple_pir_batch_plan says so (elements must be below 2^plaintext_bits, as process and from_wide leave them)."""
         if requests.dim() != 2 or requests.shape[1] != self.params["database_columns"]:
             raise ValueError("expected requests [query_count][database_columns]")
-        responses = self._words((requests.shape[0], self.params["column_size"]), requests.device)
-        _check(self._entry("he_simple_pir_compute_response_batch_device")(
+        responses = _empty((requests.shape[0], self.params["column_size"]), self._word, requests.device)
+        _check(_entry("he_simple_pir_compute_response_batch_device", self._word)(
             self.params["plaintext_bits"], self.params["ciphertext_bits"], vp(self.database.data_ptr()),
-            self.params["column_size"], self.params["database_columns"], self._word_ptr(requests), requests.shape[0],
+            self.params["column_size"], self.params["database_columns"], _ptr(requests, self._word), requests.shape[0],
             vp(responses.data_ptr()), _stream(stream)))
         return responses
 
@@ -1782,8 +1540,8 @@ class SimplePirServer:
 class SimplePirServer32(SimplePirServer):
     """SimplePirServer<UInt32>: 4-byte request / response / hint words."""
 
-    word_bits = 32
-    _suffix = "_u32"
+    _word = WORD32
+    word_bits = _word.bits
 
 
 PNNS_PACKINGS = {"denseColumn": 0, "denseRow": 1, "diagonal": 2}  # MatrixPacking's case order (HE_PNNS_PACKING_*)
@@ -1803,10 +1561,9 @@ class PnnsContext:
     def __init__(self, bfv):
         lib = load_library()
         self.bfv = bfv
-        self.word32 = bfv.word_bits == 32  # Bfv<UInt32>: packed 4-byte words, as BfvContext32 lays its slabs out
+        self._word = _word_of(bfv.word_bits)  # Bfv<UInt32>: packed 4-byte words, as BfvContext32 lays its slabs out
         h = vp()
-        create = lib.he_pnns_context_create_u32 if self.word32 else lib.he_pnns_context_create
-        _check(create(bfv.h, ctypes.byref(h)))
+        _check(_entry("he_pnns_context_create", self._word)(bfv.h, ctypes.byref(h)))
         self.h = h
 
     def __del__(self):
@@ -1848,13 +1605,11 @@ class PnnsContext:
         count = self.matrix_shape(rows, cols, "diagonal", baby_step)["plaintext_count"]
         # (a fill on the caller's stream, ahead of the build that may set the word)
         with torch.cuda.stream(stream) if stream is not None else _no_stream():
-            matrix = torch.empty((count, L, self.bfv.degree), dtype=torch.int32 if self.word32 else torch.int64,
-                                 device=signed_values.device)
+            matrix = _empty((count, L, self.bfv.degree), self._word, signed_values.device)
             out_of_range = torch.zeros(1, dtype=torch.int32, device=signed_values.device)
-        entry = "he_pnns_diagonal_matrix_device_u32" if self.word32 else "he_pnns_diagonal_matrix_device"
-        _check(getattr(load_library(), entry)(self.h, vp(signed_values.data_ptr()), rows, cols, int(baby_step),
-                                              int(bool(reduce)), L, vp(matrix.data_ptr()), vp(out_of_range.data_ptr()),
-                                              _stream(stream)))
+        _check(_entry("he_pnns_diagonal_matrix_device", self._word)(
+            self.h, vp(signed_values.data_ptr()), rows, cols, int(baby_step), int(bool(reduce)), L, vp(matrix.data_ptr()),
+            vp(out_of_range.data_ptr()), _stream(stream)))
         return matrix, out_of_range
 
     def process_database(self, vectors, scaling_factor, baby_step=0, reduce=False, moduli_count=None, stream=None):
@@ -1868,7 +1623,7 @@ class PnnsContext:
     def _respond(self, entry, matrix, rows, cols, queries, galois_keys, baby_step, out_moduli, stream):
         import torch
 
-        word = torch.int32 if self.word32 else torch.int64
+        word = getattr(torch, self._word.dtype)
         L, n = self.bfv.L, self.bfv.degree
         for name, tensor in (("matrix", matrix), ("queries", queries)):
             if tensor.dtype != word or not tensor.is_cuda or not tensor.is_contiguous():
@@ -1892,10 +1647,9 @@ class PnnsContext:
         results = -(-int(rows) // n)
         with torch.cuda.stream(stream) if stream is not None else _no_stream():
             out = torch.empty((count, results, 2, out_moduli, n), dtype=word, device=queries.device)
-        name = entry + ("_u32" if self.word32 else "")
-        _check(getattr(load_library(), name)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
-                                             shape["baby_step"], vp(queries.data_ptr()), count,
-                                             keys if galois_keys is not None else None, vp(out.data_ptr()), _stream(stream)))
+        _check(_entry(entry, self._word)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
+                                         shape["baby_step"], vp(queries.data_ptr()), count,
+                                         keys if galois_keys is not None else None, vp(out.data_ptr()), _stream(stream)))
         return out
 
     def mul_transpose(self, matrix, rows, cols, queries, galois_keys, baby_step=None, stream=None):
@@ -1925,7 +1679,7 @@ class PnnsContext:
                       stream):
         import torch
 
-        word = torch.int32 if self.word32 else torch.int64
+        word = getattr(torch, self._word.dtype)
         L, n = self.bfv.L, self.bfv.degree
         for name, tensor in (("matrix", matrix), ("queries", queries)):
             if tensor.dtype != word or not tensor.is_cuda or not tensor.is_contiguous():
@@ -1958,11 +1712,10 @@ class PnnsContext:
                         keys[stride * q + k] = key.data_ptr()
         with torch.cuda.stream(stream) if stream is not None else _no_stream():
             out = torch.empty((count, query_shape["result_ciphertexts"], 2, out_moduli, n), dtype=word, device=queries.device)
-        name = entry + ("_u32" if self.word32 else "")
-        _check(getattr(load_library(), name)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
-                                             shape["baby_step"], vp(queries.data_ptr()), int(query_rows), count,
-                                             plan if pack_steps else None, len(pack_steps),
-                                             keys if galois_keys is not None else None, vp(out.data_ptr()), _stream(stream)))
+        _check(_entry(entry, self._word)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
+                                         shape["baby_step"], vp(queries.data_ptr()), int(query_rows), count,
+                                         plan if pack_steps else None, len(pack_steps),
+                                         keys if galois_keys is not None else None, vp(out.data_ptr()), _stream(stream)))
         return out
 
     def mul_transpose_matrix(self, matrix, rows, cols, queries, query_rows, pack_steps, galois_keys, baby_step=None,

@@ -933,9 +933,9 @@ def test_bfv_uint32_packed_slabs_match_oracle(oracle):
     expected_relin = ref.relinearize(expected_product, key)
     assert np.array_equal(host(relin), expected_relin)
     assert client.decrypt(host(relin)[0]) == negacyclic_multiply(m1, m2, t)
-    # the 8-byte entry points on zero-extended words agree
-    wide = heamd.BfvContext.relinearize(ours, heamd.BfvContext.mul(ours, heamd.to_device(ct1), heamd.to_device(ct2)),
-                                        heamd.to_device(key))
+    # the 8-byte entry points on zero-extended words agree (the same Bfv<UInt32> constants, held for 8-byte slabs)
+    ours_wide = heamd.BfvContext(degree, t, q, word_bits=32)
+    wide = ours_wide.relinearize(ours_wide.mul(heamd.to_device(ct1), heamd.to_device(ct2)), heamd.to_device(key))
     assert np.array_equal(heamd.to_host(wide), expected_relin)
     # applyGalois
     element = 3

@@ -278,8 +278,10 @@ def test_device_entries_check_their_arguments_before_any_device_work(word_bits):
 
 
 # ---- the ABI -----------------------------------------------------------------------------------------------------------------------
-def test_entries_are_declared_exported_and_bound():
+def test_entries_are_declared_exported_and_bound(monkeypatch):
     import heamd
+    import torch
+    from binding_recorder import Stream, recording
 
     lib = heamd.load_library()
     bound = {name for name, _, _ in heamd.binding.SIGNATURES}
@@ -292,4 +294,11 @@ def test_entries_are_declared_exported_and_bound():
     for method in ("scan_database_file", "load_database_file", "save_database_file", "load_database_segment",
                    "save_database_segment", "database_file_byte_count"):
         assert hasattr(heamd.BfvContext, method) and hasattr(heamd.BfvContext32, method), method
-    assert heamd.BfvContext32._database_file_suffix == "_u32" and heamd.BfvContext._database_file_suffix == ""
+    for cls, suffix, word in ((heamd.BfvContext, "", torch.int64), (heamd.BfvContext32, "_u32", torch.int32)):
+        with recording(monkeypatch) as rec:  # the entries the class resolves, without a device
+            ctx = cls(8, 17, [97, 193, 257])
+            present = rec.tensor("present", (3,), torch.uint8)
+            ctx.load_database_segment(rec.tensor("records", (30,), torch.uint8), present, stream=Stream())
+            ctx.save_database_segment(rec.tensor("database", (3, 2, 8), word), present, stream=Stream())
+            reached = [name for name, _ in rec.calls if name.startswith("he_pir_database_")]
+        assert reached == ["he_pir_database_load_device" + suffix, "he_pir_database_save_device" + suffix]
