@@ -59,7 +59,14 @@ enum he_status {
     HE_ERR_SIMD_ENCODING_NOT_SUPPORTED = 22,     /* simdEncodingNotSupported      Encoding.swift:225 */
     /* PirError cases of ProcessedDatabase.init(from:context:) (PrivateInformationRetrieval/Util/Error.swift:32-33) */
     HE_ERR_INVALID_DATABASE_SERIALIZATION_VERSION = 23,      /* IndexPir/IndexPirProtocol.swift:307-311 */
-    HE_ERR_INVALID_DATABASE_SERIALIZATION_PLAINTEXT_TAG = 24 /* IndexPir/IndexPirProtocol.swift:329-330 */
+    HE_ERR_INVALID_DATABASE_SERIALIZATION_PLAINTEXT_TAG = 24, /* IndexPir/IndexPirProtocol.swift:329-330 */
+    /* PirError cases of the keyword database build (PrivateInformationRetrieval/Util/Error.swift) */
+    HE_ERR_FAILED_TO_CONSTRUCT_CUCKOO_TABLE = 25,      /* failedToConstructCuckooTable  KeywordPir/CuckooTable.swift:390,408,480,486 */
+    HE_ERR_INVALID_CUCKOO_CONFIG = 26,                 /* invalidCuckooConfig           KeywordPir/CuckooTable.swift:138-156 */
+    HE_ERR_INVALID_HASH_BUCKET_ENTRY_VALUE_SIZE = 27,  /* invalidHashBucketEntryValueSize KeywordPir/HashBucket.swift:91-93 */
+    HE_ERR_INVALID_HASH_BUCKET_SLOT_COUNT = 28,        /* invalidHashBucketSlotCount    KeywordPir/HashBucket.swift:146-148,178-181 */
+    /* not an error of the reference: he_keyword_pir_cuckoo_place asks for the larger table CuckooTable.expand() would build */
+    HE_ERR_CUCKOO_TABLE_NEEDS_EXPANSION = 29           /*                               KeywordPir/CuckooTable.swift:466-474 */
 };
 
 typedef struct he_poly_context he_poly_context; /* PolyContext<UInt64>   PolyRq/PolyContext.swift:19-35 */
@@ -662,6 +669,131 @@ int he_pir_process_database_device_u32(const he_bfv_context* ctx, const uint32_t
                                        const uint8_t* entries, const uint64_t* entry_sizes, size_t entry_count,
                                        size_t entry_size_in_bytes, int encoding_entry_size, uint32_t* database,
                                        uint8_t* present, he_stream s);
+
+/* ---- keyword PIR database (PrivateInformationRetrieval/KeywordPir/) --------------------------------------------------------
+ * KeywordPirServer.process (KeywordPirProtocol.swift:191-247) builds a cuckoo table of the keyword-value pairs, serializes
+ * every bucket and hands each sub-table's buckets to MulPirServer.process as index-PIR entries.  Here the keyword and value
+ * bytes go to the device once; the device hashes the keywords and derives the candidate buckets, the host places the entries
+ * reading 8 bytes of hash, h indices and one size per entry, and the device writes the serialized buckets as the
+ * [bucket][entry_size_in_bytes] slab he_pir_process_database_device reads.  None of the layered entries needs a context.
+ *
+ * A database is two blobs with offsets: keyword i is keywords[keyword_offsets[i], keyword_offsets[i + 1]), value i is
+ * values[value_offsets[i], value_offsets[i + 1]); both lie back to back at any byte address and may be empty. */
+
+/* CuckooTableConfig (CuckooTable.swift:18-84).  fixed_size nonzero is .fixedSize(bucketCount: bucket_count); zero is
+ * .allowExpansion(expansionFactor:targetLoadFactor:).  multiple_tables nonzero: hash function i has the sub-table
+ * [i bucketsPerTable, (i + 1) bucketsPerTable) to itself, table_count = hash_function_count; zero: one table. */
+typedef struct he_cuckoo_table_config {
+    uint32_t hash_function_count;
+    uint32_t max_eviction_count;
+    uint64_t max_serialized_bucket_size;
+    int fixed_size;
+    uint64_t bucket_count;      /* read when fixed_size is nonzero */
+    double expansion_factor;    /* read when fixed_size is zero */
+    double target_load_factor;  /* read when fixed_size is zero */
+    int multiple_tables;
+    uint32_t slot_count;
+} he_cuckoo_table_config;
+
+/* HashKeyword.hash (HashBucket.swift:264-269): SHA-256 of each keyword, the first 8 digest bytes as a little-endian UInt64.
+ *   keywords DEVICE blob; keyword_offsets DEVICE uint64 [count + 1], non-decreasing; out_hashes DEVICE uint64 [count].
+ * Nothing outside [keywords, keywords + keyword_offsets[count]) is read.  count above 2^32 - 1: HE_ERR_INVALID_ARGUMENT.
+ * Enqueue-only. */
+int he_keyword_pir_hash_keywords_device(const uint8_t* keywords, const uint64_t* keyword_offsets, size_t count,
+                                        uint64_t* out_hashes, he_stream s);
+/* HashKeyword.hashIndices (HashBucket.swift:221-257) with bucketCount = bucket_count (the table's bucketsPerTable):
+ * out_indices DEVICE uint32 [count][hash_function_count].  A repeated index is kept after the tenth retry, as the reference
+ * keeps it.  bucket_count outside 1 .. 2^32 - 1 or hash_function_count 0: HE_ERR_INVALID_ARGUMENT; hash_function_count
+ * above 8: HE_ERR_UNSUPPORTED (the reference's configurations use 1 to 3).  Enqueue-only. */
+int he_keyword_pir_hash_indices_device(const uint64_t* hashes, size_t count, uint64_t bucket_count,
+                                       uint32_t hash_function_count, uint32_t* out_indices, he_stream s);
+/* ShardingFunction.shardIndex (KeywordDatabase.swift:56-62,103-111) from the keyword hashes: hash % shard_count, or with
+ * other_shard_count nonzero doubleMod's (hash % other_shard_count) % shard_count.  out DEVICE uint32 [count].  shard_count
+ * outside 1 .. 2^32 - 1: HE_ERR_INVALID_ARGUMENT.  Enqueue-only. */
+int he_keyword_pir_shard_indices_device(const uint64_t* hashes, size_t count, uint64_t shard_count, uint64_t other_shard_count,
+                                        uint32_t* out, he_stream s);
+
+/* CuckooTableConfig.validate() (CuckooTable.swift:138-156): HE_OK or HE_ERR_INVALID_CUCKOO_CONFIG (a target load factor that is
+ * not above 0, by which the reference would divide, included); NULL: HE_ERR_INVALID_ARGUMENT.  Host. */
+int he_keyword_pir_config_validate(const he_cuckoo_table_config* config);
+/* The bucket count CuckooTable.init starts from (CuckooTable.swift:339-349): ceil(ceil(serialized size of all values in one
+ * bucket / max_serialized_bucket_size) / target_load_factor), or the fixed count, rounded up to a multiple of the table
+ * count.  value_sizes HOST [count].  Host. */
+int he_keyword_pir_bucket_count(const he_cuckoo_table_config* config, const uint64_t* value_sizes, size_t count, size_t* out);
+/* CuckooTable.insert / insertLoop (CuckooTable.swift:386-458) over integers: every entry in order into an empty table of
+ * bucket_count buckets (a multiple of the table count).  All pointers HOST; works without a device.
+ *   hashes [count], indices [count][hash_function_count] (each below bucket_count / table count), value_sizes [count]
+ *   out_bucket_offsets [bucket_count + 1], out_slot_entries [count]: bucket b holds entries out_slot_entries[
+ *   out_bucket_offsets[b] .. out_bucket_offsets[b + 1]) in slot order; out_placed = out_bucket_offsets[bucket_count]
+ * canInsert, swapIndices, index(tableIndex:index:), the size guard of insert and maxEvictionCount are the reference's.
+ * Three things are not:
+ *   1. Duplicates go by the 64-bit keyword hash and the first one wins (out_duplicates_dropped counts the others).  The
+ *      reference compares keyword bytes, so it would store two different keywords of one hash; a client finds only the first
+ *      either way (HashBucket.find(hash:)).
+ *   2. The evicted slot is candidates[splitmix64(seed).next() % candidates.count]; the reference draws from
+ *      SystemRandomNumberGenerator and so builds no reproducible table.
+ *   3. No entry is lost.  Where no resident value can be swapped out the reference expands and returns without inserting the
+ *      pair it holds (:449-457); here the pair is part of the larger table.
+ * Errors: HE_ERR_INVALID_CUCKOO_CONFIG; HE_ERR_INVALID_HASH_BUCKET_ENTRY_VALUE_SIZE for a value above 65 535 bytes;
+ * HE_ERR_FAILED_TO_CONSTRUCT_CUCKOO_TABLE for a value whose single-entry bucket exceeds max_serialized_bucket_size and, with
+ * fixed_size, wherever the reference throws it (evictions used up, nothing to swap); HE_ERR_INVALID_ARGUMENT for null
+ * pointers, a bucket_count that is zero or no multiple of the table count, an index out of range, count above 2^32 - 1.
+ * Without fixed_size a needed expansion returns HE_ERR_CUCKOO_TABLE_NEEDS_EXPANSION and out_next_bucket_count =
+ * ceil(bucket_count * expansion_factor) rounded up to a multiple of the table count (:466-474): the candidate indices depend
+ * on the bucket count, so the caller derives them anew and places every entry again, as the reference re-inserts them. */
+int he_keyword_pir_cuckoo_place(const he_cuckoo_table_config* config, const uint64_t* hashes, const uint32_t* indices,
+                                const uint64_t* value_sizes, size_t count, size_t bucket_count, uint64_t seed,
+                                uint32_t* out_bucket_offsets, uint32_t* out_slot_entries, size_t* out_placed,
+                                size_t* out_duplicates_dropped, size_t* out_next_bucket_count);
+
+/* HashBucket.serialize (HashBucket.swift:90-103,177-187) of every bucket, bucket b at out + b * entry_size_in_bytes: the slot
+ * count byte, per slot the 8-byte little-endian keyword hash, the UInt16 little-endian value size and the value; the rest of
+ * the row is written as zero (an empty bucket is all zero).  All pointers DEVICE, any byte address for values and out:
+ *   hashes [entries], values, value_offsets [entries + 1], bucket_offsets uint32 [bucket_count + 1], slot_entries uint32
+ *   [bucket_offsets[bucket_count]] as he_keyword_pir_cuckoo_place writes them, out [bucket_count][entry_size_in_bytes]
+ * Exactly the bytes of `out` are written and only bytes of the named arrays are read.  device_mismatch (optional, a DEVICE word
+ * the caller has zeroed): bit 0 when a bucket's serialization is longer than entry_size_in_bytes (the row holds its first
+ * bytes), bit 1 when a bucket has more than 255 slots (invalidHashBucketSlotCount).  Enqueue-only: the slots' running offsets
+ * go to stream-ordered scratch (4 bytes per slot), then one launch. */
+int he_keyword_pir_serialize_buckets_device(const uint64_t* hashes, const uint8_t* values, const uint64_t* value_offsets,
+                                            const uint32_t* bucket_offsets, const uint32_t* slot_entries, size_t slot_count,
+                                            size_t bucket_count, size_t entry_size_in_bytes, uint8_t* out,
+                                            uint32_t* device_mismatch, he_stream s);
+
+/* The table object: CuckooTable.init (CuckooTable.swift:328-357) of a whole database.
+ *   keywords DEVICE, keyword_offsets HOST [count + 1]; values DEVICE (not read here), value_offsets HOST [count + 1]
+ * The offsets are uploaded, the keywords hashed, the indices derived and both brought to the host; the entries are placed,
+ * with the index kernel run again after each expansion; the hashes, the value offsets and the buckets stay on the device.
+ * The call synchronises the stream (several times).  Errors as he_keyword_pir_cuckoo_place (never the expansion status), offsets that decrease:
+ * HE_ERR_INVALID_ARGUMENT.  Destroy with he_keyword_pir_table_destroy (NULL is fine). */
+typedef struct he_keyword_pir_table he_keyword_pir_table;
+int he_keyword_pir_table_create_device(const he_cuckoo_table_config* config, const uint8_t* keywords,
+                                       const uint64_t* keyword_offsets, const uint8_t* values, const uint64_t* value_offsets,
+                                       size_t count, uint64_t seed, he_keyword_pir_table** out_table, he_stream s);
+void he_keyword_pir_table_destroy(he_keyword_pir_table* table);
+size_t he_keyword_pir_table_bucket_count(const he_keyword_pir_table* table);
+size_t he_keyword_pir_table_buckets_per_table(const he_keyword_pir_table* table);
+size_t he_keyword_pir_table_table_count(const he_keyword_pir_table* table);
+/* CuckooTable.maxSerializedBucketSize() (:381-383): with .allowExpansion and without useMaxSerializedBucketSize this is the
+ * maxEntrySize of KeywordPirProtocol.swift:205-218; otherwise that is the config's max_serialized_bucket_size. */
+size_t he_keyword_pir_table_largest_bucket_size(const he_keyword_pir_table* table);
+size_t he_keyword_pir_table_entry_count(const he_keyword_pir_table* table);        /* entries placed */
+size_t he_keyword_pir_table_duplicates_dropped(const he_keyword_pir_table* table);
+size_t he_keyword_pir_table_expansion_count(const he_keyword_pir_table* table);
+float he_keyword_pir_table_load_factor(const he_keyword_pir_table* table);         /* summarize() (:361-373) */
+/* CuckooTable.serializeBuckets() (:375-378) padded: he_keyword_pir_serialize_buckets_device over the whole table into out
+ * DEVICE [bucket_count][entry_size_in_bytes]; values is the blob the table was created over.  entry_size_in_bytes below the
+ * largest bucket: HE_ERR_INVALID_ARGUMENT.  Enqueue-only. */
+int he_keyword_pir_table_entries_device(const he_keyword_pir_table* table, const uint8_t* values, size_t entry_size_in_bytes,
+                                        uint8_t* out, he_stream s);
+/* KeywordPirProtocol.swift:220-239: the entries into stream-ordered scratch, then he_pir_process_database_device once per
+ * sub-table with entry_count = buckets_per_table, no size prefix and no entry sizes.  database DEVICE [table_count][
+ * chunk_count][prod(dimensions)][L][N] and present DEVICE [table_count][chunk_count][prod(dimensions)], the order in which the
+ * reference concatenates (:230-238).  The words are those of the context: uint64_t for a Context<Bfv<UInt64>>, packed
+ * uint32_t for a Context<Bfv<UInt32>> (one entry for both: the context says which).  Enqueue-only. */
+int he_keyword_pir_process_database_device(const he_bfv_context* ctx, const he_keyword_pir_table* table, const uint8_t* values,
+                                           const uint32_t* dimensions, uint32_t dimension_count, size_t entry_size_in_bytes,
+                                           void* database, uint8_t* present, he_stream s);
 
 /* ---- processed-database files: ProcessedDatabase.serialize() / init(from:context:) ----------------------
  * The file PIRProcessDatabase writes and every index- and keyword-PIR server loads (PrivateInformationRetrieval/IndexPir/

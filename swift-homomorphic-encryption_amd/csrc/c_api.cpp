@@ -388,6 +388,11 @@ const char* he_status_string(int status) {
         case HE_ERR_SIMD_ENCODING_NOT_SUPPORTED: return "simdEncodingNotSupported";
         case HE_ERR_INVALID_DATABASE_SERIALIZATION_VERSION: return "invalidDatabaseSerializationVersion";
         case HE_ERR_INVALID_DATABASE_SERIALIZATION_PLAINTEXT_TAG: return "invalidDatabaseSerializationPlaintextTag";
+        case HE_ERR_FAILED_TO_CONSTRUCT_CUCKOO_TABLE: return "failedToConstructCuckooTable";
+        case HE_ERR_INVALID_CUCKOO_CONFIG: return "invalidCuckooConfig";
+        case HE_ERR_INVALID_HASH_BUCKET_ENTRY_VALUE_SIZE: return "invalidHashBucketEntryValueSize";
+        case HE_ERR_INVALID_HASH_BUCKET_SLOT_COUNT: return "invalidHashBucketSlotCount";
+        case HE_ERR_CUCKOO_TABLE_NEEDS_EXPANSION: return "cuckooTableNeedsExpansion";
         default: return "unknown";
     }
 }

@@ -10,8 +10,10 @@ Names follow the reference (Sources/HomomorphicEncryption): PolyContext.forwardN
 from .binding import (  # noqa: F401
     BfvContext,
     BfvContext32,
+    CuckooTableConfig,
     DeviceGroup,
     HeError,
+    KeywordPirTable,
     PnnsContext,
     PolyContext,
     SimplePirServer,
@@ -21,6 +23,12 @@ from .binding import (  # noqa: F401
     galois_element_rotating_columns,
     galois_element_swapping_rows,
     generate_primes,
+    keyword_pir_bucket_count,
+    keyword_pir_cuckoo_place,
+    keyword_pir_hash_indices,
+    keyword_pir_hash_keywords,
+    keyword_pir_serialize_buckets,
+    keyword_pir_shard_indices,
     library_path,
     load_library,
     narrow_u64,

@@ -39,6 +39,8 @@ STATUS_NAMES = {
     16: "invalidArgument", 17: "deviceError", 18: "unsupportedHeOperation", 19: "missingGaloisKey",
     20: "serializedBufferSizeMismatch", 21: "invalidCoefficientPacking", 22: "simdEncodingNotSupported",
     23: "invalidDatabaseSerializationVersion", 24: "invalidDatabaseSerializationPlaintextTag",
+    25: "failedToConstructCuckooTable", 26: "invalidCuckooConfig", 27: "invalidHashBucketEntryValueSize",
+    28: "invalidHashBucketSlotCount", 29: "cuckooTableNeedsExpansion",
 }
 
 
@@ -206,6 +208,27 @@ SIGNATURES = [
     ("he_pir_database_file_header", ctypes.c_int, [c_size, vp]),
     ("he_pir_database_load_device", ctypes.c_int, [vp, vp, c_size, vp, c_size, vp, vp, vp]),
     ("he_pir_database_save_device", ctypes.c_int, [vp, vp, vp, c_size, vp, c_size, vp, vp]),
+    ("he_keyword_pir_hash_keywords_device", ctypes.c_int, [vp, vp, c_size, vp, vp]),
+    ("he_keyword_pir_hash_indices_device", ctypes.c_int, [vp, c_size, c_u64, c_u32, vp, vp]),
+    ("he_keyword_pir_shard_indices_device", ctypes.c_int, [vp, c_size, c_u64, c_u64, vp, vp]),
+    ("he_keyword_pir_config_validate", ctypes.c_int, [vp]),
+    ("he_keyword_pir_bucket_count", ctypes.c_int, [vp, U64P, c_size, ctypes.POINTER(c_size)]),
+    ("he_keyword_pir_cuckoo_place", ctypes.c_int,
+     [vp, U64P, ctypes.POINTER(c_u32), U64P, c_size, c_size, c_u64, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32),
+      ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
+    ("he_keyword_pir_serialize_buckets_device", ctypes.c_int, [vp, vp, vp, vp, vp, c_size, c_size, c_size, vp, vp, vp]),
+    ("he_keyword_pir_table_create_device", ctypes.c_int, [vp, vp, U64P, vp, U64P, c_size, c_u64, ctypes.POINTER(vp), vp]),
+    ("he_keyword_pir_table_destroy", None, [vp]),
+    ("he_keyword_pir_table_bucket_count", c_size, [vp]),
+    ("he_keyword_pir_table_buckets_per_table", c_size, [vp]),
+    ("he_keyword_pir_table_table_count", c_size, [vp]),
+    ("he_keyword_pir_table_largest_bucket_size", c_size, [vp]),
+    ("he_keyword_pir_table_entry_count", c_size, [vp]),
+    ("he_keyword_pir_table_duplicates_dropped", c_size, [vp]),
+    ("he_keyword_pir_table_expansion_count", c_size, [vp]),
+    ("he_keyword_pir_table_load_factor", ctypes.c_float, [vp]),
+    ("he_keyword_pir_table_entries_device", ctypes.c_int, [vp, vp, c_size, vp, vp]),
+    ("he_keyword_pir_process_database_device", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(c_u32), c_u32, c_size, vp, vp, vp]),
     ("he_simple_pir_shape", ctypes.c_int,
      [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
       ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_u64), ctypes.POINTER(c_u32)]),
@@ -1734,6 +1757,198 @@ class PnnsContext:
         modSwitchDownToSingle -> [Q][M][2][1][N] Coeff over q_0."""
         return self._matrix_entry("he_pnns_compute_response_matrix_device", matrix, rows, cols, queries, query_rows,
                                   pack_steps, galois_keys, baby_step, 1, stream)
+
+
+# ---- keyword PIR database (DESIGN.md 4.12): HashKeyword, CuckooTable, HashBucket.serialize ----
+class CuckooTableConfig(ctypes.Structure):
+    """he_cuckoo_table_config: CuckooTableConfig (KeywordPir/CuckooTable.swift:18-84).  bucket_count given: .fixedSize;
+    None: .allowExpansion(expansionFactor:targetLoadFactor:)."""
+
+    _fields_ = [("hash_function_count", c_u32), ("max_eviction_count", c_u32), ("max_serialized_bucket_size", c_u64),
+                ("fixed_size", ctypes.c_int), ("bucket_count", c_u64), ("expansion_factor", ctypes.c_double),
+                ("target_load_factor", ctypes.c_double), ("multiple_tables", ctypes.c_int), ("slot_count", c_u32)]
+
+    def __init__(self, hash_function_count, max_eviction_count, max_serialized_bucket_size, bucket_count=None,
+                 expansion_factor=1.1, target_load_factor=0.9, multiple_tables=True, slot_count=255):
+        super().__init__(int(hash_function_count), int(max_eviction_count), int(max_serialized_bucket_size),
+                         int(bucket_count is not None), int(bucket_count or 0), float(expansion_factor),
+                         float(target_load_factor), int(bool(multiple_tables)), int(slot_count))
+
+    @property
+    def table_count(self):
+        return self.hash_function_count if self.multiple_tables else 1
+
+    def validate(self):
+        _check(load_library().he_keyword_pir_config_validate(ctypes.byref(self)))
+
+
+def _blob(items, device=None):
+    """bytes-like items back to back -> (uint8 array or device tensor, uint64 offsets [len + 1])"""
+    offsets = np.zeros(len(items) + 1, dtype=np.uint64)
+    np.cumsum([len(item) for item in items], out=offsets[1:])
+    blob = np.frombuffer(b"".join(bytes(item) for item in items), dtype=np.uint8).copy()
+    if device is None:
+        return blob, offsets
+    import torch
+
+    return torch.from_numpy(blob).to(device), offsets
+
+
+def _byte_ptr(tensor):
+    if not tensor.is_cuda or tensor.element_size() != 1:
+        raise ValueError("expected a uint8 CUDA (HIP) tensor")
+    if not tensor.is_contiguous():
+        raise ValueError("expected a contiguous tensor")
+    return vp(tensor.data_ptr())
+
+
+def keyword_pir_hash_keywords(keywords, keyword_offsets, stream=None):
+    """he_keyword_pir_hash_keywords_device: HashKeyword.hash of keyword i = keywords[offsets[i], offsets[i + 1]) (a uint8
+    device tensor, at any byte address; offsets: int64 device tensor [count + 1]) -> int64 tensor [count] of the hashes."""
+    import torch
+
+    count = keyword_offsets.numel() - 1
+    out = torch.empty((count,), dtype=torch.int64, device=keywords.device)
+    _check(load_library().he_keyword_pir_hash_keywords_device(_byte_ptr(keywords), _ptr(keyword_offsets), count, _ptr(out),
+                                                              _stream(stream)))
+    return out
+
+
+def keyword_pir_hash_indices(hashes, bucket_count, hash_function_count, stream=None):
+    """he_keyword_pir_hash_indices_device: HashKeyword.hashIndices -> int32 tensor [count][hash_function_count]."""
+    import torch
+
+    out = torch.empty((hashes.numel(), int(hash_function_count)), dtype=torch.int32, device=hashes.device)
+    _check(load_library().he_keyword_pir_hash_indices_device(_ptr(hashes), hashes.numel(), int(bucket_count),
+                                                             int(hash_function_count), _ptr(out, WORD32), _stream(stream)))
+    return out
+
+
+def keyword_pir_shard_indices(hashes, shard_count, other_shard_count=0, stream=None):
+    """he_keyword_pir_shard_indices_device: ShardingFunction.shardIndex (other_shard_count given: doubleMod) -> int32 [count]."""
+    import torch
+
+    out = torch.empty((hashes.numel(),), dtype=torch.int32, device=hashes.device)
+    _check(load_library().he_keyword_pir_shard_indices_device(_ptr(hashes), hashes.numel(), int(shard_count),
+                                                              int(other_shard_count), _ptr(out, WORD32), _stream(stream)))
+    return out
+
+
+def keyword_pir_bucket_count(config, value_sizes):
+    """he_keyword_pir_bucket_count: the bucket count CuckooTable.init starts from.  Host only."""
+    sizes = np.ascontiguousarray(value_sizes, dtype=np.uint64)
+    out = c_size(0)
+    _check(load_library().he_keyword_pir_bucket_count(ctypes.byref(config), sizes.ctypes.data_as(U64P), len(sizes),
+                                                      ctypes.byref(out)))
+    return out.value
+
+
+def keyword_pir_cuckoo_place(config, hashes, indices, value_sizes, bucket_count, seed):
+    """he_keyword_pir_cuckoo_place on host arrays -> dict(status name, bucket_offsets, slot_entries, placed,
+    duplicates_dropped, next_bucket_count); "ok" and "cuckooTableNeedsExpansion" are returned, everything else raises.
+    Host only."""
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+    sizes = np.ascontiguousarray(value_sizes, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    count = len(hashes)
+    if len(sizes) != count or indices.size != count * config.hash_function_count:
+        raise ValueError("one hash, one size and hash_function_count indices per entry")
+    offsets = np.zeros(int(bucket_count) + 1, dtype=np.uint32)
+    entries = np.zeros(max(count, 1), dtype=np.uint32)
+    placed, dropped, grown = c_size(0), c_size(0), c_size(0)
+    u32p = ctypes.POINTER(c_u32)
+    status = load_library().he_keyword_pir_cuckoo_place(
+        ctypes.byref(config), hashes.ctypes.data_as(U64P), indices.ctypes.data_as(u32p), sizes.ctypes.data_as(U64P), count,
+        int(bucket_count), int(seed) & (2**64 - 1), offsets.ctypes.data_as(u32p), entries.ctypes.data_as(u32p),
+        ctypes.byref(placed), ctypes.byref(dropped), ctypes.byref(grown))
+    if status not in (0, 29):
+        _check(status)
+    return {"status": STATUS_NAMES[status], "bucket_offsets": offsets, "slot_entries": entries[:placed.value],
+            "placed": placed.value, "duplicates_dropped": dropped.value, "next_bucket_count": grown.value}
+
+
+def keyword_pir_serialize_buckets(hashes, values, value_offsets, bucket_offsets, slot_entries, entry_size_in_bytes, out=None,
+                                  mismatch=None, stream=None):
+    """he_keyword_pir_serialize_buckets_device: HashBucket.serialize of every bucket of a CSR table (all device tensors: hashes
+    and value_offsets int64, bucket_offsets and slot_entries int32, values uint8) -> uint8 [bucket_count][entry_size_in_bytes]
+    (out: a contiguous uint8 tensor of that many bytes at any address)."""
+    import torch
+
+    buckets = bucket_offsets.numel() - 1
+    if out is None:
+        out = torch.empty((buckets, int(entry_size_in_bytes)), dtype=torch.uint8, device=hashes.device)
+    elif out.numel() != buckets * int(entry_size_in_bytes):
+        raise ValueError("out does not hold bucket_count * entry_size_in_bytes bytes")
+    _check(load_library().he_keyword_pir_serialize_buckets_device(
+        _ptr(hashes), _byte_ptr(values), _ptr(value_offsets), _ptr(bucket_offsets, WORD32), _ptr(slot_entries, WORD32),
+        slot_entries.numel(), buckets, int(entry_size_in_bytes), _byte_ptr(out), _opt_ptr(mismatch, WORD32), _stream(stream)))
+    return out
+
+
+class KeywordPirTable:
+    """he_keyword_pir_table: CuckooTable.init over a whole database on the device, then serializeBuckets() and the index-PIR
+    build per sub-table -- what KeywordPirServer.process does (KeywordPir/KeywordPirProtocol.swift:191-247).
+
+    keywords / values: lists of bytes-like items.  The blobs go to `device` once and `values` stays with the table."""
+
+    def __init__(self, config, keywords, values, seed=0, device="cuda", stream=None):
+        if len(keywords) != len(values):
+            raise ValueError("one value per keyword")
+        self.config = config
+        keyword_blob, keyword_offsets = _blob(keywords, device)
+        self.values, value_offsets = _blob(values, device)
+        handle = vp()
+        _check(load_library().he_keyword_pir_table_create_device(
+            ctypes.byref(config), vp(keyword_blob.data_ptr()), keyword_offsets.ctypes.data_as(U64P), vp(self.values.data_ptr()),
+            value_offsets.ctypes.data_as(U64P), len(keywords), int(seed) & (2**64 - 1), ctypes.byref(handle), _stream(stream)))
+        self.h = handle
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            load_library().he_keyword_pir_table_destroy(self.h)
+            self.h = None
+
+    def _get(self, name):
+        return getattr(load_library(), "he_keyword_pir_table_" + name)(self.h)
+
+    bucket_count = property(lambda self: self._get("bucket_count"))
+    buckets_per_table = property(lambda self: self._get("buckets_per_table"))
+    table_count = property(lambda self: self._get("table_count"))
+    largest_bucket_size = property(lambda self: self._get("largest_bucket_size"))
+    entry_count = property(lambda self: self._get("entry_count"))
+    duplicates_dropped = property(lambda self: self._get("duplicates_dropped"))
+    expansion_count = property(lambda self: self._get("expansion_count"))
+    load_factor = property(lambda self: self._get("load_factor"))
+
+    def entries(self, entry_size_in_bytes=None, out=None, stream=None):
+        """he_keyword_pir_table_entries_device -> uint8 [bucket_count][entry_size_in_bytes] (None: the largest bucket)."""
+        import torch
+
+        size = self.largest_bucket_size if entry_size_in_bytes is None else int(entry_size_in_bytes)
+        if out is None:
+            out = torch.empty((self.bucket_count, size), dtype=torch.uint8, device=self.values.device)
+        elif out.numel() != self.bucket_count * size:
+            raise ValueError("out does not hold bucket_count * entry_size_in_bytes bytes")
+        _check(load_library().he_keyword_pir_table_entries_device(self.h, vp(self.values.data_ptr()), size, _byte_ptr(out),
+                                                                  _stream(stream)))
+        return out
+
+    def process_database(self, context, dimensions, entry_size_in_bytes=None, stream=None):
+        """he_keyword_pir_process_database_device with a BfvContext / BfvContext32 -> (database [table_count][chunks][
+        prod(dims)][L][N] Eval in the context's words, present uint8 [table_count][chunks][prod(dims)])."""
+        import torch
+
+        size = self.largest_bucket_size if entry_size_in_bytes is None else int(entry_size_in_bytes)
+        shape = context.pir_database_shape(dimensions, self.buckets_per_table, size, False)
+        chunks, per_chunk = shape["chunk_count"], shape["plaintexts_per_chunk"]
+        tables = self.table_count
+        database = _empty((tables, chunks, per_chunk, context.L, context.degree), context._word, self.values.device)
+        present = torch.empty((tables, chunks, per_chunk), dtype=torch.uint8, device=self.values.device)
+        dims = (c_u32 * len(dimensions))(*[int(d) for d in dimensions])
+        _check(load_library().he_keyword_pir_process_database_device(
+            context.h, self.h, vp(self.values.data_ptr()), dims, len(dimensions), size, _ptr(database, context._word),
+            vp(present.data_ptr()), _stream(stream)))
+        return database, present
 
 
 def _no_stream():
