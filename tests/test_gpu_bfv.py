@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import heamd
+import word32_cases
 from bfv_helpers import BfvClient, negacyclic_multiply
 
 pytestmark = pytest.mark.gpu
@@ -1035,3 +1036,56 @@ def test_pipelines_on_moduli_at_the_edge_of_the_shift_folded_products(oracle, mo
         key = _uniform(rng, (ours.L, 2), ref.key_switching_context().moduli, degree)
         got = heamd.to_host(ours.relinearize(heamd.to_device(product), heamd.to_device(key), L))
         assert np.array_equal(got, ref.relinearize(product, key, L, threads=host_threads())), q
+
+
+@pytest.mark.parametrize("past_the_threshold", [False, True], ids=["three_ciphertexts", "finish_in_the_store"])
+@pytest.mark.parametrize("name", [s[0] for s in word32_cases.MANY_MODULI_SETS])
+def test_many_moduli_at_a_tiled_degree(oracle, name, past_the_threshold):
+    """ct x ct, relinearize and applyGalois (elements 3 and 2N - 1) at N = 4096 -- where the key-switching spread, the tensor
+    product and the key inner product ride the transforms' loads -- with as many ciphertext moduli as each term-count decision
+    of those loads turns on (test_more_than_eight_ciphertext_moduli runs 9 .. 16 moduli at N = 64, which has no such loads):
+
+      4-byte words  14 x 30 bits   the most the reference admits (Context.swift:122-124); the key inner product is L products
+                                   below 2^60 in one 64-bit word, 14 (p - 1)^2 = 0xE0... at most
+                                   (word32_kernels.hip launch_ntt32_key_mac_inverse: "if (L > 15) return hipErrorNotSupported")
+                    16 x 26 bits   L > 15: launch_key_switch_mac<uint32_t> and a separate inverse transform
+      8-byte words   8 x 60 bits   ntt_kernels.hip: "mod.wide_shift != 0 && L <= 8 && uint64_t(L) * mod.p < (uint64_t(1) << 63)"
+                                   -- the one-word-quotient reduction with the most and the widest terms it takes
+                     9 x 55 bits   L = 9: the general reduction
+                     4 x 61 bits,  L p on either side of 2^63 (4 p < 2^63 for every p < 2^61; word32_cases.py says why these
+                     5 x 61 bits   are the largest 61-bit primes and not the smallest)
+                    16 x 50 bits   the widest band the BEHZ kernels are specialised for
+
+    each on three ciphertexts and on the smallest batch whose key switch ends in the transform's store: polys * 2 * (L + 1)
+    above 2048 rows on 4-byte words (launch_ntt32_key_mac_inverse_finish: "polys * 2 * (L + 1) <= 2048" is refused; so is
+    "L > 15", hence the 16 x 26-bit batch ends in key_switch_finish_kernel at any size) and above 2 * kOneGeneration = 1024 on
+    8-byte words (ntt_key_mac_finish_supported: "polys * 2 * (L + 1) > 2 * kOneGeneration", ntt_rows.hpp kOneGeneration = 512)
+    -- 69 ciphertexts for the first set, 57 for the third.  Ciphertext 0 and key block 0 hold modulus - 1 in every residue,
+    ciphertext 1 is zero, the rest is uniform.  Word for word against the oracle; applyGalois of the large batch runs whole on
+    the device and is compared on nine ciphertexts spread over it (the oracle's applyGalois is single-threaded)."""
+    from conftest import host_threads
+
+    degree = word32_cases.MANY_MODULI_DEGREE
+    word_bits, t, q = word32_cases.many_moduli_set(oracle, name)
+    narrow = word_bits == 32
+    ours = (heamd.BfvContext32 if narrow else heamd.BfvContext)(degree, t, q)
+    ref = oracle.BfvContext(degree, t, q, word_bits=word_bits)
+    up, down = (heamd.to_device32, heamd.to_host32) if narrow else (heamd.to_device, heamd.to_host)
+    L, moduli = ref.L, q[:-1]
+    assert ours.L == L == len(q) - 1
+    batch = word32_cases.batch_above_finish_threshold(word_bits, L) if past_the_threshold else 3
+    threshold = word32_cases.FINISH_IN_STORE_ROWS[word_bits]
+    assert (batch * 2 * (L + 1) > threshold) == past_the_threshold and (batch - 1) * 2 * (L + 1) <= threshold
+    rng = np.random.default_rng(L * 1000 + batch)
+    lhs = word32_cases.many_moduli_slab(rng, (batch, 2), moduli)
+    rhs = word32_cases.many_moduli_slab(rng, (batch, 2), moduli)
+    assert np.array_equal(down(ours.mul(up(lhs), up(rhs))), ref.mul(lhs, rhs, threads=host_threads()))
+    ct3 = word32_cases.many_moduli_slab(rng, (batch, 3), moduli)
+    key = word32_cases.many_moduli_slab(rng, (L, 2), q, zero_second=False)
+    device_key = up(key)
+    assert np.array_equal(down(ours.relinearize(up(ct3), device_key)), ref.relinearize(ct3, key, threads=host_threads()))
+    sample = sorted({0, 1, batch - 1} | set(np.linspace(0, batch - 1, 8).astype(int).tolist()))
+    sampled = np.ascontiguousarray(lhs[sample])
+    for element in (3, 2 * degree - 1):
+        rotated = down(ours.apply_galois(up(lhs), element, device_key))
+        assert np.array_equal(rotated[sample], ref.apply_galois(sampled, element, key)), element
