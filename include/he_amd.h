@@ -66,7 +66,8 @@ enum he_status {
     HE_ERR_INVALID_HASH_BUCKET_ENTRY_VALUE_SIZE = 27,  /* invalidHashBucketEntryValueSize KeywordPir/HashBucket.swift:91-93 */
     HE_ERR_INVALID_HASH_BUCKET_SLOT_COUNT = 28,        /* invalidHashBucketSlotCount    KeywordPir/HashBucket.swift:146-148,178-181 */
     /* not an error of the reference: he_keyword_pir_cuckoo_place asks for the larger table CuckooTable.expand() would build */
-    HE_ERR_CUCKOO_TABLE_NEEDS_EXPANSION = 29           /*                               KeywordPir/CuckooTable.swift:466-474 */
+    HE_ERR_CUCKOO_TABLE_NEEDS_EXPANSION = 29,          /*                               KeywordPir/CuckooTable.swift:466-474 */
+    HE_ERR_INVALID_SHARDING = 30                       /* invalidSharding               KeywordPir/KeywordDatabase.swift:186-204 */
 };
 
 typedef struct he_poly_context he_poly_context; /* PolyContext<UInt64>   PolyRq/PolyContext.swift:19-35 */
@@ -794,6 +795,90 @@ int he_keyword_pir_table_entries_device(const he_keyword_pir_table* table, const
 int he_keyword_pir_process_database_device(const he_bfv_context* ctx, const he_keyword_pir_table* table, const uint8_t* values,
                                            const uint32_t* dimensions, uint32_t dimension_count, size_t entry_size_in_bytes,
                                            void* database, uint8_t* present, he_stream s);
+
+/* ---- sharded keyword database: KeywordDatabase.init(rows:sharding:shardingFunction:) (KeywordDatabase.swift:406-437) -------
+ * PIRProcessDatabase hashes every keyword, takes its shard index and splits the rows into one KeywordDatabaseShard per index;
+ * each shard then becomes a cuckoo table (above).  Here the rows are split on the device: a stable counting sort of the rows
+ * by shard index and a gather of both byte blobs into the new order, so that the bytes that crossed PCIe once stay where
+ * they are until every shard's Eval database is built. */
+
+/* Sharding (KeywordDatabase.swift:152-242).  by_entry_count zero: .shardCount(value); nonzero: .entryCountPerShard(value).
+ * has_max_shard_count zero: maxShardCount == nil.  require_power_of_two: nil and false behave alike in the reference. */
+typedef struct he_keyword_sharding {
+    int by_entry_count;
+    uint64_t value;
+    int has_max_shard_count;
+    uint64_t max_shard_count;
+    int require_power_of_two;
+} he_keyword_sharding;
+/* Sharding.init's checks (:186-204) and shardCount(for:) (:252-267): the flooring divide, max(.., 1), the cap and
+ * previousPowerOfTwo.  Every invalidSharding case is HE_ERR_INVALID_SHARDING.  One difference from the reference: with
+ * .entryCountPerShard and maxShardCount == 0 the reference resolves to 0 shards and would divide by zero in shardIndex; here
+ * that is HE_ERR_INVALID_SHARDING.  NULL: HE_ERR_INVALID_ARGUMENT.  Host. */
+int he_keyword_sharding_shard_count(const he_keyword_sharding* sharding, size_t row_count, size_t* out);
+
+/* The partition.  All pointers DEVICE, any byte address for the four blobs; empty keywords and values are legal.
+ *   keywords / values with keyword_offsets / value_offsets uint64 [count + 1], non-decreasing, as above; keyword_bytes /
+ *   value_bytes = offsets[count] - offsets[0]: the sizes of out_keywords / out_values, which the caller has allocated
+ *   shard_indices uint32 [count] (he_keyword_pir_shard_indices_device), shard_count in 1 .. 2^32 - 1
+ *   out_order uint32 [count]: row j of the output is input row out_order[j]
+ *   out_shard_starts uint32 [shard_count + 1]: shard s owns output rows out_shard_starts[s] .. out_shard_starts[s + 1], in
+ *   input order (the reference iterates a Dictionary and defines no order; input order makes every table downstream
+ *   reproducible).  shard_count 1 is the identity.
+ *   out_keywords / out_values: the rows back to back in the new order; out_keyword_offsets / out_value_offsets uint64
+ *   [count + 1]: their running sums, starting at 0.
+ * Exactly the bytes of the six outputs are written and only bytes of the named inputs are read.  count up to 2^32 - 2.
+ * device_mismatch (optional, a DEVICE word the caller has zeroed): bit 0 when an index is >= shard_count (the row goes to the
+ * last shard), bit 1 when a blob's offsets do not span keyword_bytes / value_bytes (the bytes both agree on are written).
+ * Nothing is written out of bounds either way.
+ * The order comes from least-significant-digit passes of 8 bits over the order array alone (none for one shard, one up to
+ * 256 shards); no blob byte moves before the order is final.  Enqueue-only; the second order array, the digit counts, the
+ * scans' sums and the row every 512 output bytes start in are stream-ordered scratch.  he_keyword_database_partition_plan says
+ * what a call runs. */
+int he_keyword_database_partition_device(const uint8_t* keywords, const uint64_t* keyword_offsets, size_t keyword_bytes,
+                                         const uint8_t* values, const uint64_t* value_offsets, size_t value_bytes,
+                                         size_t count, const uint32_t* shard_indices, size_t shard_count,
+                                         uint8_t* out_keywords, uint64_t* out_keyword_offsets, uint8_t* out_values,
+                                         uint64_t* out_value_offsets, uint32_t* out_order, uint32_t* out_shard_starts,
+                                         uint32_t* device_mismatch, he_stream s);
+/* What he_keyword_database_partition_device runs for a shape.  Host only; any out pointer may be NULL.
+ *   out_digit_passes: ceil(bits(shard_count - 1) / 8), 0 for one shard or no row
+ *   out_workgroups_per_pass = ceil(count / out_rows_per_workgroup); out_last_workgroup_rows: the rows of the last one
+ *   out_keyword_gather_form / out_value_gather_form: HE_KEYWORD_GATHER_NONE (no byte to move) or HE_KEYWORD_GATHER_CHUNK (a
+ *   lane owns an aligned 8-byte chunk of the output blob) */
+#define HE_KEYWORD_GATHER_NONE 0u
+#define HE_KEYWORD_GATHER_CHUNK 1u
+int he_keyword_database_partition_plan(size_t count, size_t shard_count, size_t keyword_bytes, size_t value_bytes,
+                                       uint32_t* out_digit_passes, size_t* out_workgroups_per_pass,
+                                       uint32_t* out_rows_per_workgroup, size_t* out_last_workgroup_rows,
+                                       uint32_t* out_keyword_gather_form, uint32_t* out_value_gather_form);
+
+/* The object: KeywordDatabase on the device.
+ *   keywords DEVICE, keyword_offsets HOST [count + 1]; values DEVICE, value_offsets HOST [count + 1]: as the table object
+ * The offsets are uploaded, the keywords hashed once, the shard indices derived (other_shard_count nonzero: doubleMod), the
+ * rows partitioned, and one cuckoo table built per shard that received a row, over the partitioned blobs, which the object
+ * owns; the input blobs are not referenced after the call returns.  Shard s's table is, field for field, the table
+ * he_keyword_pir_table_create_device builds from that shard's rows in input order with seed + s (mod 2^64); its hashes are
+ * gathered through the order, not computed again.  A shard without a row has no table (NULL, row count 0), as the reference
+ * has no such shard (:423).  shard_table(s) and shard_values(s) are the `table` and `values` arguments of
+ * he_keyword_pir_table_entries_device and he_keyword_pir_process_database_device.
+ * One difference from the reference: it throws invalidDatabaseDuplicateKeyword here (:423-433); this library resolves
+ * duplicates in the table by 64-bit hash with the first one winning (difference 1 above).  Equal keywords land in the same
+ * shard, so nothing changes, and the shard table's duplicates_dropped is the report.
+ * The call synchronises the stream.  Errors as he_keyword_pir_table_create_device; shard_count outside 1 .. 2^32 - 1:
+ * HE_ERR_INVALID_ARGUMENT.  Destroy with he_keyword_database_destroy (NULL is fine). */
+typedef struct he_keyword_database he_keyword_database;
+int he_keyword_database_create_device(const he_cuckoo_table_config* config, const uint8_t* keywords,
+                                      const uint64_t* keyword_offsets, const uint8_t* values,
+                                      const uint64_t* value_offsets, size_t count, size_t shard_count,
+                                      uint64_t other_shard_count, uint64_t seed, he_keyword_database** out, he_stream s);
+void he_keyword_database_destroy(he_keyword_database* database);
+size_t he_keyword_database_shard_count(const he_keyword_database* database);
+size_t he_keyword_database_shard_row_count(const he_keyword_database* database, size_t shard);
+const he_keyword_pir_table* he_keyword_database_shard_table(const he_keyword_database* database, size_t shard);
+const uint8_t* he_keyword_database_shard_values(const he_keyword_database* database, size_t shard);
+/* out_host HOST uint32 [count]: shard after shard, the input rows each holds */
+int he_keyword_database_order(const he_keyword_database* database, uint32_t* out_host);
 
 /* ---- processed-database files: ProcessedDatabase.serialize() / init(from:context:) ----------------------
  * The file PIRProcessDatabase writes and every index- and keyword-PIR server loads (PrivateInformationRetrieval/IndexPir/

@@ -393,6 +393,7 @@ const char* he_status_string(int status) {
         case HE_ERR_INVALID_HASH_BUCKET_ENTRY_VALUE_SIZE: return "invalidHashBucketEntryValueSize";
         case HE_ERR_INVALID_HASH_BUCKET_SLOT_COUNT: return "invalidHashBucketSlotCount";
         case HE_ERR_CUCKOO_TABLE_NEEDS_EXPANSION: return "cuckooTableNeedsExpansion";
+        case HE_ERR_INVALID_SHARDING: return "invalidSharding";
         default: return "unknown";
     }
 }

@@ -7,6 +7,7 @@
 #include "api_internal.hpp"
 #include "bfv_context.hpp"
 #include "keyword_pir.hpp"
+#include "keyword_shard.hpp"
 
 using heamd::as_stream;
 using heamd::invalid_argument;
@@ -182,10 +183,40 @@ extern "C" int he_keyword_pir_table_create_device(const he_cuckoo_table_config* 
         heamd::set_last_error("more than 8 hash functions are not supported");
         return HE_ERR_UNSUPPORTED;
     }
-    std::vector<uint64_t> sizes(count);
     for (size_t i = 0; i < count; ++i) {
         if (keyword_offsets[i + 1] < keyword_offsets[i] || value_offsets[i + 1] < value_offsets[i])
             return invalid_argument("offsets decrease");
+        if (value_offsets[i + 1] - value_offsets[i] > 0xffff) {
+            heamd::set_last_error("Invalid hash bucket entry value size: maximum 65535");
+            return HE_ERR_INVALID_HASH_BUCKET_ENTRY_VALUE_SIZE;
+        }
+    }
+    size_t bucket_count = 0;
+    {  // the bucket count's errors return here, before a copy out of the borrowed keyword_offsets is in flight
+        std::vector<uint64_t> sizes(count);
+        for (size_t i = 0; i < count; ++i) sizes[i] = value_offsets[i + 1] - value_offsets[i];
+        const int counted = he_keyword_pir_bucket_count(config, sizes.data(), count, &bucket_count);
+        if (counted != HE_OK) return counted;
+        if (bucket_count > kMaxCount) return invalid_argument("more than 2^32 - 1 buckets");
+    }
+    hipStream_t stream = as_stream(s);
+    Scratch hashes_mem(stream), offsets_mem(stream);
+    HEAMD_HIP_TRY(hashes_mem.allocate(count * sizeof(uint64_t)));
+    HEAMD_HIP_TRY(offsets_mem.allocate((count + 1) * sizeof(uint64_t)));
+    uint64_t* hashes_device = static_cast<uint64_t*>(hashes_mem.get());
+    HEAMD_HIP_TRY(hipMemcpyAsync(offsets_mem.get(), keyword_offsets, (count + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    HEAMD_HIP_TRY(heamd::launch_keyword_hash(keywords, static_cast<const uint64_t*>(offsets_mem.get()), count, hashes_device, stream));
+    // (the call below synchronises the stream before it returns: keyword_offsets is a borrowed pageable host buffer)
+    return heamd::keyword_pir_table_from_hashes(config, hashes_device, value_offsets, count, seed, out_table, stream);
+}
+
+// The table behind its hashing (keyword_shard.hpp): the sharded database builds one per shard from hashes it has gathered.
+int heamd::keyword_pir_table_from_hashes(const he_cuckoo_table_config* config, const uint64_t* hashes_device,
+                                         const uint64_t* value_offsets, size_t count, uint64_t seed,
+                                         he_keyword_pir_table** out_table, hipStream_t stream) {
+    std::vector<uint64_t> sizes(count);
+    for (size_t i = 0; i < count; ++i) {
+        if (value_offsets[i + 1] < value_offsets[i]) return invalid_argument("offsets decrease");
         sizes[i] = value_offsets[i + 1] - value_offsets[i];
         if (sizes[i] > 0xffff) {
             heamd::set_last_error("Invalid hash bucket entry value size: maximum 65535");
@@ -197,18 +228,12 @@ extern "C" int he_keyword_pir_table_create_device(const he_cuckoo_table_config* 
     if (counted != HE_OK) return counted;
     if (bucket_count > kMaxCount) return invalid_argument("more than 2^32 - 1 buckets");
 
-    hipStream_t stream = as_stream(s);
     const uint32_t h = config->hash_function_count;
     const size_t tables = config->multiple_tables ? h : 1;
     std::vector<uint64_t> hashes(count);
     std::vector<uint32_t> indices(count * h), bucket_offsets, slot_entries(count);
-    Scratch hashes_mem(stream), offsets_mem(stream), indices_mem(stream);
-    HEAMD_HIP_TRY(hashes_mem.allocate(count * sizeof(uint64_t)));
-    HEAMD_HIP_TRY(offsets_mem.allocate((count + 1) * sizeof(uint64_t)));
+    Scratch indices_mem(stream);
     HEAMD_HIP_TRY(indices_mem.allocate(count * h * sizeof(uint32_t)));
-    uint64_t* hashes_device = static_cast<uint64_t*>(hashes_mem.get());
-    HEAMD_HIP_TRY(hipMemcpyAsync(offsets_mem.get(), keyword_offsets, (count + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    HEAMD_HIP_TRY(heamd::launch_keyword_hash(keywords, static_cast<const uint64_t*>(offsets_mem.get()), count, hashes_device, stream));
     if (count != 0)
         HEAMD_HIP_TRY(hipMemcpyAsync(hashes.data(), hashes_device, count * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     size_t placed = 0, duplicates = 0, expansions = 0;

@@ -13,7 +13,9 @@ from .binding import (  # noqa: F401
     CuckooTableConfig,
     DeviceGroup,
     HeError,
+    KeywordPirShardedDatabase,
     KeywordPirTable,
+    KeywordSharding,
     PnnsContext,
     PolyContext,
     SimplePirServer,
@@ -27,7 +29,10 @@ from .binding import (  # noqa: F401
     keyword_pir_cuckoo_place,
     keyword_pir_hash_indices,
     keyword_pir_hash_keywords,
+    keyword_pir_partition,
+    keyword_pir_partition_plan,
     keyword_pir_serialize_buckets,
+    keyword_pir_shard_count,
     keyword_pir_shard_indices,
     library_path,
     load_library,

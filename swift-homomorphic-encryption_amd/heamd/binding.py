@@ -40,7 +40,7 @@ STATUS_NAMES = {
     20: "serializedBufferSizeMismatch", 21: "invalidCoefficientPacking", 22: "simdEncodingNotSupported",
     23: "invalidDatabaseSerializationVersion", 24: "invalidDatabaseSerializationPlaintextTag",
     25: "failedToConstructCuckooTable", 26: "invalidCuckooConfig", 27: "invalidHashBucketEntryValueSize",
-    28: "invalidHashBucketSlotCount", 29: "cuckooTableNeedsExpansion",
+    28: "invalidHashBucketSlotCount", 29: "cuckooTableNeedsExpansion", 30: "invalidSharding",
 }
 
 
@@ -229,6 +229,20 @@ SIGNATURES = [
     ("he_keyword_pir_table_load_factor", ctypes.c_float, [vp]),
     ("he_keyword_pir_table_entries_device", ctypes.c_int, [vp, vp, c_size, vp, vp]),
     ("he_keyword_pir_process_database_device", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(c_u32), c_u32, c_size, vp, vp, vp]),
+    ("he_keyword_sharding_shard_count", ctypes.c_int, [vp, c_size, ctypes.POINTER(c_size)]),
+    ("he_keyword_database_partition_device", ctypes.c_int,
+     [vp, vp, c_size, vp, vp, c_size, c_size, vp, c_size, vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("he_keyword_database_partition_plan", ctypes.c_int,
+     [c_size, c_size, c_size, c_size, ctypes.POINTER(c_u32), ctypes.POINTER(c_size), ctypes.POINTER(c_u32),
+      ctypes.POINTER(c_size), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    ("he_keyword_database_create_device", ctypes.c_int,
+     [vp, vp, U64P, vp, U64P, c_size, c_size, c_u64, c_u64, ctypes.POINTER(vp), vp]),
+    ("he_keyword_database_destroy", None, [vp]),
+    ("he_keyword_database_shard_count", c_size, [vp]),
+    ("he_keyword_database_shard_row_count", c_size, [vp, c_size]),
+    ("he_keyword_database_shard_table", vp, [vp, c_size]),
+    ("he_keyword_database_shard_values", vp, [vp, c_size]),
+    ("he_keyword_database_order", ctypes.c_int, [vp, ctypes.POINTER(c_u32)]),
     ("he_simple_pir_shape", ctypes.c_int,
      [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
       ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_u64), ctypes.POINTER(c_u32)]),
@@ -1949,6 +1963,159 @@ class KeywordPirTable:
             context.h, self.h, vp(self.values.data_ptr()), dims, len(dimensions), size, _ptr(database, context._word),
             vp(present.data_ptr()), _stream(stream)))
         return database, present
+
+
+# ---- sharded keyword database: Sharding, KeywordDatabase.init ----
+class KeywordSharding(ctypes.Structure):
+    """he_keyword_sharding: Sharding (KeywordPir/KeywordDatabase.swift:152-242); give shard_count or entry_count_per_shard."""
+
+    _fields_ = [("by_entry_count", ctypes.c_int), ("value", c_u64), ("has_max_shard_count", ctypes.c_int),
+                ("max_shard_count", c_u64), ("require_power_of_two", ctypes.c_int)]
+
+    def __init__(self, shard_count=None, entry_count_per_shard=None, max_shard_count=None, require_power_of_two=False):
+        if (shard_count is None) == (entry_count_per_shard is None):
+            raise ValueError("give shard_count or entry_count_per_shard")
+        value = shard_count if entry_count_per_shard is None else entry_count_per_shard
+        super().__init__(int(entry_count_per_shard is not None), int(value), int(max_shard_count is not None),
+                         int(max_shard_count or 0), int(bool(require_power_of_two)))
+
+
+def keyword_pir_shard_count(sharding, row_count):
+    """he_keyword_sharding_shard_count: Sharding.init's checks and shardCount(for:).  Host only."""
+    out = c_size(0)
+    _check(load_library().he_keyword_sharding_shard_count(ctypes.byref(sharding), int(row_count), ctypes.byref(out)))
+    return out.value
+
+
+KEYWORD_GATHER_FORMS = {0: "none", 1: "chunk"}
+
+
+def keyword_pir_partition_plan(count, shard_count, keyword_bytes, value_bytes):
+    """he_keyword_database_partition_plan: what keyword_pir_partition runs for a shape.  Host only."""
+    passes, tile, key_form, value_form = c_u32(0), c_u32(0), c_u32(0), c_u32(0)
+    workgroups, last = c_size(0), c_size(0)
+    _check(load_library().he_keyword_database_partition_plan(
+        int(count), int(shard_count), int(keyword_bytes), int(value_bytes), ctypes.byref(passes), ctypes.byref(workgroups),
+        ctypes.byref(tile), ctypes.byref(last), ctypes.byref(key_form), ctypes.byref(value_form)))
+    return {"digit_passes": passes.value, "workgroups_per_pass": workgroups.value, "rows_per_workgroup": tile.value,
+            "last_workgroup_rows": last.value, "keyword_gather_form": KEYWORD_GATHER_FORMS[key_form.value],
+            "value_gather_form": KEYWORD_GATHER_FORMS[value_form.value]}
+
+
+def keyword_pir_partition(keywords, keyword_offsets, values, value_offsets, shard_indices, shard_count, mismatch=None,
+                          stream=None):
+    """he_keyword_database_partition_device: the rows of a database in shard order (device tensors: the blobs uint8, the offsets
+    int64 [count + 1], shard_indices int32 [count]) -> dict(keywords, keyword_offsets, values, value_offsets, order int32
+    [count], shard_starts int32 [shard_count + 1]).  The blobs' sizes are the tensors'."""
+    import torch
+
+    count = shard_indices.numel()
+    if keyword_offsets.numel() != count + 1 or value_offsets.numel() != count + 1:
+        raise ValueError("count + 1 offsets per blob")
+    device = shard_indices.device
+    out = {"keywords": torch.empty_like(keywords), "keyword_offsets": torch.empty((count + 1,), dtype=torch.int64, device=device),
+           "values": torch.empty_like(values), "value_offsets": torch.empty((count + 1,), dtype=torch.int64, device=device),
+           "order": torch.empty((count,), dtype=torch.int32, device=device),
+           "shard_starts": torch.empty((int(shard_count) + 1,), dtype=torch.int32, device=device)}
+    _check(load_library().he_keyword_database_partition_device(
+        _byte_ptr(keywords), _ptr(keyword_offsets), keywords.numel(), _byte_ptr(values), _ptr(value_offsets), values.numel(),
+        count, _ptr(shard_indices, WORD32), int(shard_count), _byte_ptr(out["keywords"]), _ptr(out["keyword_offsets"]),
+        _byte_ptr(out["values"]), _ptr(out["value_offsets"]), _ptr(out["order"], WORD32), _ptr(out["shard_starts"], WORD32),
+        _opt_ptr(mismatch, WORD32), _stream(stream)))
+    return out
+
+
+class _BorrowedBytes:
+    """device bytes another object owns, as torch reads them (__cuda_array_interface__)"""
+
+    def __init__(self, address, nbytes, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (address, False), "version": 2}
+
+
+class KeywordPirShardTable(KeywordPirTable):
+    """The table of one shard of a KeywordPirShardedDatabase: every query and method of KeywordPirTable over a handle the
+    database owns."""
+
+    def __init__(self, handle, values, config, database):
+        self.h, self.values, self.config, self.database = handle, values, config, database
+
+    def __del__(self):
+        self.h = None  # the database destroys its tables
+
+
+class KeywordPirShardedDatabase:
+    """he_keyword_database: KeywordDatabase.init(rows:sharding:shardingFunction:) on the device
+    (KeywordPir/KeywordDatabase.swift:406-437) -- hash, shard, partition, one cuckoo table per shard that received a row.
+
+    keywords / values: lists of bytes-like items; shard_count: a count or a KeywordSharding; other_shard_count: doubleMod.
+    shards() yields (KeywordPirShardTable or None, the shard's values as a uint8 tensor into the object's blob)."""
+
+    def __init__(self, config, keywords, values, shard_count, other_shard_count=0, seed=0, device="cuda", stream=None):
+        if len(keywords) != len(values):
+            raise ValueError("one value per keyword")
+        if isinstance(shard_count, KeywordSharding):
+            shard_count = keyword_pir_shard_count(shard_count, len(keywords))
+        self.config, self.device = config, device
+        keyword_blob, keyword_offsets = _blob(keywords, device)
+        value_blob, value_offsets = _blob(values, device)
+        handle = vp()
+        _check(load_library().he_keyword_database_create_device(
+            ctypes.byref(config), vp(keyword_blob.data_ptr()), keyword_offsets.ctypes.data_as(U64P), vp(value_blob.data_ptr()),
+            value_offsets.ctypes.data_as(U64P), len(keywords), int(shard_count), int(other_shard_count),
+            int(seed) & (2**64 - 1), ctypes.byref(handle), _stream(stream)))
+        self.h = handle
+        self._value_sizes = np.diff(value_offsets.astype(np.int64))
+        self._bounds = None
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            load_library().he_keyword_database_destroy(self.h)
+            self.h = None
+
+    @property
+    def shard_count(self):
+        return load_library().he_keyword_database_shard_count(self.h)
+
+    def shard_row_count(self, shard):
+        return load_library().he_keyword_database_shard_row_count(self.h, int(shard))
+
+    def order(self):
+        """he_keyword_database_order -> uint32 array [count]: shard after shard, the input rows each holds"""
+        out = np.zeros(len(self._value_sizes), dtype=np.uint32)
+        _check(load_library().he_keyword_database_order(self.h, out.ctypes.data_as(ctypes.POINTER(c_u32))))
+        return out
+
+    def _shard_bytes(self):
+        """(first row, first value byte) of every shard and of the end, from the order and the row counts, once"""
+        if self._bounds is None:
+            rows = np.array([self.shard_row_count(s) for s in range(self.shard_count)], dtype=np.int64)
+            starts = np.concatenate(([0], np.cumsum(rows)))
+            running = np.concatenate(([0], np.cumsum(self._value_sizes[self.order()])))
+            self._bounds = starts, running[starts]
+        return self._bounds
+
+    def shard(self, shard):
+        """(KeywordPirShardTable, values tensor) of one shard, or (None, an empty tensor) where it received no row"""
+        import torch
+
+        lib = load_library()
+        shard = int(shard)
+        table = lib.he_keyword_database_shard_table(self.h, shard)
+        if not table:
+            return None, torch.empty((0,), dtype=torch.uint8, device=self.device)
+        _, byte_starts = self._shard_bytes()
+        nbytes = int(byte_starts[shard + 1] - byte_starts[shard])
+        if nbytes == 0:
+            values = torch.empty((0,), dtype=torch.uint8, device=self.device)
+        else:
+            address = lib.he_keyword_database_shard_values(self.h, shard)
+            values = torch.as_tensor(_BorrowedBytes(address, nbytes, self), device=self.device)
+        return KeywordPirShardTable(vp(table), values, self.config, self), values
+
+    def shards(self):
+        for shard in range(self.shard_count):
+            yield self.shard(shard)
 
 
 def _no_stream():
