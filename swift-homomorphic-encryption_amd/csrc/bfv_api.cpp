@@ -16,6 +16,7 @@
 using heamd::as_stream;
 using heamd::BfvContext;
 using heamd::DeviceContext;
+using heamd::DeviceImage;
 using heamd::invalid_argument;
 using heamd::PolyContext;
 using heamd::RnsToolLevel;
@@ -110,32 +111,22 @@ int drop_extended_base(const RnsToolLevel& tool, W* eval_qbsk, W* out, size_t po
     return HE_OK;
 }
 
+// The five helpers below try a transform with the step before or after it fused into its load or store, and on
+// hipErrorNotSupported (nothing launched) run the unfused kernels.  Each takes its image from word_image and hands on the
+// status it gave; through the C ABI none but HE_OK is reached there: context creation has validated the moduli, and check_level
+// the device and the word size.
+
 // tensor product (Bfv+Multiply.swift:80-82) and dropExtendedBase's inverse NTT: one kernel where the degree has a tiled
-// 8-byte transform (the products are formed as the inverse transform loads its row), two launches otherwise
-int tensor_and_inverse(const RnsToolLevel& tool, uint64_t* lifted, uint64_t* tensor, size_t batch, hipStream_t stream,
-                       bool* in_coeff_form) {
+// transform (the products are formed as the inverse transform loads its row), else the tensor product alone
+template <typename W>
+int tensor_and_inverse(const RnsToolLevel& tool, W* lifted, W* tensor, size_t batch, hipStream_t stream, bool* in_coeff_form) {
     DeviceContext scaled = tool.qbsk->device_context();
-    scaled.moduli = tool.qbsk_moduli_scaled_by_t;
+    scaled.moduli = tool.qbsk_moduli_scaled_by_t;  // folds the multiplication by t into N^-1
     scaled.scaled_inverse_degree = 1;
     const uint32_t rows = tool.qbsk->moduli_count();
-    hipError_t fused = heamd::launch_ntt_tensor_inverse(lifted, tensor, scaled, rows, batch, stream);
-    if (fused == hipErrorNotSupported) {
-        (void)hipGetLastError();
-        HEAMD_HIP_TRY(heamd::launch_tensor(lifted, tensor, tool.qbsk->device_context(), batch, stream));
-        *in_coeff_form = false;
-        return HE_OK;
-    }
-    HEAMD_HIP_TRY(fused);
-    *in_coeff_form = true;
-    return HE_OK;
-}
-int tensor_and_inverse(const RnsToolLevel& tool, uint32_t* lifted, uint32_t* tensor, size_t batch, hipStream_t stream,
-                       bool* in_coeff_form) {
-    const uint32_t rows = tool.qbsk->moduli_count();
-    heamd::DeviceContext32 scaled{};
-    if (tool.qbsk->device_context32(rows, scaled) != HE_OK) return invalid_argument("no 4-byte image of the [Q, Bsk] context");
-    scaled.moduli = tool.qbsk_moduli_scaled_by_t;  // folds the multiplication by t into N^-1
-    hipError_t fused = heamd::launch_ntt32_tensor_inverse(lifted, tensor, scaled, rows, batch, stream);
+    DeviceImage<W> image{};
+    HEAMD_TRY_STATUS(heamd::word_image<W>(*tool.qbsk, scaled, rows, image));
+    const hipError_t fused = heamd::launch_ntt_tensor_inverse(lifted, tensor, image, rows, batch, stream);
     if (fused == hipErrorNotSupported) {
         (void)hipGetLastError();
         HEAMD_HIP_TRY(heamd::launch_tensor(lifted, tensor, tool.qbsk->device_context(), batch, stream));
@@ -151,28 +142,19 @@ int tensor_and_inverse(const RnsToolLevel& tool, uint32_t* lifted, uint32_t* ten
 // polynomials into lifted[item][0..3] (lhs -> slots 0, 1; rhs -> slots 2, 3), then forward NTT over [Q, Bsk].  Rows
 // [0, L) of a lifted polynomial are the input itself (RnsTool.swift:329-330): where the tiled transform can read them
 // from the ciphertexts, the lift does not write the copy.
-hipError_t lift_pairs_to_eval(const RnsToolLevel& tool, uint32_t L, size_t n, size_t ext, const uint64_t* lhs,
-                              const uint64_t* rhs, uint64_t* lifted, size_t items, hipStream_t stream) {
+template <typename W>
+int lift_pairs_to_eval(const RnsToolLevel& tool, uint32_t L, size_t n, size_t ext, const W* lhs, const W* rhs, W* lifted,
+                       size_t items, hipStream_t stream) {
     const DeviceContext qbsk = tool.qbsk->device_context();
     const uint32_t rows = 2 * L + 1;
-    const bool from_source = heamd::ntt_lifted_forward_supported(qbsk, rows, L, items * 4);
-    hipError_t e = heamd::launch_lift_pair_q_to_qbsk_strided(lhs, rhs, lifted, tool.device, items, 2, 2 * L * n, 4 * ext, 0, 2 * ext,
-                                                             stream, !from_source);
-    if (e != hipSuccess) return e;
-    if (from_source) return heamd::launch_ntt_lifted_forward(lifted, qbsk, rows, items * 4, lhs, rhs, 2 * L * n, L, stream);
-    return ntt_records(false, lifted, *tool.qbsk, qbsk, rows, items * 4, stream);
-}
-hipError_t lift_pairs_to_eval(const RnsToolLevel& tool, uint32_t L, size_t n, size_t ext, const uint32_t* lhs,
-                              const uint32_t* rhs, uint32_t* lifted, size_t items, hipStream_t stream) {
-    const uint32_t rows = 2 * L + 1;
-    heamd::DeviceContext32 qbsk32{};
-    if (tool.qbsk->device_context32(rows, qbsk32) != HE_OK) return hipErrorInvalidValue;
-    const bool from_source = heamd::ntt32_lifted_forward_supported(qbsk32) && items * 4 * rows <= (size_t(1) << 30);
-    hipError_t e = heamd::launch_lift_pair_q_to_qbsk_strided(lhs, rhs, lifted, tool.device, items, 2, 2 * L * n, 4 * ext, 0, 2 * ext,
-                                                             stream, !from_source);
-    if (e != hipSuccess) return e;
-    if (from_source) return heamd::launch_ntt32_lifted_forward(lifted, qbsk32, rows, items, lhs, rhs, 2 * L * n, L, stream);
-    return ntt_records(false, lifted, *tool.qbsk, tool.qbsk->device_context(), rows, items * 4, stream);
+    DeviceImage<W> image{};
+    HEAMD_TRY_STATUS(heamd::word_image<W>(*tool.qbsk, qbsk, rows, image));
+    const bool from_source = heamd::ntt_lifted_forward_supported(image, rows, L, items * 4);
+    HEAMD_HIP_TRY(heamd::launch_lift_pair_q_to_qbsk_strided(lhs, rhs, lifted, tool.device, items, 2, 2 * L * n, 4 * ext, 0, 2 * ext,
+                                                            stream, !from_source));
+    if (from_source) HEAMD_HIP_TRY(heamd::launch_ntt_lifted_forward(lifted, image, rows, items * 4, lhs, rhs, 2 * L * n, L, stream));
+    else HEAMD_HIP_TRY(ntt_records(false, lifted, *tool.qbsk, qbsk, rows, items * 4, stream));
+    return HE_OK;
 }
 
 // multiplyWithoutScaling's transforms and tensor product and dropExtendedBase's inverse transforms row by row
@@ -275,7 +257,7 @@ int mul_pipeline(const he_bfv_context* ctx, const RnsToolLevel* tool, uint32_t L
             return HE_OK;
         }
     }
-    HEAMD_HIP_TRY(lift_pairs_to_eval(*tool, L, n, ext, lhs, rhs, lifted, batch, stream));
+    HEAMD_TRY_STATUS(lift_pairs_to_eval(*tool, L, n, ext, lhs, rhs, lifted, batch, stream));
     bool in_coeff_form = false;
     status = tensor_and_inverse(*tool, lifted, tensor, batch, stream, &in_coeff_form);
     if (status != HE_OK) return status;
@@ -285,71 +267,54 @@ int mul_pipeline(const he_bfv_context* ctx, const RnsToolLevel* tool, uint32_t L
 }
 
 // Bfv+Keys.swift:165-179: decompose the target over q_0..q_{L-1}, lift each piece to every key-switching modulus
-// and take it to Eval.  One fused kernel where the degree has a tiled 8-byte NTT, two launches otherwise.
-hipError_t spread_to_eval(const uint64_t* target, size_t target_stride, uint64_t* spread, const PolyContext& ks_ctx,
-                          uint32_t L, size_t polys, hipStream_t stream) {
+// and take it to Eval.  One fused kernel where the degree has a tiled NTT, two launches otherwise.
+template <typename W>
+int spread_to_eval(const W* target, size_t target_stride, W* spread, const PolyContext& ks_ctx, uint32_t L, size_t polys,
+                   hipStream_t stream) {
     const DeviceContext ks = ks_ctx.device_context();
-    hipError_t e = heamd::launch_ntt_spread(target, target_stride, L, polys, spread, ks, 0, stream);
-    if (e != hipErrorNotSupported) return e;
+    DeviceImage<W> image{};
+    HEAMD_TRY_STATUS(heamd::word_image<W>(ks_ctx, ks, L + 1, image));
+    const hipError_t fused = heamd::launch_ntt_spread(target, target_stride, L, polys, spread, image, 0, stream);
+    if (fused != hipErrorNotSupported) {
+        HEAMD_HIP_TRY(fused);
+        return HE_OK;
+    }
     (void)hipGetLastError();
-    e = heamd::launch_key_switch_spread(target, target_stride, spread, ks, L, polys, stream);
-    if (e != hipSuccess) return e;
-    return heamd::launch_ntt(false, spread, ks, 0, L + 1, polys * L * (L + 1), stream);
-}
-hipError_t spread_to_eval(const uint32_t* target, size_t target_stride, uint32_t* spread, const PolyContext& ks_ctx,
-                          uint32_t L, size_t polys, hipStream_t stream) {
-    const DeviceContext ks = ks_ctx.device_context();
-    heamd::DeviceContext32 ks32{};
-    if (ks_ctx.device_context32(L + 1, ks32) != HE_OK) return hipErrorInvalidValue;
-    hipError_t e = heamd::launch_ntt32_spread(target, target_stride, L, polys, spread, ks32, stream);
-    if (e != hipErrorNotSupported) return e;
-    (void)hipGetLastError();
-    e = heamd::launch_key_switch_spread(target, target_stride, spread, ks, L, polys, stream);
-    if (e != hipSuccess) return e;
-    return ntt_records(false, spread, ks_ctx, ks, L + 1, polys * L, stream);
+    HEAMD_HIP_TRY(heamd::launch_key_switch_spread(target, target_stride, spread, ks, L, polys, stream));
+    HEAMD_HIP_TRY(ntt_rows(false, spread, ks_ctx, ks, L + 1, polys * L * (L + 1), stream));
+    return HE_OK;
 }
 // Bfv+Keys.swift:180-207: the lazy inner product of the decomposed target with the key, then back to Coeff.  One
-// kernel where the degree has a tiled 8-byte NTT (the sums are formed as the inverse transform loads its row).
-hipError_t key_mac_to_coeff(const uint64_t* spread, const uint64_t* key, uint64_t* prod, const PolyContext& ks_ctx,
-                            uint32_t L, uint32_t top_rows, size_t polys, hipStream_t stream) {
+// kernel where the degree has a tiled NTT (the sums are formed as the inverse transform loads its row).
+template <typename W>
+int key_mac_to_coeff(const W* spread, const W* key, W* prod, const PolyContext& ks_ctx, uint32_t L, uint32_t top_rows,
+                     size_t polys, hipStream_t stream) {
     const DeviceContext ks = ks_ctx.device_context();
-    hipError_t e = heamd::launch_ntt_key_mac_inverse(spread, key, prod, ks, L, top_rows, polys, stream);
-    if (e != hipErrorNotSupported) return e;
+    DeviceImage<W> image{};
+    HEAMD_TRY_STATUS(heamd::word_image<W>(ks_ctx, ks, L + 1, image));
+    const hipError_t fused = heamd::launch_ntt_key_mac_inverse(spread, key, prod, image, L, top_rows, polys, stream);
+    if (fused != hipErrorNotSupported) {
+        HEAMD_HIP_TRY(fused);
+        return HE_OK;
+    }
     (void)hipGetLastError();
-    e = heamd::launch_key_switch_mac(spread, key, prod, ks, L, top_rows, polys, stream);
-    if (e != hipSuccess) return e;
-    return heamd::launch_ntt(true, prod, ks, 0, L + 1, polys * 2 * (L + 1), stream);
-}
-hipError_t key_mac_to_coeff(const uint32_t* spread, const uint32_t* key, uint32_t* prod, const PolyContext& ks_ctx,
-                            uint32_t L, uint32_t top_rows, size_t polys, hipStream_t stream) {
-    const DeviceContext ks = ks_ctx.device_context();
-    heamd::DeviceContext32 ks32{};
-    if (ks_ctx.device_context32(L + 1, ks32) != HE_OK) return hipErrorInvalidValue;
-    hipError_t e = heamd::launch_ntt32_key_mac_inverse(spread, key, prod, ks32, L, top_rows, polys, stream);
-    if (e != hipErrorNotSupported) return e;
-    (void)hipGetLastError();
-    e = heamd::launch_key_switch_mac(spread, key, prod, ks, L, top_rows, polys, stream);
-    if (e != hipSuccess) return e;
-    return ntt_records(true, prod, ks_ctx, ks, L + 1, polys * 2, stream);
+    HEAMD_HIP_TRY(heamd::launch_key_switch_mac(spread, key, prod, ks, L, top_rows, polys, stream));
+    HEAMD_HIP_TRY(ntt_rows(true, prod, ks_ctx, ks, L + 1, polys * 2 * (L + 1), stream));
+    return HE_OK;
 }
 
-// The inner product with the key, the inverse transforms and the key switch's last step (relinearize: added_polys = 2) in
-// two launches of one kernel where the degree has it (ntt_kernels.hip kInverseFromKeyMacFinish); hipErrorNotSupported
-// otherwise (nothing launched).
-hipError_t key_mac_and_finish(const uint64_t* spread, const uint64_t* key, uint64_t* prod, const uint64_t* ct_base,
-                              size_t ct_stride, uint64_t* out, const PolyContext& ks_ctx, uint32_t L, uint32_t top_rows,
-                              size_t polys, uint32_t added_polys, hipStream_t stream) {
-    const heamd::KeySwitchEnd end{ct_base, ct_stride, out, added_polys};
-    return heamd::launch_ntt_key_mac_inverse_finish(spread, key, prod, end, ks_ctx.device_context(), L, top_rows, polys,
-                                                    stream);
-}
-hipError_t key_mac_and_finish(const uint32_t* spread, const uint32_t* key, uint32_t* prod, const uint32_t* ct_base,
-                              size_t ct_stride, uint32_t* out, const PolyContext& ks_ctx, uint32_t L, uint32_t top_rows,
-                              size_t polys, uint32_t added_polys, hipStream_t stream) {
-    heamd::DeviceContext32 ks32{};
-    if (ks_ctx.device_context32(L + 1, ks32) != HE_OK) return hipErrorNotSupported;
-    return heamd::launch_ntt32_key_mac_inverse_finish(spread, key, prod, ct_base, ct_stride, out, ks32, L, top_rows, polys,
-                                                      added_polys, stream);
+// The inner product with the key, the inverse transforms and the key switch's last step (`end`: relinearize, added_polys = 2)
+// in two launches of one kernel where the degree and the batch have it (ntt_kernels.hip kInverseFromKeyMacFinish,
+// word32_kernels.hip kSource32KeyMacFinish); *finished = false otherwise (nothing launched).
+template <typename W>
+int key_mac_and_finish(const W* spread, const W* key, W* prod, const heamd::KeySwitchEnd<W>& end, const PolyContext& ks_ctx,
+                       uint32_t L, uint32_t top_rows, size_t polys, hipStream_t stream, bool* finished) {
+    DeviceImage<W> image{};
+    HEAMD_TRY_STATUS(heamd::word_image<W>(ks_ctx, ks_ctx.device_context(), L + 1, image));
+    const hipError_t fused = heamd::launch_ntt_key_mac_inverse_finish(spread, key, prod, end, image, L, top_rows, polys, stream);
+    *finished = fused != hipErrorNotSupported;
+    if (*finished) HEAMD_HIP_TRY(fused);
+    return HE_OK;
 }
 
 // _computeKeySwitchingUpdate (Bfv+Keys.swift:123-208) on polynomial `target` of every item, then
@@ -364,7 +329,7 @@ int key_switch_pipeline_grouped(const he_bfv_context* ctx, uint32_t L, const W* 
     const PolyContext* ks_ctx = ctx->impl->key_switching(L);
     const size_t n = ctx->impl->degree(), batch = groups * group_size;
     const uint32_t top_rows = ctx->impl->top_level() + 1;
-    HEAMD_HIP_TRY(spread_to_eval(target, target_stride, spread, *ks_ctx, L, batch, stream));
+    HEAMD_TRY_STATUS(spread_to_eval(target, target_stride, spread, *ks_ctx, L, batch, stream));
     auto finish = [&](size_t first, size_t end) {  // the last step for the items [first, end) left in Coeff form
         if (first == end) return hipSuccess;
         return heamd::launch_key_switch_finish(static_cast<const W*>(prod) + first * 2 * (L + 1) * n,
@@ -378,12 +343,12 @@ int key_switch_pipeline_grouped(const he_bfv_context* ctx, uint32_t L, const W* 
         const size_t first = g * group_size, polys = run * group_size;
         const W* run_spread = static_cast<const W*>(spread) + first * L * (L + 1) * n;
         W* run_prod = prod + first * 2 * (L + 1) * n;
-        const hipError_t fused = key_mac_and_finish(run_spread, keys[g], run_prod, ct_base + first * ct_stride, ct_stride,
-                                                    out + first * 2 * L * n, *ks_ctx, L, top_rows, polys, added_polys, stream);
-        if (fused == hipErrorNotSupported) {
-            HEAMD_HIP_TRY(key_mac_to_coeff(run_spread, keys[g], run_prod, *ks_ctx, L, top_rows, polys, stream));
+        const heamd::KeySwitchEnd<W> end{ct_base + first * ct_stride, ct_stride, out + first * 2 * L * n, added_polys};
+        bool finished = false;
+        HEAMD_TRY_STATUS(key_mac_and_finish(run_spread, keys[g], run_prod, end, *ks_ctx, L, top_rows, polys, stream, &finished));
+        if (!finished) {
+            HEAMD_TRY_STATUS(key_mac_to_coeff(run_spread, keys[g], run_prod, *ks_ctx, L, top_rows, polys, stream));
         } else {
-            HEAMD_HIP_TRY(fused);
             HEAMD_HIP_TRY(finish(unfinished, first));
             unfinished = first + polys;
         }
@@ -403,17 +368,23 @@ uint32_t inverse_mod_power_of_two(uint64_t g, uint64_t modulus) {
 // Bfv.applyGalois (Bfv.swift:174-198) without a rotated copy of the ciphertext: the automorphism of c1 happens as the
 // decomposition's transform loads its rows, that of c0 as the last kernel adds it to the update; expand_shift != 0
 // turns that last kernel into one step of PirUtil.expand (rns_kernels.hpp, launch_galois_finish).  One key per group of
-// `group_size` consecutive ciphertexts.  hipErrorNotSupported (nothing launched): the degree has no tiled transform.
+// `group_size` consecutive ciphertexts.  *fused = false (nothing launched): the degree has no tiled transform.
 // `own` (expand steps): the ciphertexts the children are formed with when they are not `ct` (launch_galois_finish).
-hipError_t galois_switch_fused(const he_bfv_context* ctx, uint32_t L, const uint64_t* ct, uint32_t galois_inverse,
-                               const uint64_t* const* keys, size_t groups, size_t group_size, uint64_t* out,
-                               uint32_t expand_shift, const heamd::ExpandTargets& targets, uint64_t* spread, uint64_t* prod,
-                               hipStream_t stream, const uint64_t* own = nullptr) {
+int galois_switch_fused(const he_bfv_context* ctx, uint32_t L, const uint64_t* ct, uint32_t galois_inverse,
+                        const uint64_t* const* keys, size_t groups, size_t group_size, uint64_t* out, uint32_t expand_shift,
+                        const heamd::ExpandTargets& targets, uint64_t* spread, uint64_t* prod, hipStream_t stream, bool* fused,
+                        const uint64_t* own = nullptr) {
+    *fused = false;
     const PolyContext* ks_ctx = ctx->impl->key_switching(L);
     const DeviceContext ks = ks_ctx->device_context();
     const size_t n = ctx->impl->degree(), batch = groups * group_size, ct_stride = 2 * size_t(L) * n;
-    hipError_t e = heamd::launch_ntt_spread(ct + size_t(L) * n, ct_stride, L, batch, spread, ks, galois_inverse, stream);
-    if (e != hipSuccess) return e;
+    const hipError_t spread_status = heamd::launch_ntt_spread(ct + size_t(L) * n, ct_stride, L, batch, spread, ks, galois_inverse, stream);
+    if (spread_status == hipErrorNotSupported) {
+        (void)hipGetLastError();
+        return HE_OK;
+    }
+    HEAMD_HIP_TRY(spread_status);
+    *fused = true;
     // the key switch's end (galois(c0) + update0 | update1, or the two children of an expand step) in the key-MAC
     // transform's store where the degree has that kernel; the separate finish kernel otherwise
     // -- decided on the smallest run of queries with one key: every run is two launches of its own there, against one
@@ -433,7 +404,7 @@ hipError_t galois_switch_fused(const he_bfv_context* ctx, uint32_t L, const uint
         const uint64_t* const run_spread = static_cast<const uint64_t*>(spread) + first * L * (L + 1) * n;
         uint64_t* const run_prod = prod + first * 2 * (L + 1) * n;
         if (fused_end) {
-            heamd::KeySwitchEnd end{ct, ct_stride, out, 1u};
+            heamd::KeySwitchEnd<uint64_t> end{ct, ct_stride, out, 1u};
             end.galois_inverse = galois_inverse;
             end.expand_shift = expand_shift;
             end.own_base = own;
@@ -441,17 +412,17 @@ hipError_t galois_switch_fused(const he_bfv_context* ctx, uint32_t L, const uint
             end.targets_group_size = targets.group_size;
             end.targets_group_stride = targets.group_stride;
             end.poly_base = first;
-            e = heamd::launch_ntt_key_mac_inverse_finish(run_spread, keys[g], run_prod, end, ks, L, ctx->impl->top_level() + 1,
-                                                         polys, stream);
+            HEAMD_HIP_TRY(heamd::launch_ntt_key_mac_inverse_finish(run_spread, keys[g], run_prod, end, ks, L,
+                                                                   ctx->impl->top_level() + 1, polys, stream));
         } else {
-            e = key_mac_to_coeff(run_spread, keys[g], run_prod, *ks_ctx, L, ctx->impl->top_level() + 1, polys, stream);
+            HEAMD_TRY_STATUS(key_mac_to_coeff(run_spread, keys[g], run_prod, *ks_ctx, L, ctx->impl->top_level() + 1, polys, stream));
         }
-        if (e != hipSuccess) return e;
         g += run;
     }
-    if (fused_end) return hipSuccess;
-    return heamd::launch_galois_finish(static_cast<const uint64_t*>(prod), ct, ct_stride, out, ks, L, batch,
-                                       galois_inverse, expand_shift, targets, stream, own);
+    if (fused_end) return HE_OK;
+    HEAMD_HIP_TRY(heamd::launch_galois_finish(static_cast<const uint64_t*>(prod), ct, ct_stride, out, ks, L, batch, galois_inverse,
+                                              expand_shift, targets, stream, own));
+    return HE_OK;
 }
 
 template <typename W>
@@ -488,16 +459,12 @@ int bfv_expand_step_fused(const he_bfv_context* ctx, uint32_t L, const uint64_t*
     if (workspace_bytes < he_bfv_apply_galois_workspace_bytes(ctx, L, batch)) return invalid_argument("workspace too small");
     uint64_t* spread = static_cast<uint64_t*>(workspace);    // [batch][L][L+1][N]
     uint64_t* prod = spread + batch * L * (L + 1) * n;       // [batch][2][L+1][N]
-    const hipError_t e = galois_switch_fused(ctx, L, rotated != nullptr ? rotated : parents,
-                                             inverse_mod_power_of_two(element, 2 * n), keys, groups, group_size, next, shift,
-                                             heamd::ExpandTargets{leaf_table, group_size, leaf_stride}, spread, prod, stream,
-                                             rotated != nullptr ? parents : nullptr);
-    if (e == hipErrorNotSupported) {
-        (void)hipGetLastError();
-        return kExpandStepUnavailable;
-    }
-    HEAMD_HIP_TRY(e);
-    return HE_OK;
+    bool fused = false;
+    HEAMD_TRY_STATUS(galois_switch_fused(ctx, L, rotated != nullptr ? rotated : parents, inverse_mod_power_of_two(element, 2 * n),
+                                         keys, groups, group_size, next, shift,
+                                         heamd::ExpandTargets{leaf_table, group_size, leaf_stride}, spread, prod, stream, &fused,
+                                         rotated != nullptr ? parents : nullptr));
+    return fused ? HE_OK : kExpandStepUnavailable;
 }
 }  // namespace heamd
 
@@ -737,11 +704,10 @@ int bfv_apply_galois_grouped(const he_bfv_context* ctx, uint32_t L, const W* ct,
     const uint32_t galois_inverse = inverse_mod_power_of_two(element, 2 * n);
     if constexpr (sizeof(W) == 8) {
         if (ct != out) {  // the fused kernels read ct to the end
-            const hipError_t e = galois_switch_fused(ctx, L, ct, galois_inverse, keys, groups, group_size, out, 0,
-                                                     heamd::ExpandTargets{nullptr, 1, 0}, spread, prod, stream);
-            if (e == hipSuccess) return HE_OK;
-            if (e != hipErrorNotSupported) HEAMD_HIP_TRY(e);
-            (void)hipGetLastError();
+            bool fused = false;
+            HEAMD_TRY_STATUS(galois_switch_fused(ctx, L, ct, galois_inverse, keys, groups, group_size, out, 0,
+                                                 heamd::ExpandTargets{nullptr, 1, 0}, spread, prod, stream, &fused));
+            if (fused) return HE_OK;
         }
     }
     const PolyContext* q_ctx = ctx->impl->ciphertext(L);
@@ -1179,7 +1145,7 @@ int inner_product_pipeline(const he_bfv_context* ctx, const RnsToolLevel* tool, 
     if (status != HE_OK) return status;
     W* lifted = reinterpret_cast<W*>(raw);   // [count][4][2L+1][N]
     W* sum = lifted + count * 4 * ext;       // [3][2L+1][N]
-    HEAMD_HIP_TRY(lift_pairs_to_eval(*tool, L, n, ext, lhs, rhs, lifted, count, stream));
+    HEAMD_TRY_STATUS(lift_pairs_to_eval(*tool, L, n, ext, lhs, rhs, lifted, count, stream));
     const DeviceContext qbsk = tool->qbsk->device_context();
     // maxProductCount = maxLazyProductAccumulationCount() / 2 because poly1 takes two products per pair (Bfv.swift:339)
     const uint64_t max_lazy = tool->qbsk->max_lazy_product_accumulation_count(static_cast<uint32_t>(rows)) / 2;

@@ -85,7 +85,7 @@ int heamd::poly_ntt(const he_poly_context* ctx, W* slab, size_t batch, bool inve
     if (slab == nullptr) return invalid_argument("null slab");
     if (!kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
     const hipError_t e = ntt_rows(inverse, slab, pc, pc.device_context(), pc.moduli_count(), batch * pc.moduli_count(), stream);
-    if (sizeof(W) == 4 && e == hipErrorNotSupported) {  // launch_ntt32 holds a row in the LDS
+    if (sizeof(W) == 4 && e == hipErrorNotSupported) {  // the 4-byte launch_ntt holds a row in the LDS
         set_last_error("UInt32 transform supports degrees up to 32768");
         return HE_ERR_UNSUPPORTED;
     }
@@ -134,8 +134,8 @@ int poly_mul_scalar(const he_poly_context* ctx, W* data, const W* scalar_residue
     HEAMD_HIP_TRY(hipMemcpyAsync(scratch.get(), pairs.data(), pairs.size() * sizeof(heamd::U64x2),
                                  hipMemcpyHostToDevice, stream));
     HEAMD_HIP_TRY(hipStreamSynchronize(stream));  // the pageable host vector must outlive the async copy
-    HEAMD_HIP_TRY(elementwise_rows(heamd::ElementwiseOp::MulScalar, data, nullptr, static_cast<const uint64_t*>(scratch.get()),
-                                   pc, batch * pc.moduli_count(), stream));
+    HEAMD_HIP_TRY(heamd::elementwise_rows<W>(heamd::ElementwiseOp::MulScalar, data, nullptr,
+                                             static_cast<const uint64_t*>(scratch.get()), pc, batch * pc.moduli_count(), stream));
     return HE_OK;
 }
 
@@ -1031,7 +1031,7 @@ int ciphertexts_deserialize_seeded(const he_poly_context* ctx, const uint8_t* po
             heamd::set_last_error("a modulus of this context is not an NTT modulus for degree " + std::to_string(pc.degree()));
             return HE_ERR_INVALID_NTT_MODULUS;
         }
-        // nothing is enqueued for a transform that does not exist: launch_ntt32 holds a row in the LDS, up to N = 32768
+        // nothing is enqueued for a transform that does not exist: the 4-byte launch_ntt holds a row in the LDS, up to N = 32768
         if (sizeof(W) == 4 && pc.degree() > 32768) {
             heamd::set_last_error("UInt32 transform supports degrees up to 32768");
             return HE_ERR_UNSUPPORTED;

@@ -3,6 +3,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "device_math.hpp"
 
 namespace heamd {
@@ -96,5 +98,9 @@ struct DeviceContext32 {
     const U64x2* inverse_q_last;    // [L][L]
     uint32_t degree, log_degree, moduli_count, moduli_stride;
 };
+
+// The image a launch on slabs of W takes: W = uint64_t or uint32_t
+template <typename W>
+using DeviceImage = std::conditional_t<std::is_same_v<W, uint64_t>, DeviceContext, DeviceContext32>;
 
 }  // namespace heamd

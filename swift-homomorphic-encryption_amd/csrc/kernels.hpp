@@ -1,4 +1,8 @@
-// kernels.hpp -- host-callable launchers of the HIP kernels (all asynchronous on `stream`).
+// kernels.hpp -- host-callable launchers of the HIP kernels (all asynchronous on `stream`).  A kernel family that exists on
+// both slab words has ONE launcher name, overloaded on the slab pointer: uint64_t slabs take a DeviceContext, uint32_t slabs
+// (word32_kernels.hip: PolyRq<UInt32>, every modulus <= 2^30 - 1) a DeviceContext32 -- word_layer.hpp word_image<W> yields
+// either.  Where the 8-byte kernel has something the 4-byte one lacks, the 4-byte overload returns hipErrorNotSupported before
+// any launch: the signal every caller already falls back on.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,6 +26,9 @@ enum {
 // NTT of `rows` contiguous length-N rows.  Row r uses modulus index mod_base + (r % mod_period).
 hipError_t launch_ntt(bool inverse, uint64_t* slab, const DeviceContext& ctx, uint32_t mod_base, uint32_t mod_period,
                       size_t rows, hipStream_t stream, int force_variant = kNttVariantAuto);
+// (4-byte words hold a row in the LDS: hipErrorNotSupported above N = 32768)
+hipError_t launch_ntt(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t mod_base, uint32_t mod_period,
+                      size_t rows, hipStream_t stream);
 // Inverse NTT out of place: rows read from `source`, written to the same places of `slab` (N = 4096 / 8192 with every modulus
 // below 2^61; hipErrorNotSupported, nothing launched, elsewhere)
 hipError_t launch_ntt_inverse_out_of_place(const uint64_t* source, uint64_t* slab, const DeviceContext& ctx, uint32_t mod_base,
@@ -30,9 +37,12 @@ hipError_t launch_ntt_inverse_out_of_place(const uint64_t* source, uint64_t* sla
 // (poly, j, r) = NTT_{ks modulus r}( source row j of polynomial `poly`, reduced mod r when q_j > modulus r ), read
 // from source + poly * poly_stride + j * N.  galois_inverse = g^-1 mod 2N: the source polynomial is first taken through
 // f(x) -> f(x^g) (Coeff form, PolyRq/Galois.swift:115-143) as its rows are loaded; 0: as it is.
-// hipErrorNotSupported for degrees without a tiled kernel (the caller then runs launch_key_switch_spread + launch_ntt).
+// hipErrorNotSupported for degrees without a tiled kernel (the caller then runs launch_key_switch_spread + launch_ntt),
+// and on 4-byte words for galois_inverse != 0.
 hipError_t launch_ntt_spread(const uint64_t* source, size_t poly_stride, uint32_t source_moduli, size_t polys,
                              uint64_t* spread, const DeviceContext& ks_ctx, uint32_t galois_inverse, hipStream_t stream);
+hipError_t launch_ntt_spread(const uint32_t* source, size_t poly_stride, uint32_t source_moduli, size_t polys,
+                             uint32_t* spread, const DeviceContext32& ks_ctx, uint32_t galois_inverse, hipStream_t stream);
 // Plaintext.convertToEvalFormat fused into the forward NTT (Plaintext.swift:149-170): out [polys][L][N] row (poly, r)
 // = NTT_{q_r}(centred lift of plaintexts[poly][N] mod q_r).  hipErrorNotSupported for degrees without a tiled kernel.
 hipError_t launch_ntt_lift(const uint64_t* plaintexts, uint64_t plaintext_modulus, size_t polys, uint64_t* out,
@@ -47,12 +57,21 @@ hipError_t launch_ntt_record_band(bool inverse, uint64_t* slab, const DeviceCont
 // Forward NTT of lifted [Q, Bsk] records [records][record_rows][N] whose first source_moduli rows were left unwritten by
 // the lift: they are read from the source polynomials -- record = item * 4 + slot from polynomial slot & 1 of item
 // `item` of `base` (slots 0, 1) or `second` (slots 2, 3), items `stride` words apart; second == nullptr: record r from
-// base + r * stride.  hipErrorNotSupported (ntt_lifted_forward_supported false): lift with the copy, launch_ntt_mixed.
+// base + r * stride (8-byte words only).  hipErrorNotSupported (ntt_lifted_forward_supported false): lift with the copy,
+// then launch_ntt_mixed / launch_ntt.
 bool ntt_lifted_forward_supported(const DeviceContext& ctx, uint32_t record_rows, uint32_t source_moduli, size_t records);
+bool ntt_lifted_forward_supported(const DeviceContext32& ctx, uint32_t record_rows, uint32_t source_moduli, size_t records);
 hipError_t launch_ntt_lifted_forward(uint64_t* slab, const DeviceContext& ctx, uint32_t record_rows, size_t records,
                                      const uint64_t* base, const uint64_t* second, size_t stride, uint32_t source_moduli,
                                      hipStream_t stream);
+hipError_t launch_ntt_lifted_forward(uint32_t* slab, const DeviceContext32& ctx, uint32_t record_rows, size_t records,
+                                     const uint32_t* base, const uint32_t* second, size_t stride, uint32_t source_moduli,
+                                     hipStream_t stream);
+// Bfv+Multiply.swift:80-82 into the inverse transform's load: lifted [items][4][record_rows][N] (Eval) -> out
+// [items][3][record_rows][N] (Coeff; the context carries t N^-1).  hipErrorNotSupported for degrees without a tiled kernel.
 hipError_t launch_ntt_tensor_inverse(const uint64_t* lifted, uint64_t* out, const DeviceContext& ctx, uint32_t record_rows,
+                                     size_t items, hipStream_t stream);
+hipError_t launch_ntt_tensor_inverse(const uint32_t* lifted, uint32_t* out, const DeviceContext32& ctx, uint32_t record_rows,
                                      size_t items, hipStream_t stream);
 // behz_kernels.hip -- BEHZ multiplication row by row (Bfv+Multiply.swift:18-85): per (item, [Q, Bsk] row) the four forward
 // transforms, the tensor product and the three inverse transforms scaled by t in one workgroup, the transformed rows never
@@ -69,7 +88,11 @@ constexpr int kBehzAllRows = 0, kBehzCiphertextRows = 1, kBehzLiftedRows = 2;
 hipError_t launch_behz_rows_fused(const uint64_t* lhs, const uint64_t* rhs, size_t ct_stride, const uint64_t* lifted,
                                   uint64_t* out, const DeviceContext& scaled_qbsk, uint32_t record_rows, uint32_t source_moduli,
                                   size_t items, hipStream_t stream, int part = kBehzAllRows);
+// Bfv+Keys.swift:180-207 into the inverse transform's load: spread [polys][L][L+1][N], key [L][2][top_rows][N] -> out
+// [polys][2][L+1][N] (Coeff).  hipErrorNotSupported for degrees without a tiled kernel (4-byte words: and for L > 15).
 hipError_t launch_ntt_key_mac_inverse(const uint64_t* spread, const uint64_t* key, uint64_t* out, const DeviceContext& ks,
+                                      uint32_t L, uint32_t top_rows, size_t polys, hipStream_t stream);
+hipError_t launch_ntt_key_mac_inverse(const uint32_t* spread, const uint32_t* key, uint32_t* out, const DeviceContext32& ks,
                                       uint32_t L, uint32_t top_rows, size_t polys, hipStream_t stream);
 // launch_ntt_key_mac_inverse with the key switch's last step (drop the special modulus, add the update to the first
 // `added_polys` polynomials of the ciphertext at ct_base + polynomial * ct_stride) applied as the rows are stored:
@@ -80,33 +103,45 @@ hipError_t launch_ntt_key_mac_inverse(const uint64_t* spread, const uint64_t* ke
 // of PirUtil.expand on top of that (expand_shift != 0: out takes the two children of every polynomial; own_base: the
 // ciphertexts the children are formed with, nullptr = ct_base; targets_*: rns_kernels.hpp ExpandTargets).  poly_base: the
 // launch's first polynomial in ct_base / own_base / out (spread, key and prod are passed from a run's own start).
+// 4-byte words have the relinearize end only: any other field off its default is hipErrorNotSupported.
+template <typename W>
 struct KeySwitchEnd {
-    const uint64_t* ct_base;
+    const W* ct_base;
     size_t ct_stride;
-    uint64_t* out;
+    W* out;
     uint32_t added_polys;
     uint32_t galois_inverse = 0, expand_shift = 0;
-    const uint64_t* own_base = nullptr;
+    const W* own_base = nullptr;
     const uint32_t* targets_table = nullptr;
     size_t targets_group_size = 1, targets_group_stride = 0;
     size_t poly_base = 0;
 };
 bool ntt_key_mac_finish_supported(const DeviceContext& ks, uint32_t L, size_t polys);
+bool ntt_key_mac_finish_supported(const DeviceContext32& ks, uint32_t L, size_t polys);
 hipError_t launch_ntt_key_mac_inverse_finish(const uint64_t* spread, const uint64_t* key, uint64_t* prod,
-                                             const KeySwitchEnd& end, const DeviceContext& ks, uint32_t L, uint32_t top_rows,
-                                             size_t polys, hipStream_t stream);
+                                             const KeySwitchEnd<uint64_t>& end, const DeviceContext& ks, uint32_t L,
+                                             uint32_t top_rows, size_t polys, hipStream_t stream);
+hipError_t launch_ntt_key_mac_inverse_finish(const uint32_t* spread, const uint32_t* key, uint32_t* prod,
+                                             const KeySwitchEnd<uint32_t>& end, const DeviceContext32& ks, uint32_t L,
+                                             uint32_t top_rows, size_t polys, hipStream_t stream);
 const char* ntt_variant_name(uint32_t log_degree);
 
 enum class ElementwiseOp : int { Add = 0, Sub = 1, Neg = 2, Mul = 3, MulScalar = 4 };
-// lhs[k] = op(lhs[k], rhs[k]) over `rows` rows of [..][L][N]; rhs may be NULL for Neg.  For MulScalar `rhs` is a
-// device array of L (scalar, shoup) pairs.
-hipError_t launch_elementwise(ElementwiseOp op, uint64_t* lhs, const uint64_t* rhs, const DeviceContext& ctx,
-                              size_t rows, hipStream_t stream);
-// ct [batch][polys][L][N] *= pt [batch][L][N]
+// lhs[k] = op(lhs[k], rhs[k]) over `rows` rows of [..][L][N]; rhs may be NULL for Neg and MulScalar.  MulScalar reads
+// `scalars`, a device array of L (scalar, 64-bit Shoup factor) pairs, and nothing else does.
+hipError_t launch_elementwise(ElementwiseOp op, uint64_t* lhs, const uint64_t* rhs, const uint64_t* scalars,
+                              const DeviceContext& ctx, size_t rows, hipStream_t stream);
+hipError_t launch_elementwise(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
+                              const DeviceContext32& ctx, size_t rows, hipStream_t stream);
+// ct [batch][polys][L][N] *= pt [batch][L][N] (either word under the 8-byte image)
 hipError_t launch_mul_plain(uint64_t* ct, const uint64_t* pt, const DeviceContext& ctx, uint32_t poly_count,
                             size_t batch, hipStream_t stream);
+hipError_t launch_mul_plain(uint32_t* ct, const uint32_t* pt, const DeviceContext& ctx, uint32_t poly_count, size_t batch,
+                            hipStream_t stream);
 // divideAndRoundQLast with the first `moduli_count` moduli of ctx: in [polys][L][N] -> out [polys][L-1][N]
 hipError_t launch_divide_and_round_q_last(const uint64_t* in, uint64_t* out, const DeviceContext& ctx,
+                                          uint32_t moduli_count, size_t polys, hipStream_t stream);
+hipError_t launch_divide_and_round_q_last(const uint32_t* in, uint32_t* out, const DeviceContext32& ctx,
                                           uint32_t moduli_count, size_t polys, hipStream_t stream);
 // Ciphertext.modSwitchDownToSingle: in [polys][moduli_count][N] -> out [polys][1][N], the moduli_count - 1 steps of
 // divideAndRoundQLast in one kernel (2..8 moduli; hipErrorNotSupported otherwise: chain the kernel above).
@@ -147,36 +182,8 @@ hipError_t launch_inner_product_plain_packed(const uint64_t* cts, const uint64_t
                                              const uint8_t* present_device, uint64_t* out, const DeviceContext& ctx,
                                              uint32_t poly_count, size_t count, size_t columns, uint64_t cadence,
                                              bool narrow_moduli, hipStream_t stream);
-// ct [batch][polys][L][N] *= pt [batch][L][N] on 4-byte words
-hipError_t launch_mul_plain32(uint32_t* ct, const uint32_t* pt, const DeviceContext& ctx, uint32_t poly_count, size_t batch,
-                              hipStream_t stream);
 
-
-// word32_kernels.hip: PolyRq<UInt32> (4-byte words; every modulus <= 2^30 - 1)
-hipError_t launch_ntt32(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t mod_base, uint32_t mod_period,
-                        size_t rows, hipStream_t stream);
-// the same transforms with the step before them applied to the words as they are loaded (word32_kernels.hip Source32):
-// the key-switching decomposition, the BEHZ tensor product, the inner product with the key-switching key.
-// hipErrorNotSupported where the degree has no tiled 4-byte transform (the caller runs the unfused kernels).
-hipError_t launch_ntt32_spread(const uint32_t* target, size_t stride, uint32_t L, size_t polys, uint32_t* spread,
-                               const DeviceContext32& ks_ctx, hipStream_t stream);
-bool ntt32_lifted_forward_supported(const DeviceContext32& ctx);
-hipError_t launch_ntt32_lifted_forward(uint32_t* lifted, const DeviceContext32& ctx, uint32_t record_rows, size_t items,
-                                       const uint32_t* lhs, const uint32_t* rhs, size_t stride, uint32_t L,
-                                       hipStream_t stream);
-hipError_t launch_ntt32_tensor_inverse(const uint32_t* lifted, uint32_t* out, const DeviceContext32& ctx, uint32_t record_rows,
-                                       size_t items, hipStream_t stream);
-hipError_t launch_ntt32_key_mac_inverse(const uint32_t* spread, const uint32_t* key, uint32_t* out,
-                                        const DeviceContext32& ks_ctx, uint32_t L, uint32_t top_rows, size_t polys,
-                                        hipStream_t stream);
-// ... and the key switch's last step applied as the rows r < L are stored (launch_ntt_key_mac_inverse_finish's 4-byte twin)
-hipError_t launch_ntt32_key_mac_inverse_finish(const uint32_t* spread, const uint32_t* key, uint32_t* prod,
-                                               const uint32_t* ct_base, size_t ct_stride, uint32_t* out,
-                                               const DeviceContext32& ks_ctx, uint32_t L, uint32_t top_rows, size_t polys,
-                                               uint32_t added_polys, hipStream_t stream);
-// scalars: device array of L (scalar, 64-bit Shoup factor) pairs, only for MulScalar
-hipError_t launch_elementwise32(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
-                                const DeviceContext32& ctx, size_t rows, hipStream_t stream);
+// word32_kernels.hip: the bridge between the two slab words
 // packed [UInt32] words <-> the zero-extended 8-byte words of the Bfv<UInt32> scheme layer (16-byte aligned slabs)
 hipError_t launch_widen_words(const uint32_t* in, uint64_t* out, size_t words, hipStream_t stream);
 hipError_t launch_stream_copy(const uint64_t* in, uint64_t* out, size_t words, bool non_temporal, hipStream_t stream);
@@ -185,8 +192,6 @@ hipError_t launch_stream_copy(const uint64_t* in, uint64_t* out, size_t words, b
 hipError_t launch_copy_records(const uint64_t* in, size_t src_stride, uint64_t* out, size_t dst_stride, size_t record_words,
                                size_t records, hipStream_t stream);
 hipError_t launch_narrow_words(const uint64_t* in, uint32_t* out, size_t words, hipStream_t stream);
-hipError_t launch_divide_and_round_q_last32(const uint32_t* in, uint32_t* out, const DeviceContext32& ctx,
-                                            uint32_t moduli_count, size_t polys, hipStream_t stream);
 
 // seeded_kernels.hip: out[b] = PolyRq.random(context, NistAes128Ctr(seed: seeds[b])), seeds [batch][32] bytes
 // scratch: seeded_uniform_scratch_bytes(ctx, batch) bytes (the per-chunk round keys of every seed's re-key chain)

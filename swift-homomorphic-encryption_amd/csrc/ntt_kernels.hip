@@ -1679,8 +1679,8 @@ bool ntt_key_mac_finish_supported(const DeviceContext& ks, uint32_t L, size_t po
            polys * 2 * (L + 1) <= (size_t(1) << 30);
 }
 hipError_t launch_ntt_key_mac_inverse_finish(const uint64_t* spread, const uint64_t* key, uint64_t* prod,
-                                             const KeySwitchEnd& end, const DeviceContext& ks, uint32_t L, uint32_t top_rows,
-                                             size_t polys, hipStream_t stream) {
+                                             const KeySwitchEnd<uint64_t>& end, const DeviceContext& ks, uint32_t L,
+                                             uint32_t top_rows, size_t polys, hipStream_t stream) {
     if (!ntt_key_mac_finish_supported(ks, L, polys)) return hipErrorNotSupported;
     if (polys == 0) return hipSuccess;
     const InverseSource spec{spread, key, L, top_rows, end.ct_base, end.ct_stride, end.out, end.added_polys,

@@ -660,15 +660,15 @@ __global__ void __launch_bounds__(kTileWords * kTileWavefronts)
 
 }  // namespace
 
-hipError_t launch_elementwise(ElementwiseOp op, uint64_t* lhs, const uint64_t* rhs, const DeviceContext& ctx,
-                              size_t rows, hipStream_t stream) {
+hipError_t launch_elementwise(ElementwiseOp op, uint64_t* lhs, const uint64_t* rhs, const uint64_t* scalars,
+                              const DeviceContext& ctx, size_t rows, hipStream_t stream) {
     switch (op) {
         case ElementwiseOp::Add: return launch_elementwise_op<ElementwiseOp::Add>(lhs, rhs, ctx, rows, stream);
         case ElementwiseOp::Sub: return launch_elementwise_op<ElementwiseOp::Sub>(lhs, rhs, ctx, rows, stream);
         case ElementwiseOp::Neg: return launch_elementwise_op<ElementwiseOp::Neg>(lhs, rhs, ctx, rows, stream);
         case ElementwiseOp::Mul: return launch_elementwise_op<ElementwiseOp::Mul>(lhs, rhs, ctx, rows, stream);
         case ElementwiseOp::MulScalar:
-            return launch_elementwise_op<ElementwiseOp::MulScalar>(lhs, rhs, ctx, rows, stream);
+            return launch_elementwise_op<ElementwiseOp::MulScalar>(lhs, scalars, ctx, rows, stream);  // the kernel's rhs
     }
     return hipErrorInvalidValue;
 }
@@ -890,8 +890,8 @@ __global__ void __launch_bounds__(kThreads)
 }
 }  // namespace
 
-hipError_t launch_mul_plain32(uint32_t* ct, const uint32_t* pt, const DeviceContext& ctx, uint32_t poly_count, size_t batch,
-                              hipStream_t stream) {
+hipError_t launch_mul_plain(uint32_t* ct, const uint32_t* pt, const DeviceContext& ctx, uint32_t poly_count, size_t batch,
+                            hipStream_t stream) {
     const size_t words_per_poly = static_cast<size_t>(ctx.moduli_count) * ctx.degree;
     if (words_per_poly * batch == 0) return hipSuccess;
     hipLaunchKernelGGL(mul_plain_kernel32, dim3(grid_for(words_per_poly * batch)), dim3(kThreads), 0, stream, ct, pt, ctx,

@@ -30,7 +30,7 @@ constexpr unsigned kThreads = 256;
 inline unsigned grid_for(size_t work_items) { return launch_grid::grid_for(work_items, kThreads); }
 
 // +1 word per 32: de-conflicts the power-of-two strides of the late forward / early inverse stages
-__device__ __forceinline__ uint32_t slot32(uint32_t idx) { return idx + (idx >> 5); }
+__host__ __device__ constexpr uint32_t tile32_slot(uint32_t idx) { return idx + (idx >> 5); }
 
 template <bool INVERSE>
 __global__ void __launch_bounds__(1024)
@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(1024)
     const uint32_t p = static_cast<uint32_t>(mod.p), two_p = 2 * p;
     const U32x2* __restrict__ tw = (INVERSE ? ctx.inverse_twiddles : ctx.forward_twiddles) + static_cast<size_t>(mi) * n;
     uint32_t* x = slab + row * n;
-    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) tile[slot32(k)] = x[k];
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) tile[tile32_slot(k)] = x[k];
     __syncthreads();
     if (!INVERSE) {
         for (uint32_t s = 0; s < logn; ++s) {  // Cooley-Tukey, natural -> bit-reversed (PolyRq+Ntt.swift:271-287)
@@ -52,14 +52,14 @@ __global__ void __launch_bounds__(1024)
                 const uint32_t i = k >> (logn - 1 - s), o = k & (t - 1);
                 const uint32_t a = 2 * i * t + o;
                 const U32x2 w = tw[(1u << s) + i];
-                const uint32_t xv = csub32(tile[slot32(a)], two_p);
-                const uint32_t tv = shoup32_lazy(tile[slot32(a + t)], w.x, w.y, p);
-                tile[slot32(a)] = xv + tv;
-                tile[slot32(a + t)] = xv + two_p - tv;
+                const uint32_t xv = csub32(tile[tile32_slot(a)], two_p);
+                const uint32_t tv = shoup32_lazy(tile[tile32_slot(a + t)], w.x, w.y, p);
+                tile[tile32_slot(a)] = xv + tv;
+                tile[tile32_slot(a + t)] = xv + two_p - tv;
             }
             __syncthreads();
         }
-        for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) x[k] = csub32(csub32(tile[slot32(k)], two_p), p);
+        for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) x[k] = csub32(csub32(tile[tile32_slot(k)], two_p), p);
     } else {
         const uint32_t inv_n = static_cast<uint32_t>(mod.inv_degree), inv_n_f = static_cast<uint32_t>(mod.inv_degree_shoup >> 32);
         const uint32_t inv_r = static_cast<uint32_t>(mod.inv_degree_root),
@@ -70,20 +70,20 @@ __global__ void __launch_bounds__(1024)
             for (uint32_t k = threadIdx.x; k < (n >> 1); k += blockDim.x) {
                 const uint32_t i = k >> b, o = k & (t - 1);
                 const uint32_t a = 2 * i * t + o;
-                const uint32_t xv = tile[slot32(a)], yv = tile[slot32(a + t)];
+                const uint32_t xv = tile[tile32_slot(a)], yv = tile[tile32_slot(a + t)];
                 const uint32_t sum = xv + yv, diff = xv + two_p - yv;
                 if (last) {  // N^-1 and N^-1 psi^(-N/2) folded into the last stage (:407-421)
-                    tile[slot32(a)] = csub32(shoup32_lazy(sum, inv_n, inv_n_f, p), p);
-                    tile[slot32(a + t)] = csub32(shoup32_lazy(diff, inv_r, inv_r_f, p), p);
+                    tile[tile32_slot(a)] = csub32(shoup32_lazy(sum, inv_n, inv_n_f, p), p);
+                    tile[tile32_slot(a + t)] = csub32(shoup32_lazy(diff, inv_r, inv_r_f, p), p);
                 } else {
                     const U32x2 w = tw[(n - 2 * m + 1) + i];
-                    tile[slot32(a)] = csub32(sum, two_p);
-                    tile[slot32(a + t)] = shoup32_lazy(diff, w.x, w.y, p);
+                    tile[tile32_slot(a)] = csub32(sum, two_p);
+                    tile[tile32_slot(a + t)] = shoup32_lazy(diff, w.x, w.y, p);
                 }
             }
             __syncthreads();
         }
-        for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) x[k] = tile[slot32(k)];
+        for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) x[k] = tile[tile32_slot(k)];
     }
 }
 
@@ -169,7 +169,6 @@ __device__ __forceinline__ void inverse_pass32(uint32_t (&v)[1 << LOGE], uint32_
     }
 }
 
-__host__ __device__ constexpr uint32_t tile32_slot(uint32_t idx) { return idx + (idx >> 5); }
 constexpr uint32_t tile32_words(uint32_t n) { return n + (n >> 5) + 8; }
 
 template <int LOGN, int LOGE, int LO, int W>
@@ -273,19 +272,19 @@ constexpr int kSource32Slab = 0, kSource32Spread = 1, kSource32Tensor = 2, kSour
               kSource32KeyMacFinish = 5;
 constexpr bool is_key_mac32(int source) { return source == kSource32KeyMac || source == kSource32KeyMacFinish; }
 struct Source32 {
-    const uint32_t* first;
-    const uint32_t* second;  // key MAC: the key
-    size_t stride;           // spread: words between source polynomials
-    uint32_t L, top_rows;    // spread / key MAC: source moduli; key MAC: rows per key polynomial
+    const uint32_t* first = nullptr;
+    const uint32_t* second = nullptr;  // key MAC: the key
+    size_t stride = 0;                 // spread: words between source polynomials
+    uint32_t L = 0, top_rows = 0;      // spread / key MAC: source moduli; key MAC: rows per key polynomial
     // key MAC: the launch covers the band [band_offset, band_offset + band_rows) of every record's rows (band_rows = 0: all)
-    uint32_t band_offset, band_rows;
+    uint32_t band_offset = 0, band_rows = 0;
     // kSource32KeyMacFinish: the ciphertexts the update is added to ([item] ct_stride words apart, polynomial c at c L N; the
     // first `added_polys` polynomials are added, the others replaced) and where the result goes ([item][2][L][N]); the
     // kernel's slab is the product slab whose q_ks rows are read
-    const uint32_t* ct_base;
-    size_t ct_stride;
-    uint32_t* out;
-    uint32_t added_polys;
+    const uint32_t* ct_base = nullptr;
+    size_t ct_stride = 0;
+    uint32_t* out = nullptr;
+    uint32_t added_polys = 0;
 };
 
 template <int LOGN, int LOGT, bool INVERSE, int SOURCE = kSource32Slab>
@@ -486,9 +485,8 @@ __global__ void __launch_bounds__(1 << LOGT)
 }
 
 template <int LOGN, int LOGT, int SOURCE = kSource32Slab>
-hipError_t launch_ntt32_tiled(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t mod_base,
-                              uint32_t mod_period, size_t rows, hipStream_t stream,
-                              const Source32& source = Source32{nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, 0, nullptr, 0}) {
+hipError_t launch_tiled(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t mod_base, uint32_t mod_period,
+                        size_t rows, hipStream_t stream, const Source32& source = Source32{}) {
     constexpr size_t lds_bytes = tile32_words(1u << LOGN) * sizeof(uint32_t);
     using Kernel = void (*)(uint32_t*, const DeviceContext32, uint32_t, uint32_t, const Source32);
     Kernel kernel;
@@ -513,14 +511,14 @@ hipError_t launch_ntt32_tiled(bool inverse, uint32_t* slab, const DeviceContext3
 
 // the fused-source launches: every record's rows in one launch (rows <= 2^30), tiled degrees only
 template <int SOURCE>
-hipError_t launch_ntt32_fused(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t record_rows, size_t rows,
-                              const Source32& source, hipStream_t stream) {
+hipError_t launch_fused(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t record_rows, size_t rows,
+                        const Source32& source, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
     if (rows > (size_t(1) << 30) || ctx.degree < 2) return hipErrorNotSupported;
     switch (ctx.log_degree) {
-        case 12: return launch_ntt32_tiled<12, 9, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
-        case 13: return launch_ntt32_tiled<13, 10, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
-        case 14: return launch_ntt32_tiled<14, 10, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
+        case 12: return launch_tiled<12, 9, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
+        case 13: return launch_tiled<13, 10, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
+        case 14: return launch_tiled<14, 10, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
         default: return hipErrorNotSupported;
     }
 }
@@ -578,62 +576,83 @@ __global__ void __launch_bounds__(kThreads)
 
 }  // namespace
 
-// Bfv+Keys.swift:165-179 into the forward transform's load: target polynomials of L rows, `stride` words apart ->
-// spread [polys][L][L+1][N] (Eval).  hipErrorNotSupported where the degree has no tiled 4-byte transform.
-hipError_t launch_ntt32_spread(const uint32_t* target, size_t stride, uint32_t L, size_t polys, uint32_t* spread,
-                               const DeviceContext32& ks_ctx, hipStream_t stream) {
+// The fused-source launchers (kernels.hpp): what the 8-byte kernels have and these lack is refused before any launch.
+hipError_t launch_ntt_spread(const uint32_t* source, size_t poly_stride, uint32_t source_moduli, size_t polys,
+                             uint32_t* spread, const DeviceContext32& ks_ctx, uint32_t galois_inverse, hipStream_t stream) {
+    const uint32_t L = source_moduli;
+    if (galois_inverse != 0) return hipErrorNotSupported;
     if (ks_ctx.moduli_count < L + 1) return hipErrorInvalidValue;
-    return launch_ntt32_fused<kSource32Spread>(false, spread, ks_ctx, L + 1, polys * L * (L + 1),
-                                               Source32{target, nullptr, stride, L, 0, 0, 0, nullptr, 0, nullptr, 0}, stream);
+    Source32 from;
+    from.first = source;
+    from.stride = poly_stride;
+    from.L = L;
+    return launch_fused<kSource32Spread>(false, spread, ks_ctx, L + 1, polys * L * (L + 1), from, stream);
 }
-// Forward transform of lifted [items][4][rows][N] records whose rows [0, L) were left unwritten by the lift: they are read
-// from the ciphertext pairs (Bfv+Multiply.swift:51-57)
-bool ntt32_lifted_forward_supported(const DeviceContext32& ctx) { return ctx.log_degree >= 12 && ctx.log_degree <= 14; }
-hipError_t launch_ntt32_lifted_forward(uint32_t* lifted, const DeviceContext32& ctx, uint32_t record_rows, size_t items,
-                                       const uint32_t* lhs, const uint32_t* rhs, size_t stride, uint32_t L,
-                                       hipStream_t stream) {
-    return launch_ntt32_fused<kSource32Rows>(false, lifted, ctx, record_rows, items * 4 * record_rows,
-                                             Source32{lhs, rhs, stride, L, 0, 0, 0, nullptr, 0, nullptr, 0}, stream);
+// the rows [0, source_moduli) of the lifted records are read from the ciphertext pairs (Bfv+Multiply.swift:51-57)
+bool ntt_lifted_forward_supported(const DeviceContext32& ctx, uint32_t record_rows, uint32_t, size_t records) {
+    return ctx.log_degree >= 12 && ctx.log_degree <= 14 && records * record_rows <= (size_t(1) << 30);
 }
-// Bfv+Multiply.swift:80-82 into the inverse transform's load: lifted [items][4][rows][N] (Eval) -> out [items][3][rows][N]
-// (Coeff; the context carries t N^-1)
-hipError_t launch_ntt32_tensor_inverse(const uint32_t* lifted, uint32_t* out, const DeviceContext32& ctx, uint32_t record_rows,
-                                       size_t items, hipStream_t stream) {
-    return launch_ntt32_fused<kSource32Tensor>(true, out, ctx, record_rows, items * 3 * record_rows,
-                                               Source32{lifted, nullptr, 0, 0, 0, 0, 0, nullptr, 0, nullptr, 0}, stream);
+hipError_t launch_ntt_lifted_forward(uint32_t* slab, const DeviceContext32& ctx, uint32_t record_rows, size_t records,
+                                     const uint32_t* base, const uint32_t* second, size_t stride, uint32_t source_moduli,
+                                     hipStream_t stream) {
+    if (second == nullptr) return hipErrorNotSupported;
+    Source32 from;
+    from.first = base;
+    from.second = second;
+    from.stride = stride;
+    from.L = source_moduli;
+    return launch_fused<kSource32Rows>(false, slab, ctx, record_rows, records * record_rows, from, stream);
 }
-// Bfv+Keys.swift:180-207 into the inverse transform's load: spread [polys][L][L+1][N], key [L][2][top_rows][N] ->
-// out [polys][2][L+1][N] (Coeff)
-hipError_t launch_ntt32_key_mac_inverse(const uint32_t* spread, const uint32_t* key, uint32_t* out,
-                                        const DeviceContext32& ks_ctx, uint32_t L, uint32_t top_rows, size_t polys,
-                                        hipStream_t stream) {
+hipError_t launch_ntt_tensor_inverse(const uint32_t* lifted, uint32_t* out, const DeviceContext32& ctx, uint32_t record_rows,
+                                     size_t items, hipStream_t stream) {
+    Source32 from;
+    from.first = lifted;
+    return launch_fused<kSource32Tensor>(true, out, ctx, record_rows, items * 3 * record_rows, from, stream);
+}
+hipError_t launch_ntt_key_mac_inverse(const uint32_t* spread, const uint32_t* key, uint32_t* out, const DeviceContext32& ks,
+                                      uint32_t L, uint32_t top_rows, size_t polys, hipStream_t stream) {
     if (L > 15) return hipErrorNotSupported;  // the sum of L products below 2^60 stays in 64 bits
-    return launch_ntt32_fused<kSource32KeyMac>(true, out, ks_ctx, L + 1, polys * 2 * (L + 1),
-                                               Source32{spread, key, 0, L, top_rows, 0, 0, nullptr, 0, nullptr, 0}, stream);
+    Source32 from;
+    from.first = spread;
+    from.second = key;
+    from.L = L;
+    from.top_rows = top_rows;
+    return launch_fused<kSource32KeyMac>(true, out, ks, L + 1, polys * 2 * (L + 1), from, stream);
 }
 // The same with the key switch's last step in the store of the rows r < L (kSource32KeyMacFinish): first the q_ks row of
-// every (polynomial, c) into `prod`, then the other rows, which read it: out [polys][2][L][N].  hipErrorNotSupported
-// (nothing launched) where the degree has no tiled 4-byte transform.
-hipError_t launch_ntt32_key_mac_inverse_finish(const uint32_t* spread, const uint32_t* key, uint32_t* prod,
-                                               const uint32_t* ct_base, size_t ct_stride, uint32_t* out,
-                                               const DeviceContext32& ks_ctx, uint32_t L, uint32_t top_rows, size_t polys,
-                                               uint32_t added_polys, hipStream_t stream) {
-    // (beyond two workgroup generations only -- 4 x 256 workgroups at N = 4096: a smaller batch is latency-bound and two
-    // transforms in a row cost more than one transform and the small element-wise kernel)
-    if (L == 0 || L > 15 || ks_ctx.moduli_count != L + 1 || ks_ctx.log_degree < 12 || ks_ctx.log_degree > 14 ||
-        polys * 2 * (L + 1) <= 2048)
-        return hipErrorNotSupported;
-    if (polys == 0) return hipSuccess;
-    hipError_t e = launch_ntt32_fused<kSource32KeyMac>(
-        true, prod, ks_ctx, L + 1, polys * 2, Source32{spread, key, 0, L, top_rows, L, 1, nullptr, 0, nullptr, 0}, stream);
+// every (polynomial, c) into `prod`, then the other rows, which read it: out [polys][2][L][N].
+// (beyond two workgroup generations only -- 4 x 256 workgroups at N = 4096: a smaller batch is latency-bound and two
+// transforms in a row cost more than one transform and the small element-wise kernel)
+bool ntt_key_mac_finish_supported(const DeviceContext32& ks, uint32_t L, size_t polys) {
+    return L != 0 && L <= 15 && ks.moduli_count == L + 1 && ks.log_degree >= 12 && ks.log_degree <= 14 &&
+           polys * 2 * (L + 1) > 2048;
+}
+hipError_t launch_ntt_key_mac_inverse_finish(const uint32_t* spread, const uint32_t* key, uint32_t* prod,
+                                             const KeySwitchEnd<uint32_t>& end, const DeviceContext32& ks, uint32_t L,
+                                             uint32_t top_rows, size_t polys, hipStream_t stream) {
+    const bool relinearize_end = end.galois_inverse == 0 && end.expand_shift == 0 && end.own_base == nullptr &&
+                                 end.targets_table == nullptr && end.poly_base == 0;
+    if (!relinearize_end || !ntt_key_mac_finish_supported(ks, L, polys)) return hipErrorNotSupported;
+    Source32 from;
+    from.first = spread;
+    from.second = key;
+    from.L = L;
+    from.top_rows = top_rows;
+    from.band_offset = L;
+    from.band_rows = 1;
+    hipError_t e = launch_fused<kSource32KeyMac>(true, prod, ks, L + 1, polys * 2, from, stream);
     if (e != hipSuccess) return e;
-    return launch_ntt32_fused<kSource32KeyMacFinish>(
-        true, prod, ks_ctx, L + 1, polys * 2 * L, Source32{spread, key, 0, L, top_rows, 0, L, ct_base, ct_stride, out, added_polys},
-        stream);
+    from.band_offset = 0;
+    from.band_rows = L;
+    from.ct_base = end.ct_base;
+    from.ct_stride = end.ct_stride;
+    from.out = end.out;
+    from.added_polys = end.added_polys;
+    return launch_fused<kSource32KeyMacFinish>(true, prod, ks, L + 1, polys * 2 * L, from, stream);
 }
 
-hipError_t launch_ntt32(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t mod_base, uint32_t mod_period,
-                        size_t rows, hipStream_t stream) {
+hipError_t launch_ntt(bool inverse, uint32_t* slab, const DeviceContext32& ctx, uint32_t mod_base, uint32_t mod_period,
+                      size_t rows, hipStream_t stream) {
     if (rows == 0 || ctx.degree < 2) return hipSuccess;
     if (ctx.log_degree > 15) return hipErrorNotSupported;  // the row must fit the LDS (4 N bytes + padding)
     constexpr size_t kMaxRowsPerLaunch = size_t(1) << 30;
@@ -642,9 +661,9 @@ hipError_t launch_ntt32(bool inverse, uint32_t* slab, const DeviceContext32& ctx
         const size_t now = rows - done < chunk ? rows - done : chunk;
         const uint32_t n = ctx.degree;
         if (ctx.log_degree >= 12 && ctx.log_degree <= 14) {  // register-tiled kernels, 8 (16) words per lane
-            hipError_t e = ctx.log_degree == 12   ? launch_ntt32_tiled<12, 9>(inverse, slab + done * n, ctx, mod_base, mod_period, now, stream)
-                           : ctx.log_degree == 13 ? launch_ntt32_tiled<13, 10>(inverse, slab + done * n, ctx, mod_base, mod_period, now, stream)
-                                                  : launch_ntt32_tiled<14, 10>(inverse, slab + done * n, ctx, mod_base, mod_period, now, stream);
+            hipError_t e = ctx.log_degree == 12   ? launch_tiled<12, 9>(inverse, slab + done * n, ctx, mod_base, mod_period, now, stream)
+                           : ctx.log_degree == 13 ? launch_tiled<13, 10>(inverse, slab + done * n, ctx, mod_base, mod_period, now, stream)
+                                                  : launch_tiled<14, 10>(inverse, slab + done * n, ctx, mod_base, mod_period, now, stream);
             if (e != hipSuccess) return e;
             done += now;
             continue;
@@ -666,8 +685,8 @@ hipError_t launch_ntt32(bool inverse, uint32_t* slab, const DeviceContext32& ctx
     return hipSuccess;
 }
 
-hipError_t launch_elementwise32(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
-                                const DeviceContext32& ctx, size_t rows, hipStream_t stream) {
+hipError_t launch_elementwise(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
+                              const DeviceContext32& ctx, size_t rows, hipStream_t stream) {
     const size_t words = rows << ctx.log_degree;
     if (words == 0) return hipSuccess;
     const dim3 grid(grid_for(words)), block(kThreads);
@@ -786,8 +805,8 @@ hipError_t launch_narrow_words(const uint64_t* in, uint32_t* out, size_t words, 
     return hipGetLastError();
 }
 
-hipError_t launch_divide_and_round_q_last32(const uint32_t* in, uint32_t* out, const DeviceContext32& ctx,
-                                            uint32_t moduli_count, size_t polys, hipStream_t stream) {
+hipError_t launch_divide_and_round_q_last(const uint32_t* in, uint32_t* out, const DeviceContext32& ctx,
+                                          uint32_t moduli_count, size_t polys, hipStream_t stream) {
     const size_t total = polys << ctx.log_degree;
     if (total == 0 || moduli_count < 2) return hipSuccess;
     hipLaunchKernelGGL(divide_and_round_q_last32_kernel, dim3(grid_for(total)), dim3(kThreads), 0, stream, in, out, ctx,

@@ -1,8 +1,9 @@
 // word_layer.hpp -- the host layer under the C ABI written once for both slab words (not exported): W = uint64_t for
 // Bfv<UInt64>, W = uint32_t for Bfv<UInt32> on packed 4-byte slabs (every modulus, Bsk primes included, <= 2^30 - 1).
-// Most launchers are templates on W already; the few that come as a pair of names are overloaded by word here, and the
-// operations that c_api.cpp, bfv_api.cpp, pnns_api.cpp and pir_api.cpp share are declared here, each defined once in the
-// translation unit that owns it.  An extern "C" entry point and its `_u32` twin are one-line wrappers of such a body.
+// Most launchers are templates on W already; the others are overloaded on the slab pointer and differ in the image they
+// take, which word_image yields here.  The operations that c_api.cpp, bfv_api.cpp, pnns_api.cpp and pir_api.cpp share are
+// declared here, each defined once in the translation unit that owns it.  An extern "C" entry point and its `_u32` twin
+// are one-line wrappers of such a body.
 #pragma once
 
 #include "api_internal.hpp"
@@ -17,57 +18,54 @@
 namespace heamd {
 
 // ---- launchers by slab word.  `dc` is the 8-byte image the caller chose (a level of the context, constants it may have
-// substituted); the 4-byte image is built from `pc` over the moduli the launch walks, with dc's constants.
-// Transform of `rows` rows, row r under modulus r % period: ntt_kernels.hip / word32_kernels.hip
-inline hipError_t ntt_rows(bool inverse, uint64_t* slab, const PolyContext&, const DeviceContext& dc, uint32_t period,
-                           size_t rows, hipStream_t stream) {
-    return launch_ntt(inverse, slab, dc, 0, period, rows, stream);
+// substituted, t N^-1 for instance); word_image yields the image a launch on slabs of W takes: dc itself, or the 4-byte
+// image built from `pc` over the `moduli` moduli the launch walks, with dc's constants.  An he_status.
+template <typename W>
+int word_image(const PolyContext& pc, const DeviceContext& dc, uint32_t moduli, DeviceImage<W>& out) {
+    if constexpr (sizeof(W) == 8) {
+        out = dc;
+        return HE_OK;
+    } else {
+        const int status = pc.device_context32(moduli, out);
+        out.moduli = dc.moduli;
+        return status;
+    }
 }
-inline hipError_t ntt_rows(bool inverse, uint32_t* slab, const PolyContext& pc, const DeviceContext& dc, uint32_t period,
-                           size_t rows, hipStream_t stream) {
-    DeviceContext32 dc32{};
-    if (pc.device_context32(period, dc32) != HE_OK) return hipErrorInvalidValue;
-    dc32.moduli = dc.moduli;  // the caller may have substituted constants (t N^-1)
-    return launch_ntt32(inverse, slab, dc32, 0, period, rows, stream);
+// Transform of `rows` rows, row r under modulus r % period: ntt_kernels.hip / word32_kernels.hip
+template <typename W>
+hipError_t ntt_rows(bool inverse, W* slab, const PolyContext& pc, const DeviceContext& dc, uint32_t period, size_t rows,
+                    hipStream_t stream) {
+    DeviceImage<W> image{};
+    if (word_image<W>(pc, dc, period, image) != HE_OK) return hipErrorInvalidValue;
+    return launch_ntt(inverse, slab, image, 0, period, rows, stream);
 }
 // Transform of `records` records of record_rows rows: 8-byte words take the mixed schedule of the [Q, Bsk] slabs
-inline hipError_t ntt_records(bool inverse, uint64_t* slab, const PolyContext&, const DeviceContext& dc, uint32_t record_rows,
-                              size_t records, hipStream_t stream) {
-    return launch_ntt_mixed(inverse, slab, dc, record_rows, records, stream);
-}
-inline hipError_t ntt_records(bool inverse, uint32_t* slab, const PolyContext& pc, const DeviceContext& dc,
-                              uint32_t record_rows, size_t records, hipStream_t stream) {
-    return ntt_rows(inverse, slab, pc, dc, record_rows, records * record_rows, stream);
+template <typename W>
+hipError_t ntt_records(bool inverse, W* slab, const PolyContext& pc, const DeviceContext& dc, uint32_t record_rows,
+                       size_t records, hipStream_t stream) {
+    if constexpr (sizeof(W) == 8) return launch_ntt_mixed(inverse, slab, dc, record_rows, records, stream);
+    else return ntt_rows(inverse, slab, pc, dc, record_rows, records * record_rows, stream);
 }
 // lhs = op(lhs, rhs) over `rows` rows of every modulus of pc; MulScalar reads `scalars`, (scalar, Shoup factor) pairs
-inline hipError_t elementwise_rows(ElementwiseOp op, uint64_t* lhs, const uint64_t* rhs, const uint64_t* scalars,
-                                   const PolyContext& pc, size_t rows, hipStream_t stream) {
-    return launch_elementwise(op, lhs, op == ElementwiseOp::MulScalar ? scalars : rhs, pc.device_context(), rows, stream);
-}
-inline hipError_t elementwise_rows(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
-                                   const PolyContext& pc, size_t rows, hipStream_t stream) {
-    DeviceContext32 dc32{};
-    if (pc.device_context32(pc.moduli_count(), dc32) != HE_OK) return hipErrorInvalidValue;
-    return launch_elementwise32(op, lhs, rhs, scalars, dc32, rows, stream);
+template <typename W>
+hipError_t elementwise_rows(ElementwiseOp op, W* lhs, const W* rhs, const uint64_t* scalars, const PolyContext& pc, size_t rows,
+                            hipStream_t stream) {
+    DeviceImage<W> image{};
+    if (word_image<W>(pc, pc.device_context(), pc.moduli_count(), image) != HE_OK) return hipErrorInvalidValue;
+    return launch_elementwise(op, lhs, rhs, scalars, image, rows, stream);
 }
 // divideAndRoundQLast of `polys` polynomials over the first moduli_count moduli of pc
-inline hipError_t divide_and_round_q_last(const uint64_t* in, uint64_t* out, const PolyContext& pc, uint32_t moduli_count,
-                                          size_t polys, hipStream_t stream) {
-    return launch_divide_and_round_q_last(in, out, pc.device_context(), moduli_count, polys, stream);
+template <typename W>
+hipError_t divide_and_round_q_last(const W* in, W* out, const PolyContext& pc, uint32_t moduli_count, size_t polys,
+                                   hipStream_t stream) {
+    DeviceImage<W> image{};
+    if (word_image<W>(pc, pc.device_context(), moduli_count, image) != HE_OK) return hipErrorInvalidValue;
+    return launch_divide_and_round_q_last(in, out, image, moduli_count, polys, stream);
 }
-inline hipError_t divide_and_round_q_last(const uint32_t* in, uint32_t* out, const PolyContext& pc, uint32_t moduli_count,
-                                          size_t polys, hipStream_t stream) {
-    DeviceContext32 dc32{};
-    if (pc.device_context32(moduli_count, dc32) != HE_OK) return hipErrorInvalidValue;
-    return launch_divide_and_round_q_last32(in, out, dc32, moduli_count, polys, stream);
-}
-inline hipError_t mul_plain(uint64_t* ct, const uint64_t* pt, const DeviceContext& dc, uint32_t poly_count, size_t batch,
-                            hipStream_t stream) {
+// ct [batch][polys][L][N] *= pt [batch][L][N]: both words read the 8-byte image
+template <typename W>
+hipError_t mul_plain(W* ct, const W* pt, const DeviceContext& dc, uint32_t poly_count, size_t batch, hipStream_t stream) {
     return launch_mul_plain(ct, pt, dc, poly_count, batch, stream);
-}
-inline hipError_t mul_plain(uint32_t* ct, const uint32_t* pt, const DeviceContext& dc, uint32_t poly_count, size_t batch,
-                            hipStream_t stream) {
-    return launch_mul_plain32(ct, pt, dc, poly_count, batch, stream);
 }
 
 // What an entry point needs of pc before it launches on slabs of W: its tables on the current device, and for 4-byte
@@ -75,8 +73,8 @@ inline hipError_t mul_plain(uint32_t* ct, const uint32_t* pt, const DeviceContex
 template <typename W>
 int check_word_device(const PolyContext& pc) {
     if constexpr (sizeof(W) == 8) return pc.check_device();
-    DeviceContext32 dc32{};
-    return pc.device_context32(pc.moduli_count(), dc32);
+    DeviceImage<W> image{};
+    return word_image<W>(pc, pc.device_context(), pc.moduli_count(), image);
 }
 // The 4-byte polynomial entries make that check before they look at the batch, the 8-byte ones behind their argument checks.
 template <typename W>

@@ -9,7 +9,7 @@ test_word32_cases.py:
   grids beyond one generation        1200, 300 and 10 rows at N = 8192 / 16384 / 32768     test_word32_more_rows_than_the_chip_holds
   forward, mul, inverse              a negacyclic product on 4-byte words only             test_word32_negacyclic_product
   elementwise32_kernel               all 49 pairs of {0, 1, 2, (p -+ 1) / 2, p - 2, p - 1} test_word32_elementwise_edge_table
-  launch_ntt32                       N = 65536 refused, the slab untouched                 test_word32_refuses_degree_65536
+  launch_ntt (4-byte)                N = 65536 refused, the slab untouched                 test_word32_refuses_degree_65536
 """
 import numpy as np
 import pytest
