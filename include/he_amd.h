@@ -527,6 +527,53 @@ int he_bfv_plaintext_to_eval_device(const he_bfv_context* ctx, uint32_t moduli_c
 int he_bfv_plaintext_to_coeff_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* plaintext_eval,
                                      uint64_t* out, size_t batch, he_stream s);
 
+/* ---- decryption of resident ciphertexts: plaintexts, noise budgets, transparency ----
+ * The entries below take the slab word as an argument (word_bits 32 or 64, as he_ciphertexts_wire_plan does; 4-byte slabs
+ * need a context from he_bfv_context_create_u32) and have no _u32 twins.  Common to all of them:
+ *   cts         [batch][poly_count][L][N], L = moduli_count, Eval form when is_eval != 0, else Coeff; never written
+ *   secret_key  [L_all][N] Eval over the secret-key context (every coefficient modulus); its first L rows are read
+ *               (PolyRq.mulAssign(secretPoly:), PolyRq/PolyRq.swift:184-194)
+ *   workspace   NULL = stream-ordered scratch, else at least he_bfv_decrypt_workspace_bytes() bytes, 16-byte aligned
+ * Errors: word_bits other than 32 / 64 and moduli_count outside 1..he_bfv_ciphertext_moduli_count are
+ * HE_ERR_INVALID_ARGUMENT, poly_count outside 1..3 is HE_ERR_UNSUPPORTED (no reference ciphertext has more); batch 0 does
+ * nothing.  All enqueue-only on `s`. */
+/* The scratch of the three entries that take a workspace (0 on invalid arguments).  Host only. */
+size_t he_bfv_decrypt_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                                      int is_eval, size_t batch);
+/* Bfv.dotProduct (Bfv/Bfv+Decrypt.swift:188-204): out [batch][L][N] Coeff = c0 + c1 s [+ c2 s^2].  Every ciphertext word is
+ * read once by one kernel; s^2 is formed in registers and never stored.  Of Coeff-form input the polynomials behind the first
+ * are copied into the workspace and transformed there; c0 joins after the inverse transform (the transform is linear). */
+int he_bfv_secret_dot_product_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                                     int is_eval, const void* cts, const void* secret_key, void* out, size_t batch,
+                                     void* workspace, size_t workspace_bytes, he_stream s);
+/* Bfv.decryptCoeff / decryptEval (Bfv/Bfv+Decrypt.swift:21-39): out_plaintexts [batch][N] in slab words, values < t.  The
+ * scaling factor of scaleAndRound is correction_factor^-1 mod t, computed on the host: a factor without an inverse is
+ * HE_ERR_NOT_INVERTIBLE, one that is not below t HE_ERR_INVALID_ARGUMENT. */
+int he_bfv_decrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count, int is_eval,
+                          const void* cts, const void* secret_key, uint64_t correction_factor, void* out_plaintexts,
+                          size_t batch, void* workspace, size_t workspace_bytes, he_stream s);
+/* The integer behind Bfv.noiseBudgetCoeff / noiseBudgetEval (Bfv/Bfv+Decrypt.swift:116-149): per ciphertext the exact
+ * max_k |[t dot_k]_Q|, each composed coefficient (CrtComposer.swift:76-97) centred as `coeff > (Q + 1) >> 1 ? Q - coeff : coeff`.
+ * out_limbs [batch][he_bfv_noise_norm_limbs()] little-endian 64-bit limbs (a DEVICE array).  At most 16 moduli. */
+int he_bfv_noise_norm_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                             int is_eval, const void* cts, const void* secret_key, uint64_t* out_limbs, size_t batch,
+                             void* workspace, size_t workspace_bytes, he_stream s);
+/* Bfv.isTransparentCoeff / isTransparentEval (Bfv/Bfv+Encrypt.swift:48-62): out_flags[b] (a DEVICE byte) = 1 iff every
+ * polynomial of ciphertext b but the first is zero (poly_count 1: always 1). */
+int he_bfv_is_transparent_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                                 const void* cts, uint8_t* out_flags, size_t batch, he_stream s);
+/* ceil(bitlength(q_0 .. q_{L-1}) / 64), 1..16; 0 on invalid arguments.  Host only. */
+uint32_t he_bfv_noise_norm_limbs(const he_bfv_context* ctx, uint32_t moduli_count);
+/* The noise budget of one norm (`limbs`: a HOST array of he_bfv_noise_norm_limbs() limbs), Bfv/Bfv+Decrypt.swift:144-148:
+ * +infinity for 0, else log2(qDouble / (2 Double(norm))) with qDouble the left-to-right product of the Double(q_i) from 1.0 and
+ * Double(norm) rounded to nearest, ties to even.  word_bits is the width of the scheme's scalar T: when
+ * crtComposeMaxIntermediateValue() (CrtComposer.swift:54-61) is not below Double(T.max) the reference composes in a wider
+ * integer and demands variableTime (:151-173) -- variable_time == 0 is then HE_ERR_INVALID_ARGUMENT.  Host only.
+ * Warning (the reference's, :111-112): the noise budget must never be forwarded to another party.  Sharing it acts as an
+ * oracle that can be used to recover the secret key. */
+int he_bfv_noise_budget_from_norm(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, const uint64_t* limbs,
+                                  int variable_time, double* out);
+
 /* =====================================================================================================
  * B4: application hook -- the PIR server's per-chunk response, device-resident
  * =================================================================================================== */

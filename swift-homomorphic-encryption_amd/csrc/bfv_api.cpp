@@ -1,6 +1,8 @@
 // bfv_api.cpp -- B3 entry points: Context<Bfv<UInt64>> and the HeScheme operations on the hot path
 // (reference Sources/HomomorphicEncryption/Bfv/*.swift).  Each operation is a short pipeline of HIP kernels on the
 // caller's stream; nothing here touches the data on the host.
+#include <cmath>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <type_traits>
@@ -8,6 +10,7 @@
 
 #include "api_internal.hpp"
 #include "bfv_context.hpp"
+#include "decrypt_kernels.hpp"
 #include "kernels.hpp"
 #include "rns_kernels.hpp"
 #include "side_lane.hpp"
@@ -771,6 +774,273 @@ int he_rns_scale_and_round_device(const he_bfv_context* ctx, uint32_t moduli_cou
 int he_rns_scale_and_round_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* in,
                                       uint64_t scaling_factor, uint32_t* out, size_t batch, he_stream s) {
     return scale_and_round(ctx, moduli_count, in, scaling_factor, out, batch, s);
+}
+
+// ------------------------------------------------------------------------------------------ decrypt, noise budget
+extern "C++" {
+namespace {
+
+using heamd::NoiseNormTables;
+using heamd::u64;
+
+// the checks the entries with void* slabs share, in this order: the word, the level (check_level), the polynomial count
+int check_decrypt_arguments(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                            const RnsToolLevel** tool) {
+    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    HEAMD_TRY_STATUS(check_level(ctx, moduli_count, tool, word_bits / 8));
+    if (poly_count < 1 || poly_count > heamd::kMaxDecryptPolys) {
+        heamd::set_last_error("a ciphertext has 1..3 polynomials");
+        return HE_ERR_UNSUPPORTED;
+    }
+    return HE_OK;
+}
+
+// Of Coeff-form ciphertexts the polynomials behind the first are transformed in a copy (the caller's slab is const); c0 is
+// added in Coeff form after the inverse transform -- the transform is linear -- and is neither copied nor transformed
+size_t decrypt_copy_words(const BfvContext& bfv, uint32_t moduli_count, uint32_t poly_count, bool is_eval, size_t batch) {
+    return is_eval || poly_count == 1 ? 0 : batch * (poly_count - 1) * moduli_count * bfv.degree();
+}
+size_t decrypt_dot_words(const BfvContext& bfv, uint32_t moduli_count, size_t batch) {
+    return batch * moduli_count * bfv.degree();
+}
+
+// Bfv.dotProduct (Bfv+Decrypt.swift:188-204): out [batch][L][N] Coeff.  eval_copy: decrypt_copy_words words.
+template <typename W>
+int secret_dot_product(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, bool is_eval, const W* cts,
+                       const W* secret_key, W* out, size_t batch, W* eval_copy, hipStream_t stream) {
+    const PolyContext* pc = ctx->impl->ciphertext(moduli_count);
+    const DeviceContext dc = pc->device_context();
+    const size_t poly_words = size_t(moduli_count) * ctx->impl->degree();
+    if (!is_eval && poly_count == 1) {  // the dot product is c0: its two transforms cancel
+        HEAMD_HIP_TRY(hipMemcpyAsync(out, cts, batch * poly_words * sizeof(W), hipMemcpyDeviceToDevice, stream));
+        return HE_OK;
+    }
+    if (is_eval) {
+        HEAMD_HIP_TRY(heamd::launch_secret_dot_product(cts, secret_key, out, dc, poly_count, true, batch, stream));
+        HEAMD_HIP_TRY(ntt_rows(true, out, *pc, dc, moduli_count, batch * moduli_count, stream));
+        return HE_OK;
+    }
+    const size_t tail_bytes = (poly_count - 1) * poly_words * sizeof(W);  // c1.. of one ciphertext
+    HEAMD_HIP_TRY(hipMemcpy2DAsync(eval_copy, tail_bytes, cts + poly_words, poly_count * poly_words * sizeof(W), tail_bytes, batch,
+                                   hipMemcpyDeviceToDevice, stream));
+    HEAMD_HIP_TRY(ntt_rows(false, eval_copy, *pc, dc, moduli_count, batch * (poly_count - 1) * moduli_count, stream));
+    HEAMD_HIP_TRY(heamd::launch_secret_dot_product(eval_copy, secret_key, out, dc, poly_count, false, batch, stream));
+    HEAMD_HIP_TRY(ntt_rows(true, out, *pc, dc, moduli_count, batch * moduli_count, stream));
+    HEAMD_HIP_TRY(heamd::launch_add_first_polynomial(cts, out, dc, poly_count, batch, stream));
+    return HE_OK;
+}
+
+// The dot product of a batch into `dot` (the caller's slab, or the head of the workspace when dot == nullptr), with the checks
+// every entry below makes.  HE_OK with *dot_out == nullptr: nothing to do (batch 0).
+template <typename W>
+int decrypt_dot(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, int is_eval, const void* cts,
+                const void* secret_key, void* dot, size_t batch, void* workspace, size_t workspace_bytes, Scratch& scratch,
+                hipStream_t stream, W** dot_out) {
+    *dot_out = nullptr;
+    if (batch == 0) return HE_OK;
+    if (cts == nullptr || secret_key == nullptr) return invalid_argument("null ciphertexts or secret key");
+    const BfvContext& bfv = *ctx->impl;
+    const size_t copy_words = decrypt_copy_words(bfv, moduli_count, poly_count, is_eval != 0, batch);
+    const size_t dot_words = dot == nullptr ? decrypt_dot_words(bfv, moduli_count, batch) : 0;
+    uint64_t* base = nullptr;
+    if (copy_words + dot_words != 0)
+        HEAMD_TRY_STATUS(resolve_workspace(workspace, workspace_bytes, (copy_words + dot_words) * sizeof(W), scratch, &base));
+    W* words = reinterpret_cast<W*>(base);
+    W* out = dot != nullptr ? static_cast<W*>(dot) : words;
+    HEAMD_TRY_STATUS(secret_dot_product(ctx, moduli_count, poly_count, is_eval != 0, static_cast<const W*>(cts),
+                                        static_cast<const W*>(secret_key), out, batch, words + dot_words, stream));
+    *dot_out = out;
+    return HE_OK;
+}
+
+template <typename W>
+int decrypt_words(const he_bfv_context* ctx, const RnsToolLevel& tool, uint32_t moduli_count, uint32_t poly_count, int is_eval,
+                  const void* cts, const void* secret_key, u64 scaling_factor, void* out_plaintexts, size_t batch,
+                  void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (batch != 0 && out_plaintexts == nullptr) return invalid_argument("null plaintexts");
+    Scratch scratch(stream);
+    W* dot = nullptr;
+    HEAMD_TRY_STATUS(decrypt_dot<W>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, nullptr, batch, workspace,
+                                    workspace_bytes, scratch, stream, &dot));
+    if (dot == nullptr) return HE_OK;
+    const u64 t = ctx->impl->plaintext_modulus();
+    const u64 scaled = heamd::mul_mod(tool.device.inv_gamma_mod_t, scaling_factor, t);  // RnsTool.swift:298
+    const heamd::U64x2 final_scale{scaled, heamd::shoup_factor(scaled, t)};
+    HEAMD_HIP_TRY(heamd::launch_scale_and_round(dot, static_cast<W*>(out_plaintexts), tool.device, final_scale, batch, stream));
+    return HE_OK;
+}
+
+// Q = q_0 .. q_{L-1} as little-endian 64-bit limbs, without leading zero limbs
+std::vector<u64> modulus_product_limbs(const std::vector<u64>& moduli) {
+    std::vector<u64> limbs{1};
+    for (u64 q : moduli) {
+        u64 carry = 0;
+        for (u64& limb : limbs) {
+            const heamd::u128 product = static_cast<heamd::u128>(limb) * q + carry;
+            limb = static_cast<u64>(product);
+            carry = static_cast<u64>(product >> 64);
+        }
+        if (carry != 0) limbs.push_back(carry);
+    }
+    return limbs;
+}
+
+// t mod q_i, and (Q + 1) >> 1 in the norm kernel's mixed radix (decrypt_kernels.hpp).  Q is odd -- every q_i is an NTT
+// modulus --, so (Q + 1) >> 1 is the inverse of 2 mod Q and its residue mod q_i is (q_i + 1) / 2; Garner's digits follow from
+// the residues with the q_j^-1 mod q_i the context holds for divideAndRoundQLast.
+void noise_norm_tables(const BfvContext& bfv, uint32_t moduli_count, NoiseNormTables& tables) {
+    const PolyContext& pc = *bfv.ciphertext(moduli_count);
+    const std::vector<u64>& q = pc.moduli();
+    u64 residue[heamd::kMaxNoiseModuli];
+    for (uint32_t i = 0; i < moduli_count; ++i) {
+        const u64 t = bfv.plaintext_modulus() % q[i];
+        tables.t_mod_q[i] = heamd::U64x2{t, heamd::shoup_factor(t, q[i])};
+        residue[i] = (q[i] + 1) / 2;
+    }
+    for (uint32_t j = moduli_count; j-- > 0;) {
+        tables.half_digits[j] = residue[j];
+        const heamd::U64x2* inverse_q_j = pc.host_inverse_q_last(j);
+        for (uint32_t i = 0; i < j; ++i) {
+            const u64 difference = (residue[i] + q[i] - residue[j] % q[i]) % q[i];  // (moduli are below 2^62)
+            residue[i] = heamd::mul_mod(difference, inverse_q_j[i].x, q[i]);
+        }
+    }
+    tables.limbs = static_cast<uint32_t>(modulus_product_limbs(q).size());
+}
+
+template <typename W>
+int noise_norm_words(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, int is_eval, const void* cts,
+                     const void* secret_key, uint64_t* out_limbs, size_t batch, void* workspace, size_t workspace_bytes,
+                     hipStream_t stream) {
+    if (batch != 0 && out_limbs == nullptr) return invalid_argument("null limbs");
+    Scratch scratch(stream);
+    W* dot = nullptr;
+    HEAMD_TRY_STATUS(decrypt_dot<W>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, nullptr, batch, workspace,
+                                    workspace_bytes, scratch, stream, &dot));
+    if (dot == nullptr) return HE_OK;
+    NoiseNormTables tables{};
+    noise_norm_tables(*ctx->impl, moduli_count, tables);
+    const DeviceContext dc = ctx->impl->ciphertext(moduli_count)->device_context();
+    HEAMD_HIP_TRY(heamd::launch_noise_norm(dot, out_limbs, dc, tables, batch, stream));
+    return HE_OK;
+}
+
+// Double(norm) for a multi-limb integer, rounded to nearest, ties to even: the top 64 bits with every lower bit folded into
+// the lowest of them (far below the 53 bits a double keeps), converted by the hardware's own rounding, then scaled exactly
+double limbs_to_double(const uint64_t* limbs, uint32_t count) {
+    while (count != 0 && limbs[count - 1] == 0) --count;
+    if (count == 0) return 0.0;
+    if (count == 1) return static_cast<double>(limbs[0]);
+    const int shift = 64 * static_cast<int>(count - 2) + heamd::bit_length(limbs[count - 1]);  // bits below the top 64
+    const uint32_t word = static_cast<uint32_t>(shift / 64), offset = static_cast<uint32_t>(shift % 64);
+    uint64_t top = limbs[word] >> offset;
+    if (offset != 0) top |= limbs[word + 1] << (64 - offset);
+    bool sticky = offset != 0 && (limbs[word] & ((uint64_t(1) << offset) - 1)) != 0;
+    for (uint32_t i = 0; i < word; ++i) sticky = sticky || limbs[i] != 0;
+    return std::ldexp(static_cast<double>(top | (sticky ? 1 : 0)), shift);
+}
+
+}  // namespace
+}  // extern "C++"
+
+size_t he_bfv_decrypt_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                                      int is_eval, size_t batch) {
+    if (ctx == nullptr || !ctx->impl->valid(moduli_count) || (word_bits != 32 && word_bits != 64) || poly_count < 1 ||
+        poly_count > heamd::kMaxDecryptPolys)
+        return 0;
+    const BfvContext& bfv = *ctx->impl;
+    return (decrypt_dot_words(bfv, moduli_count, batch) + decrypt_copy_words(bfv, moduli_count, poly_count, is_eval != 0, batch)) *
+           (word_bits / 8);
+}
+
+int he_bfv_secret_dot_product_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                                     int is_eval, const void* cts, const void* secret_key, void* out, size_t batch,
+                                     void* workspace, size_t workspace_bytes, he_stream s) {
+    const RnsToolLevel* tool = nullptr;
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    if (batch != 0 && out == nullptr) return invalid_argument("null dot product");
+    Scratch scratch(as_stream(s));
+    if (word_bits == 32) {
+        uint32_t* dot = nullptr;
+        return decrypt_dot<uint32_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out, batch, workspace,
+                                     workspace_bytes, scratch, as_stream(s), &dot);
+    }
+    uint64_t* dot = nullptr;
+    return decrypt_dot<uint64_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out, batch, workspace, workspace_bytes,
+                                 scratch, as_stream(s), &dot);
+}
+
+int he_bfv_decrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count, int is_eval,
+                          const void* cts, const void* secret_key, uint64_t correction_factor, void* out_plaintexts,
+                          size_t batch, void* workspace, size_t workspace_bytes, he_stream s) {
+    const RnsToolLevel* tool = nullptr;
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    const u64 t = ctx->impl->plaintext_modulus();
+    if (correction_factor >= t) return invalid_argument("correction factor not reduced mod t");
+    u64 scaling_factor = 0;  // correctionFactor.inverseMod(modulus: t) (Bfv+Decrypt.swift:34)
+    if (!heamd::inverse_mod(correction_factor, t, scaling_factor)) {
+        heamd::set_last_error("the correction factor has no inverse mod t");
+        return HE_ERR_NOT_INVERTIBLE;
+    }
+    if (word_bits == 32)
+        return decrypt_words<uint32_t>(ctx, *tool, moduli_count, poly_count, is_eval, cts, secret_key, scaling_factor,
+                                       out_plaintexts, batch, workspace, workspace_bytes, as_stream(s));
+    return decrypt_words<uint64_t>(ctx, *tool, moduli_count, poly_count, is_eval, cts, secret_key, scaling_factor, out_plaintexts,
+                                   batch, workspace, workspace_bytes, as_stream(s));
+}
+
+int he_bfv_noise_norm_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                             int is_eval, const void* cts, const void* secret_key, uint64_t* out_limbs, size_t batch,
+                             void* workspace, size_t workspace_bytes, he_stream s) {
+    const RnsToolLevel* tool = nullptr;
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    if (word_bits == 32)
+        return noise_norm_words<uint32_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out_limbs, batch, workspace,
+                                          workspace_bytes, as_stream(s));
+    return noise_norm_words<uint64_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out_limbs, batch, workspace,
+                                      workspace_bytes, as_stream(s));
+}
+
+int he_bfv_is_transparent_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
+                                 const void* cts, uint8_t* out_flags, size_t batch, he_stream s) {
+    const RnsToolLevel* tool = nullptr;
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    if (batch == 0) return HE_OK;
+    if (cts == nullptr || out_flags == nullptr) return invalid_argument("null ciphertexts or flags");
+    const uint32_t log_degree = tool->device.log_degree;
+    if (word_bits == 32)
+        HEAMD_HIP_TRY(heamd::launch_is_transparent(static_cast<const uint32_t*>(cts), out_flags, log_degree, moduli_count,
+                                                   poly_count, batch, as_stream(s)));
+    else
+        HEAMD_HIP_TRY(heamd::launch_is_transparent(static_cast<const uint64_t*>(cts), out_flags, log_degree, moduli_count,
+                                                   poly_count, batch, as_stream(s)));
+    return HE_OK;
+}
+
+uint32_t he_bfv_noise_norm_limbs(const he_bfv_context* ctx, uint32_t moduli_count) {
+    if (ctx == nullptr || !ctx->impl->valid(moduli_count)) return 0;
+    return static_cast<uint32_t>(modulus_product_limbs(ctx->impl->ciphertext(moduli_count)->moduli()).size());
+}
+
+int he_bfv_noise_budget_from_norm(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, const uint64_t* limbs,
+                                  int variable_time, double* out) {
+    if (ctx == nullptr) return invalid_argument("null context");
+    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    if (!ctx->impl->valid(moduli_count)) return invalid_argument("moduli_count out of range");
+    if (limbs == nullptr || out == nullptr) return invalid_argument("null limbs or result");
+    const std::vector<u64>& q = ctx->impl->ciphertext(moduli_count)->moduli();
+    double q_double = 1.0;
+    for (u64 modulus : q) q_double *= static_cast<double>(modulus);
+    // the reference composes in the narrowest of T, T.DoubleWidth, ... that holds crtComposeMaxIntermediateValue
+    // (CrtComposer.swift:54-61), and anything wider than T is precondition(variableTime) (Bfv+Decrypt.swift:151-173)
+    const double t_max = word_bits == 32 ? static_cast<double>(UINT32_MAX) : static_cast<double>(UINT64_MAX);
+    const double crt_max = q.size() == 1 ? static_cast<double>(q[0]) : 2.0 * q_double;
+    if (!(crt_max < std::pow(t_max, 32))) return invalid_argument("crtComposeMaxIntermediateValue too large");
+    if (!(crt_max < t_max) && variable_time == 0)
+        return invalid_argument("the composed coefficients are wider than a word: variable_time must be set");
+    const double norm = limbs_to_double(limbs, he_bfv_noise_norm_limbs(ctx, moduli_count));
+    *out = norm == 0.0 ? std::numeric_limits<double>::infinity() : std::log2(q_double / (2.0 * norm));
+    return HE_OK;
 }
 
 // ------------------------------------------------------------------------------------------ plaintext <-> Eval

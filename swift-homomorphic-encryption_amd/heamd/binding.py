@@ -182,6 +182,15 @@ SIGNATURES = [
     ("he_rns_scale_and_round_device", ctypes.c_int, [vp, c_u32, vp, c_u64, vp, c_size, vp]),
     ("he_bfv_plaintext_to_eval_device", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp]),
     ("he_bfv_plaintext_to_coeff_device", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp]),
+    # decryption of resident ciphertexts: the slab word is an argument (word_bits), so these have no 4-byte twins
+    ("he_bfv_decrypt_workspace_bytes", c_size, [vp, c_u32, c_u32, c_u32, ctypes.c_int, c_size]),
+    ("he_bfv_secret_dot_product_device", ctypes.c_int, [vp, c_u32, c_u32, c_u32, ctypes.c_int, vp, vp, vp, c_size, vp, c_size,
+                                                        vp]),
+    ("he_bfv_decrypt_device", ctypes.c_int, [vp, c_u32, c_u32, c_u32, ctypes.c_int, vp, vp, c_u64, vp, c_size, vp, c_size, vp]),
+    ("he_bfv_noise_norm_device", ctypes.c_int, [vp, c_u32, c_u32, c_u32, ctypes.c_int, vp, vp, vp, c_size, vp, c_size, vp]),
+    ("he_bfv_is_transparent_device", ctypes.c_int, [vp, c_u32, c_u32, c_u32, vp, vp, c_size, vp]),
+    ("he_bfv_noise_norm_limbs", c_u32, [vp, c_u32]),
+    ("he_bfv_noise_budget_from_norm", ctypes.c_int, [vp, c_u32, c_u32, U64P, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     ("he_pir_compute_response_chunk_device", ctypes.c_int,
      [vp, ctypes.POINTER(c_u32), c_u32, vp, vp, c_size, vp, ctypes.POINTER(ctypes.c_uint8), vp, vp, vp]),
     ("he_pir_dim0_columns_device", ctypes.c_int, [vp, vp, c_size, vp, vp, c_size, vp, vp]),
@@ -1041,6 +1050,84 @@ class BfvContext:
         out = _empty((batch, self.degree), w, plaintext_eval.device)
         _check(_entry("he_bfv_plaintext_to_coeff_device", w)(
             self.h, L, _ptr(plaintext_eval, w), _ptr(out, w), batch, _stream(stream)))
+        return out
+
+    # ---- decryption of resident ciphertexts.  cts: [batch][polys][L][N] in the class's slab word, Coeff form unless
+    # eval_format; secret_key: [L_all][N] Eval over every coefficient modulus (its first L rows are read).
+    @staticmethod
+    def _ciphertext_shape(cts):
+        if cts.dim() != 4:
+            raise ValueError("expected ciphertexts as [batch][polys][L][N]")
+        return cts.shape[0], cts.shape[1], cts.shape[2]
+
+    def decrypt_workspace_bytes(self, batch, poly_count=2, eval_format=False, moduli_count=None):
+        return int(load_library().he_bfv_decrypt_workspace_bytes(
+            self.h, self._word.bits, self._L(moduli_count), poly_count, int(eval_format), batch))
+
+    def secret_dot_product(self, cts, secret_key, eval_format=False, stream=None, workspace=None):
+        """Bfv.dotProduct: c0 + c1 s [+ c2 s^2] -> [batch][L][N] Coeff."""
+        (batch, polys, L), w = self._ciphertext_shape(cts), self._word
+        out = _empty((batch, L, self.degree), w, cts.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_secret_dot_product_device(
+            self.h, w.bits, L, polys, int(eval_format), _ptr(cts, w), _ptr(secret_key, w), _ptr(out, w), batch, ws_ptr,
+            ws_bytes, _stream(stream)))
+        return out
+
+    def decrypt(self, cts, secret_key, correction_factor=1, eval_format=False, stream=None, workspace=None):
+        """Bfv.decryptCoeff / decryptEval -> [batch][N], values < t."""
+        (batch, polys, L), w = self._ciphertext_shape(cts), self._word
+        out = _empty((batch, self.degree), w, cts.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_decrypt_device(
+            self.h, w.bits, L, polys, int(eval_format), _ptr(cts, w), _ptr(secret_key, w), int(correction_factor),
+            _ptr(out, w), batch, ws_ptr, ws_bytes, _stream(stream)))
+        return out
+
+    def noise_norm_limbs(self, moduli_count=None):
+        return int(load_library().he_bfv_noise_norm_limbs(self.h, self._L(moduli_count)))
+
+    def noise_norm_device(self, cts, secret_key, eval_format=False, stream=None, workspace=None):
+        """max_k |[t (c0 + c1 s + ..)_k]_Q| per ciphertext -> [batch][limbs] little-endian 64-bit limbs (int64), enqueue-only."""
+        (batch, polys, L), w = self._ciphertext_shape(cts), self._word
+        out = _empty((batch, self.noise_norm_limbs(L)), WORD64, cts.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_noise_norm_device(
+            self.h, w.bits, L, polys, int(eval_format), _ptr(cts, w), _ptr(secret_key, w), _ptr(out), batch, ws_ptr, ws_bytes,
+            _stream(stream)))
+        return out
+
+    def noise_norm(self, cts, secret_key, eval_format=False, stream=None, workspace=None):
+        """The same as Python integers (synchronises)."""
+        limbs = self.noise_norm_device(cts, secret_key, eval_format, stream, workspace)
+        if stream is not None:
+            stream.synchronize()
+        return [sum(int(limb) << (64 * i) for i, limb in enumerate(row)) for row in to_host(limbs).reshape(limbs.shape)]
+
+    def noise_budget_from_norm(self, norm, moduli_count=None, variable_time=True):
+        """Bfv.noiseBudget's last step for one norm (host only).  Never forward a noise budget to another party."""
+        L = self._L(moduli_count)
+        limbs = _u64([(int(norm) >> (64 * i)) & (2**64 - 1) for i in range(self.noise_norm_limbs(L))])
+        out = ctypes.c_double(0.0)
+        _check(load_library().he_bfv_noise_budget_from_norm(
+            self.h, self.word_bits, L, limbs.ctypes.data_as(U64P), int(variable_time), ctypes.byref(out)))
+        return out.value
+
+    def noise_budget(self, cts, secret_key, eval_format=False, variable_time=True, stream=None, workspace=None):
+        """Bfv.noiseBudgetCoeff / noiseBudgetEval per ciphertext -> floats (synchronises).  Never forward a noise budget to
+        another party: sharing it acts as an oracle that can be used to recover the secret key."""
+        L = self._ciphertext_shape(cts)[2]
+        return [self.noise_budget_from_norm(norm, L, variable_time)
+                for norm in self.noise_norm(cts, secret_key, eval_format, stream, workspace)]
+
+    def is_transparent(self, cts, stream=None):
+        """Bfv.isTransparent per ciphertext -> [batch] uint8 (1: every polynomial but the first is zero)."""
+        import torch
+
+        (batch, polys, L), w = self._ciphertext_shape(cts), self._word
+        out = torch.empty((batch,), dtype=torch.uint8, device=cts.device)
+        _check(load_library().he_bfv_is_transparent_device(
+            self.h, w.bits, L, polys, _ptr(cts, w), vp(out.data_ptr()), batch, _stream(stream)))
         return out
 
     def pir_expand(self, ciphertexts, output_count, galois_keys, stream=None):
