@@ -574,6 +574,86 @@ uint32_t he_bfv_noise_norm_limbs(const he_bfv_context* ctx, uint32_t moduli_coun
 int he_bfv_noise_budget_from_norm(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, const uint64_t* limbs,
                                   int variable_time, double* out);
 
+/* ---- secret keys, encryption and evaluation keys made on the device from caller-supplied seeds ----
+ * The reference draws the secret key and the error polynomials from SystemRandomNumberGenerator and `a` from
+ * NistAes128Ctr(seed:); its samplers are written over any generator (PolyRq/PolyRq+Randomize.swift:87, :120).  Here EVERY
+ * random polynomial is a function of a 32-byte seed through NistAes128Ctr(seed:) and equals, word for word, what the
+ * reference's sampler gives on that generator.  The library generates no seed: seeds come from the caller's CSPRNG, one fresh
+ * seed per polynomial, and error and key seeds are as secret as the key.  Only an `a` seed may be published (it is the seed of a
+ * seeded ciphertext).
+ * The entries take the slab word as an argument (word_bits 32 or 64; 4-byte slabs need a context from
+ * he_bfv_context_create_u32) and have no _u32 twins.  Common to them:
+ *   seeds       DEVICE bytes, [..][32]
+ *   secret_key  [L_all][N] Eval over the secret-key context (every coefficient modulus), as he_bfv_decrypt_device reads it
+ *   workspace   NULL = stream-ordered scratch, else at least he_bfv_encrypt_workspace_bytes() bytes, 16-byte aligned.
+ *               Everything in it that depends on a secret (the DRBG records of error and key seeds, error polynomials and
+ *               their transforms, s^2 and rotated keys) is overwritten with zeros on `s` before the entry releases it or returns:
+ *               the first he_bfv_encrypt_workspace_bytes() bytes of a caller's workspace read zero once the stream has drained.
+ * Errors: word_bits other than 32 / 64 and moduli_count outside its range HE_ERR_INVALID_ARGUMENT; a 4-byte call on a
+ * Bfv<UInt64> context HE_ERR_INVALID_ARGUMENT, as the decryption entries; key generation on a context with one coefficient
+ * modulus HE_ERR_UNSUPPORTED (supportsEvaluationKey, Bfv/Bfv+Keys.swift:35-37); on 4-byte words a degree above 32768
+ * HE_ERR_UNSUPPORTED.  All are reported before anything is enqueued.  A count of 0 does nothing.  All enqueue-only on `s`.
+ * Known limitation: the AES behind the stream is a T-table implementation in LDS; its timing depends on the bank pattern of
+ * data-dependent lookups, i.e. it is not constant-time, and secret seeds pass through it. */
+enum he_encrypt_operation {
+    HE_ENCRYPT_OP_SECRET_KEY = 0,         /* count = batch; moduli_count and eval_out ignored */
+    HE_ENCRYPT_OP_ENCRYPT_ZERO = 1,       /* count = batch */
+    HE_ENCRYPT_OP_ENCRYPT = 2,            /* count = batch; eval_out ignored */
+    HE_ENCRYPT_OP_KEY_SWITCH_KEYS = 3,    /* count = keys; moduli_count and eval_out ignored */
+    HE_ENCRYPT_OP_RELINEARIZATION_KEY = 4, /* count ignored */
+    HE_ENCRYPT_OP_GALOIS_KEYS = 5         /* count = elements */
+};
+/* The scratch of the entry `operation` (0 on invalid arguments).  Host only. */
+size_t he_bfv_encrypt_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, int operation, uint32_t moduli_count,
+                                      int eval_out, size_t count);
+/* Bfv.generateSecretKey (Bfv/Bfv+Keys.swift:20-26): randomizeTernary, then forwardNtt.  out [batch][L_all][N] Eval. */
+int he_bfv_generate_secret_key_device(const he_bfv_context* ctx, uint32_t word_bits, const uint8_t* seeds, void* out,
+                                      size_t batch, void* workspace, size_t workspace_bytes, he_stream s);
+/* Bfv.encryptZero(for:using:with:) (Bfv/Bfv+Encrypt.swift:150-181) over the first m = moduli_count coefficient moduli,
+ * 1 <= m <= L_all (m = L_all: the key-switching context of key generation); the first m rows of the one secret key are read.
+ * out [batch][2][m][N].  eval_out == 0: Coeff form, [-(INTT(a s) + e), INTT(a)], the canonical ciphertext; eval_out != 0: the
+ * words of that ciphertext forward-transformed, [-(a s + NTT(e)), a], formed without an inverse transform.  a_seeds[b] is the
+ * `seed` of ciphertext b. */
+int he_bfv_encrypt_zero_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, int eval_out,
+                               const void* secret_key, const uint8_t* a_seeds, const uint8_t* error_seeds, void* out,
+                               size_t batch, void* workspace, size_t workspace_bytes, he_stream s);
+/* Bfv.encrypt (Bfv/Bfv+Encrypt.swift:66-73) = encryptZero + plaintextTranslate(.Add) (:75-139): plaintexts [batch][N] slab
+ * words, values < t; out [batch][2][m][N] Coeff, 1 <= m <= he_bfv_ciphertext_moduli_count.  Word for word
+ * he_bfv_encrypt_zero_device followed by he_bfv_add_plain_device. */
+int he_bfv_encrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, const void* secret_key,
+                          const uint8_t* a_seeds, const uint8_t* error_seeds, const void* plaintexts, void* out, size_t batch,
+                          void* workspace, size_t workspace_bytes, he_stream s);
+/* Bfv._generateKeySwitchKey (Bfv/Bfv+Keys.swift:69-103) for `keys` current keys at once: current_keys [keys][L+1][N] Eval,
+ * a_seeds / error_seeds [keys][L][32], out [keys][L][2][L+1][N] Eval, L = he_bfv_ciphertext_moduli_count.  Ciphertext j of a key
+ * is an Eval encryption of zero over all L + 1 moduli with (q_ks mod q_j) currentKey[j] added to row j of polynomial 0.  The
+ * current keys belong to the caller (the reference zeroizes its own copy).  At most 32 ciphertext moduli. */
+int he_bfv_generate_key_switch_keys_device(const he_bfv_context* ctx, uint32_t word_bits, const void* secret_key,
+                                           const void* current_keys, const uint8_t* a_seeds, const uint8_t* error_seeds,
+                                           void* out, size_t keys, void* workspace, size_t workspace_bytes, he_stream s);
+/* Bfv.generateRelinearizationKey (Bfv/Bfv+Keys.swift:58-65): the key-switch key of s s, formed in the workspace.
+ * a_seeds / error_seeds [L][32], out [L][2][L+1][N] Eval as he_bfv_relinearize_device takes it. */
+int he_bfv_generate_relinearization_key_device(const he_bfv_context* ctx, uint32_t word_bits, const void* secret_key,
+                                               const uint8_t* a_seeds, const uint8_t* error_seeds, void* out, void* workspace,
+                                               size_t workspace_bytes, he_stream s);
+/* The Galois keys of Bfv.generateEvaluationKey (Bfv/Bfv+Keys.swift:38-45): per element the key-switch key of
+ * applyGalois(s, element), formed in the workspace.  elements: a HOST array of `count` elements, each odd and in (1, 2N) as
+ * he_poly_apply_galois_device demands (else HE_ERR_INVALID_ARGUMENT); a_seeds / error_seeds [count][L][32]; out
+ * [count][L][2][L+1][N] Eval, slice e the key he_bfv_apply_galois_device takes for elements[e]. */
+int he_bfv_generate_galois_keys_device(const he_bfv_context* ctx, uint32_t word_bits, const void* secret_key,
+                                       const uint64_t* elements, size_t count, const uint8_t* a_seeds,
+                                       const uint8_t* error_seeds, void* out, void* workspace, size_t workspace_bytes,
+                                       he_stream s);
+/* The polynomial-level samplers, twins of he_poly_random_from_seeds_device: seeds [batch][32] DEVICE bytes -> out
+ * [batch][L][N] Coeff in slab words of word_bits.  randomizeTernary (PolyRq/PolyRq+Randomize.swift:87-104): 12 stream bytes
+ * per coefficient, (value mod 3) - 1 in every row.  randomizeCenteredBinomialDistribution (:120-167) at the only
+ * ErrorStdDev, stdDev32: 16 stream bytes per coefficient, popcount of 21 bits minus popcount of 21 bits.  Their DRBG records
+ * live in stream-ordered scratch and are zeroized before it is released.  A modulus that does not fit 4-byte words:
+ * HE_ERR_INVALID_MODULUS. */
+int he_poly_random_ternary_from_seeds_device(const he_poly_context* ctx, uint32_t word_bits, const uint8_t* seeds, size_t batch,
+                                             void* out, he_stream s);
+int he_poly_random_centered_binomial_from_seeds_device(const he_poly_context* ctx, uint32_t word_bits, const uint8_t* seeds,
+                                                       size_t batch, void* out, he_stream s);
+
 /* =====================================================================================================
  * B4: application hook -- the PIR server's per-chunk response, device-resident
  * =================================================================================================== */
@@ -1366,6 +1446,9 @@ int he_ntt_device_variant(const he_poly_context* ctx, uint64_t* device_slab, siz
  * (RnsTool.swift:28-33). */
 int he_bfv_context_create_host_only(uint32_t degree, uint64_t plaintext_modulus, const uint64_t* coefficient_moduli,
                                     uint32_t moduli_count, he_bfv_context** out);
+/* The same for Context<Bfv<UInt32>> (he_bfv_context_create_u32's checks and constants, nothing uploaded). */
+int he_bfv_context_create_u32_host_only(uint32_t degree, uint64_t plaintext_modulus, const uint64_t* coefficient_moduli,
+                                        uint32_t moduli_count, he_bfv_context** out);
 int he_bfv_copy_bsk_moduli(const he_bfv_context* ctx, uint64_t* out_bsk);
 
 #ifdef __cplusplus

@@ -485,6 +485,10 @@ int he_bfv_context_create_u32(uint32_t degree, uint64_t plaintext_modulus, const
                               uint32_t moduli_count, he_bfv_context** out) {
     return bfv_create(degree, plaintext_modulus, coefficient_moduli, moduli_count, false, out, 32);
 }
+int he_bfv_context_create_u32_host_only(uint32_t degree, uint64_t plaintext_modulus, const uint64_t* coefficient_moduli,
+                                        uint32_t moduli_count, he_bfv_context** out) {
+    return bfv_create(degree, plaintext_modulus, coefficient_moduli, moduli_count, true, out, 32);
+}
 void he_bfv_context_destroy(he_bfv_context* ctx) {
     heamd::RelaxedCapture relaxed;  // (api_internal.hpp: safe beside another thread's -- or this thread's -- graph capture)
     delete ctx;

@@ -15,6 +15,7 @@
 
 #include "device_context.hpp"
 #include "device_math.hpp"
+#include "galois_index.hpp"
 #include "kernels.hpp"
 #include "launch_grid.hpp"
 #include "serialize_form.hpp"
@@ -70,10 +71,7 @@ __global__ void __launch_bounds__(kThreads)
          idx += static_cast<size_t>(gridDim.x) * kThreads) {
         const size_t row = idx >> logn;
         const uint32_t i = static_cast<uint32_t>(idx) & (n - 1);
-        const uint32_t reversed = __brev(i + n) >> (32 - (logn + 1));
-        const uint32_t raw = ((element * reversed) >> 1) & (n - 1);
-        const uint32_t source = logn == 0 ? 0 : __brev(raw) >> (32 - logn);
-        out[idx] = in[(row << logn) + source];
+        out[idx] = in[(row << logn) + galois_eval_source(i, logn, element)];
     }
 }
 

@@ -191,6 +191,16 @@ SIGNATURES = [
     ("he_bfv_is_transparent_device", ctypes.c_int, [vp, c_u32, c_u32, c_u32, vp, vp, c_size, vp]),
     ("he_bfv_noise_norm_limbs", c_u32, [vp, c_u32]),
     ("he_bfv_noise_budget_from_norm", ctypes.c_int, [vp, c_u32, c_u32, U64P, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
+    # secret keys, encryption, evaluation keys from caller-supplied seeds: word_bits is an argument here too
+    ("he_bfv_encrypt_workspace_bytes", c_size, [vp, c_u32, ctypes.c_int, c_u32, ctypes.c_int, c_size]),
+    ("he_bfv_generate_secret_key_device", ctypes.c_int, [vp, c_u32, vp, vp, c_size, vp, c_size, vp]),
+    ("he_bfv_encrypt_zero_device", ctypes.c_int, [vp, c_u32, c_u32, ctypes.c_int, vp, vp, vp, vp, c_size, vp, c_size, vp]),
+    ("he_bfv_encrypt_device", ctypes.c_int, [vp, c_u32, c_u32, vp, vp, vp, vp, vp, c_size, vp, c_size, vp]),
+    ("he_bfv_generate_key_switch_keys_device", ctypes.c_int, [vp, c_u32, vp, vp, vp, vp, vp, c_size, vp, c_size, vp]),
+    ("he_bfv_generate_relinearization_key_device", ctypes.c_int, [vp, c_u32, vp, vp, vp, vp, vp, c_size, vp]),
+    ("he_bfv_generate_galois_keys_device", ctypes.c_int, [vp, c_u32, vp, U64P, c_size, vp, vp, vp, vp, c_size, vp]),
+    ("he_poly_random_ternary_from_seeds_device", ctypes.c_int, [vp, c_u32, vp, c_size, vp, vp]),
+    ("he_poly_random_centered_binomial_from_seeds_device", ctypes.c_int, [vp, c_u32, vp, c_size, vp, vp]),
     ("he_pir_compute_response_chunk_device", ctypes.c_int,
      [vp, ctypes.POINTER(c_u32), c_u32, vp, vp, c_size, vp, ctypes.POINTER(ctypes.c_uint8), vp, vp, vp]),
     ("he_pir_dim0_columns_device", ctypes.c_int, [vp, vp, c_size, vp, vp, c_size, vp, vp]),
@@ -283,6 +293,7 @@ SIGNATURES = [
     ("he_poly_context_copy_ntt_tables", ctypes.c_int, [vp, c_u32, U64P, U64P, U64P, U64P, U64P, U64P]),
     ("he_ntt_device_variant", ctypes.c_int, [vp, vp, c_size, ctypes.c_int, ctypes.c_int, vp]),
     ("he_bfv_context_create_host_only", ctypes.c_int, [c_u32, c_u64, U64P, c_u32, ctypes.POINTER(vp)]),
+    ("he_bfv_context_create_u32_host_only", ctypes.c_int, [c_u32, c_u64, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_bfv_copy_bsk_moduli", ctypes.c_int, [vp, U64P]),
 ]
 _TWINNED = (
@@ -804,6 +815,21 @@ class PolyContext:
     def random_from_seeds_u32(self, seeds, stream=None):
         return self._random_from_seeds(seeds, WORD32, stream)
 
+    def _sample_from_seeds(self, entry, seeds, word, stream):
+        batch = seeds.numel() // 32
+        out = _empty((batch, len(self.moduli), self.degree), word, seeds.device)
+        _check(getattr(load_library(), entry)(self.h, word.bits, vp(seeds.data_ptr()), batch, vp(out.data_ptr()),
+                                              _stream(stream)))
+        return out
+
+    def random_ternary_from_seeds(self, seeds, word=WORD64, stream=None):
+        """randomizeTernary over NistAes128Ctr(seed:) per seed: uint8 tensor [batch][32] -> [batch][L][N] Coeff in `word`."""
+        return self._sample_from_seeds("he_poly_random_ternary_from_seeds_device", seeds, word, stream)
+
+    def random_centered_binomial_from_seeds(self, seeds, word=WORD64, stream=None):
+        """randomizeCenteredBinomialDistribution (stdDev32) over NistAes128Ctr(seed:) per seed -> [batch][L][N] Coeff."""
+        return self._sample_from_seeds("he_poly_random_centered_binomial_from_seeds_device", seeds, word, stream)
+
     def serialization_byte_count(self, skip_lsbs=0):
         return int(load_library().he_poly_serialization_byte_count(self.h, skip_lsbs))
 
@@ -1128,6 +1154,79 @@ class BfvContext:
         out = torch.empty((batch,), dtype=torch.uint8, device=cts.device)
         _check(load_library().he_bfv_is_transparent_device(
             self.h, w.bits, L, polys, _ptr(cts, w), vp(out.data_ptr()), batch, _stream(stream)))
+        return out
+
+    # ---- secret keys, encryption and evaluation keys from caller-supplied seeds (uint8 tensors [..][32] on the device; the
+    # library generates none: draw them from os.urandom).  Error and key seeds are as secret as the key.
+    ENCRYPT_OPERATIONS = {"secret_key": 0, "encrypt_zero": 1, "encrypt": 2, "key_switch_keys": 3, "relinearization_key": 4,
+                          "galois_keys": 5}
+
+    @property
+    def coefficient_moduli_count(self):
+        return len(self.coefficient_moduli)
+
+    def encrypt_workspace_bytes(self, operation, count=1, moduli_count=None, eval_out=False):
+        return int(load_library().he_bfv_encrypt_workspace_bytes(
+            self.h, self._word.bits, self.ENCRYPT_OPERATIONS[operation], self._L(moduli_count), int(eval_out), count))
+
+    def generate_secret_key(self, seeds, stream=None, workspace=None):
+        """Bfv.generateSecretKey per seed -> [batch][L_all][N] Eval; one key is what decrypt and encrypt take."""
+        batch, w = seeds.numel() // 32, self._word
+        out = _empty((batch, self.coefficient_moduli_count, self.degree), w, seeds.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_generate_secret_key_device(
+            self.h, w.bits, vp(seeds.data_ptr()), _ptr(out, w), batch, ws_ptr, ws_bytes, _stream(stream)))
+        return out
+
+    def encrypt_zero(self, secret_key, a_seeds, error_seeds, moduli_count=None, eval_out=False, stream=None, workspace=None):
+        """Bfv.encryptZero over the first moduli_count coefficient moduli (up to L_all) -> [batch][2][m][N]."""
+        batch, m, w = a_seeds.numel() // 32, self._L(moduli_count), self._word
+        out = _empty((batch, 2, m, self.degree), w, a_seeds.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_encrypt_zero_device(
+            self.h, w.bits, m, int(eval_out), _ptr(secret_key, w), vp(a_seeds.data_ptr()), vp(error_seeds.data_ptr()),
+            _ptr(out, w), batch, ws_ptr, ws_bytes, _stream(stream)))
+        return out
+
+    def encrypt(self, plaintexts, secret_key, a_seeds, error_seeds, moduli_count=None, stream=None, workspace=None):
+        """Bfv.encrypt: plaintexts [batch][N] (values < t) -> [batch][2][L][N] Coeff; a_seeds[b] is ciphertext b's seed."""
+        batch, m, w = a_seeds.numel() // 32, self._L(moduli_count), self._word
+        out = _empty((batch, 2, m, self.degree), w, a_seeds.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_encrypt_device(
+            self.h, w.bits, m, _ptr(secret_key, w), vp(a_seeds.data_ptr()), vp(error_seeds.data_ptr()), _ptr(plaintexts, w),
+            _ptr(out, w), batch, ws_ptr, ws_bytes, _stream(stream)))
+        return out
+
+    def generate_key_switch_keys(self, secret_key, current_keys, a_seeds, error_seeds, stream=None, workspace=None):
+        """Bfv._generateKeySwitchKey: current_keys [keys][L+1][N] Eval, seeds [keys][L][32] -> [keys][L][2][L+1][N] Eval."""
+        keys, w = current_keys.numel() // ((self.L + 1) * self.degree), self._word
+        out = _empty((keys, self.L, 2, self.L + 1, self.degree), w, current_keys.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_generate_key_switch_keys_device(
+            self.h, w.bits, _ptr(secret_key, w), _ptr(current_keys, w), vp(a_seeds.data_ptr()), vp(error_seeds.data_ptr()),
+            _ptr(out, w), keys, ws_ptr, ws_bytes, _stream(stream)))
+        return out
+
+    def generate_relinearization_key(self, secret_key, a_seeds, error_seeds, stream=None, workspace=None):
+        """Bfv.generateRelinearizationKey: seeds [L][32] -> [L][2][L+1][N] Eval, what relinearize takes."""
+        w = self._word
+        out = _empty((self.L, 2, self.L + 1, self.degree), w, secret_key.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_generate_relinearization_key_device(
+            self.h, w.bits, _ptr(secret_key, w), vp(a_seeds.data_ptr()), vp(error_seeds.data_ptr()), _ptr(out, w), ws_ptr,
+            ws_bytes, _stream(stream)))
+        return out
+
+    def generate_galois_keys(self, secret_key, elements, a_seeds, error_seeds, stream=None, workspace=None):
+        """The Galois keys of Bfv.generateEvaluationKey: seeds [elements][L][32] -> [elements][L][2][L+1][N] Eval, slice e the
+        key apply_galois takes for elements[e]."""
+        w, element_array = self._word, _u64(list(elements))
+        out = _empty((len(element_array), self.L, 2, self.L + 1, self.degree), w, secret_key.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_bfv_generate_galois_keys_device(
+            self.h, w.bits, _ptr(secret_key, w), element_array.ctypes.data_as(U64P), len(element_array),
+            vp(a_seeds.data_ptr()), vp(error_seeds.data_ptr()), _ptr(out, w), ws_ptr, ws_bytes, _stream(stream)))
         return out
 
     def pir_expand(self, ciphertexts, output_count, galois_keys, stream=None):
