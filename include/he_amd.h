@@ -21,6 +21,27 @@
  *    (he_device_malloc / any HIP allocation, e.g. a torch tensor's data_ptr()).
  *  - A context lives on the HIP device that was current when it was created; calls must be made with that device
  *    current (one process per GPU).
+ *  - Pointer contract: what may alias among the device slabs of ONE call (every `*_device` entry of B1-B3; the composite
+ *    protocol entries of B4 and below -- he_pir_*, he_pnns_*, he_simple_pir_*, he_keyword_*, he_*_group -- are not covered
+ *    yet).  A slab is the byte range its layout spans, [pointer, pointer + bytes); a caller's `workspace` is the range
+ *    [workspace, workspace + workspace_bytes) and counts as written; records `stride` bytes apart span from the first
+ *    record's first byte to the last record's last byte.
+ *      1. Slabs a call only reads (the operands of a product, a key, a plaintext, seeds) may be the same memory or overlap
+ *         freely: he_bfv_mul_device(ct, ct) squares, he_bfv_inner_product_device(v, v) is fine.
+ *      2. An in-place entry (`lhs` / `data` / `ct` is updated) takes its read-only operand at EXACTLY the slab it updates where
+ *         each lane reads only the words it writes: he_poly_add/sub/mul_device(x, x) double, clear and square x;
+ *         he_bfv_mul_plain_device with pt == ct for one ciphertext (batch == 1: the ciphertext times its own first
+ *         polynomial) or one polynomial per ciphertext.  Any other overlap of the two is HE_ERR_INVALID_ARGUMENT.
+ *      3. An out-of-place entry refuses every overlap between a slab it writes and any other slab of the call:
+ *         HE_ERR_INVALID_ARGUMENT, text "<operation>: <written> overlaps <other>", before anything is enqueued -- the
+ *         lanes of a kernel run in no particular order, so such a call would be right for some shapes and silently wrong
+ *         for others.  The exceptions, each lane-local by construction and stated again at its entry:
+ *           he_bfv_relinearize_device             batch == 1 and out == ct3: one ciphertext onto its own (c0, c1)
+ *           he_bfv_apply_galois[_grouped]_device  out == ct: ct is permuted into the workspace before out is stored
+ *           he_bfv_mod_switch_down_to_single_device  moduli_count == 1 and out == in: already there, nothing is done
+ *      4. Abutting ranges do not overlap.  Empty ranges (a batch of 0) overlap nothing: such calls stay no-ops.
+ *    The refusal is an argument check: the scheme, decrypt and encrypt entries make it ahead of the device check (a host-only
+ *    context refuses an overlap too), the 4-byte polynomial entries behind it, where their null-slab check is.
  */
 #ifndef HE_AMD_H
 #define HE_AMD_H
@@ -165,7 +186,8 @@ int he_ntt_inverse_rows_device(const he_poly_context* ctx, uint64_t modulus, uin
                                he_stream stream);
 
 /* PolyRq += / -= / prefix - / *= (Eval) / *= [T]  (PolyRq/PolyRq.swift:147-174,299-309,184-204,232-245).
- * lhs/data are updated in place; slabs are [batch][L][N]. */
+ * lhs/data are updated in place; slabs are [batch][L][N].  rhs may be lhs itself (x + x, x - x, x * x: a lane reads only the
+ * words it writes); any other overlap of the two is HE_ERR_INVALID_ARGUMENT. */
 int he_poly_add_device(const he_poly_context* ctx, uint64_t* lhs, const uint64_t* rhs, size_t batch, he_stream s);
 int he_poly_sub_device(const he_poly_context* ctx, uint64_t* lhs, const uint64_t* rhs, size_t batch, he_stream s);
 int he_poly_neg_device(const he_poly_context* ctx, uint64_t* data, size_t batch, he_stream s);
@@ -174,20 +196,21 @@ int he_poly_mul_device(const he_poly_context* ctx, uint64_t* lhs, const uint64_t
 int he_poly_mul_scalar_device(const he_poly_context* ctx, uint64_t* data, const uint64_t* scalar_residues,
                               size_t batch, he_stream s);
 /* PolyRq<_,Coeff>.divideAndRoundQLast() (PolyRq/PolyRq.swift:365-393): in [batch][L][N] -> out [batch][L-1][N].
- * invalidPolyContext when the context has no next (L == 1). */
+ * invalidPolyContext when the context has no next (L == 1).  out overlapping in is HE_ERR_INVALID_ARGUMENT: polynomial p
+ * reads rows p L .. and writes rows p (L - 1) .., which in place are rows an earlier polynomial still reads. */
 int he_poly_divide_and_round_q_last_device(const he_poly_context* ctx, const uint64_t* in, uint64_t* out,
                                            size_t batch, he_stream s);
 int he_poly_divide_and_round_q_last(const he_poly_context* ctx, const uint64_t* host_in, uint64_t* host_out,
                                     size_t batch);
 /* PolyRq.addingLazyProduct (PolyRq/PolyRq.swift:210-225): acc[k] &+= lhs[k]*rhs[k] in wrapping UInt128.
  * acc is [L][N] UInt128 stored little-endian as (lo, hi) word pairs.  he_poly_reduce_accumulator_device is
- * Bfv.reduceToCiphertext's per-polynomial step (Bfv/Bfv.swift:380-394). */
+ * Bfv.reduceToCiphertext's per-polynomial step (Bfv/Bfv.swift:380-394).  acc overlaps neither operand, out not acc. */
 int he_poly_adding_lazy_product_device(const he_poly_context* ctx, const uint64_t* lhs, const uint64_t* rhs,
                                        uint64_t* acc_lo_hi, he_stream s);
 int he_poly_reduce_accumulator_device(const he_poly_context* ctx, const uint64_t* acc_lo_hi, uint64_t* out,
                                       he_stream s);
 
-/* ---- "next" rows of the scope table: index permutations; in and out must not alias ---- */
+/* ---- "next" rows of the scope table: index permutations; out overlapping in is HE_ERR_INVALID_ARGUMENT ---- */
 /* PolyRq.applyGalois(element:) f(x) -> f(x^element) on [batch][L][N] slabs; eval_format = 0 for Coeff
  * (PolyRq/Galois.swift:115-143), 1 for Eval (PolyRq/Galois.swift:153-168).  An invalid element (even, <= 1,
  * >= 2N; Galois.swift:100-105) is the reference's precondition -> HE_ERR_INVALID_ARGUMENT. */
@@ -202,7 +225,8 @@ int he_poly_multiply_power_of_x_device(const he_poly_context* ctx, const uint64_
  * to a byte; rows follow one another (CoefficientPacking.swift:169-213, PolyRq/PolyRq+Serialize.swift:69-99).
  * he_poly_serialization_byte_count = PolyContext.serializationByteCount(skipLSBs:) (0 on invalid arguments).
  * device_bytes is [batch][byte count] (serialize) / [batch][bytes_per_poly] (deserialize; the leading byte count
- * of each record is read, a shorter record is serializedBufferSizeMismatch). */
+ * of each record is read, a shorter record is serializedBufferSizeMismatch).  The bytes and the slab of a call do not overlap
+ * (HE_ERR_INVALID_ARGUMENT), here and in the seeded, the ciphertext and the 4-byte forms below. */
 size_t he_poly_serialization_byte_count(const he_poly_context* ctx, int skip_lsbs);
 int he_poly_serialize_device(const he_poly_context* ctx, const uint64_t* device_slab, size_t batch, int skip_lsbs,
                              uint8_t* device_bytes, he_stream s);
@@ -230,8 +254,8 @@ int he_poly_neg_device_u32(const he_poly_context* ctx, uint32_t* data, size_t ba
 int he_poly_mul_device_u32(const he_poly_context* ctx, uint32_t* lhs, const uint32_t* rhs, size_t batch, he_stream s);
 int he_poly_mul_scalar_device_u32(const he_poly_context* ctx, uint32_t* data, const uint32_t* scalar_residues,
                                   size_t batch, he_stream s);
-int he_poly_divide_and_round_q_last_device_u32(const he_poly_context* ctx, const uint32_t* device_in,
-                                               uint32_t* device_out, size_t batch, he_stream s);
+int he_poly_divide_and_round_q_last_device_u32(const he_poly_context* ctx, const uint32_t* in, uint32_t* out, size_t batch,
+                                               he_stream s);
 
 /* The wire entries above on slabs of 4-byte words: the same contracts, widths at most 30 (HE_ERR_INVALID_MODULUS for a larger
  * modulus).  4-byte slabs take the 8-bytes-per-lane and the byte kernels (he_ciphertexts_wire_plan with poly_count 0 says which). */
@@ -320,20 +344,23 @@ const he_poly_context* he_bfv_qbsk_context(const he_bfv_context* ctx, uint32_t m
 
 /* _RnsTool pieces, exposed so each can be parity-tested on its own (RnsTool.swift):
  *   liftQToQBsk  :324-331  in [batch][L][N]    -> out [batch][2L+1][N]
- *   floorQBskToQ :453-456  in [batch][2L+1][N] -> out [batch][L][N]          */
+ *   floorQBskToQ :453-456  in [batch][2L+1][N] -> out [batch][L][N]
+ * out overlapping in is HE_ERR_INVALID_ARGUMENT (a polynomial's rows lie at different strides in the two). */
 int he_rns_lift_q_to_qbsk_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in, uint64_t* out,
                                  size_t batch, he_stream s);
 int he_rns_floor_qbsk_to_q_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in, uint64_t* out,
                                   size_t batch, he_stream s);
 
 /* Workspace: multi-kernel operations need device scratch.  Pass workspace == NULL to let the library allocate
- * stream-ordered scratch itself (hipMallocAsync on `s`); otherwise pass at least *_workspace_bytes(). */
+ * stream-ordered scratch itself (hipMallocAsync on `s`); otherwise pass at least *_workspace_bytes().  The workspace is
+ * written: [workspace, workspace + workspace_bytes) overlapping any other slab of the call is HE_ERR_INVALID_ARGUMENT. */
 size_t he_bfv_mul_workspace_bytes(const he_bfv_context* ctx, uint32_t moduli_count, size_t batch);
 size_t he_bfv_relinearize_workspace_bytes(const he_bfv_context* ctx, uint32_t moduli_count, size_t batch);
 
 /* Bfv.mulAssign(_: inout CanonicalCiphertext, _: CanonicalCiphertext) = multiplyWithoutScaling + dropExtendedBase
  * (Bfv/Bfv+Multiply.swift:18-85).  lhs, rhs: [batch][2][L][N] Coeff; out: [batch][3][L][N] Coeff, overlapping neither
- * operand (HE_ERR_INVALID_ARGUMENT: parts of the batch are stored while others are still read).  Enqueue-only on `s` as seen
+ * operand (HE_ERR_INVALID_ARGUMENT: parts of the batch are stored while others are still read); lhs and rhs may be one
+ * ciphertext.  Enqueue-only on `s` as seen
  * from the caller: large batches also run part of the pipeline on a second stream the context owns, forked off `s` and joined
  * back into `s` by events before the call returns (not while `s` is being captured into a graph).  The context keeps up to 8
  * such streams and gives each caller stream the one it used last, so calls on different streams do not queue behind one
@@ -349,22 +376,28 @@ int he_bfv_mul_device(const he_bfv_context* ctx, uint32_t moduli_count, const ui
 int he_bfv_relinearize_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* ct3,
                               const uint64_t* key, uint64_t* out, size_t batch, void* workspace,
                               size_t workspace_bytes, he_stream s);
-/* Bfv.modSwitchDown (Bfv/Bfv.swift:163-171): [batch][polys][L][N] -> [batch][polys][L-1][N]. */
+/* Bfv.modSwitchDown (Bfv/Bfv.swift:163-171): [batch][polys][L][N] -> [batch][polys][L-1][N]; out overlapping in is
+ * HE_ERR_INVALID_ARGUMENT, as for he_poly_divide_and_round_q_last_device. */
 int he_bfv_mod_switch_down_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
                                   const uint64_t* in, uint64_t* out, size_t batch, he_stream s);
 /* Ciphertext.modSwitchDownToSingle (Bfv/Bfv.swift:163-171): in [batch][polys][moduli_count][N] -> out [batch][polys][1][N],
- * the moduli_count - 1 divideAndRoundQLast steps in one kernel (word for word the chain of he_bfv_mod_switch_down_device). */
+ * the moduli_count - 1 divideAndRoundQLast steps in one kernel (word for word the chain of he_bfv_mod_switch_down_device).
+ * out overlapping in is HE_ERR_INVALID_ARGUMENT, except out == in at moduli_count == 1, where the ciphertext is already
+ * there and nothing is done. */
 int he_bfv_mod_switch_down_to_single_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
                                             const uint64_t* in, uint64_t* out, size_t batch, he_stream s);
 /* Bfv.mulAssign(_: inout EvalCiphertext, _: EvalPlaintext) (Bfv/Bfv.swift:120-129):
- * ct [batch][polys][L][N] *= pt [batch][L][N]. */
+ * ct [batch][polys][L][N] *= pt [batch][L][N].  pt may be ct itself for batch == 1 (the ciphertext times its own first
+ * polynomial) or poly_count == 1 (squares): a lane then reads only words it writes; any other overlap is
+ * HE_ERR_INVALID_ARGUMENT. */
 int he_bfv_mul_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint64_t* ct,
                             const uint64_t* pt, size_t batch, he_stream s);
 /* Bfv.addAssignCoeff / subAssignCoeff(_: inout CoeffCiphertext, _: CoeffPlaintext) (Bfv/Bfv.swift:110-117), i.e.
  * plaintextTranslate (Bfv/Bfv+Encrypt.swift:75-140): c0 +-= floor(Q/t) m + floor(((Q mod t) m + (t + 1)/2) / t) per
  * residue row.  ct [batch][polys][L][N] Coeff in place (only c0 is touched), plaintexts [batch][N] Coeff plaintexts
  * with values < t (batch b's plaintext goes to batch b's ciphertext).  `plaintext - ciphertext`
- * (HeScheme.swift:1540-1548) is he_poly_neg_device over the ciphertext's polynomials, then this add. */
+ * (HeScheme.swift:1540-1548) is he_poly_neg_device over the ciphertext's polynomials, then this add.  plaintexts overlapping
+ * ct is HE_ERR_INVALID_ARGUMENT. */
 int he_bfv_add_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint64_t* ct,
                             const uint64_t* plaintexts, size_t batch, he_stream s);
 int he_bfv_sub_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, uint64_t* ct,
@@ -378,7 +411,9 @@ int he_bfv_sub_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, ui
  * Every word must be a canonical residue (< q_i), as the reference's polynomials are: the accumulators count on it.
  * polys = 1, 2 or 3 polynomials per ciphertext -- or 4, 6, 8: the ciphertext vectors of 2, 3 or 4 QUERIES laid side by
  * side ([count][query][2][L][N]), which then share every plaintext word the kernel streams (out [columns][query][2]
- * [L][N]): a server that answers several queries over one database reads the database once for all of them. */
+ * [L][N]): a server that answers several queries over one database reads the database once for all of them.
+ * out overlaps none of cts, pts and the device mask (HE_ERR_INVALID_ARGUMENT), here and in the resident and packed forms;
+ * he_bfv_pack_plaintexts_device refuses packed overlapping plaintexts_eval. */
 int he_bfv_inner_product_plain_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
                                       const uint64_t* cts, const uint64_t* pts, const uint8_t* present, size_t count,
                                       size_t columns, uint64_t* out, he_stream s);
@@ -402,7 +437,8 @@ int he_bfv_inner_product_plain_packed_device(const he_bfv_context* ctx, uint32_t
                                              const uint64_t* cts, const uint64_t* packed_pts, const uint8_t* present_device,
                                              size_t count, size_t columns, uint64_t* out, he_stream s);
 /* Bfv.innerProduct(_: [CanonicalCiphertext], _: [CanonicalCiphertext]) (Bfv/Bfv.swift:315-361):
- * lhs, rhs [count][2][L][N] Coeff -> out [3][L][N] Coeff. */
+ * lhs, rhs [count][2][L][N] Coeff -> out [3][L][N] Coeff.  lhs and rhs may be one vector; out and the workspace overlap
+ * neither (HE_ERR_INVALID_ARGUMENT). */
 int he_bfv_inner_product_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
                                 const uint64_t* rhs, size_t count, uint64_t* out, void* workspace,
                                 size_t workspace_bytes, he_stream s);
@@ -410,7 +446,8 @@ size_t he_bfv_inner_product_workspace_bytes(const he_bfv_context* ctx, uint32_t 
 /* `items` such inner products that share their left vector -- the remaining-dimension step of a PIR response over all
  * result groups of all chunks (PirUtil.swift:448-479): lhs [count][2][L][N], rhs [items][count][2][L][N] Coeff ->
  * out [items][3][L][N] Coeff.  Item i equals he_bfv_inner_product_device(lhs, rhs + i * count ciphertexts); every stage is
- * one launch over all items and the left vector is lifted and transformed once.  Stream-ordered scratch. */
+ * one launch over all items and the left vector is lifted and transformed once.  Stream-ordered scratch.  lhs may be an
+ * item of rhs; out overlaps neither (HE_ERR_INVALID_ARGUMENT). */
 int he_bfv_inner_product_shared_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
                                        const uint64_t* rhs, size_t count, size_t items, uint64_t* out, he_stream s);
 
@@ -489,7 +526,8 @@ int he_bfv_plaintext_to_coeff_device_u32(const he_bfv_context* ctx, uint32_t mod
 /* A Bfv<UInt32> context also works with every 8-byte entry point (he_bfv_*, he_rns_*, he_pir_*) on slabs of
  * zero-extended words; the PIR hooks (he_pir_*) exist in that form only.  Word-size bridge: widen a packed slab to
  * zero-extended 8-byte words and narrow results back (values of a UInt32 context are < 2^30, so the low half is the
- * word).  `words` counts coefficients; slabs 16-byte aligned; in != out. */
+ * word).  `words` counts coefficients; slabs 16-byte aligned; device_out overlapping device_in is HE_ERR_INVALID_ARGUMENT
+ * (word k is read at 4 k and stored at 8 k), for he_words_copy_device too. */
 int he_words_widen_u32_device(const uint32_t* device_in, uint64_t* device_out, size_t words, he_stream s);
 int he_words_narrow_u64_device(const uint64_t* device_in, uint32_t* device_out, size_t words, he_stream s);
 
@@ -497,7 +535,8 @@ int he_words_narrow_u64_device(const uint64_t* device_in, uint32_t* device_out, 
 /* Bfv.applyGalois(ciphertext:element:using:) (Bfv/Bfv.swift:174-198): ct [batch][2][L][N] Coeff,
  * galois_key = EvaluationKey.galoisKey.keys[element] in the relinearization key's layout
  * ([L_top][2][L_top+1][N] Eval; Bfv+Keys.swift:38-45,69-103) -> out [batch][2][L][N] Coeff.
- * NULL key -> HE_ERR_MISSING_GALOIS_KEY. */
+ * NULL key -> HE_ERR_MISSING_GALOIS_KEY.  out may be ct itself (ct is permuted into the workspace before the first word of
+ * out is stored); any other overlap of out or the workspace with ct, the key or one another is HE_ERR_INVALID_ARGUMENT. */
 int he_bfv_apply_galois_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* ct,
                                uint64_t element, const uint64_t* galois_key, uint64_t* out, size_t batch,
                                void* workspace, size_t workspace_bytes, he_stream s);
@@ -516,7 +555,8 @@ int he_bfv_apply_galois_grouped_device(const he_bfv_context* ctx, uint32_t modul
 size_t he_bfv_apply_galois_workspace_bytes(const he_bfv_context* ctx, uint32_t moduli_count, size_t batch);
 /* _RnsTool.scaleAndRound(poly:scalingFactor:) (RnsTool.swift:272-302), the RNS step of Bfv.decrypt
  * (Bfv/Bfv+Decrypt.swift): in [batch][L][N] Coeff (c0 + c1 s [+ c2 s^2]) -> out [batch][N], values < t.
- * scaling_factor < t (the ciphertext's correction factor). */
+ * scaling_factor < t (the ciphertext's correction factor).  out overlapping in is HE_ERR_INVALID_ARGUMENT, as it is for the
+ * two plaintext conversions below (L rows on one side, one row on the other). */
 int he_rns_scale_and_round_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* in,
                                   uint64_t scaling_factor, uint64_t* out, size_t batch, he_stream s);
 /* Plaintext<Coeff>.convertToEvalFormat(moduliCount:) (Plaintext.swift:149-170): plaintext [batch][N] (values < t)
@@ -534,6 +574,7 @@ int he_bfv_plaintext_to_coeff_device(const he_bfv_context* ctx, uint32_t moduli_
  *   secret_key  [L_all][N] Eval over the secret-key context (every coefficient modulus); its first L rows are read
  *               (PolyRq.mulAssign(secretPoly:), PolyRq/PolyRq.swift:184-194)
  *   workspace   NULL = stream-ordered scratch, else at least he_bfv_decrypt_workspace_bytes() bytes, 16-byte aligned
+ * The result slab and the workspace overlap neither cts nor secret_key nor one another (HE_ERR_INVALID_ARGUMENT).
  * Errors: word_bits other than 32 / 64 and moduli_count outside 1..he_bfv_ciphertext_moduli_count are
  * HE_ERR_INVALID_ARGUMENT, poly_count outside 1..3 is HE_ERR_UNSUPPORTED (no reference ciphertext has more); batch 0 does
  * nothing.  All enqueue-only on `s`. */
@@ -589,6 +630,8 @@ int he_bfv_noise_budget_from_norm(const he_bfv_context* ctx, uint32_t word_bits,
  *               Everything in it that depends on a secret (the DRBG records of error and key seeds, error polynomials and
  *               their transforms, s^2 and rotated keys) is overwritten with zeros on `s` before the entry releases it or returns:
  *               the first he_bfv_encrypt_workspace_bytes() bytes of a caller's workspace read zero once the stream has drained.
+ * `out` and the workspace overlap none of the slabs the entry reads nor one another (HE_ERR_INVALID_ARGUMENT); slabs that are
+ * only read may alias (the secret key as a current key of he_bfv_generate_key_switch_keys_device).
  * Errors: word_bits other than 32 / 64 and moduli_count outside its range HE_ERR_INVALID_ARGUMENT; a 4-byte call on a
  * Bfv<UInt64> context HE_ERR_INVALID_ARGUMENT, as the decryption entries; key generation on a context with one coefficient
  * modulus HE_ERR_UNSUPPORTED (supportsEvaluationKey, Bfv/Bfv+Keys.swift:35-37); on 4-byte words a degree above 32768

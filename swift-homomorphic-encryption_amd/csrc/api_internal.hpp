@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdint>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -52,6 +54,41 @@ class RelaxedCapture {
 inline int invalid_argument(const char* what) {
     set_last_error(std::string("invalid argument: ") + what);
     return HE_ERR_INVALID_ARGUMENT;
+}
+
+// ---- the pointer contract of include/he_amd.h: what may alias among the slabs of one call
+// Byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte.  Abutting ranges do not; an empty range shares nothing.
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    if (a_bytes == 0 || b_bytes == 0) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+// One device slab of a call: the argument's name, where it lies, the bytes the call may touch there, whether it writes them.
+// A null slab (an optional argument left out) takes part in nothing.
+struct Slab {
+    const char* name;
+    const void* ptr;
+    size_t bytes;
+    bool written;
+};
+// HE_OK, or HE_ERR_INVALID_ARGUMENT "<what>: <a> overlaps <b>" for the first two of `slabs` that share a byte and of which the
+// call writes one.  Slabs the call only reads may lie anywhere.  `alias_ok`, a pair of indices into `slabs`: those two may be
+// exactly the same memory (the same first byte; the form's kernel is lane-local) -- any other overlap of theirs is refused too.
+inline int check_slabs(const char* what, std::initializer_list<Slab> slabs, std::pair<int, int> alias_ok = {-1, -1}) {
+    int i = 0;
+    for (const Slab* a = slabs.begin(); a != slabs.end(); ++a, ++i) {
+        int j = i + 1;
+        for (const Slab* b = a + 1; b != slabs.end(); ++b, ++j) {
+            if (!(a->written || b->written) || a->ptr == nullptr || b->ptr == nullptr) continue;
+            if (!ranges_overlap(a->ptr, a->bytes, b->ptr, b->bytes)) continue;
+            const bool named = (alias_ok.first == i && alias_ok.second == j) || (alias_ok.first == j && alias_ok.second == i);
+            if (named && a->ptr == b->ptr) continue;
+            const Slab* w = a->written ? a : b;
+            const Slab* r = a->written ? b : a;
+            return invalid_argument((std::string(what) + ": " + w->name + " overlaps " + r->name).c_str());
+        }
+    }
+    return HE_OK;
 }
 
 // Stream-ordered scratch (c_api.cpp): from a memory pool the LIBRARY owns (one per device, release threshold 0 -- never the

@@ -70,9 +70,14 @@ int bfv_create(uint32_t degree, uint64_t t, const uint64_t* q, uint32_t count, b
 
 // Common argument checks; returns the level's tool on success.  word_bytes 4: the slabs are packed [UInt32], the same kernels
 // run on 4-byte words (widened in registers) and the context must come from he_bfv_context_create_u32.
-int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolLevel** tool, size_t word_bytes = 8) {
+// `slabs(n)`: the entry's pointer contract (api_internal.hpp check_slabs over its slabs, n the degree).  It is an argument check
+// like the two before it, so it comes ahead of the device: an overlap is refused on a host-only context too, and before anything
+// is enqueued.  Null slabs and empty batches overlap nothing, so every status the entry had keeps its place.
+template <typename SlabCheck>
+int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolLevel** tool, size_t word_bytes, SlabCheck slabs) {
     if (ctx == nullptr) return invalid_argument("null context");
     if (!ctx->impl->valid(moduli_count)) return invalid_argument("moduli_count out of range");
+    HEAMD_TRY_STATUS(slabs(size_t(ctx->impl->degree())));
     if (ctx->impl->host_only()) {
         heamd::set_last_error("context was created host-only (no device tables)");
         return HE_ERR_DEVICE;
@@ -86,6 +91,9 @@ int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolL
     }
     if (word_bytes == 4 && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     return HE_OK;
+}
+int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolLevel** tool, size_t word_bytes = 8) {
+    return check_level(ctx, moduli_count, tool, word_bytes, [](size_t) { return HE_OK; });
 }
 
 size_t qbsk_poly_words(const BfvContext& ctx, uint32_t L) { return size_t(2 * L + 1) * ctx.degree(); }
@@ -516,7 +524,12 @@ namespace {
 template <typename W>
 int rns_base_change(const he_bfv_context* ctx, uint32_t moduli_count, bool lift, const W* in, W* out, size_t batch, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    // a polynomial's L rows and its 2L + 1 rows lie at different strides: in place, polynomials store over one another's input
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
+        const size_t q_bytes = batch * moduli_count * n * sizeof(W), qbsk_bytes = batch * (2 * moduli_count + 1) * n * sizeof(W);
+        return heamd::check_slabs(lift ? "liftQToQBsk" : "floorQBskToQ", {{"out", out, lift ? qbsk_bytes : q_bytes, true},
+                                                                         {"in", in, lift ? q_bytes : qbsk_bytes, false}});
+    });
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null slab");
@@ -556,21 +569,20 @@ template <typename W>
 int mul_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, W* out, size_t batch,
               void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    // out must not overlap lhs or rhs: with the batch in parts, one part's floor stores its products while another
+    // part's row band still reads the operands -- whether that happens depends on the batch size and the moduli, so an
+    // overlap would be right for some shapes and silently wrong for others.  lhs and rhs are only read: they may be one
+    // ciphertext (a square).
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
+        const size_t poly_bytes = batch * moduli_count * n * sizeof(W);
+        return heamd::check_slabs("ct x ct", {{"out", out, 3 * poly_bytes, true},
+                                              {"workspace", workspace, workspace_bytes, true},
+                                              {"lhs", lhs, 2 * poly_bytes, false},
+                                              {"rhs", rhs, 2 * poly_bytes, false}});
+    });
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    {
-        // out must not overlap lhs or rhs: with the batch in parts, one part's floor stores its products while another
-        // part's row band still reads the operands -- whether that happens depends on the batch size and the moduli, so an
-        // overlap would be right for some shapes and silently wrong for others
-        const size_t words = size_t(moduli_count) * ctx->impl->degree();
-        const uintptr_t out_begin = reinterpret_cast<uintptr_t>(out), out_end = out_begin + batch * 3 * words * sizeof(W);
-        for (const W* operand : {lhs, rhs}) {
-            const uintptr_t begin = reinterpret_cast<uintptr_t>(operand), end = begin + batch * 2 * words * sizeof(W);
-            if (out_begin < end && begin < out_end) return invalid_argument("ct x ct: out overlaps an operand");
-        }
-    }
     return mul_pipeline(ctx, tool, moduli_count, lhs, rhs, out, batch, workspace, workspace_bytes, as_stream(s));
 }
 }  // namespace
@@ -598,7 +610,20 @@ template <typename W>
 int relinearize_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* ct3, const W* key, W* out, size_t batch,
                       void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    // out must not overlap ct3: the last kernel adds the update to (c0, c1) of one item while it stores another item's
+    // result (items are 3 L N words apart in ct3 and 2 L N apart in out), in no particular order -- and which kernel
+    // that is depends on the batch size, so an overlap would be right for some batches and silently wrong for others.
+    // The one overlap that is word-for-word in place -- a single ciphertext relinearized onto its own (c0, c1) -- is
+    // allowed: it takes the element-wise finish kernel (a batch of one is never fused).
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
+        const size_t poly_bytes = batch * moduli_count * n * sizeof(W), top = ctx->impl->top_level();
+        if (batch == 0) return int(HE_OK);  // (nothing is read or written, the key and the workspace included)
+        return heamd::check_slabs("relinearize", {{"out", out, 2 * poly_bytes, true},
+                                                  {"ct3", ct3, 3 * poly_bytes, false},
+                                                  {"workspace", workspace, workspace_bytes, true},
+                                                  {"key", key, top * 2 * (top + 1) * n * sizeof(W), false}},
+                                  batch == 1 ? std::pair<int, int>{0, 1} : std::pair<int, int>{-1, -1});
+    });
     if (status != HE_OK) return status;
     if (key == nullptr || !ctx->impl->has_key_switching()) {
         heamd::set_last_error("no relinearization key");
@@ -606,19 +631,6 @@ int relinearize_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W*
     }
     if (batch == 0) return HE_OK;
     if (ct3 == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    {
-        // out must not overlap ct3: the last kernel adds the update to (c0, c1) of one item while it stores another item's
-        // result (items are 3 L N words apart in ct3 and 2 L N apart in out), in no particular order -- and which kernel
-        // that is depends on the batch size, so an overlap would be right for some batches and silently wrong for others.
-        // The one overlap that is word-for-word in place -- a single ciphertext relinearized onto its own (c0, c1) -- is
-        // allowed: it takes the element-wise finish kernel (a batch of one is never fused).
-        const size_t words = size_t(moduli_count) * ctx->impl->degree();
-        const uintptr_t in_begin = reinterpret_cast<uintptr_t>(ct3), in_end = in_begin + batch * 3 * words * sizeof(W);
-        const uintptr_t out_begin = reinterpret_cast<uintptr_t>(out), out_end = out_begin + batch * 2 * words * sizeof(W);
-        const bool overlap = out_begin < in_end && in_begin < out_end;
-        if (overlap && !(batch == 1 && out_begin == in_begin))
-            return invalid_argument("relinearize: out overlaps ct3 (only a single ciphertext may be relinearized in place)");
-    }
     return relinearize_pipeline(ctx, moduli_count, ct3, key, out, batch, workspace, workspace_bytes, as_stream(s));
 }
 }  // namespace
@@ -685,7 +697,21 @@ int bfv_apply_galois_grouped(const he_bfv_context* ctx, uint32_t L, const W* ct,
                              size_t groups, size_t group_size, W* out, void* workspace, size_t workspace_bytes,
                              hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, L, &tool, sizeof(W));
+    // out may be ct itself: the whole of ct goes through the permutation into the workspace before the first word of out is
+    // stored (the fused kernels, which read ct to the end, are not taken then).  Any other overlap is refused.
+    int status = check_level(ctx, L, &tool, sizeof(W), [&](size_t n) {
+        const size_t ct_bytes = groups * group_size * 2 * L * n * sizeof(W), top = ctx->impl->top_level();
+        if (ct_bytes == 0) return int(HE_OK);  // (nothing is read or written, the keys and the workspace included)
+        HEAMD_TRY_STATUS(heamd::check_slabs("applyGalois", {{"out", out, ct_bytes, true},
+                                                            {"ct", ct, ct_bytes, false},
+                                                            {"workspace", workspace, workspace_bytes, true}},
+                                            {0, 1}));
+        for (size_t g = 0; keys != nullptr && g < groups; ++g)
+            HEAMD_TRY_STATUS(heamd::check_slabs("applyGalois", {{"out", out, ct_bytes, true},
+                                                                {"workspace", workspace, workspace_bytes, true},
+                                                                {"galois_key", keys[g], top * 2 * (top + 1) * n * sizeof(W), false}}));
+        return int(HE_OK);
+    });
     if (status != HE_OK) return status;
     bool missing = keys == nullptr || !ctx->impl->has_key_switching();
     for (size_t g = 0; !missing && g < groups; ++g) missing = keys[g] == nullptr;
@@ -756,7 +782,10 @@ template <typename W>
 int scale_and_round(const he_bfv_context* ctx, uint32_t moduli_count, const W* in, uint64_t scaling_factor, W* out, size_t batch,
                     he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {  // L rows in, one row out per polynomial
+        return heamd::check_slabs("scaleAndRound", {{"out", out, batch * n * sizeof(W), true},
+                                                    {"in", in, batch * moduli_count * n * sizeof(W), false}});
+    });
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null polynomial");
@@ -788,10 +817,24 @@ using heamd::NoiseNormTables;
 using heamd::u64;
 
 // the checks the entries with void* slabs share, in this order: the word, the level (check_level), the polynomial count
+// `result`: the slab the entry writes, its size as bytes per coefficient (the degree is the context's, which may still be null
+// here) plus result_fixed_bytes; it, the ciphertexts, the secret key and a caller's workspace go through check_slabs
 int check_decrypt_arguments(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
-                            const RnsToolLevel** tool) {
+                            const RnsToolLevel** tool, const char* what, const void* cts, const void* secret_key, size_t batch,
+                            heamd::Slab result, size_t result_fixed_bytes, const void* workspace, size_t workspace_bytes) {
     if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
-    HEAMD_TRY_STATUS(check_level(ctx, moduli_count, tool, word_bits / 8));
+    HEAMD_TRY_STATUS(check_level(ctx, moduli_count, tool, word_bits / 8, [&](size_t n) {
+        const size_t poly_bytes = size_t(moduli_count) * n * (word_bits / 8);
+        if (batch == 0) return int(HE_OK);  // (nothing is read or written, the secret key and the workspace included)
+        // (a polynomial count the entry is about to refuse says nothing about where the ciphertexts end)
+        if (poly_count < 1 || poly_count > heamd::kMaxDecryptPolys) return int(HE_OK);
+        result.bytes *= n;  // (given per coefficient)
+        result.bytes += result_fixed_bytes;
+        return heamd::check_slabs(what, {result,
+                                         {"workspace", workspace, workspace_bytes, true},
+                                         {"cts", cts, batch * poly_count * poly_bytes, false},
+                                         {"secret_key", secret_key, poly_bytes, false}});
+    }));
     if (poly_count < 1 || poly_count > heamd::kMaxDecryptPolys) {
         heamd::set_last_error("a ciphertext has 1..3 polynomials");
         return HE_ERR_UNSUPPORTED;
@@ -961,7 +1004,9 @@ int he_bfv_secret_dot_product_device(const he_bfv_context* ctx, uint32_t word_bi
                                      int is_eval, const void* cts, const void* secret_key, void* out, size_t batch,
                                      void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool, "dotProduct", cts, secret_key, batch,
+                                             {"out", out, batch * moduli_count * (word_bits / 8), true}, 0, workspace,
+                                             workspace_bytes));
     if (batch != 0 && out == nullptr) return invalid_argument("null dot product");
     Scratch scratch(as_stream(s));
     if (word_bits == 32) {
@@ -978,7 +1023,9 @@ int he_bfv_decrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_
                           const void* cts, const void* secret_key, uint64_t correction_factor, void* out_plaintexts,
                           size_t batch, void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool, "decrypt", cts, secret_key, batch,
+                                             {"out_plaintexts", out_plaintexts, batch * (word_bits / 8), true}, 0, workspace,
+                                             workspace_bytes));
     const u64 t = ctx->impl->plaintext_modulus();
     if (correction_factor >= t) return invalid_argument("correction factor not reduced mod t");
     u64 scaling_factor = 0;  // correctionFactor.inverseMod(modulus: t) (Bfv+Decrypt.swift:34)
@@ -997,7 +1044,10 @@ int he_bfv_noise_norm_device(const he_bfv_context* ctx, uint32_t word_bits, uint
                              int is_eval, const void* cts, const void* secret_key, uint64_t* out_limbs, size_t batch,
                              void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool, "noiseNorm", cts, secret_key, batch,
+                                             {"out_limbs", out_limbs, 0, true},
+                                             batch * he_bfv_noise_norm_limbs(ctx, moduli_count) * sizeof(uint64_t), workspace,
+                                             workspace_bytes));
     if (word_bits == 32)
         return noise_norm_words<uint32_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out_limbs, batch, workspace,
                                           workspace_bytes, as_stream(s));
@@ -1008,7 +1058,8 @@ int he_bfv_noise_norm_device(const he_bfv_context* ctx, uint32_t word_bits, uint
 int he_bfv_is_transparent_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
                                  const void* cts, uint8_t* out_flags, size_t batch, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool));
+    HEAMD_TRY_STATUS(check_decrypt_arguments(ctx, word_bits, moduli_count, poly_count, &tool, "isTransparent", cts, nullptr, batch,
+                                             {"out_flags", out_flags, 0, true}, batch, nullptr, 0));
     if (batch == 0) return HE_OK;
     if (cts == nullptr || out_flags == nullptr) return invalid_argument("null ciphertexts or flags");
     const uint32_t log_degree = tool->device.log_degree;
@@ -1053,7 +1104,10 @@ template <typename W>
 int heamd::bfv_plaintext_to_eval(const he_bfv_context* ctx, uint32_t moduli_count, const W* plaintext, W* out, size_t batch,
                                  hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {  // one row in, L rows out per plaintext
+        return heamd::check_slabs("convertToEvalFormat", {{"out", out, batch * moduli_count * n * sizeof(W), true},
+                                                          {"plaintext", plaintext, batch * n * sizeof(W), false}});
+    });
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (plaintext == nullptr || out == nullptr) return invalid_argument("null plaintext");
@@ -1081,7 +1135,10 @@ template <typename W>
 int plaintext_to_coeff(const he_bfv_context* ctx, uint32_t moduli_count, const W* plaintext_eval, W* out, size_t batch,
                        he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {  // L rows in, one row out per plaintext
+        return heamd::check_slabs("convertToCoeffFormat", {{"out", out, batch * n * sizeof(W), true},
+                                                           {"plaintext_eval", plaintext_eval, batch * moduli_count * n * sizeof(W), false}});
+    });
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (plaintext_eval == nullptr || out == nullptr) return invalid_argument("null plaintext");
@@ -1124,7 +1181,10 @@ template <typename W>
 int mod_switch_down(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* in, W* out, size_t batch,
                     he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {  // as he_poly_divide_and_round_q_last_device
+        const size_t row = batch * poly_count * n * sizeof(W);
+        return heamd::check_slabs("modSwitchDown", {{"out", out, row * (moduli_count - 1), true}, {"in", in, row * moduli_count, false}});
+    });
     if (status != HE_OK) return status;
     if (moduli_count < 2) return HE_ERR_INVALID_POLY_CONTEXT;  // PolyRq.swift:366-368
     if (batch == 0 || poly_count == 0) return HE_OK;
@@ -1138,7 +1198,13 @@ template <typename W>
 int mul_plain_entry(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, W* ct, const W* pt, size_t batch,
                     he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    // a lane reads word k of plaintext b and updates word k of every polynomial of ciphertext b: pt may be ct itself where no
+    // lane reads what another writes -- one polynomial per ciphertext (a square), or one ciphertext (times its own c0)
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
+        const size_t poly_bytes = batch * moduli_count * n * sizeof(W);
+        return heamd::check_slabs("ct x pt", {{"ct", ct, poly_count * poly_bytes, true}, {"pt", pt, poly_bytes, false}},
+                                  batch == 1 || poly_count == 1 ? std::pair<int, int>{0, 1} : std::pair<int, int>{-1, -1});
+    });
     if (status != HE_OK) return status;
     if (batch == 0 || poly_count == 0) return HE_OK;
     if (ct == nullptr || pt == nullptr) return invalid_argument("null operand");
@@ -1153,7 +1219,11 @@ template <typename W>
 int plaintext_translate(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, W* ct, const W* plaintexts,
                         bool subtract, size_t batch, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    const int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    const int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {  // one plaintext row spreads over L rows
+        return heamd::check_slabs(subtract ? "ct - pt" : "ct + pt",
+                                  {{"ct", ct, batch * poly_count * moduli_count * n * sizeof(W), true},
+                                   {"plaintexts", plaintexts, batch * n * sizeof(W), false}});
+    });
     if (status != HE_OK) return status;
     if (poly_count == 0) return invalid_argument("a ciphertext has at least one polynomial");
     if (batch == 0) return HE_OK;
@@ -1168,7 +1238,13 @@ template <typename W>
 int heamd::bfv_mod_switch_down_to_single(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* in,
                                          W* out, size_t batch, hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    // at one modulus the ciphertext is already there: out == in is the no-op it always was; any other overlap, and every
+    // overlap at more moduli (rows L p .. read, row p written), is refused
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
+        const size_t row = batch * poly_count * n * sizeof(W);
+        return heamd::check_slabs("modSwitchDownToSingle", {{"out", out, row, true}, {"in", in, row * moduli_count, false}},
+                                  moduli_count == 1 ? std::pair<int, int>{0, 1} : std::pair<int, int>{-1, -1});
+    });
     if (status != HE_OK) return status;
     if (batch == 0 || poly_count == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null ciphertext");
@@ -1259,13 +1335,21 @@ int inner_product_plain(const he_bfv_context* ctx, uint32_t moduli_count, uint32
 }
 // (the resident entry looks at the word size before the level, unlike every other 4-byte entry;
 // tests/test_word_twin_status.py pins the order)
+// plaintext_bytes(n): the bytes of one plaintext in pts (L rows of words, or packed); present_device: the device mask or null
+template <typename PlaintextBytes>
 int check_inner_product_plain(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const void* cts,
-                              const void* pts, size_t count, size_t columns, const void* out, bool* nothing_to_do,
-                              size_t word_bytes = 8) {
+                              const void* pts, const void* present_device, size_t count, size_t columns, const void* out,
+                              bool* nothing_to_do, size_t word_bytes, PlaintextBytes plaintext_bytes) {
     if (word_bytes == 4 && ctx != nullptr && ctx->impl->word_bits() != 32)
         return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool);
+    int status = check_level(ctx, moduli_count, &tool, 8, [&](size_t n) {
+        const size_t ct_bytes = size_t(poly_count) * moduli_count * n * word_bytes;
+        return heamd::check_slabs("innerProduct", {{"out", out, columns * ct_bytes, true},
+                                                   {"cts", cts, count * ct_bytes, false},
+                                                   {"pts", pts, columns * count * plaintext_bytes(n), false},
+                                                   {"present_device", present_device, columns * count, false}});
+    });
     if (status != HE_OK) return status;
     *nothing_to_do = false;
     if (count == 0) return invalid_argument("empty ciphertext vector");  // precondition, Bfv.swift:481-483
@@ -1282,7 +1366,8 @@ template <typename W>
 int inner_product_plain_resident(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* cts,
                                  const W* pts, const uint8_t* present_device, size_t count, size_t columns, W* out, he_stream s) {
     bool nothing = false;
-    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, count, columns, out, &nothing, sizeof(W));
+    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, &nothing,
+                                           sizeof(W), [&](size_t n) { return moduli_count * n * sizeof(W); });
     if (status != HE_OK || nothing) return status;
     return inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, as_stream(s));
 }
@@ -1309,7 +1394,8 @@ int he_bfv_inner_product_plain_device(const he_bfv_context* ctx, uint32_t moduli
                                       const uint64_t* cts, const uint64_t* pts, const uint8_t* present, size_t count,
                                       size_t columns, uint64_t* out, he_stream s) {
     bool nothing = false;
-    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, count, columns, out, &nothing);
+    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, nullptr, count, columns, out, &nothing, 8,
+                                           [&](size_t n) { return moduli_count * n * sizeof(uint64_t); });
     if (status != HE_OK || nothing) return status;
     hipStream_t stream = as_stream(s);
     Scratch scratch(stream);
@@ -1338,6 +1424,14 @@ int he_bfv_inner_product_plain_resident_device_u32(const he_bfv_context* ctx, ui
 // ------------------------------------------------------------------------------------------ packed plaintexts
 extern "C++" {
 namespace {
+// 8-byte words of one packed plaintext over pc: what packed_layout lays out, without looking at the device (the pointer contract
+// of the packed entries is checked on host-only contexts too)
+size_t packed_plaintext_words(const PolyContext& pc) {
+    size_t words = 0;
+    for (uint64_t q : pc.moduli()) words += pc.degree() / 64 * static_cast<size_t>(64 - __builtin_clzll(q));
+    return words;
+}
+
 // bits(q_r) per word, rows in whole 8-byte words (degree a multiple of 64)
 int packed_layout(const he_bfv_context* ctx, uint32_t moduli_count, heamd::PackedLayout& layout) {
     const RnsToolLevel* tool = nullptr;
@@ -1367,6 +1461,12 @@ size_t he_bfv_packed_plaintext_words(const he_bfv_context* ctx, uint32_t moduli_
 
 int he_bfv_pack_plaintexts_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* plaintexts_eval,
                                   size_t count, uint64_t* packed, he_stream s) {
+    if (ctx != nullptr && ctx->impl->valid(moduli_count)) {  // (an argument check: ahead of the device, as in check_level)
+        const PolyContext& pc = *ctx->impl->ciphertext(moduli_count);
+        HEAMD_TRY_STATUS(heamd::check_slabs(
+            "pack", {{"packed", packed, count * packed_plaintext_words(pc) * sizeof(uint64_t), true},
+                     {"plaintexts_eval", plaintexts_eval, count * moduli_count * pc.degree() * sizeof(uint64_t), false}}));
+    }
     heamd::PackedLayout layout{};
     int status = packed_layout(ctx, moduli_count, layout);
     if (status != HE_OK) return status;
@@ -1382,7 +1482,10 @@ int he_bfv_inner_product_plain_packed_device(const he_bfv_context* ctx, uint32_t
                                              const uint64_t* cts, const uint64_t* packed_pts, const uint8_t* present_device,
                                              size_t count, size_t columns, uint64_t* out, he_stream s) {
     bool nothing = false;
-    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, packed_pts, count, columns, out, &nothing);
+    int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, packed_pts, present_device, count, columns, out,
+                                           &nothing, 8, [&](size_t) {
+                                               return packed_plaintext_words(*ctx->impl->ciphertext(moduli_count)) * sizeof(uint64_t);
+                                           });
     if (status != HE_OK || nothing) return status;
     if (poly_count > 3) return invalid_argument("packed plaintexts take poly_count 1..3");
     heamd::PackedLayout layout{};
@@ -1512,7 +1615,13 @@ template <typename W>
 int inner_product_shared_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count,
                                size_t items, W* out, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    // lhs and rhs are only read (lifted into scratch): lhs may be an item of rhs, or all of it
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
+        const size_t poly_bytes = size_t(moduli_count) * n * sizeof(W);
+        return heamd::check_slabs("innerProduct", {{"out", out, items * 3 * poly_bytes, true},
+                                                   {"lhs", lhs, count * 2 * poly_bytes, false},
+                                                   {"rhs", rhs, items * count * 2 * poly_bytes, false}});
+    });
     if (status != HE_OK) return status;
     if (count == 0) return invalid_argument("empty ciphertext vector");
     if (items == 0) return HE_OK;
@@ -1523,7 +1632,14 @@ template <typename W>
 int inner_product_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count, W* out,
                         void* workspace, size_t workspace_bytes, he_stream s) {
     const RnsToolLevel* tool = nullptr;
-    int status = check_level(ctx, moduli_count, &tool, sizeof(W));
+    // lhs and rhs are only read (lifted into the workspace): they may be one vector
+    int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
+        const size_t poly_bytes = size_t(moduli_count) * n * sizeof(W);
+        return heamd::check_slabs("innerProduct", {{"out", out, 3 * poly_bytes, true},
+                                                   {"workspace", workspace, workspace_bytes, true},
+                                                   {"lhs", lhs, count * 2 * poly_bytes, false},
+                                                   {"rhs", rhs, count * 2 * poly_bytes, false}});
+    });
     if (status != HE_OK) return status;
     if (count == 0) return invalid_argument("empty ciphertext vector");
     if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");

@@ -103,6 +103,11 @@ int heamd::poly_elementwise(const he_poly_context* ctx, ElementwiseOp op, W* lhs
     if (kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
     if (batch == 0) return HE_OK;
     if (lhs == nullptr || (rhs == nullptr && op != ElementwiseOp::Neg)) return invalid_argument("null slab");
+    {
+        // a lane reads lhs[k] and rhs[k] and writes lhs[k]: rhs may be lhs itself (x + x, x - x, x * x), no other overlap
+        const size_t bytes = batch * pc.moduli_count() * pc.degree() * sizeof(W);
+        HEAMD_TRY_STATUS(heamd::check_slabs("element-wise", {{"lhs", lhs, bytes, true}, {"rhs", rhs, bytes, false}}, {0, 1}));
+    }
     if (!kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
     HEAMD_HIP_TRY(elementwise_rows(op, lhs, rhs, nullptr, pc, batch * pc.moduli_count(), stream));
     return HE_OK;
@@ -147,6 +152,13 @@ int poly_divide_and_round_q_last(const he_poly_context* ctx, const W* in, W* out
     if (kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
     if (batch == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null slab");
+    {
+        // polynomial p reads rows p L .. p L + L - 1 and writes rows p (L - 1) ..: in place, what one polynomial stores is
+        // what an earlier one still reads, in no particular order
+        const size_t row = batch * pc.degree() * sizeof(W);
+        HEAMD_TRY_STATUS(heamd::check_slabs("divideAndRoundQLast", {{"out", out, row * (pc.moduli_count() - 1), true},
+                                                                    {"in", in, row * pc.moduli_count(), false}}));
+    }
     if (!kChecksDeviceFirst<W>) HEAMD_TRY_STATUS(check_word_device<W>(pc));
     HEAMD_HIP_TRY(divide_and_round_q_last(in, out, pc, pc.moduli_count(), batch, as_stream(s)));
     return HE_OK;
@@ -718,7 +730,9 @@ int he_poly_apply_galois_device(const he_poly_context* ctx, const uint64_t* in, 
     // isValidGaloisElement (Galois.swift:100-105) is a precondition of applyGalois
     if ((element & 1) == 0 || element <= 1 || element >= 2 * n) return invalid_argument("invalid Galois element");
     if (batch == 0) return HE_OK;
-    if (in == nullptr || out == nullptr || in == out) return invalid_argument("null or aliased slabs");
+    if (in == nullptr || out == nullptr) return invalid_argument("null slabs");
+    const size_t slab_bytes = batch * pc.moduli_count() * pc.degree() * sizeof(uint64_t);  // an index permutation of each row
+    HEAMD_TRY_STATUS(heamd::check_slabs("applyGalois", {{"out", out, slab_bytes, true}, {"in", in, slab_bytes, false}}));
     int status = pc.check_device();
     if (status != HE_OK) return status;
     const size_t rows = batch * pc.moduli_count();
@@ -739,7 +753,9 @@ int he_poly_multiply_power_of_x_device(const he_poly_context* ctx, const uint64_
     if (ctx == nullptr) return invalid_argument("null context");
     const PolyContext& pc = *ctx->impl;
     if (batch == 0) return HE_OK;
-    if (in == nullptr || out == nullptr || in == out) return invalid_argument("null or aliased slabs");
+    if (in == nullptr || out == nullptr) return invalid_argument("null slabs");
+    const size_t slab_bytes = batch * pc.moduli_count() * pc.degree() * sizeof(uint64_t);  // an index permutation of each row
+    HEAMD_TRY_STATUS(heamd::check_slabs("multiplyPowerOfX", {{"out", out, slab_bytes, true}, {"in", in, slab_bytes, false}}));
     int status = pc.check_device();
     if (status != HE_OK) return status;
     const int64_t twice = 2 * static_cast<int64_t>(pc.degree());
@@ -804,6 +820,9 @@ int poly_serialize(const he_poly_context* ctx, const W* device_slab, size_t batc
     if (status != HE_OK) return status;
     if (batch == 0) return HE_OK;
     if (device_slab == nullptr || device_bytes == nullptr) return invalid_argument("null buffer");
+    HEAMD_TRY_STATUS(heamd::check_slabs(
+        "serialize", {{"device_bytes", device_bytes, batch * static_cast<size_t>(layout.byte_offset[layout.rows]), true},
+                      {"device_slab", device_slab, batch * pc.moduli_count() * pc.degree() * sizeof(W), false}}));
     status = pc.check_device();
     if (status != HE_OK) return status;
     HEAMD_HIP_TRY(heamd::launch_serialize(device_slab, device_bytes, layout, log2_of_degree(pc),
@@ -830,6 +849,9 @@ int poly_deserialize(const he_poly_context* ctx, const uint8_t* device_bytes, si
     }
     if (batch == 0) return HE_OK;
     if (device_slab == nullptr || device_bytes == nullptr) return invalid_argument("null buffer");
+    HEAMD_TRY_STATUS(heamd::check_slabs(
+        "deserialize", {{"device_slab", device_slab, batch * pc.moduli_count() * pc.degree() * sizeof(W), true},
+                        {"device_bytes", device_bytes, batch * bytes_per_poly, false}}));
     status = pc.check_device();
     if (status != HE_OK) return status;
     HEAMD_HIP_TRY(heamd::launch_deserialize(device_bytes, device_slab, layout, log2_of_degree(pc),
@@ -848,6 +870,9 @@ int poly_random_from_seeds(const he_poly_context* ctx, const uint8_t* device_see
     }
     if (batch == 0) return HE_OK;
     if (device_seeds == nullptr || device_slab == nullptr) return invalid_argument("null buffer");
+    HEAMD_TRY_STATUS(heamd::check_slabs(
+        "random(seed:)", {{"device_slab", device_slab, batch * pc.moduli_count() * pc.degree() * sizeof(W), true},
+                          {"device_seeds", device_seeds, batch * 32, false}}));
     int status = pc.check_device();
     if (status != HE_OK) return status;
     heamd::Scratch chain(as_stream(s));
@@ -893,6 +918,8 @@ int he_poly_add_device_u32(const he_poly_context* ctx, uint32_t* lhs, const uint
 int he_words_widen_u32_device(const uint32_t* in, uint64_t* out, size_t words, he_stream s) {
     if (words == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null slab");
+    // word k is read at 4 k and stored at 8 k: in place, a lane stores over words that another has yet to read
+    HEAMD_TRY_STATUS(heamd::check_slabs("widen", {{"device_out", out, words * 8, true}, {"device_in", in, words * 4, false}}));
     if ((reinterpret_cast<uintptr_t>(in) & 15u) != 0 || (reinterpret_cast<uintptr_t>(out) & 15u) != 0)
         return invalid_argument("slabs must be 16-byte aligned");
     HEAMD_HIP_TRY(heamd::launch_widen_words(in, out, words, as_stream(s)));
@@ -901,12 +928,14 @@ int he_words_widen_u32_device(const uint32_t* in, uint64_t* out, size_t words, h
 int he_words_copy_device(const uint64_t* in, uint64_t* out, size_t words, int non_temporal, he_stream s) {
     if (words == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null slab");
+    HEAMD_TRY_STATUS(heamd::check_slabs("copy", {{"device_out", out, words * 8, true}, {"device_in", in, words * 8, false}}));
     HEAMD_HIP_TRY(heamd::launch_stream_copy(in, out, words, non_temporal != 0, as_stream(s)));
     return HE_OK;
 }
 int he_words_narrow_u64_device(const uint64_t* in, uint32_t* out, size_t words, he_stream s) {
     if (words == 0) return HE_OK;
     if (in == nullptr || out == nullptr) return invalid_argument("null slab");
+    HEAMD_TRY_STATUS(heamd::check_slabs("narrow", {{"device_out", out, words * 4, true}, {"device_in", in, words * 8, false}}));
     if ((reinterpret_cast<uintptr_t>(in) & 15u) != 0 || (reinterpret_cast<uintptr_t>(out) & 15u) != 0)
         return invalid_argument("slabs must be 16-byte aligned");
     HEAMD_HIP_TRY(heamd::launch_narrow_words(in, out, words, as_stream(s)));
@@ -981,6 +1010,10 @@ int ciphertexts_serialize(const he_poly_context* ctx, const W* cts, size_t count
     if (record_stride < record_bytes) return short_stride(record_stride, record_bytes);
     if (count == 0) return HE_OK;
     if (cts == nullptr || records == nullptr) return invalid_argument("null buffer");
+    // (the records' range runs from the first record's first byte to the last one's last, the gaps between them included)
+    HEAMD_TRY_STATUS(heamd::check_slabs(
+        "serialize", {{"records", records, (count - 1) * record_stride + static_cast<size_t>(record_bytes), true},
+                      {"cts", cts, count * poly_count * pc.moduli_count() * pc.degree() * sizeof(W), false}}));
     status = pc.check_device();
     if (status != HE_OK) return status;
     HEAMD_HIP_TRY(heamd::launch_ciphertexts_serialize(cts, size_t(poly_count) * pc.moduli_count() * pc.degree(), records,
@@ -1004,6 +1037,10 @@ int ciphertexts_deserialize(const he_poly_context* ctx, const uint8_t* records, 
     if (record_stride < record_bytes) return short_stride(record_stride, record_bytes);
     if (count == 0) return HE_OK;
     if (cts == nullptr || records == nullptr) return invalid_argument("null buffer");
+    HEAMD_TRY_STATUS(heamd::check_slabs(
+        "deserialize", {{"cts", cts, count * poly_count * pc.moduli_count() * pc.degree() * sizeof(W), true},
+                        {"device_header_mismatch", device_header_mismatch, sizeof(uint32_t), true},
+                        {"records", records, (count - 1) * record_stride + static_cast<size_t>(record_bytes), false}}));
     status = pc.check_device();
     if (status != HE_OK) return status;
     HEAMD_HIP_TRY(heamd::launch_ciphertexts_deserialize(records, record_stride, cts,
@@ -1039,6 +1076,10 @@ int ciphertexts_deserialize_seeded(const he_poly_context* ctx, const uint8_t* po
     }
     if (count == 0) return HE_OK;
     if (cts == nullptr) return invalid_argument("null ciphertexts");
+    HEAMD_TRY_STATUS(heamd::check_slabs(
+        "deserialize(seeded:)", {{"cts", cts, count * 2 * pc.moduli_count() * pc.degree() * sizeof(W), true},
+                                 {"poly0_bytes", poly0_bytes, (count - 1) * record_stride + static_cast<size_t>(record_bytes), false},
+                                 {"seeds", seeds, count * 32, false}}));
     status = pc.check_device();
     if (status != HE_OK) return status;
     hipStream_t stream = as_stream(s);
@@ -1237,6 +1278,10 @@ int he_poly_divide_and_round_q_last(const he_poly_context* ctx, const uint64_t* 
 int he_poly_adding_lazy_product_device(const he_poly_context* ctx, const uint64_t* lhs, const uint64_t* rhs,
                                        uint64_t* acc_lo_hi, he_stream s) {
     if (ctx == nullptr || lhs == nullptr || rhs == nullptr || acc_lo_hi == nullptr) return invalid_argument("null");
+    const size_t poly_bytes = size_t(ctx->impl->moduli_count()) * ctx->impl->degree() * sizeof(uint64_t);
+    HEAMD_TRY_STATUS(heamd::check_slabs("addingLazyProduct", {{"acc_lo_hi", acc_lo_hi, 2 * poly_bytes, true},
+                                                              {"lhs", lhs, poly_bytes, false},
+                                                              {"rhs", rhs, poly_bytes, false}}));
     int status = ctx->impl->check_device();
     if (status != HE_OK) return status;
     HEAMD_HIP_TRY(heamd::launch_adding_lazy_product(lhs, rhs, acc_lo_hi, ctx->impl->device_context(), as_stream(s)));
@@ -1245,6 +1290,9 @@ int he_poly_adding_lazy_product_device(const he_poly_context* ctx, const uint64_
 int he_poly_reduce_accumulator_device(const he_poly_context* ctx, const uint64_t* acc_lo_hi, uint64_t* out,
                                       he_stream s) {
     if (ctx == nullptr || acc_lo_hi == nullptr || out == nullptr) return invalid_argument("null");
+    const size_t poly_bytes = size_t(ctx->impl->moduli_count()) * ctx->impl->degree() * sizeof(uint64_t);
+    HEAMD_TRY_STATUS(heamd::check_slabs("reduceAccumulator", {{"out", out, poly_bytes, true},
+                                                              {"acc_lo_hi", acc_lo_hi, 2 * poly_bytes, false}}));
     int status = ctx->impl->check_device();
     if (status != HE_OK) return status;
     HEAMD_HIP_TRY(heamd::launch_reduce_accumulator(acc_lo_hi, out, ctx->impl->device_context(), as_stream(s)));

@@ -219,6 +219,21 @@ int check_key_generation(const he_bfv_context* ctx, uint32_t word_bits, const Bf
     return HE_OK;
 }
 
+// The pointer contract of the entries that encrypt `count` zeros over m moduli of pc (he_amd.h): out and a caller's workspace are
+// written; the secret key, the seeds ([count][32] each) and the plaintexts or current keys (`extra`) are only read and may lie
+// anywhere but in those two.
+int check_encrypt_slabs(const char* what, const PolyContext& pc, uint32_t m, size_t word_bytes, const void* secret_key,
+                        const uint8_t* a_seeds, const uint8_t* error_seeds, heamd::Slab extra, const void* out, size_t count,
+                        const void* workspace, size_t workspace_bytes) {
+    const size_t row = size_t(pc.degree()) * word_bytes;
+    return heamd::check_slabs(what, {{"out", out, count * 2 * m * row, true},
+                                     {"workspace", workspace, workspace_bytes, true},
+                                     {"secret_key", secret_key, m * row, false},
+                                     {"a_seeds", a_seeds, count * 32, false},
+                                     {"error_seeds", error_seeds, count * 32, false},
+                                     extra});
+}
+
 int check_moduli_fit_word(const PolyContext& pc, uint32_t word_bits) {
     if (word_bits == 64) return HE_OK;
     for (heamd::u64 q : pc.moduli())
@@ -252,6 +267,9 @@ int poly_sample_entry(const he_poly_context* ctx, uint32_t word_bits, bool terna
     HEAMD_TRY_STATUS(check_moduli_fit_word(pc, word_bits));
     if (batch == 0) return HE_OK;
     if (seeds == nullptr || out == nullptr) return invalid_argument("null buffer");
+    HEAMD_TRY_STATUS(heamd::check_slabs(ternary ? "randomizeTernary" : "randomizeCenteredBinomialDistribution",
+                                        {{"out", out, batch * pc.moduli_count() * pc.degree() * (word_bits / 8), true},
+                                         {"seeds", seeds, batch * 32, false}}));
     HEAMD_TRY_STATUS(pc.check_device());
     if (word_bits == 32) return poly_sample(pc, ternary, seeds, batch, static_cast<uint32_t*>(out), as_stream(s));
     return poly_sample(pc, ternary, seeds, batch, static_cast<uint64_t*>(out), as_stream(s));
@@ -294,6 +312,10 @@ int he_bfv_generate_secret_key_device(const he_bfv_context* ctx, uint32_t word_b
     if (batch == 0) return HE_OK;
     if (seeds == nullptr || out == nullptr) return invalid_argument("null seeds or keys");
     const PolyContext& pc = secret_key_context(*bfv);
+    HEAMD_TRY_STATUS(heamd::check_slabs(
+        "generateSecretKey", {{"out", out, batch * pc.moduli_count() * pc.degree() * (word_bits / 8), true},
+                              {"workspace", workspace, workspace_bytes, true},
+                              {"seeds", seeds, batch * 32, false}}));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, pc.moduli_count()));
     const hipStream_t stream = as_stream(s);
     const EncryptPlan plan = plan_secret_keys(pc, batch);
@@ -325,6 +347,8 @@ int he_bfv_encrypt_zero_device(const he_bfv_context* ctx, uint32_t word_bits, ui
     if (batch == 0) return HE_OK;
     if (secret_key == nullptr || a_seeds == nullptr || error_seeds == nullptr || out == nullptr)
         return invalid_argument("null secret key, seeds or ciphertexts");
+    HEAMD_TRY_STATUS(check_encrypt_slabs("encryptZero", secret_key_context(*bfv), moduli_count, word_bits / 8, secret_key, a_seeds,
+                                         error_seeds, {"", nullptr, 0, false}, out, batch, workspace, workspace_bytes));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, moduli_count));
     if (word_bits == 32)
         return encrypt_zero_entry<uint32_t>(*bfv, moduli_count, eval_out != 0, secret_key, a_seeds, error_seeds, nullptr, out,
@@ -342,6 +366,9 @@ int he_bfv_encrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_
     if (batch == 0) return HE_OK;
     if (secret_key == nullptr || a_seeds == nullptr || error_seeds == nullptr || plaintexts == nullptr || out == nullptr)
         return invalid_argument("null secret key, seeds, plaintexts or ciphertexts");
+    HEAMD_TRY_STATUS(check_encrypt_slabs("encrypt", secret_key_context(*bfv), moduli_count, word_bits / 8, secret_key, a_seeds,
+                                         error_seeds, {"plaintexts", plaintexts, batch * bfv->degree() * (word_bits / 8), false}, out,
+                                         batch, workspace, workspace_bytes));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, moduli_count));
     if (word_bits == 32)
         return encrypt_zero_entry<uint32_t>(*bfv, moduli_count, false, secret_key, a_seeds, error_seeds, plaintexts, out, batch,
@@ -358,6 +385,13 @@ int he_bfv_generate_key_switch_keys_device(const he_bfv_context* ctx, uint32_t w
     if (keys == 0) return HE_OK;
     if (secret_key == nullptr || current_keys == nullptr || a_seeds == nullptr || error_seeds == nullptr || out == nullptr)
         return invalid_argument("null keys or seeds");
+    {
+        const PolyContext& pc = secret_key_context(*bfv);  // (the secret key may itself be a current key: both are only read)
+        const size_t key_bytes = size_t(pc.moduli_count()) * pc.degree() * (word_bits / 8);
+        HEAMD_TRY_STATUS(check_encrypt_slabs("generateKeySwitchKey", pc, pc.moduli_count(), word_bits / 8, secret_key, a_seeds,
+                                             error_seeds, {"current_keys", current_keys, keys * key_bytes, false}, out,
+                                             keys * bfv->top_level(), workspace, workspace_bytes));
+    }
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, bfv->top_level() + 1));
     if (word_bits == 32)
         return key_switch_keys_entry<uint32_t>(*bfv, CurrentKeys::Callers, secret_key, current_keys, nullptr, a_seeds,
@@ -373,6 +407,9 @@ int he_bfv_generate_relinearization_key_device(const he_bfv_context* ctx, uint32
     HEAMD_TRY_STATUS(check_key_generation(ctx, word_bits, &bfv));
     if (secret_key == nullptr || a_seeds == nullptr || error_seeds == nullptr || out == nullptr)
         return invalid_argument("null keys or seeds");
+    HEAMD_TRY_STATUS(check_encrypt_slabs("generateRelinearizationKey", secret_key_context(*bfv), bfv->top_level() + 1, word_bits / 8,
+                                         secret_key, a_seeds, error_seeds, {"", nullptr, 0, false}, out, bfv->top_level(), workspace,
+                                         workspace_bytes));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, bfv->top_level() + 1));
     if (word_bits == 32)
         return key_switch_keys_entry<uint32_t>(*bfv, CurrentKeys::Square, secret_key, nullptr, nullptr, a_seeds, error_seeds, out,
@@ -395,6 +432,9 @@ int he_bfv_generate_galois_keys_device(const he_bfv_context* ctx, uint32_t word_
     if (count == 0) return HE_OK;
     if (secret_key == nullptr || a_seeds == nullptr || error_seeds == nullptr || out == nullptr)
         return invalid_argument("null keys or seeds");
+    HEAMD_TRY_STATUS(check_encrypt_slabs("generateGaloisKeys", secret_key_context(*bfv), bfv->top_level() + 1, word_bits / 8,
+                                         secret_key, a_seeds, error_seeds, {"", nullptr, 0, false}, out, count * bfv->top_level(),
+                                         workspace, workspace_bytes));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, bfv->top_level() + 1));
     if (word_bits == 32)
         return key_switch_keys_entry<uint32_t>(*bfv, CurrentKeys::Galois, secret_key, nullptr, elements, a_seeds, error_seeds, out,

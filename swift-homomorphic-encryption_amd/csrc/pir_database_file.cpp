@@ -41,11 +41,6 @@ int truncated(const std::string& where, size_t at, size_t byte_count) {
     return HE_ERR_INVALID_ARGUMENT;
 }
 
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 // the checks both device entries share, in the order the header states; HE_OK with *run = false: nothing to do
 template <typename W>
 int check_device_call(const he_bfv_context* ctx, const void* records, size_t records_bytes, const uint8_t* present,
@@ -59,7 +54,7 @@ int check_device_call(const he_bfv_context* ctx, const void* records, size_t rec
     if (count == 0) return HE_OK;
     if (records == nullptr || present == nullptr || database == nullptr) return invalid_argument("null buffer");
     const size_t slab_bytes = count * layout.rows * bfv.degree() * sizeof(W);
-    if (overlap(records, records_bytes, database, slab_bytes)) return invalid_argument("database overlaps records");
+    if (heamd::ranges_overlap(records, records_bytes, database, slab_bytes)) return invalid_argument("database overlaps records");
     const he_poly_context* top = he_bfv_ciphertext_context(ctx, he_bfv_ciphertext_moduli_count(ctx));
     const int ready = top->impl->check_device();  // a host-only context: HE_ERR_DEVICE
     if (ready != HE_OK) return ready;

@@ -169,21 +169,22 @@ def test_seeded_coeff_refuses_what_has_no_transform_before_any_launch():
 
     lib = heamd.load_library()
     fake = ctypes.c_void_p(0x1000)
+    seeds, cts = ctypes.c_void_p(1 << 28), ctypes.c_void_p(2 << 28)  # a range each: the slabs of a call must not overlap
     plain = _context(64, (30, 27, 2))  # 3 is no NTT modulus for degree 64
     for name in ("he_ciphertexts_deserialize_seeded_device", "he_ciphertexts_deserialize_seeded_device_u32"):
         seeded = getattr(lib, name)
-        assert seeded(plain.h, fake, 1 << 20, fake, 1, 1, fake, None) == _status("invalidNttModulus")
+        assert seeded(plain.h, fake, 1 << 20, seeds, 1, 1, cts, None) == _status("invalidNttModulus")
         assert b"not an NTT modulus" in lib.he_last_error_message()
         # Eval takes no transform, and neither does a call that skips the seeds: both get as far as the device
-        assert seeded(plain.h, fake, 1 << 20, fake, 1, 0, fake, None) == _status("deviceError")
-        assert seeded(plain.h, fake, 1 << 20, None, 1, 1, fake, None) == _status("deviceError")
+        assert seeded(plain.h, fake, 1 << 20, seeds, 1, 0, cts, None) == _status("deviceError")
+        assert seeded(plain.h, fake, 1 << 20, None, 1, 1, cts, None) == _status("deviceError")
     degree = 65536
     wide = heamd.PolyContext(degree, heamd.generate_primes([28], False, degree), host_only=True)
-    assert lib.he_ciphertexts_deserialize_seeded_device_u32(wide.h, fake, 1 << 20, fake, 1, 1, fake,
+    assert lib.he_ciphertexts_deserialize_seeded_device_u32(wide.h, fake, 1 << 20, seeds, 1, 1, cts,
                                                             None) == _status("unsupportedHeOperation")
     assert b"32768" in lib.he_last_error_message()
-    assert lib.he_ciphertexts_deserialize_seeded_device_u32(wide.h, fake, 1 << 20, fake, 1, 0, fake, None) == _status("deviceError")
-    assert lib.he_ciphertexts_deserialize_seeded_device(wide.h, fake, 1 << 20, fake, 1, 1, fake, None) == _status("deviceError")
+    assert lib.he_ciphertexts_deserialize_seeded_device_u32(wide.h, fake, 1 << 20, seeds, 1, 0, cts, None) == _status("deviceError")
+    assert lib.he_ciphertexts_deserialize_seeded_device(wide.h, fake, 1 << 20, seeds, 1, 1, cts, None) == _status("deviceError")
 
 
 # ---- the kernel form -----------------------------------------------------------------------------------------------------------

@@ -142,17 +142,16 @@ def _all_entries(lib, ctx, word_bits, moduli_count=1, elements=(3,), count=1):
     """every device entry with non-null dummy pointers (none is dereferenced before the device check)"""
     import ctypes
 
-    fake = ctypes.c_void_p(16)
+    a, b, c, d, e = (ctypes.c_void_p(n << 24) for n in range(1, 6))  # a slab each, far apart: slabs of a call must not overlap
     element_array = (ctypes.c_uint64 * max(len(elements), 1))(*elements)
     return {
-        "secret_key": lib.he_bfv_generate_secret_key_device(ctx, word_bits, fake, fake, count, None, 0, None),
-        "encrypt_zero": lib.he_bfv_encrypt_zero_device(ctx, word_bits, moduli_count, 0, fake, fake, fake, fake, count, None, 0, None),
-        "encrypt": lib.he_bfv_encrypt_device(ctx, word_bits, moduli_count, fake, fake, fake, fake, fake, count, None, 0, None),
-        "key_switch_keys": lib.he_bfv_generate_key_switch_keys_device(ctx, word_bits, fake, fake, fake, fake, fake, count, None, 0,
-                                                                      None),
-        "relinearization_key": lib.he_bfv_generate_relinearization_key_device(ctx, word_bits, fake, fake, fake, fake, None, 0, None),
-        "galois_keys": lib.he_bfv_generate_galois_keys_device(ctx, word_bits, fake, element_array, len(elements), fake, fake, fake,
-                                                              None, 0, None),
+        "secret_key": lib.he_bfv_generate_secret_key_device(ctx, word_bits, a, b, count, None, 0, None),
+        "encrypt_zero": lib.he_bfv_encrypt_zero_device(ctx, word_bits, moduli_count, 0, a, b, c, d, count, None, 0, None),
+        "encrypt": lib.he_bfv_encrypt_device(ctx, word_bits, moduli_count, a, b, c, d, e, count, None, 0, None),
+        "key_switch_keys": lib.he_bfv_generate_key_switch_keys_device(ctx, word_bits, a, b, c, d, e, count, None, 0, None),
+        "relinearization_key": lib.he_bfv_generate_relinearization_key_device(ctx, word_bits, a, b, c, d, None, 0, None),
+        "galois_keys": lib.he_bfv_generate_galois_keys_device(ctx, word_bits, a, element_array, len(elements), b, c, d, None, 0,
+                                                              None),
     }
 
 
@@ -239,7 +238,7 @@ def test_polynomial_sampler_argument_errors():
     import ctypes
 
     lib = heamd.load_library()
-    fake = ctypes.c_void_p(16)
+    fake, other = ctypes.c_void_p(16), ctypes.c_void_p(1 << 24)  # seeds and polynomials must not overlap
     host = heamd.PolyContext(8, heamd.generate_primes([40, 41], False, 8), host_only=True)
     for entry in (lib.he_poly_random_ternary_from_seeds_device, lib.he_poly_random_centered_binomial_from_seeds_device):
         assert _status(entry(host.h, 16, fake, 1, fake, None)) == "invalidArgument"
@@ -247,7 +246,7 @@ def test_polynomial_sampler_argument_errors():
         assert _status(entry(host.h, 32, fake, 1, fake, None)) == "invalidModulus"  # 40 bits do not fit a 4-byte word
         assert entry(host.h, 64, None, 0, None, None) == 0
         assert _status(entry(host.h, 64, None, 1, fake, None)) == "invalidArgument"
-        assert _status(entry(host.h, 64, fake, 1, fake, None)) == "deviceError"
+        assert _status(entry(host.h, 64, fake, 1, other, None)) == "deviceError"
 
 
 def test_header_exports_and_binding_name_the_entries():

@@ -30,6 +30,12 @@ BFV_PAIRS = [
 # the one 4-byte entry that looks at the word size before the level
 WORD_SIZE_FIRST = "he_bfv_inner_product_plain_resident_device_u32"
 
+def elsewhere(slab):
+    """A second slab, far from the first: in and out of an out-of-place entry must not overlap (the in-place entries above it
+    may take one slab as both operands: x + x, x - x, x * x)."""
+    return None if slab is None else slab + 0x100000
+
+
 # (entry, arguments between the context and the stream for a batch of `batch` with slabs at `slab`)
 POLY_PAIRS = {
     "he_ntt_forward_device": lambda slab, batch: (slab, batch),
@@ -39,7 +45,7 @@ POLY_PAIRS = {
     "he_poly_neg_device": lambda slab, batch: (slab, batch),
     "he_poly_mul_device": lambda slab, batch: (slab, slab, batch),
     "he_poly_mul_scalar_device": lambda slab, batch: (slab, None, batch),  # the residues are filled in by poly_call
-    "he_poly_divide_and_round_q_last_device": lambda slab, batch: (slab, slab, batch),
+    "he_poly_divide_and_round_q_last_device": lambda slab, batch: (slab, elsewhere(slab), batch),
 }
 TRANSFORMS = ("he_ntt_forward_device", "he_ntt_inverse_device")
 
