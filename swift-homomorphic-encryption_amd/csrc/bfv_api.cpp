@@ -605,10 +605,9 @@ size_t he_bfv_relinearize_workspace_bytes(const he_bfv_context* ctx, uint32_t mo
 }
 
 extern "C++" {
-namespace {
 template <typename W>
-int relinearize_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* ct3, const W* key, W* out, size_t batch,
-                      void* workspace, size_t workspace_bytes, he_stream s) {
+int heamd::bfv_relinearize(const he_bfv_context* ctx, uint32_t moduli_count, const W* ct3, const W* key, W* out, size_t batch,
+                           void* workspace, size_t workspace_bytes, hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
     // out must not overlap ct3: the last kernel adds the update to (c0, c1) of one item while it stores another item's
     // result (items are 3 L N words apart in ct3 and 2 L N apart in out), in no particular order -- and which kernel
@@ -631,20 +630,23 @@ int relinearize_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W*
     }
     if (batch == 0) return HE_OK;
     if (ct3 == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    return relinearize_pipeline(ctx, moduli_count, ct3, key, out, batch, workspace, workspace_bytes, as_stream(s));
+    return relinearize_pipeline(ctx, moduli_count, ct3, key, out, batch, workspace, workspace_bytes, stream);
 }
-}  // namespace
+template int heamd::bfv_relinearize(const he_bfv_context*, uint32_t, const uint64_t*, const uint64_t*, uint64_t*, size_t, void*,
+                                    size_t, hipStream_t);
+template int heamd::bfv_relinearize(const he_bfv_context*, uint32_t, const uint32_t*, const uint32_t*, uint32_t*, size_t, void*,
+                                    size_t, hipStream_t);
 }  // extern "C++"
 
 int he_bfv_relinearize_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* ct3,
                               const uint64_t* key, uint64_t* out, size_t batch, void* workspace,
                               size_t workspace_bytes, he_stream s) {
-    return relinearize_entry(ctx, moduli_count, ct3, key, out, batch, workspace, workspace_bytes, s);
+    return heamd::bfv_relinearize(ctx, moduli_count, ct3, key, out, batch, workspace, workspace_bytes, as_stream(s));
 }
 int he_bfv_relinearize_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* ct3,
                                   const uint32_t* key, uint32_t* out, size_t batch, void* workspace,
                                   size_t workspace_bytes, he_stream s) {
-    return relinearize_entry(ctx, moduli_count, ct3, key, out, batch, workspace, workspace_bytes, s);
+    return heamd::bfv_relinearize(ctx, moduli_count, ct3, key, out, batch, workspace, workspace_bytes, as_stream(s));
 }
 
 // ------------------------------------------------------------------------------------------ Galois automorphism
@@ -1362,16 +1364,21 @@ int check_inner_product_plain(const he_bfv_context* ctx, uint32_t moduli_count, 
         return invalid_argument("poly_count must be 1, 2, 3, 4, 6 or 8");
     return HE_OK;
 }
+}  // namespace
 template <typename W>
-int inner_product_plain_resident(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* cts,
-                                 const W* pts, const uint8_t* present_device, size_t count, size_t columns, W* out, he_stream s) {
+int heamd::bfv_inner_product_plain_resident(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* cts,
+                                            const W* pts, const uint8_t* present_device, size_t count, size_t columns, W* out,
+                                            hipStream_t stream) {
     bool nothing = false;
     int status = check_inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, &nothing,
                                            sizeof(W), [&](size_t n) { return moduli_count * n * sizeof(W); });
     if (status != HE_OK || nothing) return status;
-    return inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, as_stream(s));
+    return inner_product_plain(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, stream);
 }
-}  // namespace
+template int heamd::bfv_inner_product_plain_resident(const he_bfv_context*, uint32_t, uint32_t, const uint64_t*, const uint64_t*,
+                                                     const uint8_t*, size_t, size_t, uint64_t*, hipStream_t);
+template int heamd::bfv_inner_product_plain_resident(const he_bfv_context*, uint32_t, uint32_t, const uint32_t*, const uint32_t*,
+                                                     const uint8_t*, size_t, size_t, uint32_t*, hipStream_t);
 
 heamd::AccumulatorCadence heamd::accumulator_cadence(const PolyContext& pc, uint32_t level) {
     AccumulatorCadence lazy{pc.max_lazy_product_accumulation_count(level), 0, true};
@@ -1412,13 +1419,15 @@ int he_bfv_inner_product_plain_device(const he_bfv_context* ctx, uint32_t moduli
 int he_bfv_inner_product_plain_resident_device(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
                                                const uint64_t* cts, const uint64_t* pts, const uint8_t* present_device,
                                                size_t count, size_t columns, uint64_t* out, he_stream s) {
-    return inner_product_plain_resident(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, s);
+    return heamd::bfv_inner_product_plain_resident(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out,
+                                                   as_stream(s));
 }
 int he_bfv_inner_product_plain_resident_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count,
                                                    const uint32_t* cts, const uint32_t* pts,
                                                    const uint8_t* present_device, size_t count, size_t columns,
                                                    uint32_t* out, he_stream s) {
-    return inner_product_plain_resident(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out, s);
+    return heamd::bfv_inner_product_plain_resident(ctx, moduli_count, poly_count, cts, pts, present_device, count, columns, out,
+                                                   as_stream(s));
 }
 
 // ------------------------------------------------------------------------------------------ packed plaintexts
@@ -1610,10 +1619,9 @@ int bfv_inner_product_shared_eval_rhs(const he_bfv_context* ctx, uint32_t L, con
 }  // extern "C++"
 
 extern "C++" {
-namespace {
 template <typename W>
-int inner_product_shared_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count,
-                               size_t items, W* out, he_stream s) {
+int heamd::bfv_inner_product_shared(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count,
+                                    size_t items, W* out, hipStream_t stream) {
     const RnsToolLevel* tool = nullptr;
     // lhs and rhs are only read (lifted into scratch): lhs may be an item of rhs, or all of it
     int status = check_level(ctx, moduli_count, &tool, sizeof(W), [&](size_t n) {
@@ -1626,8 +1634,13 @@ int inner_product_shared_entry(const he_bfv_context* ctx, uint32_t moduli_count,
     if (count == 0) return invalid_argument("empty ciphertext vector");
     if (items == 0) return HE_OK;
     if (lhs == nullptr || rhs == nullptr || out == nullptr) return invalid_argument("null ciphertext");
-    return inner_product_shared_pipeline(ctx, tool, moduli_count, lhs, rhs, count, items, out, as_stream(s));
+    return inner_product_shared_pipeline(ctx, tool, moduli_count, lhs, rhs, count, items, out, stream);
 }
+template int heamd::bfv_inner_product_shared(const he_bfv_context*, uint32_t, const uint64_t*, const uint64_t*, size_t, size_t,
+                                             uint64_t*, hipStream_t);
+template int heamd::bfv_inner_product_shared(const he_bfv_context*, uint32_t, const uint32_t*, const uint32_t*, size_t, size_t,
+                                             uint32_t*, hipStream_t);
+namespace {
 template <typename W>
 int inner_product_entry(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count, W* out,
                         void* workspace, size_t workspace_bytes, he_stream s) {
@@ -1650,11 +1663,11 @@ int inner_product_entry(const he_bfv_context* ctx, uint32_t moduli_count, const 
 
 int he_bfv_inner_product_shared_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
                                        const uint64_t* rhs, size_t count, size_t items, uint64_t* out, he_stream s) {
-    return inner_product_shared_entry(ctx, moduli_count, lhs, rhs, count, items, out, s);
+    return heamd::bfv_inner_product_shared(ctx, moduli_count, lhs, rhs, count, items, out, as_stream(s));
 }
 int he_bfv_inner_product_shared_device_u32(const he_bfv_context* ctx, uint32_t moduli_count, const uint32_t* lhs,
                                            const uint32_t* rhs, size_t count, size_t items, uint32_t* out, he_stream s) {
-    return inner_product_shared_entry(ctx, moduli_count, lhs, rhs, count, items, out, s);
+    return heamd::bfv_inner_product_shared(ctx, moduli_count, lhs, rhs, count, items, out, as_stream(s));
 }
 int he_bfv_inner_product_device(const he_bfv_context* ctx, uint32_t moduli_count, const uint64_t* lhs,
                                 const uint64_t* rhs, size_t count, uint64_t* out, void* workspace,

@@ -8,6 +8,10 @@
 //   3. modSwitchDownToSingle                                                                         :481-485
 // The reference fans these out over Swift tasks; here every stage is one batched launch (or a short loop of
 // launches) of the kernels behind the B3 entry points on the caller's stream -- no stage returns to the host.
+//
+// The chunk loop is written once for both slab words (word_layer.hpp): W = uint64_t, and W = uint32_t for Bfv<UInt32> on
+// packed 4-byte slabs (the reference's 27/28-bit PIR parameter sets, EncryptionParameters.swift:313-345: half the database
+// bytes of the 8-byte route).  kDim0ResultsStayEval<W> says whether step 1's results skip the conversion to Coeff.
 #include <vector>
 
 #include <cstdlib>
@@ -33,7 +37,7 @@ struct ChunkShape {
 
 // the reference's preconditions on (dimensions, query) -- PirUtil.swift:420-422 and the slices taken at :454
 int chunk_shape(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
-                const uint64_t* remaining_query, size_t remaining_query_count, ChunkShape& shape) {
+                const void* remaining_query, size_t remaining_query_count, ChunkShape& shape) {
     if (ctx == nullptr) return invalid_argument("null context");
     if (dimensions == nullptr || dimension_count == 0) return invalid_argument("empty dimensions");
     shape.L = he_bfv_ciphertext_moduli_count(ctx);
@@ -58,91 +62,96 @@ int chunk_shape(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t 
 
 namespace {
 // every column's ct . pt inner product in one launch (PirUtil.swift:428-437), then back to Coeff (:438); packed: the
-// database holds packed plaintexts (he_amd.h he_bfv_pack_plaintexts_device)
-int dim0_columns(const he_bfv_context* ctx, const uint64_t* dim0_query_eval, size_t d0, const uint64_t* database, bool packed,
-                 const uint8_t* present_device, size_t columns, uint64_t* out, he_stream s, bool leave_in_eval = false) {
+// database holds packed plaintexts (he_amd.h he_bfv_pack_plaintexts_device), an 8-byte layout that no 4-byte entry asks for
+template <typename W>
+int dim0_columns(const he_bfv_context* ctx, const W* dim0_query_eval, size_t d0, const W* database, bool packed,
+                 const uint8_t* present_device, size_t columns, W* out, hipStream_t stream, bool leave_in_eval = false) {
     if (ctx == nullptr) return invalid_argument("null context");
     if (columns == 0) return HE_OK;
     if (dim0_query_eval == nullptr || database == nullptr || out == nullptr) return invalid_argument("null operand");
     const uint32_t L = he_bfv_ciphertext_moduli_count(ctx);
     const he_poly_context* q_ctx = he_bfv_ciphertext_context(ctx, L);
     if (q_ctx == nullptr) return invalid_argument("context has no ciphertext level");
-    if (packed)
-        HEAMD_TRY_STATUS(he_bfv_inner_product_plain_packed_device(ctx, L, 2, dim0_query_eval, database, present_device, d0,
-                                                                  columns, out, s));
-    else
-        HEAMD_TRY_STATUS(he_bfv_inner_product_plain_resident_device(ctx, L, 2, dim0_query_eval, database, present_device,
-                                                                    d0, columns, out, s));
+    const auto packed_product = [&]() -> int {
+        if constexpr (sizeof(W) == 8)
+            return he_bfv_inner_product_plain_packed_device(ctx, L, 2, dim0_query_eval, database, present_device, d0, columns, out,
+                                                            static_cast<he_stream>(stream));
+        else return HE_ERR_UNSUPPORTED;
+    };
+    HEAMD_TRY_STATUS(packed ? packed_product()
+                            : heamd::bfv_inner_product_plain_resident(ctx, L, 2, dim0_query_eval, database, present_device, d0,
+                                                                      columns, out, stream));
     if (leave_in_eval) return HE_OK;  // (remaining_dimensions takes them as they are: results_in_eval)
-    return he_ntt_inverse_device(q_ctx, out, columns * 2, s);
+    return heamd::poly_ntt(q_ctx, out, columns * 2, true, stream);
 }
 }  // namespace
 
 extern "C" int he_pir_dim0_columns_device(const he_bfv_context* ctx, const uint64_t* dim0_query_eval, size_t d0,
                                           const uint64_t* database, const uint8_t* present_device, size_t columns,
                                           uint64_t* out, he_stream s) {
-    return dim0_columns(ctx, dim0_query_eval, d0, database, false, present_device, columns, out, s);
+    return dim0_columns(ctx, dim0_query_eval, d0, database, false, present_device, columns, out, as_stream(s));
 }
 extern "C" int he_pir_dim0_columns_packed_device(const he_bfv_context* ctx, const uint64_t* dim0_query_eval, size_t d0,
                                                  const uint64_t* packed_database, const uint8_t* present_device,
                                                  size_t columns, uint64_t* out, he_stream s) {
-    return dim0_columns(ctx, dim0_query_eval, d0, packed_database, true, present_device, columns, out, s);
+    return dim0_columns(ctx, dim0_query_eval, d0, packed_database, true, present_device, columns, out, as_stream(s));
 }
 
 namespace {
 // PirUtil.swift:448-485 for `chunks` chunks at once: intermediate [chunks][columns][2][L][N] Coeff (consumed) ->
 // out [chunks][2][1][N].  The result groups of all chunks share each dimension's query slice, so every stage of a
-// dimension is one batch over chunks x groups.
+// dimension is one batch over chunks x groups.  results_in_eval (only where kDim0ResultsStayEval<W>): the intermediate
+// results are the dim-0 inner products as their kernel left them.
+template <typename W>
 int remaining_dimensions(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
-                         const ChunkShape& shape, size_t chunks, uint64_t* results, const uint64_t* remaining_query,
-                         const uint64_t* relinearization_key, uint64_t* out, he_stream s, bool results_in_eval = false) {
-    hipStream_t stream = as_stream(s);
+                         const ChunkShape& shape, size_t chunks, W* results, const W* remaining_query,
+                         const W* relinearization_key, W* out, hipStream_t stream, bool results_in_eval = false) {
     const uint32_t L = shape.L;
     const size_t n = shape.n, poly = size_t(L) * n, ct2 = 2 * poly, ct3 = 3 * poly;
     Scratch next_mem(stream), products_mem(stream);
     size_t count = shape.columns, cursor = 0;  // ciphertexts per chunk
     if (dimension_count > 1) {
         const size_t max_items = chunks * (shape.columns / dimensions[1]);
-        HEAMD_HIP_TRY(next_mem.allocate((max_items ? max_items : 1) * ct2 * sizeof(uint64_t)));
-        HEAMD_HIP_TRY(products_mem.allocate((max_items ? max_items : 1) * ct3 * sizeof(uint64_t)));
+        HEAMD_HIP_TRY(next_mem.allocate((max_items ? max_items : 1) * ct2 * sizeof(W)));
+        HEAMD_HIP_TRY(products_mem.allocate((max_items ? max_items : 1) * ct3 * sizeof(W)));
     }
     // the relinearized products of a dimension become the next one's operands: the two slabs swap roles
-    uint64_t* current = results;
-    uint64_t* other = static_cast<uint64_t*>(next_mem.get());
-    uint64_t* products = static_cast<uint64_t*>(products_mem.get());
+    W* current = results;
+    W* other = static_cast<W*>(next_mem.get());
+    W* products = static_cast<W*>(products_mem.get());
     for (uint32_t i = 1; i < dimension_count; ++i) {
         const size_t d = dimensions[i];
         if (count % d != 0) return invalid_argument("intermediate results do not divide by the dimension");
         const size_t items = chunks * (count / d);  // groups of d consecutive results, chunk after chunk
-        const uint64_t* query = remaining_query + cursor * ct2;
+        const W* query = remaining_query + cursor * ct2;
         // results_in_eval: the dim-0 inner products came as their kernel left them, in Eval form -- the first dimension's ct x ct
         // inner products then read those words as the Q rows of their lifted operands instead of transforming them back and
         // forth (the tail of 8 chunks of 256 x 64: 0.91 -> 0.74 ms, profiles/r06y_pir_tail_eval_rows.txt)
         int status = heamd::kInnerProductEvalUnavailable;
-        if (results_in_eval && i == 1)
-            status = heamd::bfv_inner_product_shared_eval_rhs(ctx, L, query, current, d, items, products, stream);
-        if (status == heamd::kInnerProductEvalUnavailable) {
-            if (results_in_eval && i == 1) {  // PirUtil.swift:438
-                const he_poly_context* q_ctx = he_bfv_ciphertext_context(ctx, L);
-                HEAMD_TRY_STATUS(he_ntt_inverse_device(q_ctx, current, chunks * count * 2, s));
+        if constexpr (heamd::kDim0ResultsStayEval<W>) {
+            if (results_in_eval && i == 1) {
+                status = heamd::bfv_inner_product_shared_eval_rhs(ctx, L, query, current, d, items, products, stream);
+                if (status == heamd::kInnerProductEvalUnavailable)  // PirUtil.swift:438
+                    HEAMD_TRY_STATUS(heamd::poly_ntt(shape.q_ctx, current, chunks * count * 2, true, stream));
             }
-            status = he_bfv_inner_product_shared_device(ctx, L, query, current, d, items, products, s);
         }
+        if (status == heamd::kInnerProductEvalUnavailable)
+            status = heamd::bfv_inner_product_shared(ctx, L, query, current, d, items, products, stream);
         HEAMD_TRY_STATUS(status);
-        HEAMD_TRY_STATUS(he_bfv_relinearize_device(ctx, L, products, relinearization_key, other, items, nullptr, 0, s));
-        uint64_t* swap = current;
+        HEAMD_TRY_STATUS(heamd::bfv_relinearize(ctx, L, products, relinearization_key, other, items, nullptr, 0, stream));
+        W* swap = current;
         current = other;
         other = swap;
         count /= d;
         cursor += d;
     }
     if (count != 1) return invalid_argument("dimensions leave more than one ciphertext");  // PirUtil.swift:481-482
-    if (results_in_eval && dimension_count == 1) {  // PirUtil.swift:438 with nothing after it
-        const he_poly_context* q_ctx = he_bfv_ciphertext_context(ctx, L);
-        HEAMD_TRY_STATUS(he_ntt_inverse_device(q_ctx, current, chunks * 2, s));
+    if constexpr (heamd::kDim0ResultsStayEval<W>) {
+        if (results_in_eval && dimension_count == 1)  // PirUtil.swift:438 with nothing after it
+            HEAMD_TRY_STATUS(heamd::poly_ntt(shape.q_ctx, current, chunks * 2, true, stream));
     }
     // modSwitchDownToSingle (:483) on the chunks' 2-polynomial ciphertexts
-    return he_bfv_mod_switch_down_to_single_device(ctx, L, 2, current, out, chunks, s);
+    return heamd::bfv_mod_switch_down_to_single(ctx, L, 2, current, out, chunks, stream);
 }
 
 // The chunks of a response are independent, and the reference answers them as concurrent tasks (PirUtil.swift:538-563):
@@ -167,31 +176,31 @@ size_t overlap_piece_chunks(uint32_t dimension_count, size_t chunks) {
 
 // `chunks` chunks with a device-resident mask, enqueue-only: per piece one dim-0 launch over the columns of its chunks, then
 // the remaining dimensions of those chunks together (beside the next piece's dim-0 launch)
+template <typename W>
 int response_chunks_resident(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
-                             const ChunkShape& shape, size_t chunks, const uint64_t* dim0_query_eval,
-                             const uint64_t* remaining_query, const uint64_t* database, size_t chunk_words, bool packed,
-                             const uint8_t* present_device, const uint64_t* relinearization_key, uint64_t* out,
-                             he_stream s) {
-    hipStream_t stream = as_stream(s);
+                             const ChunkShape& shape, size_t chunks, const W* dim0_query_eval, const W* remaining_query,
+                             const W* database, size_t chunk_words, bool packed, const uint8_t* present_device,
+                             const W* relinearization_key, W* out, hipStream_t stream) {
     const size_t ct2 = 2 * size_t(shape.L) * shape.n, out_words = 2 * shape.n;
     Scratch results_mem(stream);
-    HEAMD_HIP_TRY(results_mem.allocate(chunks * shape.columns * ct2 * sizeof(uint64_t)));
-    uint64_t* results = static_cast<uint64_t*>(results_mem.get());
+    HEAMD_HIP_TRY(results_mem.allocate(chunks * shape.columns * ct2 * sizeof(W)));
+    W* results = static_cast<W*>(results_mem.get());
     const size_t piece = overlap_piece_chunks(dimension_count, chunks);
     if (piece >= chunks) {
         // a chunk is [columns][d0] plaintexts and the chunks are contiguous: all their columns form one column range
+        const bool in_eval = heamd::kDim0ResultsStayEval<W>;
         HEAMD_TRY_STATUS(dim0_columns(ctx, dim0_query_eval, shape.d0, database, packed, present_device, chunks * shape.columns,
-                                      results, s, true));
+                                      results, stream, in_eval));
         return remaining_dimensions(ctx, dimensions, dimension_count, shape, chunks, results, remaining_query,
-                                    relinearization_key, out, s, true);
+                                    relinearization_key, out, stream, in_eval);
     }
     heamd::LaneLease lease(heamd::lane_pool(ctx), stream);
     if (lease.lane == nullptr) {
         // a chunk is [columns][d0] plaintexts and the chunks are contiguous: all their columns form one column range
         HEAMD_TRY_STATUS(dim0_columns(ctx, dim0_query_eval, shape.d0, database, packed, present_device, chunks * shape.columns,
-                                      results, s));
+                                      results, stream));
         return remaining_dimensions(ctx, dimensions, dimension_count, shape, chunks, results, remaining_query,
-                                    relinearization_key, out, s);
+                                    relinearization_key, out, stream);
     }
     SideLane& lane = *lease.lane;
     int status = HE_OK;
@@ -199,17 +208,17 @@ int response_chunks_resident(const he_bfv_context* ctx, const uint32_t* dimensio
     bool forked = false;
     for (size_t first = 0; first < chunks && status == HE_OK && e == hipSuccess; first += piece) {
         const size_t now = chunks - first < piece ? chunks - first : piece;
-        uint64_t* piece_results = results + first * shape.columns * ct2;
+        W* piece_results = results + first * shape.columns * ct2;
         status = dim0_columns(ctx, dim0_query_eval, shape.d0, database + first * chunk_words, packed,
                               present_device ? present_device + first * shape.per_chunk : nullptr, now * shape.columns,
-                              piece_results, s);
+                              piece_results, stream);
         if (status != HE_OK) break;
         e = hipEventRecord(lane.stage[0], stream);  // (re-recorded per piece: a wait takes the event as it is when enqueued)
         if (e == hipSuccess) e = hipStreamWaitEvent(lane.stream, lane.stage[0], 0);
         if (e != hipSuccess) break;
         forked = true;
         status = remaining_dimensions(ctx, dimensions, dimension_count, shape, now, piece_results, remaining_query,
-                                      relinearization_key, out + first * out_words, static_cast<he_stream>(lane.stream));
+                                      relinearization_key, out + first * out_words, lane.stream);
     }
     if (forked) {  // the join is enqueued whatever happened in between: the caller's stream never runs ahead of the lane's work
         const hipError_t recorded = hipEventRecord(lane.joined, lane.stream);
@@ -230,7 +239,7 @@ extern "C" int he_pir_remaining_dimensions_device(const he_bfv_context* ctx, con
     HEAMD_TRY_STATUS(chunk_shape(ctx, dimensions, dimension_count, remaining_query, remaining_query_count, shape));
     if (intermediate == nullptr || out == nullptr) return invalid_argument("null operand");
     return remaining_dimensions(ctx, dimensions, dimension_count, shape, 1, intermediate, remaining_query,
-                                relinearization_key, out, s);
+                                relinearization_key, out, as_stream(s));
 }
 
 // The remaining dimensions of `chunk_count` chunks at once (the chunk loop's second half, for callers that produced the dim-0
@@ -245,14 +254,14 @@ extern "C" int he_pir_remaining_dimensions_chunks_device(const he_bfv_context* c
     if (chunk_count == 0) return HE_OK;
     if (intermediate == nullptr || out == nullptr) return invalid_argument("null operand");
     return remaining_dimensions(ctx, dimensions, dimension_count, shape, chunk_count, intermediate, remaining_query,
-                                relinearization_key, out, s);
+                                relinearization_key, out, as_stream(s));
 }
 
 // The two halves for a caller that joins them itself (a device group: device_group.cpp) with the dim-0 results passed on in
 // EVAL form, as response_chunks_resident does inside one device (api_internal.hpp; not exported)
 int heamd::pir_dim0_columns_eval(const he_bfv_context* ctx, const uint64_t* dim0_query_eval, size_t d0, const uint64_t* database,
                                  const uint8_t* present_device, size_t columns, uint64_t* out, he_stream s) {
-    return dim0_columns(ctx, dim0_query_eval, d0, database, false, present_device, columns, out, s, true);
+    return dim0_columns(ctx, dim0_query_eval, d0, database, false, present_device, columns, out, as_stream(s), true);
 }
 int heamd::pir_remaining_dimensions_chunks_eval(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
                                                 size_t chunk_count, uint64_t* intermediate_eval, const uint64_t* remaining_query,
@@ -263,7 +272,7 @@ int heamd::pir_remaining_dimensions_chunks_eval(const he_bfv_context* ctx, const
     if (chunk_count == 0) return HE_OK;
     if (intermediate_eval == nullptr || out == nullptr) return invalid_argument("null operand");
     return remaining_dimensions(ctx, dimensions, dimension_count, shape, chunk_count, intermediate_eval, remaining_query,
-                                relinearization_key, out, s, true);
+                                relinearization_key, out, as_stream(s), true);
 }
 
 extern "C" int he_pir_compute_response_chunk_device(const he_bfv_context* ctx, const uint32_t* dimensions,
@@ -286,14 +295,15 @@ extern "C" int he_pir_compute_response_chunk_device(const he_bfv_context* ctx, c
     }
     return response_chunks_resident(ctx, dimensions, dimension_count, shape, 1, dim0_query_eval, remaining_query, database,
                                     shape.per_chunk * size_t(shape.L) * shape.n, false, present_device, relinearization_key,
-                                    out, s);
+                                    out, stream);
 }
 
 namespace {
-int compute_response(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
-                     const uint64_t* dim0_query_eval, const uint64_t* remaining_query, size_t remaining_query_count,
-                     const uint64_t* database, bool packed, const uint8_t* present_device, size_t chunk_count,
-                     const uint64_t* relinearization_key, uint64_t* out, he_stream s) {
+template <typename W>
+int compute_response(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, const W* dim0_query_eval,
+                     const W* remaining_query, size_t remaining_query_count, const W* database, bool packed,
+                     const uint8_t* present_device, size_t chunk_count, const W* relinearization_key, W* out,
+                     hipStream_t stream) {
     ChunkShape shape;
     HEAMD_TRY_STATUS(chunk_shape(ctx, dimensions, dimension_count, remaining_query, remaining_query_count, shape));
     if (chunk_count == 0) return HE_OK;
@@ -307,7 +317,7 @@ int compute_response(const he_bfv_context* ctx, const uint32_t* dimensions, uint
     // The chunks are independent (the reference maps them over tasks, PirUtil.swift:533-563) and share the query: they are
     // answered together, `group` chunks per pass -- one dim-0 launch over all their columns, one batch per stage of
     // every remaining dimension -- with the group sized to keep the intermediate ciphertexts under ~1 GiB.
-    const size_t intermediate_bytes = shape.columns * 2 * size_t(shape.L) * shape.n * sizeof(uint64_t);
+    const size_t intermediate_bytes = shape.columns * 2 * size_t(shape.L) * shape.n * sizeof(W);
     size_t group = (size_t(1) << 30) / (intermediate_bytes ? intermediate_bytes : 1);
     group = group == 0 ? 1 : group;
     for (size_t first = 0; first < chunk_count; first += group) {
@@ -315,7 +325,7 @@ int compute_response(const he_bfv_context* ctx, const uint32_t* dimensions, uint
         HEAMD_TRY_STATUS(response_chunks_resident(
             ctx, dimensions, dimension_count, shape, now, dim0_query_eval, remaining_query, database + first * chunk_words,
             chunk_words, packed, present_device ? present_device + first * shape.per_chunk : nullptr, relinearization_key,
-            out + first * out_words, s));
+            out + first * out_words, stream));
     }
     return HE_OK;
 }
@@ -328,7 +338,7 @@ extern "C" int he_pir_compute_response_device(const he_bfv_context* ctx, const u
                                               size_t chunk_count, const uint64_t* relinearization_key, uint64_t* out,
                                               he_stream s) {
     return compute_response(ctx, dimensions, dimension_count, dim0_query_eval, remaining_query, remaining_query_count,
-                            database, false, present_device, chunk_count, relinearization_key, out, s);
+                            database, false, present_device, chunk_count, relinearization_key, out, as_stream(s));
 }
 extern "C" int he_pir_compute_response_packed_device(const he_bfv_context* ctx, const uint32_t* dimensions,
                                                      uint32_t dimension_count, const uint64_t* dim0_query_eval,
@@ -337,56 +347,8 @@ extern "C" int he_pir_compute_response_packed_device(const he_bfv_context* ctx, 
                                                      size_t chunk_count, const uint64_t* relinearization_key,
                                                      uint64_t* out, he_stream s) {
     return compute_response(ctx, dimensions, dimension_count, dim0_query_eval, remaining_query, remaining_query_count,
-                            packed_database, true, present_device, chunk_count, relinearization_key, out, s);
+                            packed_database, true, present_device, chunk_count, relinearization_key, out, as_stream(s));
 }
-
-// ---- the same chunk loop for Bfv<UInt32> on packed 4-byte slabs (the reference's 27/28-bit PIR parameter sets,
-// EncryptionParameters.swift:313-345): half the database bytes of the 8-byte route --------------------------------
-namespace {
-// scratch of the 4-byte remaining-dimension stages for up to `group` chunks at a time
-struct Word32Stages {
-    Scratch next_mem, products_mem;
-    uint32_t *next = nullptr, *products = nullptr;
-    explicit Word32Stages(hipStream_t stream) : next_mem(stream), products_mem(stream) {}
-    hipError_t allocate(const ChunkShape& shape, size_t group) {
-        const size_t ct2 = 2 * size_t(shape.L) * shape.n, ct3 = 3 * size_t(shape.L) * shape.n, widest = group * shape.columns;
-        if (hipError_t e = next_mem.allocate(widest * ct2 * sizeof(uint32_t)); e != hipSuccess) return e;
-        if (hipError_t e = products_mem.allocate(widest * ct3 * sizeof(uint32_t)); e != hipSuccess) return e;
-        next = static_cast<uint32_t*>(next_mem.get());
-        products = static_cast<uint32_t*>(products_mem.get());
-        return hipSuccess;
-    }
-};
-
-// PirUtil.swift:448-485 for `chunks` chunks on 4-byte slabs: results [chunks][columns][2][L][N] Coeff (consumed) ->
-// target [chunks][2][1][N]; every stage one batch over the result groups of all chunks
-int remaining_dimensions_u32(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
-                             const ChunkShape& shape, size_t chunks, uint32_t* results, Word32Stages& stages,
-                             const uint32_t* remaining_query, const uint32_t* relinearization_key, uint32_t* target,
-                             he_stream s) {
-    const uint32_t L = shape.L;
-    const size_t ct2 = 2 * size_t(L) * shape.n;
-    uint32_t* current = results;
-    uint32_t* other = stages.next;
-    size_t count = shape.columns, cursor = 0;
-    for (uint32_t i = 1; i < dimension_count; ++i) {
-        const size_t d = dimensions[i];
-        if (count % d != 0) return invalid_argument("intermediate results do not divide by the dimension");
-        const size_t items = chunks * (count / d);
-        HEAMD_TRY_STATUS(he_bfv_inner_product_shared_device_u32(ctx, L, remaining_query + cursor * ct2, current, d, items,
-                                                                stages.products, s));
-        HEAMD_TRY_STATUS(he_bfv_relinearize_device_u32(ctx, L, stages.products, relinearization_key, other, items, nullptr, 0, s));
-        uint32_t* swap = current;
-        current = other;
-        other = swap;
-        count /= d;
-        cursor += d;
-    }
-    if (count != 1) return invalid_argument("dimensions leave more than one ciphertext");  // PirUtil.swift:481-482
-    // modSwitchDownToSingle (:483)
-    return heamd::bfv_mod_switch_down_to_single(ctx, L, 2, current, target, chunks, as_stream(s));
-}
-}  // namespace
 
 extern "C" int he_pir_compute_response_device_u32(const he_bfv_context* ctx, const uint32_t* dimensions,
                                                   uint32_t dimension_count, const uint32_t* dim0_query_eval,
@@ -394,114 +356,41 @@ extern "C" int he_pir_compute_response_device_u32(const he_bfv_context* ctx, con
                                                   const uint32_t* database, const uint8_t* present_device,
                                                   size_t chunk_count, const uint32_t* relinearization_key, uint32_t* out,
                                                   he_stream s) {
-    ChunkShape shape;
-    HEAMD_TRY_STATUS(chunk_shape(ctx, dimensions, dimension_count, reinterpret_cast<const uint64_t*>(remaining_query),
-                                 remaining_query_count, shape));
-    if (chunk_count == 0) return HE_OK;
-    if (dim0_query_eval == nullptr || database == nullptr || out == nullptr) return invalid_argument("null operand");
-    hipStream_t stream = as_stream(s);
-    const uint32_t L = shape.L;
-    const size_t poly = size_t(L) * shape.n, ct2 = 2 * poly;
-    const size_t chunk_words = shape.per_chunk * poly, out_words = 2 * shape.n;
-    size_t group = (size_t(1) << 30) / (shape.columns * ct2 * sizeof(uint32_t));
-    group = group == 0 ? 1 : (group < chunk_count ? group : chunk_count);
-    Scratch results_mem(stream);
-    Word32Stages stages(stream);
-    HEAMD_HIP_TRY(results_mem.allocate(group * shape.columns * ct2 * sizeof(uint32_t)));
-    HEAMD_HIP_TRY(stages.allocate(shape, group));
-    uint32_t* results = static_cast<uint32_t*>(results_mem.get());
-    for (size_t first = 0; first < chunk_count; first += group) {
-        const size_t chunks = chunk_count - first < group ? chunk_count - first : group;
-        // PirUtil.swift:428-438: every column of every chunk of the group in one launch, then back to Coeff
-        HEAMD_TRY_STATUS(he_bfv_inner_product_plain_resident_device_u32(
-            ctx, L, 2, dim0_query_eval, database + first * chunk_words,
-            present_device ? present_device + first * shape.per_chunk : nullptr, shape.d0, chunks * shape.columns, results, s));
-        HEAMD_TRY_STATUS(he_ntt_inverse_device_u32(shape.q_ctx, results, chunks * shape.columns * 2, s));
-        HEAMD_TRY_STATUS(remaining_dimensions_u32(ctx, dimensions, dimension_count, shape, chunks, results, stages,
-                                                  remaining_query, relinearization_key, out + first * out_words, s));
-    }
-    return HE_OK;
-}
-
-// Several queries (1..4) over one packed 4-byte database in one call: as he_pir_compute_response_queries_device, the
-// dim-0 inner products of all of them share one pass over the database.
-namespace {
-int compute_response_queries_u32(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
-                                 size_t queries, const uint32_t* dim0_queries_eval, const uint32_t* remaining_queries,
-                                 size_t remaining_query_count, size_t remaining_stride, const uint32_t* database,
-                                 const uint8_t* present_device, size_t chunk_count,
-                                 const uint32_t* const* relinearization_keys, uint32_t* out, he_stream s) {
-    ChunkShape shape;
-    HEAMD_TRY_STATUS(chunk_shape(ctx, dimensions, dimension_count, reinterpret_cast<const uint64_t*>(remaining_queries),
-                                 remaining_query_count, shape));
-    if (queries == 0 || chunk_count == 0) return HE_OK;
-    if (queries > 4) return invalid_argument("at most 4 queries share one pass over the database");
-    if (dim0_queries_eval == nullptr || database == nullptr || out == nullptr) return invalid_argument("null operand");
-    if (dimension_count > 1 && relinearization_keys == nullptr) return invalid_argument("null relinearization keys");
-    hipStream_t stream = as_stream(s);
-    const uint32_t L = shape.L;
-    const size_t ct_words = 2 * size_t(L) * shape.n, ct_bytes = ct_words * sizeof(uint32_t);
-    const size_t chunk_words = shape.per_chunk * size_t(L) * shape.n, out_words = 2 * shape.n;
-    size_t group = (size_t(1) << 30) / (shape.columns * queries * ct_bytes);
-    group = group == 0 ? 1 : (group < chunk_count ? group : chunk_count);
-    Scratch all_mem(stream), one_mem(stream);
-    Word32Stages stages(stream);
-    HEAMD_HIP_TRY(all_mem.allocate(group * shape.columns * queries * ct_bytes));
-    HEAMD_HIP_TRY(one_mem.allocate(group * shape.columns * ct_bytes));
-    HEAMD_HIP_TRY(stages.allocate(shape, group));
-    uint32_t* all = static_cast<uint32_t*>(all_mem.get());  // [chunk][column][query][2][L][N]
-    uint32_t* one = static_cast<uint32_t*>(one_mem.get());  // [chunk][column][2][L][N] of one query
-    for (size_t first = 0; first < chunk_count; first += group) {
-        const size_t now = chunk_count - first < group ? chunk_count - first : group;
-        const size_t columns = now * shape.columns;
-        HEAMD_TRY_STATUS(he_bfv_inner_product_plain_resident_device_u32(
-            ctx, L, static_cast<uint32_t>(2 * queries), dim0_queries_eval, database + first * chunk_words,
-            present_device ? present_device + first * shape.per_chunk : nullptr, shape.d0, columns, all, s));
-        HEAMD_TRY_STATUS(he_ntt_inverse_device_u32(shape.q_ctx, all, columns * 2 * queries, s));
-        for (size_t q = 0; q < queries; ++q) {
-            HEAMD_HIP_TRY(hipMemcpy2DAsync(one, ct_bytes, all + q * ct_words, queries * ct_bytes, ct_bytes, columns,
-                                           hipMemcpyDeviceToDevice, stream));
-            HEAMD_TRY_STATUS(remaining_dimensions_u32(
-                ctx, dimensions, dimension_count, shape, now, one, stages,
-                remaining_queries ? remaining_queries + q * remaining_stride * ct_words : nullptr,
-                relinearization_keys ? relinearization_keys[q] : nullptr, out + (q * chunk_count + first) * out_words, s));
-        }
-    }
-    return HE_OK;
-}
-}  // namespace
-
-extern "C" int he_pir_compute_response_queries_device_u32(const he_bfv_context* ctx, const uint32_t* dimensions,
-                                                          uint32_t dimension_count, size_t queries,
-                                                          const uint32_t* dim0_queries_eval,
-                                                          const uint32_t* remaining_queries, size_t remaining_query_count,
-                                                          const uint32_t* database, const uint8_t* present_device,
-                                                          size_t chunk_count, const uint32_t* const* relinearization_keys,
-                                                          uint32_t* out, he_stream s) {
-    return compute_response_queries_u32(ctx, dimensions, dimension_count, queries, dim0_queries_eval, remaining_queries,
-                                        remaining_query_count, remaining_query_count, database, present_device, chunk_count,
-                                        relinearization_keys, out, s);
+    return compute_response(ctx, dimensions, dimension_count, dim0_query_eval, remaining_query, remaining_query_count,
+                            database, false, present_device, chunk_count, relinearization_key, out, as_stream(s));
 }
 
 // Several queries over the same database in one call: the dim-0 inner products of all of them stream the database once
 // (their ciphertext vectors side by side, he_amd.h he_bfv_inner_product_plain_device with polys = 2 x queries); the
 // remaining dimensions, which involve only query ciphertexts and intermediate results, then run query by query.
 namespace {
+// `records` records of record_words words, src_stride words apart, side by side into dst: the copy kernel for 8-byte words
+// (hipMemcpy2DAsync for a degree below its granule), hipMemcpy2DAsync for 4-byte words
+template <typename W>
+hipError_t copy_strided_records(const W* src, size_t src_stride, W* dst, size_t record_words, size_t records, hipStream_t stream) {
+    if constexpr (sizeof(W) == 8) {
+        const hipError_t e = heamd::launch_copy_records(src, src_stride, dst, record_words, record_words, records, stream);
+        if (e != hipErrorInvalidValue) return e;
+        (void)hipGetLastError();
+    }
+    return hipMemcpy2DAsync(dst, record_words * sizeof(W), src, src_stride * sizeof(W), record_words * sizeof(W), records,
+                            hipMemcpyDeviceToDevice, stream);
+}
+
 // remaining_stride: ciphertexts from one query's remaining ciphertexts to the next query's
+template <typename W>
 int compute_response_queries(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, size_t queries,
-                             const uint64_t* dim0_queries_eval, const uint64_t* remaining_queries,
-                             size_t remaining_query_count, size_t remaining_stride, const uint64_t* database,
-                             const uint8_t* present_device, size_t chunk_count,
-                             const uint64_t* const* relinearization_keys, uint64_t* out, he_stream s) {
+                             const W* dim0_queries_eval, const W* remaining_queries, size_t remaining_query_count,
+                             size_t remaining_stride, const W* database, const uint8_t* present_device, size_t chunk_count,
+                             const W* const* relinearization_keys, W* out, hipStream_t stream) {
     ChunkShape shape;
     HEAMD_TRY_STATUS(chunk_shape(ctx, dimensions, dimension_count, remaining_queries, remaining_query_count, shape));
     if (queries == 0 || chunk_count == 0) return HE_OK;
     if (queries > 4) return invalid_argument("at most 4 queries share one pass over the database");
     if (dim0_queries_eval == nullptr || database == nullptr || out == nullptr) return invalid_argument("null operand");
     if (dimension_count > 1 && relinearization_keys == nullptr) return invalid_argument("null relinearization keys");
-    hipStream_t stream = as_stream(s);
     const uint32_t L = shape.L;
-    const size_t ct_words = 2 * size_t(L) * shape.n, ct_bytes = ct_words * sizeof(uint64_t);
+    const size_t ct_words = 2 * size_t(L) * shape.n, ct_bytes = ct_words * sizeof(W);
     const size_t chunk_words = shape.per_chunk * size_t(L) * shape.n, out_words = 2 * shape.n;
     // groups of chunks that keep the intermediate ciphertexts of all queries under ~1 GiB
     const size_t intermediate_bytes = shape.columns * queries * ct_bytes;
@@ -510,8 +399,8 @@ int compute_response_queries(const he_bfv_context* ctx, const uint32_t* dimensio
     Scratch all_mem(stream), one_mem(stream);
     HEAMD_HIP_TRY(all_mem.allocate(group * shape.columns * queries * ct_bytes));
     HEAMD_HIP_TRY(one_mem.allocate(group * shape.columns * ct_bytes));
-    uint64_t* all = static_cast<uint64_t*>(all_mem.get());  // [chunk][column][query][2][L][N]
-    uint64_t* one = static_cast<uint64_t*>(one_mem.get());  // [chunk][column][2][L][N] of one query
+    W* all = static_cast<W*>(all_mem.get());  // [chunk][column][query][2][L][N]
+    W* one = static_cast<W*>(one_mem.get());  // [chunk][column][2][L][N] of one query
     // As response_chunks_resident (one piece unless forced): a piece's dim-0 pass for every query (PirUtil.swift:428-438) on
     // the caller's stream, the queries' remaining dimensions on a lane beside the next piece's pass.  (`one` is only touched
     // on the stream the remaining dimensions run on: its uses are ordered there.)
@@ -527,17 +416,19 @@ int compute_response_queries(const he_bfv_context* ctx, const uint32_t* dimensio
         now = chunk_count - first < piece ? chunk_count - first : piece;
         now = group - first % group < now ? group - first % group : now;  // (a piece does not straddle the slabs' end)
         const size_t columns = now * shape.columns;
-        uint64_t* piece_all = all + (first % group) * shape.columns * queries * ct_words;
+        W* piece_all = all + (first % group) * shape.columns * queries * ct_words;
         if (lane != nullptr && first != 0 && first % group == 0) {
             // the slabs wrap around: the lane's work on the previous `group` chunks first
             e = hipEventRecord(lane->joined, lane->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(stream, lane->joined, 0);
             if (e != hipSuccess) break;
         }
-        status = he_bfv_inner_product_plain_resident_device(
+        status = heamd::bfv_inner_product_plain_resident(
             ctx, L, static_cast<uint32_t>(2 * queries), dim0_queries_eval, database + first * chunk_words,
-            present_device ? present_device + first * shape.per_chunk : nullptr, shape.d0, columns, piece_all, s);
-        // (left in Eval form: remaining_dimensions, results_in_eval)
+            present_device ? present_device + first * shape.per_chunk : nullptr, shape.d0, columns, piece_all, stream);
+        // left in Eval form (remaining_dimensions, results_in_eval) or taken to Coeff once, for all queries (PirUtil.swift:438)
+        if (status == HE_OK && !heamd::kDim0ResultsStayEval<W>)
+            status = heamd::poly_ntt(shape.q_ctx, piece_all, columns * 2 * queries, true, stream);
         if (status != HE_OK) break;
         if (lane != nullptr) {
             e = hipEventRecord(lane->stage[0], stream);
@@ -547,18 +438,13 @@ int compute_response_queries(const he_bfv_context* ctx, const uint32_t* dimensio
         }
         for (size_t q = 0; q < queries && status == HE_OK && e == hipSuccess; ++q) {
             // this query's results, column after column (a strided copy: they sit `queries` ciphertexts apart)
-            e = heamd::launch_copy_records(piece_all + q * ct_words, queries * ct_words, one, ct_words, ct_words, columns, tail_stream);
-            if (e == hipErrorInvalidValue) {  // (a degree below the copy kernel's granule)
-                (void)hipGetLastError();
-                e = hipMemcpy2DAsync(one, ct_bytes, piece_all + q * ct_words, queries * ct_bytes, ct_bytes, columns,
-                                     hipMemcpyDeviceToDevice, tail_stream);
-            }
+            e = copy_strided_records(piece_all + q * ct_words, queries * ct_words, one, ct_words, columns, tail_stream);
             if (e != hipSuccess) break;
             status = remaining_dimensions(
                 ctx, dimensions, dimension_count, shape, now, one,
                 remaining_queries ? remaining_queries + q * remaining_stride * ct_words : nullptr,
                 relinearization_keys ? relinearization_keys[q] : nullptr, out + (q * chunk_count + first) * out_words,
-                static_cast<he_stream>(tail_stream), true);
+                tail_stream, heamd::kDim0ResultsStayEval<W>);
         }
     }
     if (forked) {  // the join is enqueued whatever happened in between
@@ -581,7 +467,18 @@ extern "C" int he_pir_compute_response_queries_device(const he_bfv_context* ctx,
                                                       he_stream s) {
     return compute_response_queries(ctx, dimensions, dimension_count, queries, dim0_queries_eval, remaining_queries,
                                     remaining_query_count, remaining_query_count, database, present_device, chunk_count,
-                                    relinearization_keys, out, s);
+                                    relinearization_keys, out, as_stream(s));
+}
+extern "C" int he_pir_compute_response_queries_device_u32(const he_bfv_context* ctx, const uint32_t* dimensions,
+                                                          uint32_t dimension_count, size_t queries,
+                                                          const uint32_t* dim0_queries_eval,
+                                                          const uint32_t* remaining_queries, size_t remaining_query_count,
+                                                          const uint32_t* database, const uint8_t* present_device,
+                                                          size_t chunk_count, const uint32_t* const* relinearization_keys,
+                                                          uint32_t* out, he_stream s) {
+    return compute_response_queries(ctx, dimensions, dimension_count, queries, dim0_queries_eval, remaining_queries,
+                                    remaining_query_count, remaining_query_count, database, present_device, chunk_count,
+                                    relinearization_keys, out, as_stream(s));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -871,12 +768,17 @@ extern "C" int he_pir_expand_device(const he_bfv_context* ctx, const uint64_t* c
 // ciphertexts per queried index (:500-505, :565-566), take each index's first dimensions[0] of them to Eval
 // (:520-533), and answer every chunk (:545-563).  The indices of one Query share the database: up to four of them at
 // a time share one pass over it.
-extern "C" int he_pir_compute_response_to_query_device(
-    const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, const uint64_t* query_ciphertexts,
-    size_t query_ciphertext_count, size_t indices_count, const uint64_t* galois_elements,
-    const uint64_t* const* galois_keys, size_t galois_key_count, const uint64_t* relinearization_key,
-    const uint64_t* const* databases, const uint8_t* const* present_masks, size_t database_count, size_t chunk_count,
-    uint64_t* out, he_stream s) {
+//
+// For Bfv<UInt32> on packed 4-byte slabs the expansion (bound by its key switches, not by bytes) runs on widened words
+// with the 8-byte kernels -- the Galois keys are therefore taken as 8-byte slabs, as he_pir_expand_device takes them for a
+// UInt32 context -- and everything that touches the database is 4-byte.
+namespace {
+template <typename W>
+int compute_response_to_query(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
+                              const W* query_ciphertexts, size_t query_ciphertext_count, size_t indices_count,
+                              const uint64_t* galois_elements, const uint64_t* const* galois_keys, size_t galois_key_count,
+                              const W* relinearization_key, const W* const* databases, const uint8_t* const* present_masks,
+                              size_t database_count, size_t chunk_count, W* out, he_stream s) {
     if (ctx == nullptr) return invalid_argument("null context");
     if (dimensions == nullptr || dimension_count == 0) return invalid_argument("empty dimensions");
     size_t expanded_count = 0;
@@ -895,124 +797,79 @@ extern "C" int he_pir_compute_response_to_query_device(
         if (databases[d] == nullptr) return invalid_argument("null database");
     const bool shared = database_count == 1;
     hipStream_t stream = as_stream(s);
-    const size_t ct_words = 2 * size_t(shape.L) * shape.n, ct_bytes = ct_words * sizeof(uint64_t);
+    const size_t ct_words = 2 * size_t(shape.L) * shape.n, ct_bytes = ct_words * sizeof(W);
     const size_t total = expanded_count * indices_count, out_words = 2 * shape.n;
-    Scratch expanded_mem(stream), side_mem(stream);
+    Scratch expanded_mem(stream), query_mem(stream), wide_mem(stream), side_mem(stream);
     HEAMD_HIP_TRY(expanded_mem.allocate(total * ct_bytes));
-    uint64_t* expanded = static_cast<uint64_t*>(expanded_mem.get());  // [index][sum(dimensions)][2][L][N] Coeff
-    HEAMD_TRY_STATUS(he_pir_expand_device(ctx, query_ciphertexts, query_ciphertext_count, total, galois_elements,
-                                          galois_keys, galois_key_count, expanded, s));
+    W* expanded = static_cast<W*>(expanded_mem.get());  // [index][sum(dimensions)][2][L][N] Coeff
+    if constexpr (sizeof(W) == 8) {
+        HEAMD_TRY_STATUS(he_pir_expand_device(ctx, query_ciphertexts, query_ciphertext_count, total, galois_elements,
+                                              galois_keys, galois_key_count, expanded, s));
+    } else {  // widen the query, expand on 8-byte words, narrow the selection ciphertexts
+        HEAMD_HIP_TRY(query_mem.allocate(query_ciphertext_count * ct_words * sizeof(uint64_t)));
+        HEAMD_HIP_TRY(wide_mem.allocate(total * ct_words * sizeof(uint64_t)));
+        uint64_t* query_wide = static_cast<uint64_t*>(query_mem.get());
+        uint64_t* expanded_wide = static_cast<uint64_t*>(wide_mem.get());
+        HEAMD_TRY_STATUS(he_words_widen_u32_device(query_ciphertexts, query_wide, query_ciphertext_count * ct_words, s));
+        HEAMD_TRY_STATUS(he_pir_expand_device(ctx, query_wide, query_ciphertext_count, total, galois_elements, galois_keys,
+                                              galois_key_count, expanded_wide, s));
+        HEAMD_TRY_STATUS(he_words_narrow_u64_device(expanded_wide, expanded, total * ct_words, s));
+    }
     // indices with a database of their own (PirUtil.swift:518) are answered one by one; those that share one go four at
     // a time
     constexpr size_t kGroup = 4;
     const size_t kTogether = shared ? kGroup : 1;
     const size_t widest = indices_count < kTogether ? indices_count : kTogether;
-    uint64_t* side = nullptr;  // [dimensions[0]][indices of a group][2][L][N]
+    W* side = nullptr;  // [dimensions[0]][indices of a group][2][L][N]
     if (widest > 1) {
         HEAMD_HIP_TRY(side_mem.allocate(shape.d0 * widest * ct_bytes));
-        side = static_cast<uint64_t*>(side_mem.get());
+        side = static_cast<W*>(side_mem.get());
     }
-    const uint64_t* keys[kGroup] = {relinearization_key, relinearization_key, relinearization_key, relinearization_key};
+    const W* keys[kGroup] = {relinearization_key, relinearization_key, relinearization_key, relinearization_key};
     for (size_t first = 0; first < indices_count; first += kTogether) {
         const size_t now = indices_count - first < kTogether ? indices_count - first : kTogether;
-        uint64_t* mine = expanded + first * expanded_count * ct_words;  // this group's selection ciphertexts
-        const uint64_t* rest = remaining_count ? mine + shape.d0 * ct_words : nullptr;
-        uint64_t* group_out = out + first * chunk_count * out_words;
-        const uint64_t* database = databases[shared ? 0 : first];
+        W* mine = expanded + first * expanded_count * ct_words;  // this group's selection ciphertexts
+        const W* rest = remaining_count ? mine + shape.d0 * ct_words : nullptr;
+        W* group_out = out + first * chunk_count * out_words;
+        const W* database = databases[shared ? 0 : first];
         const uint8_t* present_device = present_masks ? present_masks[shared ? 0 : first] : nullptr;
         if (now == 1) {
             // convertToEvalFormat (PirUtil.swift:520-533) where the expansion left the dim-0 ciphertexts
-            HEAMD_TRY_STATUS(he_ntt_forward_device(shape.q_ctx, mine, shape.d0 * 2, s));
-            HEAMD_TRY_STATUS(he_pir_compute_response_device(ctx, dimensions, dimension_count, mine, rest, remaining_count,
-                                                            database, present_device, chunk_count, relinearization_key,
-                                                            group_out, s));
+            HEAMD_TRY_STATUS(heamd::poly_ntt(shape.q_ctx, mine, shape.d0 * 2, false, stream));
+            HEAMD_TRY_STATUS(compute_response(ctx, dimensions, dimension_count, mine, rest, remaining_count, database, false,
+                                              present_device, chunk_count, relinearization_key, group_out, stream));
             continue;
         }
         // the group's dim-0 ciphertexts side by side, then to Eval
         for (size_t q = 0; q < now; ++q)
             HEAMD_HIP_TRY(hipMemcpy2DAsync(side + q * ct_words, now * ct_bytes, mine + q * expanded_count * ct_words,
                                            ct_bytes, ct_bytes, shape.d0, hipMemcpyDeviceToDevice, stream));
-        HEAMD_TRY_STATUS(he_ntt_forward_device(shape.q_ctx, side, shape.d0 * now * 2, s));
+        HEAMD_TRY_STATUS(heamd::poly_ntt(shape.q_ctx, side, shape.d0 * now * 2, false, stream));
         HEAMD_TRY_STATUS(compute_response_queries(ctx, dimensions, dimension_count, now, side, rest, remaining_count,
                                                   expanded_count, database, present_device, chunk_count,
-                                                  dimension_count > 1 ? keys : nullptr, group_out, s));
+                                                  dimension_count > 1 ? keys : nullptr, group_out, stream));
     }
     return HE_OK;
 }
+}  // namespace
 
-// The whole-query call for Bfv<UInt32> on packed 4-byte slabs: the expansion (bound by its key switches, not by bytes)
-// runs on widened words with the 8-byte kernels -- the Galois keys are therefore taken as 8-byte slabs, as
-// he_pir_expand_device takes them for a UInt32 context -- everything that touches the database is 4-byte; indices that
-// share the database share its pass four at a time.
+extern "C" int he_pir_compute_response_to_query_device(
+    const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, const uint64_t* query_ciphertexts,
+    size_t query_ciphertext_count, size_t indices_count, const uint64_t* galois_elements,
+    const uint64_t* const* galois_keys, size_t galois_key_count, const uint64_t* relinearization_key,
+    const uint64_t* const* databases, const uint8_t* const* present_masks, size_t database_count, size_t chunk_count,
+    uint64_t* out, he_stream s) {
+    return compute_response_to_query(ctx, dimensions, dimension_count, query_ciphertexts, query_ciphertext_count, indices_count,
+                                     galois_elements, galois_keys, galois_key_count, relinearization_key, databases,
+                                     present_masks, database_count, chunk_count, out, s);
+}
 extern "C" int he_pir_compute_response_to_query_device_u32(
     const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, const uint32_t* query_ciphertexts,
     size_t query_ciphertext_count, size_t indices_count, const uint64_t* galois_elements,
     const uint64_t* const* galois_keys_wide, size_t galois_key_count, const uint32_t* relinearization_key,
     const uint32_t* const* databases, const uint8_t* const* present_masks, size_t database_count, size_t chunk_count,
     uint32_t* out, he_stream s) {
-    if (ctx == nullptr) return invalid_argument("null context");
-    if (dimensions == nullptr || dimension_count == 0) return invalid_argument("empty dimensions");
-    size_t expanded_count = 0;
-    for (uint32_t i = 0; i < dimension_count; ++i) expanded_count += dimensions[i];
-    const size_t remaining_count = expanded_count - dimensions[0];
-    ChunkShape shape;
-    HEAMD_TRY_STATUS(chunk_shape(ctx, dimensions, dimension_count,
-                                 remaining_count ? reinterpret_cast<const uint64_t*>(query_ciphertexts) : nullptr,
-                                 remaining_count, shape));
-    if (databases == nullptr || !(database_count == 1 || database_count >= indices_count))
-        return invalid_argument("database count matches neither one nor the number of indices");
-    if (indices_count == 0 || chunk_count == 0) return HE_OK;
-    if (query_ciphertexts == nullptr || out == nullptr) return invalid_argument("null operand");
-    hipStream_t stream = as_stream(s);
-    const size_t ct_words = 2 * size_t(shape.L) * shape.n;
-    const size_t total = expanded_count * indices_count, out_words = 2 * shape.n;
-    Scratch query_mem(stream), wide_mem(stream), expanded_mem(stream);
-    HEAMD_HIP_TRY(query_mem.allocate(query_ciphertext_count * ct_words * sizeof(uint64_t)));
-    HEAMD_HIP_TRY(wide_mem.allocate(total * ct_words * sizeof(uint64_t)));
-    HEAMD_HIP_TRY(expanded_mem.allocate(total * ct_words * sizeof(uint32_t)));
-    uint64_t* query_wide = static_cast<uint64_t*>(query_mem.get());
-    uint64_t* expanded_wide = static_cast<uint64_t*>(wide_mem.get());
-    uint32_t* expanded = static_cast<uint32_t*>(expanded_mem.get());  // [index][sum(dimensions)][2][L][N] Coeff
-    HEAMD_TRY_STATUS(he_words_widen_u32_device(query_ciphertexts, query_wide, query_ciphertext_count * ct_words, s));
-    HEAMD_TRY_STATUS(he_pir_expand_device(ctx, query_wide, query_ciphertext_count, total, galois_elements, galois_keys_wide,
-                                          galois_key_count, expanded_wide, s));
-    HEAMD_TRY_STATUS(he_words_narrow_u64_device(expanded_wide, expanded, total * ct_words, s));
-    // indices with a database of their own are answered one by one; those that share one go four at a time
-    const bool shared = database_count == 1;
-    constexpr size_t kGroup = 4;
-    const size_t together = shared ? kGroup : 1;
-    const size_t widest = indices_count < together ? indices_count : together;
-    for (size_t d = 0; d < (shared ? size_t(1) : indices_count); ++d)
-        if (databases[d] == nullptr) return invalid_argument("null database");
-    Scratch side_mem(stream);
-    uint32_t* side = nullptr;  // [dimensions[0]][indices of a group][2][L][N]
-    if (widest > 1) {
-        HEAMD_HIP_TRY(side_mem.allocate(shape.d0 * widest * ct_words * sizeof(uint32_t)));
-        side = static_cast<uint32_t*>(side_mem.get());
-    }
-    const uint32_t* keys[kGroup] = {relinearization_key, relinearization_key, relinearization_key, relinearization_key};
-    const size_t ct_bytes = ct_words * sizeof(uint32_t);
-    for (size_t first = 0; first < indices_count; first += together) {
-        const size_t now = indices_count - first < together ? indices_count - first : together;
-        uint32_t* mine = expanded + first * expanded_count * ct_words;
-        const uint32_t* rest = remaining_count ? mine + shape.d0 * ct_words : nullptr;
-        uint32_t* group_out = out + first * chunk_count * out_words;
-        const uint32_t* database = databases[shared ? 0 : first];
-        const uint8_t* present_device = present_masks ? present_masks[shared ? 0 : first] : nullptr;
-        if (now == 1) {
-            HEAMD_TRY_STATUS(he_ntt_forward_device_u32(shape.q_ctx, mine, shape.d0 * 2, s));
-            HEAMD_TRY_STATUS(he_pir_compute_response_device_u32(ctx, dimensions, dimension_count, mine, rest, remaining_count,
-                                                                database, present_device, chunk_count, relinearization_key,
-                                                                group_out, s));
-            continue;
-        }
-        for (size_t q = 0; q < now; ++q)
-            HEAMD_HIP_TRY(hipMemcpy2DAsync(side + q * ct_words, now * ct_bytes, mine + q * expanded_count * ct_words, ct_bytes,
-                                           ct_bytes, shape.d0, hipMemcpyDeviceToDevice, stream));
-        HEAMD_TRY_STATUS(he_ntt_forward_device_u32(shape.q_ctx, side, shape.d0 * now * 2, s));
-        HEAMD_TRY_STATUS(compute_response_queries_u32(ctx, dimensions, dimension_count, now, side, rest, remaining_count,
-                                                      expanded_count, database, present_device, chunk_count,
-                                                      dimension_count > 1 ? keys : nullptr, group_out, s));
-    }
-    return HE_OK;
+    return compute_response_to_query(ctx, dimensions, dimension_count, query_ciphertexts, query_ciphertext_count, indices_count,
+                                     galois_elements, galois_keys_wide, galois_key_count, relinearization_key, databases,
+                                     present_masks, database_count, chunk_count, out, s);
 }

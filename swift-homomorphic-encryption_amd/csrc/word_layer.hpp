@@ -105,5 +105,22 @@ struct AccumulatorCadence {
     bool narrow_moduli;
 };
 AccumulatorCadence accumulator_cadence(const PolyContext& pc, uint32_t level);
+// Bfv.innerProduct(ciphertexts:plaintexts:) per column with the nil-plaintext mask on the device, Bfv.innerProduct of `items`
+// ciphertext vectors with one shared vector, and Bfv.relinearize: the bodies, checks included, of
+// he_bfv_inner_product_plain_resident_device, he_bfv_inner_product_shared_device and he_bfv_relinearize_device
+template <typename W>
+int bfv_inner_product_plain_resident(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_count, const W* cts,
+                                     const W* pts, const uint8_t* present_device, size_t count, size_t columns, W* out,
+                                     hipStream_t stream);
+template <typename W>
+int bfv_inner_product_shared(const he_bfv_context* ctx, uint32_t moduli_count, const W* lhs, const W* rhs, size_t count,
+                             size_t items, W* out, hipStream_t stream);
+template <typename W>
+int bfv_relinearize(const he_bfv_context* ctx, uint32_t moduli_count, const W* ct3, const W* key, W* out, size_t batch,
+                    void* workspace, size_t workspace_bytes, hipStream_t stream);
+// Whether a PIR response hands its dim-0 inner products on in Eval form (pir_api.cpp): the first remaining dimension then
+// reads them through bfv_inner_product_shared_eval_rhs (api_internal.hpp), which exists for 8-byte words.
+template <typename W>
+constexpr bool kDim0ResultsStayEval = sizeof(W) == 8;
 
 }  // namespace heamd

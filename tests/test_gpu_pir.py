@@ -475,13 +475,19 @@ def test_pir_on_a_uint32_parameter_set(oracle):
     assert np.array_equal(single, got[0])
 
 
-@pytest.mark.parametrize("dims", [[5], [4, 3], [3, 2, 2]])
-def test_pir_response_on_packed_uint32_slabs(oracle, dims):
+@pytest.mark.parametrize("dims,piece", [([5], None), ([4, 3], None), ([3, 2, 2], None), ([4, 3], "1"), ([4, 3], "2")],
+                         ids=["dims0", "dims1", "dims2", "dims1-piece1", "dims1-piece2"])
+def test_pir_response_on_packed_uint32_slabs(oracle, monkeypatch, dims, piece):
     """he_pir_compute_response_device_u32: query, database, key and responses in UInt32 words (Bfv<UInt32>, the
     n_4096_logq_27_28_28 parameter set; 1-, 2- and 3-dimensional databases, three chunks, nil plaintexts): every chunk
-    response word for word the 32-bit oracle's."""
+    response word for word the 32-bit oracle's.
+    piece: as in test_multi_chunk_response_matches_oracle, with scratch from the library's block cache ("2": a ragged last
+    piece)."""
     import torch
 
+    if piece is not None:
+        monkeypatch.setenv("HEAMD_PIR_PIECE_CHUNKS", piece)
+        heamd.set_scratch_cache()
     degree = 4096
     q = [(1 << 27) - 40959, (1 << 28) - 65535, (1 << 28) - 73727]
     t = (1 << 16) + 1
@@ -503,21 +509,27 @@ def test_pir_response_on_packed_uint32_slabs(oracle, dims):
         expected = oracle.pir.compute_response_for_one_chunk(ref, dims, dim0, rest, database[chunk], present[chunk],
                                                              key if rest_count else None)
         assert np.array_equal(got[chunk], expected), chunk
+    heamd.set_scratch_cache(0)
 
 
-@pytest.mark.parametrize("dims,queries", [([4, 3], 2), ([3, 2, 2], 4), ([5], 3)])
-def test_queries_share_one_pass_on_packed_uint32_slabs(oracle, dims, queries):
+@pytest.mark.parametrize("dims,queries,piece", [([4, 3], 2, None), ([3, 2, 2], 4, None), ([5], 3, None), ([4, 3], 3, "2")],
+                         ids=["dims0-2", "dims1-4", "dims2-3", "dims0-3-piece2"])
+def test_queries_share_one_pass_on_packed_uint32_slabs(oracle, monkeypatch, dims, queries, piece):
     """he_pir_compute_response_queries_device_u32: several queries over one 4-byte database in one call, each with its own
-    relinearization key and a nil-plaintext mask: every response word for word the 32-bit oracle's single-query one."""
+    relinearization key and a nil-plaintext mask: every response word for word the 32-bit oracle's single-query one.
+    piece: as in test_queries_share_one_pass_over_the_database (three chunks then)."""
     import torch
 
+    if piece is not None:
+        monkeypatch.setenv("HEAMD_PIR_PIECE_CHUNKS", piece)
+        heamd.set_scratch_cache()
     degree = 4096
     q = [(1 << 27) - 40959, (1 << 28) - 65535, (1 << 28) - 73727]
     t = (1 << 16) + 1
     ours, ref = heamd.BfvContext32(degree, t, q), oracle.BfvContext(degree, t, q, word_bits=32)
     rng = np.random.default_rng(10 * len(dims) + queries)
     moduli = q[:-1]
-    per_chunk, chunks, rest_count = int(np.prod(dims)), 2, sum(dims[1:])
+    per_chunk, chunks, rest_count = int(np.prod(dims)), 2 if piece is None else 3, sum(dims[1:])
     database = _uniform(rng, (chunks, per_chunk), moduli, degree)
     present = np.ones((chunks, per_chunk), dtype=np.uint8)
     present[0, 1] = 0
@@ -538,6 +550,7 @@ def test_queries_share_one_pass_on_packed_uint32_slabs(oracle, dims, queries):
         five = dev(_uniform(rng, (dims[0], 5, 2), moduli, degree))
         ours.pir_compute_response_queries(dims, five, None if not rest_count else dev(np.zeros((5, rest_count, 2, ours.L, degree), dtype=np.uint64)),
                                           dev(database), chunks, [dev(keys[0])] * 5 if rest_count else None)
+    heamd.set_scratch_cache(0)
 
 
 def test_whole_query_on_packed_uint32_slabs(oracle):
