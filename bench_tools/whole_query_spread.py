@@ -41,7 +41,8 @@ dim0 = expanded[:d0].clone()
 def show(name, t):
     s = t.spread
     print(f"{name:28s} mean {t * 1e3:8.3f} ms  min {s['min_ms']:8.3f}  median {s['median_ms']:8.3f}  max {s['max_ms']:8.3f}"
-          f"  calls {s['calls']}  host max {max(t.host_enqueue_ms):8.3f} ms")
+          f"  calls {s['calls']}  host median {sorted(t.host_enqueue_ms)[len(t.host_enqueue_ms) // 2]:7.4f}"
+          f"  max {max(t.host_enqueue_ms):8.3f} ms")
     if s["max_ms"] > 1.5 * s["median_ms"]:
         print("   per call :", " ".join(f"{x:.2f}" for x in t.per_call_ms))
         print("   host     :", " ".join(f"{x:.2f}" for x in t.host_enqueue_ms))

@@ -352,8 +352,9 @@ int he_rns_floor_qbsk_to_q_device(const he_bfv_context* ctx, uint32_t moduli_cou
                                   size_t batch, he_stream s);
 
 /* Workspace: multi-kernel operations need device scratch.  Pass workspace == NULL to let the library allocate
- * stream-ordered scratch itself (hipMallocAsync on `s`); otherwise pass at least *_workspace_bytes().  The workspace is
- * written: [workspace, workspace + workspace_bytes) overlapping any other slab of the call is HE_ERR_INVALID_ARGUMENT. */
+ * stream-ordered scratch itself (from its own pool or block cache: he_set_scratch_cache, above); otherwise pass at least
+ * *_workspace_bytes().  The workspace is written: [workspace, workspace + workspace_bytes) overlapping any other slab of the
+ * call is HE_ERR_INVALID_ARGUMENT. */
 size_t he_bfv_mul_workspace_bytes(const he_bfv_context* ctx, uint32_t moduli_count, size_t batch);
 size_t he_bfv_relinearize_workspace_bytes(const he_bfv_context* ctx, uint32_t moduli_count, size_t batch);
 

@@ -199,10 +199,11 @@ int mul_rows_fused(const he_bfv_context* ctx, const RnsToolLevel& tool, uint32_t
         heamd::LaneLease lease(heamd::lane_pool(ctx), stream);
         if (lease.lane != nullptr) {
             SideLane& lane = *lease.lane;
-            HEAMD_HIP_TRY(hipEventRecord(lane.forked, stream));
-            HEAMD_HIP_TRY(hipStreamWaitEvent(lane.stream, lane.forked, 0));
-            hipError_t e = heamd::launch_behz_rows_fused(lhs, rhs, 2 * L * n, lifted, tensor, scaled, rows, L, batch, lane.stream,
-                                                         heamd::kBehzCiphertextRows);
+            hipError_t e = hipEventRecord(lane.forked, stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(lane.stream, lane.forked, 0);
+            if (e == hipSuccess)
+                e = heamd::launch_behz_rows_fused(lhs, rhs, 2 * L * n, lifted, tensor, scaled, rows, L, batch, lane.stream,
+                                                  heamd::kBehzCiphertextRows);
             if (e == hipSuccess)
                 e = heamd::launch_lift_pair_q_to_qbsk_strided(lhs, rhs, lifted, tool.device, batch, 2, 2 * L * n, 4 * ext, 0, 2 * ext, stream, false, lazy);
             // The Bsk band and the floor in kBehzFloorParts parts of the batch: a part's floor -- 256-lane workgroups of 41

@@ -23,6 +23,8 @@
 
 namespace heamd {
 
+void scratch_forget_stream(hipStream_t stream);  // api_internal.hpp
+
 struct SideLane {
     static constexpr int kStages = 4;
     hipStream_t stream = nullptr;
@@ -42,7 +44,10 @@ struct SideLane {
         if (joined != nullptr) (void)hipEventDestroy(joined);
         for (hipEvent_t e : stage)
             if (e != nullptr) (void)hipEventDestroy(e);
-        if (stream != nullptr) (void)hipStreamDestroy(stream);
+        if (stream != nullptr) {
+            scratch_forget_stream(stream);  // scratch released on the lane must not pass for a later stream's own
+            (void)hipStreamDestroy(stream);
+        }
     }
     // Stream and events.  Another thread may be capturing in hipStreamCaptureModeGlobal, where creation calls are not
     // allowed: this thread's capture mode is relaxed around them.

@@ -35,14 +35,10 @@ def test_c_program_drives_the_library(tmp_path):
     assert "abi round trip ok" in result.stdout
 
 
-@pytest.mark.gpu
-def test_c_program_drives_the_scheme_level(tmp_path, oracle):
-    """B3 from C: ct x ct, relinearize, modSwitchDownToSingle and a masked ct x pt inner product, each compared word for
-    word with the oracle's output inside the C program (tests/c/abi_scheme.c)."""
+def write_scheme_fixture(path, oracle):
+    """The words tests/c/abi_scheme.c describes, from seeded inputs and the CPU oracle's outputs (N = 256, batch 3)."""
     import numpy as np
 
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not installed")
     degree, batch, d0 = 256, 3, 5
     t = oracle.generate_primes([17], True, degree)[0]
     q = oracle.generate_primes([50, 50, 51], False, degree)
@@ -66,15 +62,46 @@ def test_c_program_drives_the_scheme_level(tmp_path, oracle):
     mask = np.array([1, 0, 1, 1, 0], dtype=np.uint64)
     inner = ref.inner_product_plain(cts, pts, present=mask.astype(np.uint8))
     head = np.array([degree, t, len(q), *q, batch, d0], dtype=np.uint64)
-    fixture = tmp_path / "scheme.bin"
-    with open(fixture, "wb") as out:
+    with open(path, "wb") as out:
         for part in (head, lhs, rhs, key, product, relinearized, single, cts, pts, mask, inner):
             out.write(np.ascontiguousarray(part, dtype=np.uint64).tobytes())
+
+
+def run_on_fixture(binary, fixture):
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
+    return subprocess.run([str(binary), str(fixture)], capture_output=True, text=True, env=env, timeout=300)
+
+
+@pytest.mark.gpu
+def test_c_program_drives_the_scheme_level(tmp_path, oracle):
+    """B3 from C: ct x ct, relinearize, modSwitchDownToSingle and a masked ct x pt inner product, each compared word for
+    word with the oracle's output inside the C program (tests/c/abi_scheme.c)."""
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not installed")
+    fixture = tmp_path / "scheme.bin"
+    write_scheme_fixture(fixture, oracle)
     binary = tmp_path / "abi_scheme"
     subprocess.run(["gcc", "-std=c99", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "c", "abi_scheme.c"),
                     "-I", INCLUDE, "-L", LIBDIR, "-lhe_amd", f"-Wl,-rpath,{LIBDIR}", "-o", str(binary)], check=True)
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    result = subprocess.run([str(binary), str(fixture)], capture_output=True, text=True, env=env, timeout=300)
+    result = run_on_fixture(binary, fixture)
     assert result.returncode == 0, result.stdout + result.stderr
     assert "abi scheme ok" in result.stdout
+
+
+@pytest.mark.gpu
+def test_c_program_takes_scratch_beside_a_global_capture(tmp_path, oracle):
+    """The block cache beside a graph capture (tests/c/abi_capture_beside_cache.cpp): while one thread captures in
+    hipStreamCaptureModeGlobal, another makes six relinearize calls through a cache too small to keep a block, waits after
+    each and trims the cache to nothing, so every call allocates and every block is queried and freed inside the capture window
+    (the program checks that each trim found the block and left nothing).  The capture ends with a graph that computes the
+    right sum, all six results are the oracle's words, and no more than the bound stays cached."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"  # what the library itself is built with: missing is a failure
+    fixture = tmp_path / "scheme.bin"
+    write_scheme_fixture(fixture, oracle)
+    binary = tmp_path / "abi_capture_beside_cache"
+    subprocess.run([hipcc, "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "c", "abi_capture_beside_cache.cpp"),
+                    "-I", INCLUDE, "-L", LIBDIR, "-lhe_amd", "-pthread", f"-Wl,-rpath,{LIBDIR}", "-o", str(binary)], check=True)
+    result = run_on_fixture(binary, fixture)
+    assert result.returncode == 0, result.stdout + result.stderr
+    assert "capture beside the cache ok (6 calls" in result.stdout
