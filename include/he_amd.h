@@ -1268,7 +1268,94 @@ int he_pnns_compute_response_matrix_device_u32(const he_pnns_context* ctx, const
                                                const he_pnns_pack_step* pack_steps, size_t pack_step_count,
                                                const uint32_t* const* galois_keys, uint32_t* out, he_stream s);
 
-/* ---- SimplePirServer (PrivateInformationRetrieval/SimplePir/) ------------------------------------------------------------
+/* ---- PNNS client (PrivateNearestNeighborSearch/Client.swift:74-127) --------------------------------------------------------
+ * Client.generateQuery(for:using:) and Client.decrypt(response:using:) on the device, and the two layers under them as entries
+ * of their own.  The conventions of the decrypt and encrypt entries hold for all of them: the slab word is an argument
+ * (word_bits 32 or 64, packed 4-byte or 8-byte words; it must be the word of the context's scheme -- he_pnns_context_create
+ * for 64, he_pnns_context_create_u32 for 32 -- else HE_ERR_INVALID_ARGUMENT) and there are no _u32 twins; enqueue-only on `s`;
+ * scratch comes from the library's stream-ordered cache; every argument error (in the order of the argument lists below: the
+ * word, the contexts, the shape, null buffers, buffers that overlap one the call writes) is returned before anything is
+ * enqueued; a host-only context is HE_ERR_DEVICE after the argument checks; an empty batch does nothing.
+ *
+ * Layer 1 -- Context.encodeSimd / decodeSimd (Encoding.swift:222-245) for `batch` plaintexts.
+ *   slots / out_slots            DEVICE [batch][N] words in slot order; a caller with fewer than N values pads with zeros, as
+ *                                encodeSimd does
+ *   plaintexts / out_plaintexts  DEVICE [batch][N] Coeff words below t
+ *   out_of_range                 DEVICE, one word the caller zeroes, may be NULL: set to 1 when a slot value is not below t
+ *                                (validDataForEncoding); that plaintext is then unspecified
+ * Encoding scatters value i to word simdEncodingMatrix[i] -- written as a gather through the inverse table, so the stores are
+ * contiguous -- into out_plaintexts and runs the inverse NTT over [t] there; decoding runs the forward NTT on a scratch copy
+ * (the input is never written) and reads out_slots[b][i] = transformed[b][simdEncodingMatrix[i]]. */
+int he_pnns_simd_encode_device(const he_pnns_context* ctx, uint32_t word_bits, const void* slots, size_t batch,
+                               void* out_plaintexts, uint32_t* out_of_range, he_stream s);
+int he_pnns_simd_decode_device(const he_pnns_context* ctx, uint32_t word_bits, const void* plaintexts, size_t batch,
+                               void* out_slots, he_stream s);
+/* Layer 2 -- PlaintextMatrix(context:dimensions:packing: .denseRow, signedValues:reduce:) (PlaintextMatrix.swift:165-236,
+ * 341-406) and PlaintextMatrix.unpack() -> [Scalar] (:489-590).
+ *   signed_values   DEVICE [rows][cols] int64 row-major; reduce and out_of_range exactly as in he_pnns_diagonal_matrix_device
+ *   out_plaintexts  DEVICE [K][N] Coeff, K from he_pnns_matrix_shape(.., HE_PNNS_PACKING_DENSE_ROW, ..)
+ *   packing         of the plaintexts handed to unpack: HE_PNNS_PACKING_DENSE_COLUMN (unpackDenseColumn, with its transposition
+ *                   to row-major) or HE_PNNS_PACKING_DENSE_ROW; plaintexts DEVICE [count][N] Coeff, count from
+ *                   he_pnns_matrix_shape under that packing
+ *   out_values      DEVICE [rows][cols] uint64 row-major, values below t
+ * Packing is one kernel with a lane per slab word of all K plaintexts -- word -> slot -> (row, column) or zero in closed form,
+ * the zero padding to nextPowerOfTwo(cols) and the repeated rows of the last plaintext (:388-402) included -- and the inverse
+ * NTT in out_plaintexts; unpacking is the forward NTT on a scratch copy and one kernel with a lane per value.  Shape errors are
+ * those of he_pnns_matrix_shape; more than 2^40 values or slab words: HE_ERR_INVALID_ARGUMENT.
+ * Out of scope: dense-column PACKING and diagonal UNPACKING -- nothing on the device produces a matrix to pack by columns or
+ * consumes an unpacked diagonal matrix.  he_pnns_unpack_device under HE_PNNS_PACKING_DIAGONAL is HE_ERR_UNSUPPORTED, and there is
+ * no he_pnns_pack_dense_columns_device. */
+int he_pnns_pack_dense_rows_device(const he_pnns_context* ctx, uint32_t word_bits, const int64_t* signed_values, size_t rows,
+                                   size_t cols, int reduce, void* out_plaintexts, uint32_t* out_of_range, he_stream s);
+int he_pnns_unpack_device(const he_pnns_context* ctx, uint32_t word_bits, int packing, const void* plaintexts, size_t rows,
+                          size_t cols, uint64_t* out_values, he_stream s);
+/* Layer 3 -- the client.  ctxs: a HOST array of context_count PNNS contexts, one per plaintext modulus (Client.contexts).
+ * HE_ERR_INVALID_ARGUMENT: context_count 0 or above 8, a NULL context, contexts that differ in degree, coefficient moduli or
+ * word, two equal plaintext moduli, 2 x the product of the plaintext moduli above UInt64.max (compose's precondition,
+ * CrtComposer.swift:78-79); HE_ERR_NOT_INVERTIBLE: plaintext moduli that are not pairwise coprime.
+ *
+ * he_pnns_generate_query_device -- Client.generateQuery(for:using:) (Client.swift:74-91):
+ *   vectors        DEVICE [query_rows][cols] float32 row-major
+ *   secret_key     as he_bfv_encrypt_device reads it
+ *   a_seeds, error_seeds   DEVICE [context_count][K][32], K the dense-row plaintext count of a query_rows x cols matrix
+ *   out            DEVICE [context_count][K][2][L][N] Coeff, L = he_bfv_ciphertext_moduli_count: slice c is a client's argument
+ *                  `queries` of he_pnns_compute_response_matrix_device under context c
+ *   out_of_range   as in layer 2 (one context: reduce is off, Client.swift:81)
+ *   workspace      DEVICE, 16-byte aligned, he_pnns_generate_query_workspace_bytes bytes, or NULL: stream-ordered scratch
+ * One normalizedScaledAndRounded (he_pnns_quantize_rows_device's kernel), then per context layer 2 with reduce =
+ * (context_count > 1) and he_bfv_encrypt_device at L moduli: every word equals that composition on the same seeds.  The
+ * quantised values, the plaintexts and the encryption's own scratch depend on the user's query: the whole workspace is
+ * overwritten with zeros on the stream before it is released or the entry returns (as he_bfv_encrypt_device's).
+ *
+ * he_pnns_decrypt_response_device -- Client.decrypt(response:using:) (Client.swift:100-127):
+ *   response       DEVICE [context_count][M][2][moduli_count][N] Coeff, M the dense-column plaintext count of a
+ *                  rows x query_rows matrix; moduli_count is 1 for a Response (he_pnns_compute_response_matrix_device's out per
+ *                  context), any level is allowed
+ *   out_distances  DEVICE [rows][query_rows] float32 row-major
+ *   workspace      as above, he_pnns_decrypt_response_workspace_bytes bytes
+ * Per context he_bfv_decrypt_device (correction factor 1) and the forward NTT over that context's [t_i]; then one kernel with
+ * a lane per distance: it gathers its residue from every context's transformed plaintexts (dense-column position -> slot ->
+ * simdEncodingMatrix), composes them as CrtComposer.compose does -- acc = addMod(acc, ((inv_i x_i) mod t_i) (q / t_i), q) in
+ * UInt64, in row order, inversePuncturedProducts from the host, q the product of the t_i; skipped for one context --, centres the
+ * result (remainderToCentered(modulus: q)) and returns Float(signed) / (scaling_factor * scaling_factor): the float product is
+ * formed first, the division is one correctly rounded division.  Plaintexts go through the workspace in groups of about 1 GiB,
+ * one kernel per group.  The decrypted plaintexts and the decryption's own scratch are zeroized as above.
+ *
+ * The two *_workspace_bytes are host only and return 0 for arguments the entries refuse. */
+size_t he_pnns_generate_query_workspace_bytes(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
+                                              size_t query_rows, size_t cols);
+int he_pnns_generate_query_device(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
+                                  const float* vectors, size_t query_rows, size_t cols, float scaling_factor,
+                                  const void* secret_key, const uint8_t* a_seeds, const uint8_t* error_seeds, void* out,
+                                  uint32_t* out_of_range, void* workspace, size_t workspace_bytes, he_stream s);
+size_t he_pnns_decrypt_response_workspace_bytes(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
+                                                uint32_t moduli_count, size_t rows, size_t query_rows);
+int he_pnns_decrypt_response_device(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
+                                    uint32_t moduli_count, const void* response, const void* secret_key, size_t rows,
+                                    size_t query_rows, float scaling_factor, float* out_distances, void* workspace,
+                                    size_t workspace_bytes, he_stream s);
+
+/* ---- SimplePirServer (PrivateInformationRetrieval/SimplePir/)------------------------------------------------------------
  * The other index-PIR server: a database matrix of plaintext_bits-wide elements, a hint for the clients, and replies that
  * are one wrap-around integer matrix product.  word_bits is the reference's Scalar: 64 (entries without suffix) or 32
  * (_u32: 4-byte request / response / hint words).

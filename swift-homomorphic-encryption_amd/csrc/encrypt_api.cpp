@@ -13,6 +13,7 @@
 #include "kernels.hpp"
 #include "rns_kernels.hpp"
 #include "word_layer.hpp"
+#include "zeroized_workspace.hpp"
 
 using heamd::as_stream;
 using heamd::BfvContext;
@@ -21,6 +22,7 @@ using heamd::invalid_argument;
 using heamd::KeySwitchFactors;
 using heamd::PolyContext;
 using heamd::Scratch;
+using heamd::ZeroizedWorkspace;
 
 extern "C++" {
 namespace {
@@ -92,35 +94,6 @@ int check_encrypt_device(const BfvContext& bfv, uint32_t word_bits, uint32_t mod
     }
     return HE_OK;
 }
-
-// The workspace of one call: the caller's or stream-ordered scratch.  Its first `bytes` bytes are set to zero on the stream when
-// the call is done with them, however it ends.
-class ZeroizedWorkspace {
-  public:
-    explicit ZeroizedWorkspace(hipStream_t stream) : scratch_(stream), stream_(stream) {}
-    ~ZeroizedWorkspace() {
-        if (base_ != nullptr && bytes_ != 0 && hipMemsetAsync(base_, 0, bytes_, stream_) != hipSuccess) (void)hipGetLastError();
-    }
-    int resolve(void* workspace, size_t workspace_bytes, size_t needed) {
-        if (workspace != nullptr) {
-            if (workspace_bytes < needed) return invalid_argument("workspace too small");
-            if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return invalid_argument("workspace not 16-byte aligned");
-            base_ = static_cast<uint8_t*>(workspace);
-        } else {
-            HEAMD_HIP_TRY(scratch_.allocate(needed));
-            base_ = static_cast<uint8_t*>(scratch_.get());
-        }
-        bytes_ = needed;
-        return HE_OK;
-    }
-    uint8_t* at(size_t offset) const { return base_ + offset; }
-
-  private:
-    Scratch scratch_;  // (released after the destructor's memset: members go after the body)
-    hipStream_t stream_;
-    uint8_t* base_ = nullptr;
-    size_t bytes_ = 0;
-};
 
 // Bfv.encryptZero over the first m moduli of pc for `count` ciphertexts, out [count][2][m][N]; with current_keys the last step
 // of _generateKeySwitchKey on top (encrypt_kernels.hpp launch_encrypt_finish_eval).  `ws`: a workspace laid out by `plan`.
@@ -276,6 +249,10 @@ int poly_sample_entry(const he_poly_context* ctx, uint32_t word_bits, bool terna
 }
 
 }  // namespace
+
+int heamd::bfv_encrypt_check_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count) {
+    return check_encrypt_device(heamd::bfv_impl(ctx), word_bits, moduli_count);
+}
 }  // extern "C++"
 
 size_t he_bfv_encrypt_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, int operation, uint32_t moduli_count,

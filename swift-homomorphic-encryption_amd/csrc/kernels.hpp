@@ -393,4 +393,55 @@ hipError_t launch_pnns_extract_rows(const W* queries, const W* masks, W* out, co
                                     const PnnsExtractLayout& layout, uint32_t ciphertext, uint32_t first_row,
                                     const uint32_t* positions, size_t count, hipStream_t stream);
 
+// ---- pnns_client_kernels.hip: the PNNS client (PrivateNearestNeighborSearch/Client.swift:74-127) ------------------------------
+// Context.encodeSimd up to inverseNtt (Encoding.swift:222-231): staging[b][w] = slots[b][slot_of_word[w]], [batch][N] each.
+// out_of_range (may be nullptr): set to 1 when a value is not below t.
+template <typename W>
+hipError_t launch_pnns_simd_scatter(const W* slots, const uint32_t* slot_of_word, uint32_t log_degree, uint64_t t, size_t batch,
+                                    W* staging, uint32_t* out_of_range, hipStream_t stream);
+// Context.decodeSimd behind forwardNtt (Encoding.swift:242-244): out_slots[b][i] = transformed[b][word_of_slot[i]]
+template <typename W>
+hipError_t launch_pnns_simd_gather(const W* transformed, const uint32_t* word_of_slot, uint32_t log_degree, size_t batch,
+                                   W* out_slots, hipStream_t stream);
+// PlaintextMatrix.denseRowPlaintexts (PlaintextMatrix.swift:341-406) up to inverseNtt for all `count` plaintexts of one
+// [rows][cols] matrix: staging [count][N] words mod t, every word written; reduce / out_of_range as launch_pnns_diagonal_pack.
+struct PnnsDenseRowLayout {
+    size_t rows, cols, padded_cols /* nextPowerOfTwo(cols) <= N / 2 */;
+    uint64_t plaintext_modulus;
+    uint32_t log_degree;
+    bool reduce;
+};
+template <typename W>
+hipError_t launch_pnns_dense_row_pack(const int64_t* values, const uint32_t* slot_of_word, const PnnsDenseRowLayout& layout,
+                                      size_t count, W* staging, uint32_t* out_of_range, hipStream_t stream);
+// PlaintextMatrix.unpackDenseColumn / unpackDenseRow (PlaintextMatrix.swift:515-590) behind forwardNtt: transformed
+// [plaintext_count][N] -> out_values [rows][cols] row-major
+struct PnnsUnpackLayout {
+    size_t rows, cols, padded_cols;
+    uint32_t log_degree;
+    bool dense_row;
+};
+template <typename W>
+hipError_t launch_pnns_unpack(const W* transformed, const uint32_t* word_of_slot, const PnnsUnpackLayout& layout,
+                              uint64_t* out_values, hipStream_t stream);
+// The end of Client.decrypt(response:) (Client.swift:104-117) for the dense-column packed distances of a rows x cols result:
+// CrtComposer.compose (CrtComposer.swift:76-97) over `count` plaintext moduli, remainderToCentered, the float scaling.
+//   transformed  context i's forwardNtt'ed plaintexts [first_plaintext, ..) at transformed + i * context_stride, [..][N]
+//   elements     values of the column-major sequence from first_element on: exactly those the plaintexts given hold
+//   out          [rows][cols] float32, the whole matrix
+constexpr uint32_t kPnnsMaxClientContexts = 8;
+struct PnnsComposeLayout {
+    size_t rows, cols, first_plaintext, first_element, elements, context_stride;
+    uint32_t log_degree;
+};
+struct PnnsComposeTables {
+    uint64_t t[kPnnsMaxClientContexts], inverse[kPnnsMaxClientContexts] /* inversePuncturedProducts */,
+        inverse_shoup[kPnnsMaxClientContexts], punctured[kPnnsMaxClientContexts] /* q / t_i */;
+    uint64_t q;  // the product of the t_i
+    uint32_t count;
+};
+template <typename W>
+hipError_t launch_pnns_compose_distances(const W* transformed, const uint32_t* word_of_slot, const PnnsComposeLayout& layout,
+                                         const PnnsComposeTables& tables, float scaling_factor, float* out, hipStream_t stream);
+
 }  // namespace heamd

@@ -25,39 +25,19 @@
 #include "api_internal.hpp"
 #include "bfv_context.hpp"
 #include "kernels.hpp"
+#include "pnns_context.hpp"
 #include "word_layer.hpp"
 
 using heamd::as_stream;
+using heamd::dividing_ceil;
 using heamd::invalid_argument;
+using heamd::matrix_plan;
+using heamd::MatrixPlan;
+using heamd::next_power_of_two;
 using heamd::Scratch;
 
-// Opaque handle of include/he_amd.h
-struct he_pnns_context {
-    const he_bfv_context* bfv = nullptr;          // borrowed
-    std::unique_ptr<heamd::PolyContext> plaintext;  // plaintextContext: [t]
-    std::vector<uint32_t> encoding_matrix;        // simdEncodingMatrix: slot -> slab word
-    uint32_t* slot_of_word_device = nullptr;      // its inverse, on the device
-    ~he_pnns_context() {
-        if (slot_of_word_device != nullptr) (void)hipFree(slot_of_word_device);
-    }
-};
-
-namespace {
-
-size_t next_power_of_two(size_t x) {
-    size_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-size_t dividing_ceil(size_t a, size_t b) { return (a + b - 1) / b; }
-
-struct MatrixPlan {
-    size_t plaintext_count = 0, padded_cols = 0, plaintexts_per_column = 0;
-    uint32_t baby_step = 0, giant_step = 0;
-};
-
 // PlaintextMatrix.plaintextCount (PlaintextMatrix.swift:246-275) and BabyStepGiantStep.init (MatrixMultiplication.swift:33-60)
-int matrix_plan(const he_pnns_context* ctx, size_t rows, size_t cols, int packing, uint32_t baby_step, MatrixPlan& plan) {
+int heamd::matrix_plan(const he_pnns_context* ctx, size_t rows, size_t cols, int packing, uint32_t baby_step, MatrixPlan& plan) {
     if (ctx == nullptr) return invalid_argument("null context");
     if (rows == 0 || cols == 0) return invalid_argument("matrix dimensions must be positive");  // MatrixDimensions.init
     if (rows > (size_t(1) << 40) || cols > (size_t(1) << 40)) return invalid_argument("matrix too large");
@@ -96,6 +76,8 @@ int matrix_plan(const he_pnns_context* ctx, size_t rows, size_t cols, int packin
     plan.giant_step = static_cast<uint32_t>(giant);
     return HE_OK;
 }
+
+namespace {
 
 // generateEncodingMatrix (Encoding.swift:197-219)
 std::vector<uint32_t> encoding_matrix(uint32_t degree, uint32_t log_degree) {
@@ -139,11 +121,15 @@ int pnns_create(const he_bfv_context* bfv_handle, int word_bits, he_pnns_context
     }
     ctx->encoding_matrix = encoding_matrix(bfv.degree(), ctx->plaintext->log_degree());
     if (!bfv.host_only()) {
-        std::vector<uint32_t> slot_of_word(bfv.degree());
-        for (uint32_t slot = 0; slot < bfv.degree(); ++slot) slot_of_word[ctx->encoding_matrix[slot]] = slot;
-        const size_t bytes = slot_of_word.size() * sizeof(uint32_t);
+        // slot_of_word, then simdEncodingMatrix itself (decodeSimd reads through it: Encoding.swift:242-244)
+        std::vector<uint32_t> tables(2 * size_t(bfv.degree()));
+        for (uint32_t slot = 0; slot < bfv.degree(); ++slot) {
+            tables[ctx->encoding_matrix[slot]] = slot;
+            tables[bfv.degree() + slot] = ctx->encoding_matrix[slot];
+        }
+        const size_t bytes = tables.size() * sizeof(uint32_t);
         HEAMD_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->slot_of_word_device), bytes));
-        HEAMD_HIP_TRY(hipMemcpy(ctx->slot_of_word_device, slot_of_word.data(), bytes, hipMemcpyHostToDevice));
+        HEAMD_HIP_TRY(hipMemcpy(ctx->slot_of_word_device, tables.data(), bytes, hipMemcpyHostToDevice));
     }
     *out = ctx.release();
     return HE_OK;

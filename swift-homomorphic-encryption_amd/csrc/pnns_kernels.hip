@@ -8,6 +8,7 @@
 // product of every query ciphertext with the masks of all the rows packed in it.
 #include "kernels.hpp"
 #include "launch_grid.hpp"
+#include "pnns_values.hpp"
 
 namespace heamd {
 
@@ -109,7 +110,6 @@ __global__ __launch_bounds__(kPackThreads) void pnns_diagonal_pack_kernel(const 
     if (last_diagonal > shape.padded_cols) last_diagonal = shape.padded_cols;
     if (last_diagonal > first_diagonal + kPackDiagonals) last_diagonal = first_diagonal + kPackDiagonals;
     const long long t = static_cast<long long>(shape.t);
-    const long long most = (t - 1) >> 1, least = -(t >> 1);
     const size_t end = shape.first + shape.count;
 
     const unsigned d = threadIdx.x % kPackDiagonals;
@@ -126,15 +126,7 @@ __global__ __launch_bounds__(kPackThreads) void pnns_diagonal_pack_kernel(const 
             const size_t row = chunk * n + source;
             const size_t column = (row + diagonal) & (shape.padded_cols - 1);
             if (row < shape.rows && column < shape.cols) {
-                long long v = values[row * shape.cols + column];
-                if (shape.reduce) {  // Modulus.reduce(SignedScalar): the remainder in [0, t)
-                    v %= t;
-                    if (v < 0) v += t;
-                } else {             // centeredToRemainder
-                    outside |= v > most || v < least;
-                    if (v < 0) v += t;
-                }
-                value = static_cast<unsigned long long>(v);
+                value = pnns_signed_to_residue(values[row * shape.cols + column], t, shape.reduce != 0, outside);
             }
         }
         tile[d * kPitch + i] = static_cast<W>(value);

@@ -92,6 +92,9 @@ int poly_elementwise(const he_poly_context* ctx, ElementwiseOp op, W* lhs, const
 template <typename W>
 int bfv_plaintext_to_eval(const he_bfv_context* ctx, uint32_t moduli_count, const W* plaintext, W* out, size_t batch,
                           hipStream_t stream);
+// encrypt_api.cpp: the device-side checks of he_bfv_encrypt_device (a host-only context, the transform of the word), for an
+// entry that has to make them before it enqueues work of its own
+int bfv_encrypt_check_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count);
 // Ciphertext.modSwitchDownToSingle, with the checks of he_bfv_mod_switch_down_to_single_device: one kernel where 8-byte words
 // have it (2..8 moduli), else divideAndRoundQLast level by level through scratch of its own
 template <typename W>

@@ -37,6 +37,10 @@ from .binding import (  # noqa: F401
     library_path,
     load_library,
     narrow_u64,
+    pnns_decrypt_response,
+    pnns_decrypt_response_workspace_bytes,
+    pnns_generate_query,
+    pnns_generate_query_workspace_bytes,
     set_device,
     scratch_cached_bytes,
     shard_bounds,

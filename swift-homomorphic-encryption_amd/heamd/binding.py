@@ -288,6 +288,16 @@ SIGNATURES = [
      [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
     ("he_pnns_compute_response_matrix_device", ctypes.c_int,
      [vp, vp, c_size, c_size, c_size, c_u32, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
+    ("he_pnns_simd_encode_device", ctypes.c_int, [vp, c_u32, vp, c_size, vp, vp, vp]),
+    ("he_pnns_simd_decode_device", ctypes.c_int, [vp, c_u32, vp, c_size, vp, vp]),
+    ("he_pnns_pack_dense_rows_device", ctypes.c_int, [vp, c_u32, vp, c_size, c_size, ctypes.c_int, vp, vp, vp]),
+    ("he_pnns_unpack_device", ctypes.c_int, [vp, c_u32, ctypes.c_int, vp, c_size, c_size, vp, vp]),
+    ("he_pnns_generate_query_workspace_bytes", c_size, [vp, c_size, c_u32, c_size, c_size]),
+    ("he_pnns_generate_query_device", ctypes.c_int,
+     [vp, c_size, c_u32, vp, c_size, c_size, ctypes.c_float, vp, vp, vp, vp, vp, vp, c_size, vp]),
+    ("he_pnns_decrypt_response_workspace_bytes", c_size, [vp, c_size, c_u32, c_u32, c_size, c_size]),
+    ("he_pnns_decrypt_response_device", ctypes.c_int,
+     [vp, c_size, c_u32, c_u32, vp, vp, c_size, c_size, ctypes.c_float, vp, vp, c_size, vp]),
     # diagnostics / test hooks
     ("he_poly_context_create_host_only", ctypes.c_int, [c_u32, U64P, c_u32, ctypes.POINTER(vp)]),
     ("he_poly_context_copy_ntt_tables", ctypes.c_int, [vp, c_u32, U64P, U64P, U64P, U64P, U64P, U64P]),
@@ -1957,6 +1967,134 @@ class PnnsContext:
         modSwitchDownToSingle -> [Q][M][2][1][N] Coeff over q_0."""
         return self._matrix_entry("he_pnns_compute_response_matrix_device", matrix, rows, cols, queries, query_rows,
                                   pack_steps, galois_keys, baby_step, 1, stream)
+
+    # ---- the client's layers (DESIGN.md 4.16): encodeSimd / decodeSimd, the dense packings
+    def _plaintext_batch(self, tensor, name):
+        import torch
+
+        if (tensor.dtype != getattr(torch, self._word.dtype) or not tensor.is_cuda or not tensor.is_contiguous()
+                or tensor.dim() != 2 or tensor.shape[1] != self.bfv.degree):
+            raise ValueError(f"{name} must be a contiguous device tensor [batch][N] of the context's words")
+        return tensor.shape[0]
+
+    def simd_encode(self, slots, stream=None):
+        """he_pnns_simd_encode_device: Context.encodeSimd per row.  slots [batch][N] in slot order (values < t) ->
+        (plaintexts [batch][N] Coeff; out_of_range, a one-word int32 device tensor: 1 when a value was not below t)."""
+        import torch
+
+        batch, w = self._plaintext_batch(slots, "slots"), self._word
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            out = _empty((batch, self.bfv.degree), w, slots.device)
+            out_of_range = torch.zeros(1, dtype=torch.int32, device=slots.device)
+        _check(load_library().he_pnns_simd_encode_device(self.h, w.bits, _ptr(slots, w), batch, _ptr(out, w),
+                                                         vp(out_of_range.data_ptr()), _stream(stream)))
+        return out, out_of_range
+
+    def simd_decode(self, plaintexts, stream=None):
+        """he_pnns_simd_decode_device: Context.decodeSimd per row.  plaintexts [batch][N] Coeff -> slots [batch][N]."""
+        import torch
+
+        batch, w = self._plaintext_batch(plaintexts, "plaintexts"), self._word
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            out = _empty((batch, self.bfv.degree), w, plaintexts.device)
+        _check(load_library().he_pnns_simd_decode_device(self.h, w.bits, _ptr(plaintexts, w), batch, _ptr(out, w),
+                                                         _stream(stream)))
+        return out
+
+    def pack_dense_rows(self, signed_values, reduce=False, stream=None):
+        """he_pnns_pack_dense_rows_device: PlaintextMatrix(.denseRow, signedValues:reduce:).  int64 CUDA tensor [rows][cols] ->
+        (plaintexts [K][N] Coeff, out_of_range as diagonal_matrix returns it)."""
+        import torch
+
+        if (signed_values.dtype != torch.int64 or not signed_values.is_cuda or not signed_values.is_contiguous()
+                or signed_values.dim() != 2):
+            raise ValueError("signed_values must be a contiguous int64 device tensor [rows][cols]")
+        rows, cols = signed_values.shape
+        count, w = self.matrix_shape(rows, cols, "denseRow")["plaintext_count"], self._word
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            out = _empty((count, self.bfv.degree), w, signed_values.device)
+            out_of_range = torch.zeros(1, dtype=torch.int32, device=signed_values.device)
+        _check(load_library().he_pnns_pack_dense_rows_device(self.h, w.bits, vp(signed_values.data_ptr()), rows, cols,
+                                                             int(bool(reduce)), _ptr(out, w), vp(out_of_range.data_ptr()),
+                                                             _stream(stream)))
+        return out, out_of_range
+
+    def unpack(self, plaintexts, rows, cols, packing="denseColumn", stream=None):
+        """he_pnns_unpack_device: PlaintextMatrix.unpack() for "denseColumn" or "denseRow".  plaintexts [count][N] Coeff ->
+        int64 tensor [rows][cols] of values below t."""
+        import torch
+
+        batch, w = self._plaintext_batch(plaintexts, "plaintexts"), self._word
+        number = int(PNNS_PACKINGS.get(packing, packing))
+        if number != PNNS_PACKINGS["diagonal"] and batch != self.matrix_shape(rows, cols, number)["plaintext_count"]:
+            raise ValueError("plaintexts must hold the packing's plaintext count for rows x cols")
+        with torch.cuda.stream(stream) if stream is not None else _no_stream():
+            out = torch.empty((int(rows), int(cols)), dtype=torch.int64, device=plaintexts.device)
+        _check(load_library().he_pnns_unpack_device(self.h, w.bits, number, _ptr(plaintexts, w), int(rows), int(cols),
+                                                    vp(out.data_ptr()), _stream(stream)))
+        return out
+
+
+def _pnns_contexts(contexts):
+    contexts = list(contexts)
+    if not contexts:
+        raise ValueError("one PnnsContext per plaintext modulus")
+    handles = (vp * len(contexts))(*[ctx.h for ctx in contexts])
+    return contexts, handles, contexts[0]._word
+
+
+def pnns_generate_query_workspace_bytes(contexts, query_rows, cols):
+    contexts, handles, w = _pnns_contexts(contexts)
+    return int(load_library().he_pnns_generate_query_workspace_bytes(handles, len(contexts), w.bits, int(query_rows), int(cols)))
+
+
+def pnns_generate_query(contexts, vectors, scaling_factor, secret_key, a_seeds, error_seeds, stream=None, workspace=None):
+    """he_pnns_generate_query_device: Client.generateQuery(for:using:) for a client with one PnnsContext per plaintext modulus.
+    vectors float32 CUDA tensor [query_rows][cols], seeds uint8 [contexts][K][32] -> (queries [contexts][K][2][L][N] Coeff,
+    out_of_range); queries[c] is one client's `queries` of contexts[c].compute_response_matrix."""
+    import torch
+
+    contexts, handles, w = _pnns_contexts(contexts)
+    if vectors.dtype != torch.float32 or not vectors.is_cuda or not vectors.is_contiguous() or vectors.dim() != 2:
+        raise ValueError("vectors must be a contiguous float32 device tensor [query_rows][cols]")
+    rows, cols = vectors.shape
+    bfv = contexts[0].bfv
+    count = contexts[0].matrix_shape(rows, cols, "denseRow")["plaintext_count"]
+    with torch.cuda.stream(stream) if stream is not None else _no_stream():
+        out = _empty((len(contexts), count, 2, bfv.L, bfv.degree), w, vectors.device)
+        out_of_range = torch.zeros(1, dtype=torch.int32, device=vectors.device)
+    ws_ptr, ws_bytes = _workspace(workspace)
+    _check(load_library().he_pnns_generate_query_device(
+        handles, len(contexts), w.bits, vp(vectors.data_ptr()), rows, cols, float(scaling_factor), _ptr(secret_key, w),
+        vp(a_seeds.data_ptr()), vp(error_seeds.data_ptr()), _ptr(out, w), vp(out_of_range.data_ptr()), ws_ptr, ws_bytes,
+        _stream(stream)))
+    return out, out_of_range
+
+
+def pnns_decrypt_response_workspace_bytes(contexts, rows, query_rows, moduli_count=1):
+    contexts, handles, w = _pnns_contexts(contexts)
+    return int(load_library().he_pnns_decrypt_response_workspace_bytes(handles, len(contexts), w.bits, int(moduli_count),
+                                                                       int(rows), int(query_rows)))
+
+
+def pnns_decrypt_response(contexts, response, secret_key, rows, query_rows, scaling_factor, stream=None, workspace=None):
+    """he_pnns_decrypt_response_device: Client.decrypt(response:using:).  response [contexts][M][2][moduli_count][N] Coeff (M the
+    dense-column plaintext count of rows x query_rows) -> distances, float32 [rows][query_rows]."""
+    import torch
+
+    contexts, handles, w = _pnns_contexts(contexts)
+    if (response.dtype != getattr(torch, w.dtype) or not response.is_cuda or not response.is_contiguous() or response.dim() != 5
+            or response.shape[0] != len(contexts) or response.shape[2] != 2 or response.shape[4] != contexts[0].bfv.degree):
+        raise ValueError("response must be a contiguous device tensor [contexts][M][2][moduli_count][N] of the contexts' words")
+    if response.shape[1] != contexts[0].matrix_shape(rows, query_rows, "denseColumn")["plaintext_count"]:
+        raise ValueError("response must hold the dense-column plaintext count of rows x query_rows per context")
+    with torch.cuda.stream(stream) if stream is not None else _no_stream():
+        out = torch.empty((int(rows), int(query_rows)), dtype=torch.float32, device=response.device)
+    ws_ptr, ws_bytes = _workspace(workspace)
+    _check(load_library().he_pnns_decrypt_response_device(
+        handles, len(contexts), w.bits, int(response.shape[3]), _ptr(response, w), _ptr(secret_key, w), int(rows),
+        int(query_rows), float(scaling_factor), vp(out.data_ptr()), ws_ptr, ws_bytes, _stream(stream)))
+    return out
 
 
 # ---- keyword PIR database (DESIGN.md 4.12): HashKeyword, CuckooTable, HashBucket.serialize ----
