@@ -890,6 +890,11 @@ int decrypt_dot(const he_bfv_context* ctx, uint32_t moduli_count, uint32_t poly_
     if (batch == 0) return HE_OK;
     if (cts == nullptr || secret_key == nullptr) return invalid_argument("null ciphertexts or secret key");
     const BfvContext& bfv = *ctx->impl;
+    // A caller's workspace holds what he_bfv_decrypt_workspace_bytes reports, whichever entry this is (he_amd.h): the dot
+    // product, which leaves its result in the caller's slab, uses less of it, and still refuses a shorter one.
+    if (workspace != nullptr &&
+        workspace_bytes < he_bfv_decrypt_workspace_bytes(ctx, 8 * sizeof(W), moduli_count, poly_count, is_eval, batch))
+        return invalid_argument("workspace too small");
     const size_t copy_words = decrypt_copy_words(bfv, moduli_count, poly_count, is_eval != 0, batch);
     const size_t dot_words = dot == nullptr ? decrypt_dot_words(bfv, moduli_count, batch) : 0;
     uint64_t* base = nullptr;

@@ -1879,7 +1879,7 @@ class PnnsContext:
                         keys[2 * q + k] = key.data_ptr()
         results = -(-int(rows) // n)
         with torch.cuda.stream(stream) if stream is not None else _no_stream():
-            out = torch.empty((count, results, 2, out_moduli, n), dtype=word, device=queries.device)
+            out = _empty((count, results, 2, out_moduli, n), self._word, queries.device)
         _check(_entry(entry, self._word)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
                                          shape["baby_step"], vp(queries.data_ptr()), count,
                                          keys if galois_keys is not None else None, vp(out.data_ptr()), _stream(stream)))
@@ -1944,7 +1944,7 @@ class PnnsContext:
                             raise ValueError("a Galois key must be a contiguous device tensor of the context's words")
                         keys[stride * q + k] = key.data_ptr()
         with torch.cuda.stream(stream) if stream is not None else _no_stream():
-            out = torch.empty((count, query_shape["result_ciphertexts"], 2, out_moduli, n), dtype=word, device=queries.device)
+            out = _empty((count, query_shape["result_ciphertexts"], 2, out_moduli, n), self._word, queries.device)
         _check(_entry(entry, self._word)(self.h, vp(matrix.data_ptr()), matrix.shape[0], int(rows), int(cols),
                                          shape["baby_step"], vp(queries.data_ptr()), int(query_rows), count,
                                          plan if pack_steps else None, len(pack_steps),
