@@ -842,6 +842,87 @@ int he_pir_process_database_device_u32(const he_bfv_context* ctx, const uint32_t
                                        size_t entry_size_in_bytes, int encoding_entry_size, uint32_t* database,
                                        uint8_t* present, he_stream s);
 
+/* ---- the MulPIR client (PrivateInformationRetrieval/IndexPir/MulPir.swift:117-289): queries from indices, entries from replies
+ * The IndexPirParameter is given as its fields, exactly as he_pir_database_shape takes them.  With N the degree, t the plaintext
+ * modulus, bits = floor(log2 t), bpp = N bits / 8, w the entry-size encoding width (0 without encoding), E =
+ * entry_size_in_bytes, enc = w + E, S = sum(dimensions), I = indices_count:
+ *   per = bpp / enc when bpp >= enc, else 1    entryChunksPerPlaintext (MulPir.swift:150-155)
+ *   R   = ceil(enc / bpp)                      expectedResponseCiphertextCount (:229-231)
+ *   C   = ceil(S I / N)                        the ciphertexts of a Query (PirUtil.swift:381-404)
+ * he_pir_client_plan is the plan (no device work, host-only contexts too); any out pointer may be NULL.  Its errors are those of
+ * he_pir_database_shape, then indices_count == 0 or above 2^20 (HE_ERR_INVALID_ARGUMENT) and dimension_count > 16
+ * (HE_ERR_UNSUPPORTED: the kernels take the dimensions by value). */
+int he_pir_client_plan(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, size_t entry_count,
+                       size_t entry_size_in_bytes, int encoding_entry_size, size_t indices_count, size_t* out_expanded_query_count,
+                       size_t* out_query_ciphertext_count, size_t* out_reply_ciphertext_count, size_t* out_entries_per_plaintext,
+                       size_t* out_bytes_per_plaintext, size_t* out_entry_size_encoding_width);
+/* MulPir.evaluationKeyConfig(expandedQueryCount:degree:keyCompression:) (MulPir.swift:86-109): the Galois elements of the
+ * evaluation key he_pir_expand_device needs for a query of expanded_query_count = S I inputs, in the reference's order -- the
+ * `elements` of he_bfv_generate_galois_keys_device.  *out_count (may be NULL) is their number; out_elements (a HOST array of
+ * `capacity` elements, or NULL to ask for the count) too small: HE_ERR_INVALID_ARGUMENT.  One input needs no expansion: without
+ * compression the list is empty (the reference's range is empty there), with compression it is the reference's 2N + 1, which no
+ * key generation takes.  Host only. */
+enum he_pir_key_compression {
+    HE_PIR_KEY_COMPRESSION_NONE = 0,   /* PirKeyCompressionStrategy.noCompression */
+    HE_PIR_KEY_COMPRESSION_HYBRID = 1, /* .hybridCompression */
+    HE_PIR_KEY_COMPRESSION_MAX = 2     /* .maxCompression */
+};
+int he_pir_evaluation_key_elements(uint32_t degree, size_t expanded_query_count, int key_compression, uint64_t* out_elements,
+                                   size_t capacity, size_t* out_count);
+/* The two device entries take the slab word as an argument (word_bits 32 or 64; 4-byte slabs need a context from
+ * he_bfv_context_create_u32) and have no _u32 twins.  Both are enqueue-only on `s`.  Every argument error is returned before anything is enqueued, in this order: the
+ * word, the context, the shape (he_pir_client_plan's errors, moduli_count, a batch too large for one call, HE_ERR_NOT_INVERTIBLE),
+ * null buffers, buffers that overlap one the call writes; HE_ERR_DEVICE comes last on a host-only context.  queries == 0 does
+ * nothing.  workspace: DEVICE, 16-byte aligned, at least the bytes the entry's _workspace_bytes function gives (0 on refused
+ * arguments), or NULL for stream-ordered scratch.  It holds the plaintexts in the clear and the scratch of encryption or
+ * decryption: all of it is overwritten with zeros on `s` before the entry releases it or returns.
+ *
+ * he_pir_generate_query_device -- MulPirClient.generateQuery(at:using:) for `queries` queries of I indices each:
+ *   indices       DEVICE uint64 [queries][I]; they are secret
+ *   secret_key    as he_bfv_encrypt_device reads it; one key per call
+ *   a_seeds, error_seeds  DEVICE [queries][C][32]
+ *   out           DEVICE [queries][C][2][L][N] Coeff, L = he_bfv_ciphertext_moduli_count; slice q is the query_ciphertexts of
+ *                 he_pir_compute_response_to_query_device
+ *   out_of_range  DEVICE word the caller zeroes, or NULL: set to 1 when an index is >= entry_count (PirError.invalidIndex);
+ *                 that index selects nothing, the other indices of its query are unaffected
+ * One kernel writes the plaintexts of PirUtil.compressBinaryInputs, one lane per word: input p = c N + x of ciphertext c is
+ * index i = p / S and dimension k whose range of S holds p mod S; the word is (2^ceilLog2(count_c))^-1 mod t, count_c =
+ * min(N, S I - c N), when coordinate k of plaintext indices[q][i] / per (computeCoordinates, MulPir.swift:181-193) is that
+ * input, else 0.  A t without that inverse: HE_ERR_NOT_INVERTIBLE.  Then he_bfv_encrypt_device's pipeline at L moduli: every
+ * output word equals that entry's on the same plaintexts and seeds. */
+size_t he_pir_generate_query_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                             uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                             int encoding_entry_size, size_t indices_count, size_t queries);
+int he_pir_generate_query_device(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                 uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes, int encoding_entry_size,
+                                 size_t indices_count, const uint64_t* indices, size_t queries, const void* secret_key,
+                                 const uint8_t* a_seeds, const uint8_t* error_seeds, void* out, uint32_t* out_of_range,
+                                 void* workspace, size_t workspace_bytes, he_stream s);
+/* he_pir_decrypt_response_device -- MulPirClient.decrypt(response:at:using:) and decryptFull (MulPir.swift:245-288):
+ *   response     DEVICE [queries][I][R][2][moduli_count][N] Coeff: per query the `out` of
+ *                he_pir_compute_response_to_query_device (moduli_count 1); any level is allowed
+ *   indices      as above; NULL selects decryptFull
+ *   out_entries  DEVICE bytes [queries][I][E]; decryptFull: [queries][I][R bpp]
+ *   out_sizes    DEVICE uint64 [queries][I]; may be NULL without a size prefix and for decryptFull
+ * he_bfv_decrypt_device with correction factor 1, then one kernel with one lane per output byte.  A reply's byte string is
+ * CoefficientPacking.coefficientsToBytes(bitsPerCoeff: bits) of its R plaintexts back to back, bpp bytes each, MSB first: stream
+ * bit s is bit bits - 1 - (s mod bits) of coefficient s / bits.  As in the reference a coefficient is not masked to `bits`
+ * bits: bit `bits` of a coefficient in [2^bits, t) is OR-ed into the last bit of the field before it when its own field does
+ * not begin a byte, and is dropped when it does (CoefficientPacking.swift:186-205).
+ * Entry (q, i) lies at byte pos enc of its reply, pos = indices[q][i] mod per.  Without a size prefix it is the E bytes there
+ * and out_sizes, if given, is E.  With one, the first w bytes are the little-endian size z: out_sizes = min(z, E) and
+ * out_entries holds the next min(z, E) bytes, then zeros up to E (the reference traps for z >= 2^63 and returns what there is
+ * for E < z; here both clamp).  decryptFull: out_sizes, if given, is R bpp. */
+size_t he_pir_decrypt_response_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                               uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                               int encoding_entry_size, size_t indices_count, uint32_t moduli_count,
+                                               size_t queries);
+int he_pir_decrypt_response_device(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                   uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                   int encoding_entry_size, size_t indices_count, uint32_t moduli_count, const void* response,
+                                   const uint64_t* indices, size_t queries, const void* secret_key, uint8_t* out_entries,
+                                   uint64_t* out_sizes, void* workspace, size_t workspace_bytes, he_stream s);
+
 /* ---- keyword PIR database (PrivateInformationRetrieval/KeywordPir/) --------------------------------------------------------
  * KeywordPirServer.process (KeywordPirProtocol.swift:191-247) builds a cuckoo table of the keyword-value pairs, serializes
  * every bucket and hands each sub-table's buckets to MulPirServer.process as index-PIR entries.  Here the keyword and value

@@ -221,6 +221,19 @@ SIGNATURES = [
       ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
     ("he_pir_process_database_device", ctypes.c_int,
      [vp, ctypes.POINTER(c_u32), c_u32, vp, U64P, c_size, c_size, ctypes.c_int, vp, vp, vp]),
+    ("he_pir_client_plan", ctypes.c_int,
+     [vp, ctypes.POINTER(c_u32), c_u32, c_size, c_size, ctypes.c_int, c_size] + [ctypes.POINTER(c_size)] * 6),
+    ("he_pir_evaluation_key_elements", ctypes.c_int, [c_u32, c_size, ctypes.c_int, U64P, c_size, ctypes.POINTER(c_size)]),
+    ("he_pir_generate_query_workspace_bytes", c_size,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, ctypes.c_int, c_size, c_size]),
+    ("he_pir_generate_query_device", ctypes.c_int,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, ctypes.c_int, c_size, vp, c_size, vp, vp, vp, vp, vp, vp,
+      c_size, vp]),
+    ("he_pir_decrypt_response_workspace_bytes", c_size,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, ctypes.c_int, c_size, c_u32, c_size]),
+    ("he_pir_decrypt_response_device", ctypes.c_int,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, ctypes.c_int, c_size, c_u32, vp, vp, c_size, vp, vp, vp, vp,
+      c_size, vp]),
     ("he_pir_database_file_scan", ctypes.c_int,
      [vp, vp, c_size, vp, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
     ("he_pir_database_file_byte_count", ctypes.c_int, [vp, vp, c_size, ctypes.POINTER(c_size)]),
@@ -1477,6 +1490,100 @@ class BfvContext:
             self.h, dims, len(dimensions), vp(entries.data_ptr()), size_ptr, count, int(entry_size_in_bytes),
             int(bool(encoding_entry_size)), _ptr(database, self._word), vp(present.data_ptr()), _stream(stream)))
         return database, present
+
+    # ---- the MulPIR client: MulPirClient.generateQuery / decrypt(response:) / decryptFull on the device.  The
+    # IndexPirParameter is given as its fields, as pir_database_shape takes them.
+    PIR_KEY_COMPRESSION = {"none": 0, "hybrid": 1, "max": 2}
+
+    @staticmethod
+    def _pir_parameter(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, indices_count):
+        dims = (c_u32 * max(len(dimensions), 1))(*[int(d) for d in dimensions])
+        return (dims, len(dimensions), int(entry_count), int(entry_size_in_bytes), int(bool(encoding_entry_size)),
+                int(indices_count))
+
+    def pir_client_plan(self, dimensions, entry_count, entry_size_in_bytes, encoding_entry_size=False, indices_count=1):
+        """he_pir_client_plan -> dict with expanded_query_count (S I), query_ciphertext_count (C), reply_ciphertext_count (R),
+        entries_per_plaintext (per), bytes_per_plaintext and entry_size_encoding_width."""
+        outs = [c_size() for _ in range(6)]
+        _check(load_library().he_pir_client_plan(
+            self.h, *self._pir_parameter(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, indices_count),
+            *[ctypes.byref(o) for o in outs]))
+        names = ("expanded_query_count", "query_ciphertext_count", "reply_ciphertext_count", "entries_per_plaintext",
+                 "bytes_per_plaintext", "entry_size_encoding_width")
+        return {name: int(o.value) for name, o in zip(names, outs)}
+
+    def pir_evaluation_key_elements(self, expanded_query_count, key_compression="none"):
+        """MulPir.evaluationKeyConfig's Galois elements, in the reference's order: what generate_galois_keys takes."""
+        lib, strategy, count = load_library(), self.PIR_KEY_COMPRESSION[key_compression], c_size()
+        _check(lib.he_pir_evaluation_key_elements(self.degree, int(expanded_query_count), strategy, None, 0, ctypes.byref(count)))
+        elements = _u64([0] * max(count.value, 1))
+        _check(lib.he_pir_evaluation_key_elements(self.degree, int(expanded_query_count), strategy,
+                                                  elements.ctypes.data_as(U64P), count.value, None))
+        return [int(e) for e in elements[:count.value]]
+
+    def pir_generate_query_workspace_bytes(self, dimensions, entry_count, entry_size_in_bytes, encoding_entry_size=False,
+                                           indices_count=1, queries=1):
+        return int(load_library().he_pir_generate_query_workspace_bytes(
+            self.h, self._word.bits,
+            *self._pir_parameter(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, indices_count), int(queries)))
+
+    def pir_generate_query(self, indices, dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, secret_key,
+                           a_seeds, error_seeds, out_of_range=None, stream=None, workspace=None):
+        """MulPirClient.generateQuery(at:using:) per row of indices (int64 CUDA tensor [queries][I]); seeds uint8
+        [queries][C][32] -> (ciphertexts [queries][C][2][L][N] Coeff, out_of_range int32 [1]); ciphertexts[q] is the
+        query_ciphertexts of pir_compute_response_to_query."""
+        import torch
+
+        if indices.dtype != torch.int64 or not indices.is_cuda or not indices.is_contiguous() or indices.dim() != 2:
+            raise ValueError("indices must be a contiguous int64 device tensor [queries][indices_count]")
+        queries, count = int(indices.shape[0]), int(indices.shape[1])
+        w = self._word
+        plan = self.pir_client_plan(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, max(count, 1))
+        out = _empty((queries, plan["query_ciphertext_count"], 2, self.L, self.degree), w, indices.device)
+        if out_of_range is None:
+            out_of_range = torch.zeros((1,), dtype=torch.int32, device=indices.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_pir_generate_query_device(
+            self.h, w.bits, *self._pir_parameter(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, count),
+            vp(indices.data_ptr()), queries, _ptr(secret_key, w), vp(a_seeds.data_ptr()), vp(error_seeds.data_ptr()),
+            _ptr(out, w), vp(out_of_range.data_ptr()), ws_ptr, ws_bytes, _stream(stream)))
+        return out, out_of_range
+
+    def pir_decrypt_response_workspace_bytes(self, dimensions, entry_count, entry_size_in_bytes, encoding_entry_size=False,
+                                             indices_count=1, queries=1, moduli_count=1):
+        return int(load_library().he_pir_decrypt_response_workspace_bytes(
+            self.h, self._word.bits,
+            *self._pir_parameter(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, indices_count),
+            int(moduli_count), int(queries)))
+
+    def pir_decrypt_response(self, response, indices, dimensions, entry_count, entry_size_in_bytes, encoding_entry_size,
+                             secret_key, stream=None, workspace=None):
+        """MulPirClient.decrypt(response:at:using:): response [queries][I][R][2][moduli_count][N] Coeff, indices as
+        pir_generate_query takes them -> (entries uint8 [queries][I][E], zeros behind each entry's size; sizes int64
+        [queries][I]).  indices None: decryptFull, entries [queries][I][R bpp]."""
+        import torch
+
+        w = self._word
+        if (response.dim() != 6 or response.shape[3] != 2 or response.shape[5] != self.degree
+                or (indices is not None and tuple(indices.shape) != tuple(response.shape[:2]))):
+            raise ValueError("expected the response as [queries][indices][R][2][moduli_count][N] and indices as [queries][indices]")
+        if indices is not None and (indices.dtype != torch.int64 or not indices.is_cuda or not indices.is_contiguous()):
+            raise ValueError("indices must be a contiguous int64 device tensor")
+        queries, count, moduli_count = int(response.shape[0]), int(response.shape[1]), int(response.shape[4])
+        plan = self.pir_client_plan(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, max(count, 1))
+        if response.shape[2] != plan["reply_ciphertext_count"]:  # PirError.invalidReply
+            raise HeError(16, f"Invalid reply: ciphertext count {int(response.shape[2])}, expected "
+                              f"{plan['reply_ciphertext_count']}")
+        stride = (int(entry_size_in_bytes) if indices is not None
+                  else plan["reply_ciphertext_count"] * plan["bytes_per_plaintext"])
+        entries = torch.empty((queries, count, stride), dtype=torch.uint8, device=response.device)
+        sizes = torch.empty((queries, count), dtype=torch.int64, device=response.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_pir_decrypt_response_device(
+            self.h, w.bits, *self._pir_parameter(dimensions, entry_count, entry_size_in_bytes, encoding_entry_size, count),
+            moduli_count, _ptr(response, w), vp() if indices is None else vp(indices.data_ptr()), queries,
+            _ptr(secret_key, w), vp(entries.data_ptr()), vp(sizes.data_ptr()), ws_ptr, ws_bytes, _stream(stream)))
+        return entries, sizes
 
     # ---- processed-database files (DESIGN.md 4.11): ProcessedDatabase.serialize() / init(from:context:) ----
     def database_file_payload_bytes(self):
