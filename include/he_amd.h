@@ -1552,6 +1552,112 @@ int he_simple_pir_batch_response_plan(uint32_t plaintext_bits, uint32_t cipherte
                                       size_t* out_fold_columns,        /* columns after which the i32 accumulators are folded */
                                       size_t* out_workspace_bytes);    /* scratch from the stream-ordered cache: 0 */
 
+/* ---- the SimplePIR client (PrivateInformationRetrieval/SimplePir/SimplePir+Client.swift, SimplePir+Precompute.swift) ----------
+ * Batches of `batch` independent precomputed queries on the device, bit for bit the reference's words.  With N the lattice
+ * dimension, C = chunks_per_entry, D = database_columns and p the modulus of he_simple_pir_shape:
+ *   a_polynomials              [a_poly_count][N] words mod p, Eval form
+ *   secrets                    [batch][C][N] Coeff words in {0, 1, p - 1}
+ *   queries                    [batch][C][D] words below 2^ciphertext_bits (Requests: C rows per query)
+ *   results_without_response   [batch][C][column_size] words mod p
+ *   responses                  [batch][C][column_size] words: he_simple_pir_compute_response_device of `queries` as batch x C
+ *                              stacked requests
+ * word_bits (32 / 64) is an argument and must be the context's (HE_ERR_INVALID_ARGUMENT otherwise); there are no _u32 twins.
+ * Every random value is a function of a caller-supplied 32-byte seed through NistAes128Ctr(seed:): the library generates no
+ * seed, and a seed must never be used twice.  Every call is enqueue-only on `s`.  The workspace is the caller's: DEVICE, 16-byte
+ * aligned, at least he_simple_pir_client_workspace_bytes() bytes (NULL or fewer: HE_ERR_INVALID_ARGUMENT); whatever a call
+ * leaves there depends on secrets, errors, indices or entries and is set to zero on `s` before the call's work is done, as are
+ * the secret codes the hint product holds in LDS.  Written slabs may overlap nothing else (HE_ERR_INVALID_ARGUMENT).  batch 0: a
+ * no-op returning HE_OK after the argument checks that need no buffer.  HE_ERR_DEVICE: no device, or another device current.
+ * Known limitation, as for the encryption entries: the AES behind the stream is a T-table implementation in LDS; its timing
+ * depends on the bank pattern of data-dependent lookups, i.e. it is not constant-time, and secret seeds pass through it.
+ * Not here: DefaultQueryGenerator's queue and actor, seed generation, protobuf Requests / Responses, DatabaseMap sharding. */
+#define HE_SIMPLE_PIR_ERROR_STDDEV32 0 /* ErrorStdDev.stdDev32: sigma 3.2, k = 21 trial bits a side, 16 stream bytes a coefficient */
+#define HE_SIMPLE_PIR_ERROR_STDDEV64 1 /* ErrorStdDev.stdDev64: sigma 6.4, k = 82, 32 stream bytes, mask 2^18 - 1 on words 1 and 3 */
+/* What the client entries do for a shape (the first six arguments are he_simple_pir_shape's, with its errors) and a batch.  Host
+ * only: callable without a GPU.  Any out pointer may be NULL.  HE_ERR_INVALID_ARGUMENT also for an unknown error_std_dev and a
+ * batch above 2^20.
+ *   out_chunk_size               SimplePirParameters.chunkSize = ceil(entry_size_in_scalar / C)
+ *   out_query_words              C D: words of one precomputed query      out_result_words   C column_size
+ *   out_error_stream_bytes       stream bytes per error coefficient: 16 or 32 (a query's error is ONE generator over C D
+ *                                coefficients, drawn in 4096-byte refills)
+ *   out_secret_rows_per_pass     secret rows answered per read of the hint by the hint product (16: one 64-bit accumulator
+ *                                per row and lane)
+ *   out_fold_terms               terms of at most p a 64-bit accumulator of the hint product holds before it is folded to
+ *                                below p: floor((2^64 - 1) / p)
+ *   out_row_block                secret rows encrypt_zero stages at a time (its staged sample stays near 128 MiB);
+ *                                HEAMD_SIMPLE_PIR_CLIENT_ROW_BLOCK=<rows> lowers it and never raises it
+ *   out_hint_product_lds_bytes   LDS of a workgroup of the hint product: the codes of a slab of 1024 columns and the sums
+ *   out_*_workspace_bytes        he_simple_pir_client_workspace_bytes of each entry for `batch` (secret x hint: batch x C rows) */
+int he_simple_pir_client_plan(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t lattice_dimension, uint32_t word_bits,
+                              size_t entry_count, size_t entry_size_in_bytes, int error_std_dev, size_t batch,
+                              size_t* out_chunk_size, size_t* out_query_words, size_t* out_result_words,
+                              uint32_t* out_error_stream_bytes, uint32_t* out_secret_rows_per_pass, uint64_t* out_fold_terms,
+                              size_t* out_row_block, size_t* out_hint_product_lds_bytes,
+                              size_t* out_a_polynomials_workspace_bytes, size_t* out_encrypt_zero_workspace_bytes,
+                              size_t* out_secret_times_hint_workspace_bytes, size_t* out_precompute_workspace_bytes,
+                              size_t* out_decrypt_responses_workspace_bytes);
+#define HE_SIMPLE_PIR_CLIENT_OP_A_POLYNOMIALS 0
+#define HE_SIMPLE_PIR_CLIENT_OP_ENCRYPT_ZERO 1
+#define HE_SIMPLE_PIR_CLIENT_OP_SECRET_TIMES_HINT 2 /* count: secret rows */
+#define HE_SIMPLE_PIR_CLIENT_OP_PRECOMPUTE 3
+#define HE_SIMPLE_PIR_CLIENT_OP_DECRYPT_RESPONSES 4
+/* Workspace bytes of a client entry for `count` queries (secret rows for SECRET_TIMES_HINT), a multiple of 16; 0 for a NULL
+ * context, an unknown operation, an unknown standard deviation (only ENCRYPT_ZERO and PRECOMPUTE depend on it; every operation
+ * but SECRET_TIMES_HINT checks it) and a count above 2^20.  add_indices takes no workspace. */
+size_t he_simple_pir_client_workspace_bytes(const he_simple_pir_context* ctx, int operation, int error_std_dev, size_t count);
+/* generateAPolynomials (SimplePir+Database.swift:178-181) and convertToEvalFormat, as DefaultQueryGenerator.init caches them
+ * (SimplePir+Precompute.swift:331): a_poly_count polynomials from ONE NistAes128Ctr(seed), the sampler process uses, without its
+ * Galois map.  Once per database; every precompute call reads the result.
+ *   seed  DEVICE [32], the database's seed      out  DEVICE [a_poly_count][N] words mod p, Eval form */
+int he_simple_pir_a_polynomials_device(const he_simple_pir_context* ctx, uint32_t word_bits, const uint8_t* seed, void* out,
+                                       void* workspace, size_t workspace_bytes, he_stream s);
+/* SimplePirContext.encryptZero (SimplePir+Client.swift:59-82) for `batch` queries: noiselessSample (:29-50) -- the forward NTT
+ * of the secrets, a_k s for every k through the inverse NTT, concatenated and cut to D --, then in one kernel
+ * Array2d.divideAndRound(initialMod: p, newMod: 2^c) (Array2d.swift:489-514), the error of
+ * Array2d.randomCenteredBinomialDistribution(standardDeviation:mod: [2^c]) (:382-429) and the mask.  The error of query b is ONE
+ * generator NistAes128Ctr(error_seeds[b]) over C D coefficients; row q of the query takes coefficients q D ... (the reference
+ * reshapes a 1 x n array).  The error never reaches memory; the un-noised sample is staged in the workspace row_block secret
+ * rows at a time and zeroed.
+ *   a_polynomials  DEVICE, he_simple_pir_a_polynomials_device's      secrets      DEVICE [batch][C][N]
+ *   error_seeds    DEVICE [batch][32]                                queries      DEVICE [batch][C][D], written whole */
+int he_simple_pir_encrypt_zero_device(const he_simple_pir_context* ctx, uint32_t word_bits, int error_std_dev,
+                                      const void* a_polynomials, const void* secrets, const uint8_t* error_seeds, void* queries,
+                                      size_t batch, void* workspace, size_t workspace_bytes, he_stream s);
+/* secretMatrix.multiply(transposing: hint, modulus: p) (Array2d.multiply(transposing:modulus:), SimplePir+Precompute.swift:
+ * 122-188) for `rows` secret rows: results[r][j] = sum_n secrets[r][n] hint[j][n] mod p.
+ *   secrets  DEVICE [rows][N]      hint  DEVICE [column_size][N] as he_simple_pir_process_database_device writes it, 16-byte
+ *   aligned (HE_ERR_INVALID_ARGUMENT otherwise)      results  DEVICE [rows][column_size]
+ * column_size is an argument (any number of hint rows over the context's ring; the precompute entry passes the shape's).
+ * PRECONDITION: every secret word is 0, 1 or p - 1 -- any other word counts as 0 (the kernel adds hint words, it does not
+ * multiply; the reference's product takes any matrix).  The secrets are packed to 2-bit codes in the workspace; a workgroup
+ * reads a tile of 64 hint rows once per pass of 16 secret rows, 16 bytes per lane. */
+int he_simple_pir_secret_times_hint_device(const he_simple_pir_context* ctx, uint32_t word_bits, const void* secrets, size_t rows,
+                                           const void* hint, size_t column_size, void* results, void* workspace,
+                                           size_t workspace_bytes, he_stream s);
+/* PrecomputedQueries.WithoutIndices.init (SimplePir+Precompute.swift:199-227) for `batch` queries: generateSecretPolys
+ * (SimplePir+Client.swift:21-27; polynomial (b, q) is randomizeTernary over NistAes128Ctr(secret_seeds[b][q])), then the two
+ * entries above on the same secrets, which live in the workspace alone.
+ *   secret_seeds  DEVICE [batch][C][32]      error_seeds  DEVICE [batch][32]
+ *   queries       DEVICE [batch][C][D]       results_without_response  DEVICE [batch][C][column_size] */
+int he_simple_pir_precompute_queries_device(const he_simple_pir_context* ctx, uint32_t word_bits, int error_std_dev,
+                                            const void* a_polynomials, const void* hint, const uint8_t* secret_seeds,
+                                            const uint8_t* error_seeds, void* queries, void* results_without_response,
+                                            size_t batch, void* workspace, size_t workspace_bytes, he_stream s);
+/* WithoutIndices.add(index:) (SimplePir+Precompute.swift:241-256) for `batch` queries in place: for q < C,
+ * queries[b][q][(q + indices[b] C) / entries_per_column] = (... + 2^(c - plaintext_bits)) & (2^c - 1).
+ *   indices  DEVICE [batch] 8-byte words      flags  DEVICE [batch] or NULL: 1 for an index at or above entry_count, whose query
+ *   stays untouched (the reference would trap), 0 otherwise */
+int he_simple_pir_add_indices_device(const he_simple_pir_context* ctx, uint32_t word_bits, void* queries, const uint64_t* indices,
+                                     uint32_t* flags, size_t batch, he_stream s);
+/* prepareResponse, integrate and SimplePirClient.decrypt (SimplePir+Precompute.swift:281-311, SimplePir+Client.swift:85-95,
+ * 112-121) for `batch` queries: extractEntries of both slabs at the index, ((response - result + (delta >> 1)) & mask) >>
+ * (c - plaintext_bits) wrapping in the word, then coefficientsToBytes(bitsPerCoeff: plaintext_bits) cut to
+ * entry_size_in_bytes.
+ *   entries  DEVICE [batch][entry_size_in_bytes]; all zero for an index at or above entry_count      flags  as above, or NULL */
+int he_simple_pir_decrypt_responses_device(const he_simple_pir_context* ctx, uint32_t word_bits, const void* responses,
+                                           const void* results_without_response, const uint64_t* indices, uint8_t* entries,
+                                           uint32_t* flags, size_t batch, void* workspace, size_t workspace_bytes, he_stream s);
+
 /* PirUtil.expand(ciphertexts:outputCount:using:) (PrivateInformationRetrieval/IndexPir/PirUtil.swift:196-355):
  * oblivious expansion of `ciphertext_count` query ciphertexts [..][2][L][N] (Coeff, top level) into `output_count`
  * ciphertexts, in the reference's output order.  The evaluation key is given as parallel host arrays:

@@ -15,20 +15,14 @@
 #include "api_internal.hpp"
 #include "kernels.hpp"
 #include "simple_pir_batch_plan.hpp"
+#include "simple_pir_context.hpp"
 
 using heamd::as_stream;
 using heamd::invalid_argument;
 using heamd::Scratch;
+using heamd::SimplePirPlan;
 
 namespace {
-
-struct SimplePirPlan {
-    uint32_t plaintext_bits = 0, ciphertext_bits = 0, lattice_dimension = 0, word_bits = 0, element_bytes = 0;
-    size_t entry_count = 0, entry_size_in_bytes = 0;
-    size_t entry_size_in_scalar = 0, entries_per_column = 0, chunks_per_entry = 0, database_columns = 0, column_size = 0,
-           padded_entry_size = 0, a_poly_count = 0;
-    uint64_t modulus = 0;
-};
 
 uint32_t element_bytes_of(uint32_t plaintext_bits) {
     return plaintext_bits <= 8 ? 1 : plaintext_bits <= 16 ? 2 : plaintext_bits <= 32 ? 4 : 8;
@@ -44,10 +38,12 @@ int check_bits(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t word_
     return HE_OK;
 }
 
+}  // namespace
+
 // computingParams (SimplePir+Database.swift:209-243), the padded column size of process (:262-268) and SimplePirContext.init's
 // modulus (SimplePirContext.swift:76-87).  Double.rounded() rounds halves away from zero, as std::round does.
-int simple_pir_plan(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t lattice_dimension, uint32_t word_bits,
-                    size_t entry_count, size_t entry_size_in_bytes, SimplePirPlan& plan) {
+int heamd::simple_pir_plan(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t lattice_dimension, uint32_t word_bits,
+                           size_t entry_count, size_t entry_size_in_bytes, SimplePirPlan& plan) {
     const int status = check_bits(plaintext_bits, ciphertext_bits, word_bits);
     if (status != HE_OK) return status;
     if (lattice_dimension < 2 || (lattice_dimension & (lattice_dimension - 1)) != 0)
@@ -99,13 +95,7 @@ int simple_pir_plan(uint32_t plaintext_bits, uint32_t ciphertext_bits, uint32_t 
     return HE_OK;
 }
 
-}  // namespace
-
-// Opaque handle of include/he_amd.h: the plan and SimplePirContext.extraContext on the device
-struct he_simple_pir_context {
-    SimplePirPlan plan;
-    std::unique_ptr<heamd::PolyContext> ring;
-};
+using heamd::simple_pir_plan;
 
 namespace {
 

@@ -288,6 +288,19 @@ SIGNATURES = [
     ("he_simple_pir_batch_response_plan", ctypes.c_int,
      [c_u32, c_u32, c_u32, c_size, c_size, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32),
       ctypes.POINTER(c_u32), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
+    ("he_simple_pir_client_plan", ctypes.c_int,
+     [c_u32, c_u32, c_u32, c_u32, c_size, c_size, ctypes.c_int, c_size, ctypes.POINTER(c_size), ctypes.POINTER(c_size),
+      ctypes.POINTER(c_size), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u64), ctypes.POINTER(c_size),
+      ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size),
+      ctypes.POINTER(c_size)]),
+    ("he_simple_pir_client_workspace_bytes", c_size, [vp, ctypes.c_int, ctypes.c_int, c_size]),
+    ("he_simple_pir_a_polynomials_device", ctypes.c_int, [vp, c_u32, vp, vp, vp, c_size, vp]),
+    ("he_simple_pir_encrypt_zero_device", ctypes.c_int, [vp, c_u32, ctypes.c_int, vp, vp, vp, vp, c_size, vp, c_size, vp]),
+    ("he_simple_pir_secret_times_hint_device", ctypes.c_int, [vp, c_u32, vp, c_size, vp, c_size, vp, vp, c_size, vp]),
+    ("he_simple_pir_precompute_queries_device", ctypes.c_int,
+     [vp, c_u32, ctypes.c_int, vp, vp, vp, vp, vp, vp, c_size, vp, c_size, vp]),
+    ("he_simple_pir_add_indices_device", ctypes.c_int, [vp, c_u32, vp, vp, vp, c_size, vp]),
+    ("he_simple_pir_decrypt_responses_device", ctypes.c_int, [vp, c_u32, vp, vp, vp, vp, vp, c_size, vp, c_size, vp]),
     ("he_pnns_context_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
     ("he_pnns_context_destroy", None, [vp]),
     ("he_pnns_matrix_shape", ctypes.c_int,
@@ -1882,6 +1895,145 @@ class SimplePirServer32(SimplePirServer):
 
     _word = WORD32
     word_bits = _word.bits
+
+
+SIMPLE_PIR_ERROR_STD_DEVS = {"stdDev32": 0, "stdDev64": 1}  # ErrorStdDev (HE_SIMPLE_PIR_ERROR_*)
+_SIMPLE_PIR_CLIENT_OPS = {"a_polynomials": 0, "encrypt_zero": 1, "secret_times_hint": 2, "precompute": 3, "decrypt_responses": 4}
+
+
+def simple_pir_client_plan(plaintext_bits, ciphertext_bits, lattice_dimension, entry_count, entry_size_in_bytes,
+                           error_std_dev="stdDev32", batch=1, word_bits=64):
+    """he_simple_pir_client_plan: what the SimplePirClient entries do for a shape and a batch -> dict.  Host only."""
+    sizes = {name: c_size(0) for name in (
+        "chunk_size", "query_words", "result_words", "row_block", "hint_product_lds_bytes", "a_polynomials_workspace_bytes",
+        "encrypt_zero_workspace_bytes", "secret_times_hint_workspace_bytes", "precompute_workspace_bytes",
+        "decrypt_responses_workspace_bytes")}
+    stream_bytes, rows_per_pass, fold_terms = c_u32(0), c_u32(0), c_u64(0)
+    ref = ctypes.byref
+    _check(load_library().he_simple_pir_client_plan(
+        int(plaintext_bits), int(ciphertext_bits), int(lattice_dimension), int(word_bits), int(entry_count),
+        int(entry_size_in_bytes), SIMPLE_PIR_ERROR_STD_DEVS.get(error_std_dev, error_std_dev), int(batch),
+        ref(sizes["chunk_size"]), ref(sizes["query_words"]), ref(sizes["result_words"]), ref(stream_bytes), ref(rows_per_pass),
+        ref(fold_terms), ref(sizes["row_block"]), ref(sizes["hint_product_lds_bytes"]),
+        ref(sizes["a_polynomials_workspace_bytes"]), ref(sizes["encrypt_zero_workspace_bytes"]),
+        ref(sizes["secret_times_hint_workspace_bytes"]), ref(sizes["precompute_workspace_bytes"]),
+        ref(sizes["decrypt_responses_workspace_bytes"])))
+    out = {name: v.value for name, v in sizes.items()}
+    out.update(error_stream_bytes=stream_bytes.value, secret_rows_per_pass=rows_per_pass.value, fold_terms=fold_terms.value)
+    return out
+
+
+class SimplePirClient:
+    """SimplePirClient / PrecomputedQueries (PrivateInformationRetrieval/SimplePir/SimplePir+Client.swift,
+    SimplePir+Precompute.swift) on the device, for batches of B independent queries: made from a server's params, hint and
+    seed.  Slabs are torch tensors of words of `word_bits` (int64 / int32 storage); seeds uint8 CUDA tensors [..][32].  Every
+    method allocates its workspace unless one is passed (a uint8 CUDA tensor, 16-byte aligned) and is enqueue-only."""
+
+    def __init__(self, params, hint, seed, word_bits=64, error_std_dev="stdDev32"):
+        import torch
+
+        self._word = _word_of(word_bits)
+        self.word_bits = self._word.bits
+        self.params, self.hint = params, hint
+        self.error_std_dev = SIMPLE_PIR_ERROR_STD_DEVS[error_std_dev]
+        if not torch.is_tensor(seed):
+            seed = torch.from_numpy(np.frombuffer(bytes(seed), dtype=np.uint8).copy()).to(hint.device)
+        self.seed = seed
+        self.h = vp()
+        _check(load_library().he_simple_pir_context_create(
+            params["plaintext_bits"], params["ciphertext_bits"], params["lattice_dimension"], self.word_bits,
+            params["entry_count"], params["entry_size_in_bytes"], ctypes.byref(self.h)))
+        self._a = None
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            load_library().he_simple_pir_context_destroy(self.h)
+            self.h = None
+
+    def plan(self, batch=1):
+        p = self.params
+        return simple_pir_client_plan(p["plaintext_bits"], p["ciphertext_bits"], p["lattice_dimension"], p["entry_count"],
+                                      p["entry_size_in_bytes"], self.error_std_dev, batch, self.word_bits)
+
+    def workspace_bytes(self, operation, count=1):
+        return load_library().he_simple_pir_client_workspace_bytes(self.h, _SIMPLE_PIR_CLIENT_OPS[operation], self.error_std_dev,
+                                                                   int(count))
+
+    def _scratch(self, operation, count, workspace):
+        import torch
+
+        if workspace is None:
+            workspace = torch.empty(max(self.workspace_bytes(operation, count), 16), dtype=torch.uint8, device=self.hint.device)
+        return _workspace(workspace)
+
+    def a_polynomials(self, stream=None, workspace=None):
+        """generateAPolynomials + convertToEvalFormat -> [a_poly_count][N], computed once and kept."""
+        if self._a is None:
+            out = _empty((self.params["a_poly_count"], self.params["lattice_dimension"]), self._word, self.hint.device)
+            _check(load_library().he_simple_pir_a_polynomials_device(
+                self.h, self.word_bits, vp(self.seed.data_ptr()), vp(out.data_ptr()), *self._scratch("a_polynomials", 1, workspace),
+                _stream(stream)))
+            self._a = out
+        return self._a
+
+    def _shape(self, batch, width):
+        return (batch, self.params["chunks_per_entry"], width)
+
+    def encrypt_zero(self, secrets, error_seeds, stream=None, workspace=None):
+        """SimplePirContext.encryptZero: secrets [B][chunks][N] Coeff ternary, error_seeds [B][32] -> queries [B][chunks][D]."""
+        batch = secrets.shape[0]
+        queries = _empty(self._shape(batch, self.params["database_columns"]), self._word, secrets.device)
+        _check(load_library().he_simple_pir_encrypt_zero_device(
+            self.h, self.word_bits, self.error_std_dev, _ptr(self.a_polynomials(stream), self._word), _ptr(secrets, self._word),
+            vp(error_seeds.data_ptr()), vp(queries.data_ptr()), batch, *self._scratch("encrypt_zero", batch, workspace),
+            _stream(stream)))
+        return queries
+
+    def secret_times_hint(self, secrets, hint=None, stream=None, workspace=None):
+        """secretMatrix.multiply(transposing: hint, modulus: p): secrets [R][N] ternary -> [R][column_size]."""
+        hint = self.hint if hint is None else hint
+        rows = secrets.shape[0]
+        results = _empty((rows, hint.shape[0]), self._word, secrets.device)
+        _check(load_library().he_simple_pir_secret_times_hint_device(
+            self.h, self.word_bits, _ptr(secrets, self._word), rows, vp(hint.data_ptr()), hint.shape[0], vp(results.data_ptr()),
+            *self._scratch("secret_times_hint", rows, workspace), _stream(stream)))
+        return results
+
+    def precompute(self, secret_seeds, error_seeds, stream=None, workspace=None):
+        """PrecomputedQueries.WithoutIndices.init for B queries: secret_seeds [B][chunks][32], error_seeds [B][32] ->
+        (queries [B][chunks][D], results_without_response [B][chunks][column_size])."""
+        batch = error_seeds.shape[0]
+        queries = _empty(self._shape(batch, self.params["database_columns"]), self._word, error_seeds.device)
+        results = _empty(self._shape(batch, self.params["column_size"]), self._word, error_seeds.device)
+        _check(load_library().he_simple_pir_precompute_queries_device(
+            self.h, self.word_bits, self.error_std_dev, _ptr(self.a_polynomials(stream), self._word), _ptr(self.hint, self._word),
+            vp(secret_seeds.data_ptr()), vp(error_seeds.data_ptr()), vp(queries.data_ptr()), vp(results.data_ptr()), batch,
+            *self._scratch("precompute", batch, workspace), _stream(stream)))
+        return queries, results
+
+    def add_indices(self, queries, indices, stream=None):
+        """WithoutIndices.add(index:) in place: indices an int64 CUDA tensor [B] -> flags [B] (1: index out of range)."""
+        import torch
+
+        flags = torch.empty(queries.shape[0], dtype=torch.int32, device=queries.device)
+        _check(load_library().he_simple_pir_add_indices_device(
+            self.h, self.word_bits, _ptr(queries, self._word), _ptr(indices, WORD64), vp(flags.data_ptr()), queries.shape[0],
+            _stream(stream)))
+        return flags
+
+    def decrypt(self, responses, results, indices, stream=None, workspace=None):
+        """prepareResponse + integrate + decrypt: responses, results [B][chunks][column_size] -> (entries uint8
+        [B][entry_size_in_bytes], flags [B])."""
+        import torch
+
+        batch = responses.shape[0]
+        entries = torch.empty((batch, self.params["entry_size_in_bytes"]), dtype=torch.uint8, device=responses.device)
+        flags = torch.empty(batch, dtype=torch.int32, device=responses.device)
+        _check(load_library().he_simple_pir_decrypt_responses_device(
+            self.h, self.word_bits, _ptr(responses, self._word), _ptr(results, self._word), _ptr(indices, WORD64),
+            vp(entries.data_ptr()), vp(flags.data_ptr()), batch, *self._scratch("decrypt_responses", batch, workspace),
+            _stream(stream)))
+        return entries, flags
 
 
 PNNS_PACKINGS = {"denseColumn": 0, "denseRow": 1, "diagonal": 2}  # MatrixPacking's case order (HE_PNNS_PACKING_*)
