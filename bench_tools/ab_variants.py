@@ -11,7 +11,8 @@ and links them with the production objects into lib/variants/libhe_amd_NAME.so. 
   python bench_tools/ab_variants.py build NAME [NAME ...]     (no GPU needed; `all` = every module in variants/)
   python bench_tools/ab_variants.py run [--what ntt|degrees|large|c3|small|pir|c4|mid|script:PATH] [--rounds N] [NAME ...]     (on the GPU box)
       times the production library and each variant, one process per library (HEAMD_LIBRARY), interleaved over rounds
-      so that clock drift shows up as spread
+      so that clock drift shows up as spread; AB_LAUNCHES in the environment: timed launches per direction of the
+      ntt / degrees / large timers (default 50 -- a window of 25 ms at the headline shape; 1000 makes it half a second)
 """
 import concurrent.futures
 import glob
@@ -31,8 +32,9 @@ SPECS = os.path.join(ROOT, "bench_tools", "variants")
 NTT_TIMER = r'''
 import sys
 sys.path.insert(0, %r)
-import torch, heamd
+import os, torch, heamd
 heamd.set_scratch_cache()
+launches = int(os.environ.get("AB_LAUNCHES", "50"))  # timed launches per direction (and 2/5 as many warm-ups before them)
 out = []
 for degree, count, batch in %%s:
     moduli = heamd.generate_primes([55] * count, False, degree)
@@ -41,14 +43,14 @@ for degree, count, batch in %%s:
     x = torch.randint(0, 1 << 62, (batch, count, degree), dtype=torch.int64, device="cuda") %%%% bound
     for inverse in (False, True):
         f = ctx.inverse_ntt_ if inverse else ctx.forward_ntt_
-        for _ in range(20):
+        for _ in range(launches * 2 // 5):
             f(x)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize(); a.record()
-        for _ in range(50):
+        for _ in range(launches):
             f(x)
         b.record(); b.synchronize()
-        out.append("N=%%%%d %%%%s %%%%.4f" %%%% (degree, "inv" if inverse else "fwd", a.elapsed_time(b) / 50))
+        out.append("N=%%%%d %%%%s %%%%.4f" %%%% (degree, "inv" if inverse else "fwd", a.elapsed_time(b) / launches))
 print("  ".join(out))
 ''' % PKG
 SHAPES = {"ntt": [(8192, 4, 4096)], "degrees": [(4096, 2, 8192), (8192, 4, 4096), (16384, 4, 1024)],

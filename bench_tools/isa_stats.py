@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "swift-homomorphic-encryption_amd", "csrc")
 
 SLOTS = {
-    "v_mad_u64_u32": 2, "v_mul_lo_u32": 2, "v_mul_hi_u32": 4, "v_lshl_add_u64": 2, "v_lshlrev_b64": 2,
+    "v_mad_u64_u32": 2, "v_mad_i64_i32": 2, "v_mul_lo_u32": 2, "v_mul_hi_u32": 4, "v_lshl_add_u64": 2, "v_lshlrev_b64": 2,
     "v_lshrrev_b64": 2, "v_cmp_gt_u64_e32": 2, "v_cmp_lt_u64_e32": 2, "v_cmp_ge_u64_e32": 2, "v_cmp_le_u64_e32": 2,
     "v_fma_f64": 2, "v_mul_f64": 2, "v_add_f64": 2,
 }

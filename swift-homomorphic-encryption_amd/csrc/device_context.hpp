@@ -71,6 +71,10 @@ struct DeviceContext {
     const uint64_t* forward_split_factors_lanes;
     const uint64_t* inverse_split_factors_lanes;
     const uint64_t* inverse_split_factors_lanes_top;
+    // N = 8192 only (nullptr elsewhere): the lane-major pairs of the plain-slab pair's partitions -- forward `_lanes`, inverse
+    // `_lanes_top` -- with w 2^32 mod p in signed limbs, for the signed shift-folded products (ntt_common.hpp kModeFoldSigned)
+    const U64x2* forward_split_pairs_signed_lanes;
+    const U64x2* inverse_split_pairs_signed_lanes_top;
     uint32_t degree;
     uint32_t log_degree;
     uint32_t moduli_count;         // active moduli (a prefix of the context's list)

@@ -376,6 +376,7 @@ struct FoldConstants {
     uint32_t shift, mask; // V >> (b + 2) = U >> shift for U = V >> 32; mask = 2^shift - 1
     uint32_t high_bias;   // plus form: the high word of 2^60
     uint64_t addend;      // plus form: e
+    uint64_t signed_bias; // minus form: K of fold_mul_signed, the multiple of p just above 2^61
 };
 template <bool PLUS>
 __device__ __forceinline__ FoldConstants fold_constants(uint64_t p) {
@@ -392,6 +393,8 @@ __device__ __forceinline__ FoldConstants fold_constants(uint64_t p) {
         c.shift = static_cast<uint32_t>(bits - 30);
         c.high_bias = 0;
         c.addend = 0;
+        // 2^61 = 2^(61-b) p + 2^(61-b) d with 0 < 2^(61-b) d < 2^29: ceil((2^61 + 1) / p) = 2^(61-b) + 1, no division
+        c.signed_bias = bits <= 55 ? (p << (61 - bits)) + p : 0;
     }
     c.mask = (1u << c.shift) - 1u;
     return c;
@@ -445,6 +448,62 @@ __device__ __forceinline__ uint64_t fold_mul(uint64_t y, uint64_t w, uint64_t wt
     if constexpr (PLUS) kept = kept + fc.high_bias - high;
     uint64_t r = pack64(lo32(t), kept), carry3;
     asm("v_mad_u64_u32 %0, %1, %2, %3, %0" : "+v"(r), "=&s"(carry3) : "v"(high), "s"(fc.multiplier));
+    return r;
+}
+
+// The minus-form product for a SIGNED multiplicand y = b0 + b1 2^32 in [-2^62, 2^62) (b0 = the low word, unsigned; b1 = the
+// high word read as signed, in [-2^30, 2^30)), p = 2^b - d with 41 <= b <= 55 and d < 2^(b-32): a butterfly's x - r or x - y
+// as it leaves the subtraction, without the multiple of p that would keep it non-negative (one 64-bit addition per
+// butterfly).  The constant's second word comes in signed-limb form like split_mul_signed's: wt = t0s + t1' 2^32 with t0s the
+// low word read as signed and t1' = hi32(wt) + (lo32(wt) >> 31) <= 2^(b-32).  The same five multiply-adds as fold_mul, the ones
+// on b1 (and the fold's own) signed:
+//     a = b1 t0s + K          K = p ceil((2^61 + 1) / p) = (p << (61 - b)) + p: 0 mod p, in [2^61 + 1, 2^61 + p), and
+//                             |b1 t0s| <= 2^61, so a lies in (0, 2^63) whatever the signs
+//     t = b0 w0 + a           below 2^64 + 2^63: the low column with its one carry bit, as in fold_mul
+//     u = b0 w1 + (t >> 32)   in [0, 2^b + 2^33)
+//     u = b1 t1' + u          two's complement, in [-2^(b-2), 2^b + 2^(b-2) + 2^33): |u| < 2^56
+// so that V = lo32(t) + u 2^32 = b0 w + b1 wt + K = y w (mod p) exactly, and the fold at F = 2^(b+2) = 4d (mod p):
+//     high = u >> (b - 30)    arithmetic; a signed word in [-2^28, 2^30 + 2^28 + 2^22]
+//     r = (V mod F) + high 4d
+// r = y w (mod p),  -2^(b-2) < -2^30 d <= r < 2^(b+2) + (2^30 + 2^28 + 2^22) 4d < 5.27 2^b: inside (-p, 6p) for every
+// y in range (tests/test_fold_signed_bounds.py walks the sequence limb by limb).  `bias` = K (FoldConstants::signed_bias):
+// the one scalar operand of its instruction beside a gathered constant; UNIFORM: the constant's words are wave-uniform and
+// take the scalar operand, K then comes in a VGPR pair.
+template <bool UNIFORM>
+__device__ __forceinline__ uint64_t fold_mul_signed(uint64_t y, uint64_t w, uint64_t wt_signed_limbs, const FoldConstants& fc,
+                                                   uint64_t bias) {
+    const uint32_t b0 = lo32(y), b1 = hi32(y), w0 = lo32(w), w1 = hi32(w);
+    const uint32_t t0 = lo32(wt_signed_limbs), t1 = hi32(wt_signed_limbs);
+    uint64_t a, t, carry0, carry;
+    if constexpr (UNIFORM) {
+        asm("v_mad_i64_i32 %0, %2, %5, %7, %8\n\t"
+            "v_mad_u64_u32 %1, %3, %4, %6, %0"
+            : "=&v"(a), "=&v"(t), "=&s"(carry0), "=&s"(carry)
+            : "v"(b0), "v"(b1), "s"(w0), "s"(t0), "v"(bias));
+    } else {
+        asm("v_mad_i64_i32 %0, %2, %5, %7, %8\n\t"
+            "v_mad_u64_u32 %1, %3, %4, %6, %0"
+            : "=&v"(a), "=&v"(t), "=&s"(carry0), "=&s"(carry)
+            : "v"(b0), "v"(b1), "v"(w0), "v"(t0), "s"(bias));
+    }
+    uint32_t carry_bit;
+    asm("v_addc_co_u32 %0, %1, 0, 0, %1" : "=v"(carry_bit), "+s"(carry));
+    uint64_t u = pack64(hi32(t), carry_bit), carry2;
+    if constexpr (UNIFORM) {
+        asm("v_mad_u64_u32 %0, %1, %2, %4, %0\n\t"
+            "v_mad_i64_i32 %0, %1, %3, %5, %0"
+            : "+v"(u), "=&s"(carry2)
+            : "v"(b0), "v"(b1), "s"(w1), "s"(t1));
+    } else {
+        asm("v_mad_u64_u32 %0, %1, %2, %4, %0\n\t"
+            "v_mad_i64_i32 %0, %1, %3, %5, %0"
+            : "+v"(u), "=&s"(carry2)
+            : "v"(b0), "v"(b1), "v"(w1), "v"(t1));
+    }
+    const uint32_t high = __builtin_amdgcn_alignbit(hi32(u), lo32(u), fc.shift);
+    const uint32_t kept = lo32(u) & fc.mask;
+    uint64_t r = pack64(lo32(t), kept), carry3;
+    asm("v_mad_i64_i32 %0, %1, %2, %3, %0" : "+v"(r), "=&s"(carry3) : "v"(high), "s"(fc.multiplier));
     return r;
 }
 

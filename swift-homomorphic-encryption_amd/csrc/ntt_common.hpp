@@ -142,13 +142,27 @@ __device__ __forceinline__ uint64_t load_twiddle_word(const uint64_t* entry) {
 //                    product folds back by a shift (device_math.hpp fold_mul: 5 multiply-adds, products in [0, 6p), no
 //                    factor table), values in [0, 14p) with one conditional subtract per butterfly like the [0, 8p)
 //                    schedule it replaces where the moduli allow it (DeviceContext::fold_minus_mask / fold_plus_mask).
+//   kModeFoldSigned  kModeFoldLazy's products and passes with SIGNED words (device_math.hpp fold_mul_signed: the product of a
+//                    signed word, in (-p, 6p)): the forward butterfly is (x + r, x - r), the inverse one (x + y, (x - y) w) --
+//                    no multiple of p added to keep the difference non-negative, one 64-bit addition less per butterfly.
+//                    Forward words grow by less than 6p in magnitude per stage (|word| < (1 + 6 log2 N) p = 79 p < 2^62 at
+//                    N = 8192) and are brought to [0, 2^10 p) once, in front of the final reducer (canonicalize_all).  The
+//                    inverse multiplies differences of words below 2^6 p in magnitude (|x - y| < 2^7 p < 2^62 for p < 2^55),
+//                    so its sums come back under 2p every four stages instead of once (kInverseCapLog = 6), each after
+//                    2^(s+1) p is added to make it non-negative; the last stage adds 2^7 p to its sum and its difference in
+//                    front of the exact division by N and the N^-1 psi^(-N/2) product.  Tables: the twiddles' second words in
+//                    signed limbs, lane-major (DeviceContext::forward_split_pairs_signed_lanes /
+//                    inverse_split_pairs_signed_lanes_top).  The plain-slab pair at N = 8192 (ntt_kernels.hip
+//                    kFoldSignedForward / kFoldSignedInverse).
 constexpr int kModeExact = 0, kModeApprox = 1, kModeSplit = 3, kModeFoldLazy = 4, kModeFoldMinus = 5, kModeFoldPlus = 6,
-              kModeSplitSigned = 7;
-constexpr bool is_split(int mode) { return mode == kModeSplit || mode == kModeFoldLazy || mode == kModeSplitSigned; }
+              kModeSplitSigned = 7, kModeFoldSigned = 8;
+// the shift-folded products on the lazy schedule, words unsigned or signed
+constexpr bool is_fold_lazy(int mode) { return mode == kModeFoldLazy || mode == kModeFoldSigned; }
+constexpr bool is_split(int mode) { return mode == kModeSplit || is_fold_lazy(mode) || mode == kModeSplitSigned; }
 constexpr bool is_fold(int mode) { return mode == kModeFoldMinus || mode == kModeFoldPlus; }
 template <int MODE>
 __device__ __forceinline__ FoldConstants mode_fold_constants(uint64_t p) {
-    if constexpr (is_fold(MODE) || MODE == kModeFoldLazy) return fold_constants<MODE == kModeFoldPlus>(p);
+    if constexpr (is_fold(MODE) || is_fold_lazy(MODE)) return fold_constants<MODE == kModeFoldPlus>(p);
     else return FoldConstants{};
 }
 
@@ -196,7 +210,10 @@ struct Twiddles {
             factors = (inverse ? ctx.inverse_split_factors : ctx.forward_split_factors) + at;
             // (lane_major is a constant at every call site: 1 = the pass partition with the partial pass on the low bits,
             // 2 = on the top bit -- the plain-slab inverse at N = 8192)
-            if (lane_major == 1) {
+            if constexpr (MODE == kModeFoldSigned) {
+                // signed-limb second words; only the lane-major copies the N = 8192 pair reads exist
+                pairs = (inverse ? ctx.inverse_split_pairs_signed_lanes_top : ctx.forward_split_pairs_signed_lanes) + at;
+            } else if (lane_major == 1) {
                 pairs = (inverse ? (MODE == kModeSplitSigned ? ctx.inverse_split_pairs_signed_lanes : ctx.inverse_split_pairs_lanes)
                                  : ctx.forward_split_pairs_lanes) + at;
                 factors = (inverse ? ctx.inverse_split_factors_lanes : ctx.forward_split_factors_lanes) + at;
@@ -212,6 +229,13 @@ struct Twiddles {
         }
     }
 };
+
+// a wave-uniform 64-bit value in vector registers, made where it is written (not hoisted, not merged)
+__device__ __forceinline__ uint64_t vector_copy(uint64_t uniform_value) {
+    uint64_t out;
+    asm volatile("v_mov_b64 %0, %1" : "=v"(out) : "s"(uniform_value));
+    return out;
+}
 
 // one twiddle in registers
 struct TwiddleWords {
@@ -232,7 +256,7 @@ __device__ __forceinline__ TwiddleWords fetch_twiddle(const Twiddles<MODE>& tw, 
         t.w = pack64(pair.x, pair.y);
         t.second = pack64(pair.z, pair.w);
         t.factors = pack64(factors.x, factors.y);
-    } else if constexpr (is_fold(MODE) || MODE == kModeFoldLazy) {
+    } else if constexpr (is_fold(MODE) || is_fold_lazy(MODE)) {
         const Dwordx4 pair = __builtin_amdgcn_raw_buffer_load_b128(tw.pair_resource, lane_index << 4, fixed_index << 4, 0);
         t.w = pack64(pair.x, pair.y);
         t.second = pack64(pair.z, pair.w);
@@ -252,7 +276,7 @@ __device__ __forceinline__ TwiddleWords fetch_twiddle(const Twiddles<MODE>& tw, 
 // forward 0 / -0.7 % at N = 8192 for the second and the third (profiles/r05ad_fold_lazy_butterflies_ab.txt,
 // r05ap_twiddles_in_flight_ab.txt).
 template <int MODE>
-constexpr int kTwiddlesAhead = MODE == kModeFoldLazy ? 3 : 1;
+constexpr int kTwiddlesAhead = is_fold_lazy(MODE) ? 3 : 1;
 // ... and of the row groups of three and four (behz_kernels.hip: one workgroup per CU at 128 registers per lane -- there are
 // registers for deeper requests, and with 4 wavefronts per SIMD less else to hide a gather's latency)
 constexpr int kWideGroupTwiddlesAhead = 1;
@@ -267,7 +291,9 @@ struct Lazy {
     // in forward_butterfly / inverse_butterfly; the two constants below are not used for them)
     static constexpr int kProductLog = MODE == kModeExact ? 1 : MODE == kModeApprox ? 2 : 3;
     // cap on stage inputs of the inverse transform, as a shift of p (split: sums of two stay below 2^9 p < 2^64)
-    static constexpr int kInverseCapLog = MODE == kModeExact ? 1 : MODE == kModeApprox ? 2 : is_fold(MODE) ? 3 : 8;
+    // (kModeFoldSigned: differences of words below 2^6 p in magnitude stay inside [-2^62, 2^62) for p < 2^55)
+    static constexpr int kInverseCapLog =
+        MODE == kModeExact ? 1 : MODE == kModeApprox ? 2 : is_fold(MODE) ? 3 : MODE == kModeFoldSigned ? 6 : 8;
     // `reduction` = 2^64 - p (exact / approx) or 2^64 - 2p (split)
     template <bool UNIFORM = false>
     __device__ static __forceinline__ uint64_t mul(uint64_t x, const TwiddleWords& w, uint64_t reduction) {
@@ -426,7 +452,7 @@ __device__ __forceinline__ TwiddleWords forward_twiddle(const Twiddles<MODE>& tw
 template <int MODE>
 __device__ __forceinline__ void forward_butterfly(uint64_t& first, uint64_t& second, const TwiddleWords& w, bool uniform,
                                                   uint64_t neg_p, uint64_t half_bound, bool fold,
-                                                  const FoldConstants& fc = FoldConstants{}) {
+                                                  const FoldConstants& fc = FoldConstants{}, uint64_t bias = 0) {
     uint64_t x = first;
     const uint64_t y = second;
     if constexpr (is_fold(MODE)) {
@@ -444,6 +470,13 @@ __device__ __forceinline__ void forward_butterfly(uint64_t& first, uint64_t& sec
         const uint64_t r = uniform ? fold_mul<true, false>(y, w.w, w.second, fc) : fold_mul<false, false>(y, w.w, w.second, fc);
         first = x + r;
         second = x + half_bound - r;
+        return;
+    }
+    if constexpr (MODE == kModeFoldSigned) {
+        // signed words: the product of the signed y in (-p, 6p), nothing added to the difference (`bias`: fold_mul_signed's K)
+        const uint64_t r = uniform ? fold_mul_signed<true>(y, w.w, w.second, fc, bias) : fold_mul_signed<false>(y, w.w, w.second, fc, bias);
+        first = x + r;
+        second = x - r;
         return;
     }
     if (!is_split(MODE) && fold) x = csub_uniform(x, half_bound);
@@ -498,12 +531,18 @@ __device__ __forceinline__ void forward_pass(uint64_t (&v)[ROWS][1 << LOGE], uin
         if (k + AHEAD < COUNT)
             pending[AHEAD - 1] = forward_twiddle<LOGN, LOGE, LO, W, MODE, UNIFORM_TWIDDLES>(tw, lane_elements, k + AHEAD);
         if (k + 1 < COUNT) __builtin_amdgcn_sched_barrier(0);  // the request stays ahead of the butterflies below
+        // kModeFoldSigned: the signed product's K -- a scalar operand beside gathered twiddles, a vector copy made here, once
+        // per twiddle, beside wave-uniform ones (as inverse_pass does for the limb-wise signed product)
+        uint64_t bias = fc.signed_bias;
+        if constexpr (MODE == kModeFoldSigned) {
+            if (uniform) bias = vector_copy(bias);
+        }
 #pragma unroll
         for (int row = 0; row < ROWS; ++row) {
 #pragma unroll
             for (int o = 0; o < stride; ++o)
                 forward_butterfly<MODE>(v[row][base + o], v[row][base + o + stride], w, uniform, neg_p, half_bound,
-                                        !(first_stage_canonical && j == 0), fc);
+                                        !(first_stage_canonical && j == 0), fc, bias);
         }
         if (k + 1 < COUNT) __builtin_amdgcn_sched_barrier(0);
     }
@@ -556,12 +595,6 @@ __device__ __forceinline__ TwiddleWords inverse_twiddle(const Twiddles<MODE>& tw
 
 // beta + 2^31 p (mod 2^64) with beta = p: what split_mul_signed starts its 2^0 column at
 __device__ __forceinline__ uint64_t split_signed_bias(uint64_t p) { return p + (p << 31); }
-// a wave-uniform 64-bit value in vector registers, made where it is written (not hoisted, not merged)
-__device__ __forceinline__ uint64_t vector_copy(uint64_t uniform_value) {
-    uint64_t out;
-    asm volatile("v_mov_b64 %0, %1" : "=v"(out) : "s"(uniform_value));
-    return out;
-}
 
 // ---- inverse pass over element bits [LO, LO+W): stages run from the low bit up; the very last stage of the
 // transform (bit LOGN-1) folds in N^-1 and N^-1 psi^(-N/2) and produces canonical words --------------------------
@@ -586,6 +619,15 @@ __device__ __forceinline__ void inverse_butterfly(uint64_t& first, uint64_t& sec
         return;
     }
     uint64_t sum = x + y;
+    if constexpr (MODE == kModeFoldSigned) {
+        // signed words below `bound` in magnitude: x - y goes to the product as it is (|x - y| < 2 bound <= 2^62, `bias`:
+        // fold_mul_signed's K) and comes back in (-p, 6p).  `fold`: the sum, in (-2 bound, 2 bound), plus 2 bound is
+        // non-negative and below 4 bound <= 2^8 p, which the reducer takes; the sum is then in [0, 2p).
+        second = uniform ? fold_mul_signed<true>(x - y, w.w, w.second, fc, bias) : fold_mul_signed<false>(x - y, w.w, w.second, fc, bias);
+        if (fold) sum = LazyReducer(p).lazy(sum + (bound << 1));
+        first = sum;
+        return;
+    }
     if constexpr (MODE == kModeSplitSigned) {
         // x - y goes to the product as a signed word (device_math.hpp split_mul_signed: the bound that would keep it
         // non-negative is one 64-bit addition per butterfly; inputs are below 2^63, so the difference cannot wrap); the
@@ -657,8 +699,8 @@ __device__ __forceinline__ void inverse_pass(uint64_t (&v)[ROWS][1 << LOGE], uin
         // split mode: the signed product's bias (device_math.hpp split_mul_signed) -- a scalar operand beside gathered
         // twiddles; beside wave-uniform ones (their words take the instruction's one scalar operand) a vector copy made
         // here, once per twiddle, so that it is not carried through the gathered stages
-        uint64_t bias = split_signed_bias(p);
-        if constexpr (MODE == kModeSplitSigned) {
+        uint64_t bias = MODE == kModeFoldSigned ? fc.signed_bias : split_signed_bias(p);
+        if constexpr (MODE == kModeSplitSigned || MODE == kModeFoldSigned) {
             if (uniform && !last_stage) bias = vector_copy(bias);
         }
 #pragma unroll
@@ -672,8 +714,12 @@ __device__ __forceinline__ void inverse_pass(uint64_t (&v)[ROWS][1 << LOGE], uin
                 }
                 const uint64_t x = v[row][base + o];
                 const uint64_t y = v[row][base + o + stride];
-                const uint64_t sum = x + y;
-                const uint64_t diff = x + bound - y;
+                // (kModeFoldSigned: signed words below `bound` in magnitude; 2 bound = 2^7 p brings the sum and the difference
+                // to (0, 2^8 p), where the division by N and the last product take them as the unsigned schedule's)
+                static_assert(MODE != kModeFoldSigned || !SCALED, "the signed schedule ends in the exact division by N");
+                const uint64_t last_bound = MODE == kModeFoldSigned ? bound << 1 : bound;
+                const uint64_t sum = MODE == kModeFoldSigned ? x + last_bound + y : x + y;
+                const uint64_t diff = x + last_bound - y;
                 {
                     if constexpr (is_split(MODE)) {
                         const LazyReducer reduce(p);
@@ -892,8 +938,11 @@ __device__ __forceinline__ void canonicalize_all(uint64_t (&v)[ROWS][N], uint64_
     for (int row = 0; row < ROWS; ++row) {
         if constexpr (is_split(MODE)) {
             const LazyReducer reduce(p);
+            // kModeFoldSigned: forward words are signed, below (1 + 6 log2 N) p < 2^7 p in magnitude; 2^7 p makes them
+            // non-negative and leaves them below 2^8 p
+            const uint64_t lift = MODE == kModeFoldSigned ? p << 7 : 0;
 #pragma unroll
-            for (int r = 0; r < N; ++r) v[row][r] = reduce(v[row][r]);
+            for (int r = 0; r < N; ++r) v[row][r] = reduce(v[row][r] + lift);
         } else {
 #pragma unroll
             for (int r = 0; r < N; ++r) v[row][r] = canonicalize<MODE>(v[row][r], p);

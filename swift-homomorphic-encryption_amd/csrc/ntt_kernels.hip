@@ -268,7 +268,7 @@ struct InverseSource {
 // (4 registers per twiddle, 62 of its 64 in use) takes three: -2.9 % at N = 8192 (two: -2.0 %; four spill: +7.7 %;
 // profiles/r05ao_inverse_head_twiddles_ab.txt) -- with no gathers at all the kernel would be 12 % faster (r05an).
 template <int LOGN, int LOGE, int MODE, int SOURCE, int ROWS>
-constexpr int kInverseHeadTwiddles = (MODE == kModeFoldLazy && SOURCE == 0) ? 3 : 1;
+constexpr int kInverseHeadTwiddles = (is_fold_lazy(MODE) && SOURCE == 0) ? 3 : 1;
 
 template <int LOGN, int LOGT, int MODE, int SOURCE = kInverseFromSlab, int ROWS = 1>
 __global__ void __launch_bounds__(1 << LOGT, min_waves_per_simd(LOGN - LOGT, ROWS))
@@ -1119,6 +1119,15 @@ constexpr bool kFoldLazyForward = (LOGN == 12 && LOGT == 9) || (LOGN == 13 && LO
 template <int LOGN, int LOGT, int SOURCE>
 constexpr bool kFoldLazyInverse = (LOGN == 12 && LOGT == 9) || (LOGN == 13 && LOGT == 10);
 constexpr bool kFoldLazyInterleaved = true;
+// Where the signed form of those products (ntt_common.hpp kModeFoldSigned: one 64-bit addition less per butterfly) replaces them:
+// the plain-slab pair at N = 8192, each direction on its own measurement
+constexpr bool kFoldSignedForward = true, kFoldSignedInverse = true;
+template <int LOGN, int LOGT, int SPREAD>
+constexpr int kFoldLazyForwardMode =
+    (kFoldSignedForward && LOGN == 13 && LOGT == 10 && SPREAD == kSourceSlab) ? kModeFoldSigned : kModeFoldLazy;
+template <int LOGN, int LOGT, int SOURCE>
+constexpr int kFoldLazyInverseMode =
+    (kFoldSignedInverse && LOGN == 13 && LOGT == 10 && SOURCE == kInverseFromSlab) ? kModeFoldSigned : kModeFoldLazy;
 // ... and the fold butterflies of the plus form (ntt_common.hpp kModeFoldPlus) for the BEHZ primes' rows of N = 16384 / 32768: the
 // Bsk bands of ct x ct ran on the [0, 8p) butterflies there (0.38 / 0.27 of 8 TB/s forward / inverse at N = 16384 against the Q
 // band's 0.54 / 0.35: profiles/r06q_fold_plus_interleaved.txt)
@@ -1263,7 +1272,14 @@ hipError_t launch_forward_kernel(int mode, uint64_t* slab, const DeviceContext& 
                                         : ntt_forward_tiled<LOGN, LOGT, kModeExact, SPREAD, ROWS>;
     if constexpr (kFoldLazyForward<LOGN, LOGT>) {
         // every modulus of the launch is just below a power of two: products folded by a shift, no quotient, no factors
-        if (mode == kModeSplit && fold_lazy_band(ctx, map)) kernel = ntt_forward_tiled<LOGN, LOGT, kModeFoldLazy, SPREAD, ROWS>;
+        if (mode == kModeSplit && fold_lazy_band(ctx, map)) {
+            kernel = ntt_forward_tiled<LOGN, LOGT, kModeFoldLazy, SPREAD, ROWS>;
+            if constexpr (kFoldLazyForwardMode<LOGN, LOGT, SPREAD> == kModeFoldSigned) {
+                // the signed form reads its own tables (PolyContext::upload builds them at N = 8192); an image without them
+                // keeps the unsigned kernel
+                if (ctx.forward_split_pairs_signed_lanes != nullptr) kernel = ntt_forward_tiled<LOGN, LOGT, kModeFoldSigned, SPREAD, ROWS>;
+            }
+        }
     }
     if constexpr (kFoldShape<LOGN, LOGT> && (SPREAD == kSourceSlab || SPREAD == kSourceSpread)) {
         if (mode == kModeApprox && ctx.forward_split_pairs != nullptr) {
@@ -1324,7 +1340,12 @@ hipError_t launch_inverse_kernel(int mode, uint64_t* slab, const DeviceContext& 
                   : mode == kModeApprox ? ntt_inverse_tiled<LOGN, LOGT, kModeApprox, SOURCE, ROWS>
                                         : ntt_inverse_tiled<LOGN, LOGT, kModeExact, SOURCE, ROWS>;
     if constexpr (kFoldLazyInverse<LOGN, LOGT, SOURCE>) {
-        if (mode == kModeSplit && fold_lazy_band(ctx, map)) kernel = ntt_inverse_tiled<LOGN, LOGT, kModeFoldLazy, SOURCE, ROWS>;
+        if (mode == kModeSplit && fold_lazy_band(ctx, map)) {
+            kernel = ntt_inverse_tiled<LOGN, LOGT, kModeFoldLazy, SOURCE, ROWS>;
+            if constexpr (kFoldLazyInverseMode<LOGN, LOGT, SOURCE> == kModeFoldSigned) {
+                if (ctx.inverse_split_pairs_signed_lanes_top != nullptr) kernel = ntt_inverse_tiled<LOGN, LOGT, kModeFoldSigned, SOURCE, ROWS>;
+            }
+        }
     }
     if constexpr (kFoldShape<LOGN, LOGT>) {
         if (mode == kModeApprox && ctx.forward_split_pairs != nullptr) {

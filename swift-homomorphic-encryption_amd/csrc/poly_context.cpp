@@ -185,7 +185,11 @@ int PolyContext::upload() {
     // exactly as an N = 8192 transform indexes its own
     const bool sub_rows = log_degree_ == 14 || log_degree_ == 15;
     const bool lane_major = log_degree_ == 12 || log_degree_ == 13 || sub_rows;
-    const size_t total = bytes_moduli + (lane_major ? 9 : 5) * bytes_twiddles + bytes_inverse_q_last + (lane_major ? 5 : 2) * bytes_factors;
+    // N = 8192: two more lane-major pair tables, signed limbs, for the plain-slab pair on the signed shift-folded products
+    // (ntt_common.hpp kModeFoldSigned): 128 KiB per modulus each
+    const bool signed_fold = log_degree_ == 13;
+    const size_t total = bytes_moduli + ((lane_major ? 9 : 5) + (signed_fold ? 2 : 0)) * bytes_twiddles + bytes_inverse_q_last +
+                         (lane_major ? 5 : 2) * bytes_factors;
     HEAMD_HIP_TRY(hipMalloc(&device_block_, total));
     char* base = static_cast<char*>(device_block_);
     HEAMD_HIP_TRY(hipMemcpy(base, host_moduli_.data(), count * sizeof(DeviceModulus), hipMemcpyHostToDevice));
@@ -201,9 +205,11 @@ int PolyContext::upload() {
     char* forward_factors = inverse_pairs + bytes_twiddles;
     char* inverse_factors = forward_factors + bytes_factors;
     char* inverse_pairs_signed = inverse_factors + bytes_factors;
-    // lane-major copies: pairs forward | inverse | inverse signed | inverse, top partition; factors forward | inverse | inverse, top
+    // lane-major copies: pairs forward | inverse | inverse signed | inverse, top partition; factors forward | inverse | inverse, top;
+    // then (N = 8192) pairs forward signed | inverse signed, top partition
     char* lanes_pairs = inverse_pairs_signed + bytes_twiddles;
     char* lanes_factors = lanes_pairs + 4 * bytes_twiddles;
+    char* lanes_pairs_signed_fold = lanes_factors + 3 * bytes_factors;
     {
         // Every stage's block lane-major (ntt_common.hpp Twiddles::lanes): the stage on element bit b lies in a pass whose highest
         // bit is top(b); its lanes hold 2^g twiddles each, g = top(b) - b, and entry o of its block moves to
@@ -254,6 +260,13 @@ int PolyContext::upload() {
                                         hipMemcpyHostToDevice));
                 HEAMD_HIP_TRY(hipMemcpy(lanes_factors + direction * bytes_factors, moved_factors.data(), count * n * sizeof(u64),
                                         hipMemcpyHostToDevice));
+                if (direction == 0 && signed_fold) {
+                    // the forward pairs in signed limbs (as the inverse ones below), lane-major
+                    std::vector<U64x2> signed_pairs = pairs;
+                    for (U64x2& pair : signed_pairs) pair.y += (pair.y & 0x80000000ull) << 1;
+                    lane_major_copy(false, false, signed_pairs, moved_pairs);
+                    HEAMD_HIP_TRY(hipMemcpy(lanes_pairs_signed_fold, moved_pairs.data(), count * n * sizeof(U64x2), hipMemcpyHostToDevice));
+                }
                 if (direction == 1 && !sub_rows) {
                     lane_major_copy(true, true, pairs, moved_pairs);
                     lane_major_copy(true, true, factors, moved_factors);
@@ -274,6 +287,11 @@ int PolyContext::upload() {
             HEAMD_HIP_TRY(hipMemcpy(lanes_pairs + 2 * bytes_twiddles, moved_pairs.data(), count * n * sizeof(U64x2),
                                     hipMemcpyHostToDevice));
         }
+        if (signed_fold) {
+            lane_major_copy(true, true, pairs, moved_pairs);
+            HEAMD_HIP_TRY(hipMemcpy(lanes_pairs_signed_fold + bytes_twiddles, moved_pairs.data(), count * n * sizeof(U64x2),
+                                    hipMemcpyHostToDevice));
+        }
     }
     dev_.forward_split_pairs = reinterpret_cast<const U64x2*>(forward_pairs);
     dev_.inverse_split_pairs = reinterpret_cast<const U64x2*>(inverse_pairs);
@@ -284,6 +302,9 @@ int PolyContext::upload() {
     dev_.inverse_split_pairs_lanes = pairs_at(1);
     dev_.inverse_split_pairs_signed_lanes = pairs_at(2);
     dev_.inverse_split_pairs_lanes_top = pairs_at(3);
+    dev_.forward_split_pairs_signed_lanes = signed_fold ? reinterpret_cast<const U64x2*>(lanes_pairs_signed_fold) : nullptr;
+    dev_.inverse_split_pairs_signed_lanes_top =
+        signed_fold ? reinterpret_cast<const U64x2*>(lanes_pairs_signed_fold + bytes_twiddles) : nullptr;
     dev_.forward_split_factors_lanes = factors_at(0);
     dev_.inverse_split_factors_lanes = factors_at(1);
     dev_.inverse_split_factors_lanes_top = factors_at(2);
