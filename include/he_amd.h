@@ -1048,6 +1048,109 @@ int he_keyword_pir_process_database_device(const he_bfv_context* ctx, const he_k
                                            const uint32_t* dimensions, uint32_t dimension_count, size_t entry_size_in_bytes,
                                            void* database, uint8_t* present, he_stream s);
 
+/* ---- the keyword PIR client (PrivateInformationRetrieval/KeywordPir/KeywordPirProtocol.swift:279-392): queries from keywords,
+ * values from replies.  The index-PIR parameter of a keyword database has no size prefix and a batch of h = hashFunctionCount
+ * indices (:221-228), so everything below is the MulPIR client above at encoding_entry_size = 0, indices_count = h,
+ * entry_count = the table's buckets_per_table and E = entry_size_in_bytes the bucket row, with HashKeyword in front of it and
+ * HashBucket.init(deserialize:) / find(hash:) behind it.  A batch of keywords is given as the database is: keywords a DEVICE
+ * blob at any byte address, keyword_offsets DEVICE uint64 [queries + 1], non-decreasing; keyword q is keywords[
+ * keyword_offsets[q], keyword_offsets[q + 1]).
+ *
+ * he_keyword_client_plan (host only, host-only contexts too; any out pointer may be NULL): he_pir_client_plan's values and
+ *   value_capacity   min(E - 11, 65535), 0 for E < 11: the longest value a row holds (count byte, one 10-byte slot header)
+ *   find_form        the form he_keyword_client_find_in_buckets_device takes for this E: staged for E <= 32768, else direct
+ *   staged_lds_bytes the LDS of the staged kernel's instantiation for this E (0 for the direct form)
+ *   reply_bytes      R bpp: what he_keyword_client_count_entries_device scans per reply
+ * Errors: those of he_pir_client_plan; hash_function_count 0: HE_ERR_INVALID_ARGUMENT, above 8: HE_ERR_UNSUPPORTED (as
+ * he_keyword_pir_hash_indices_device); E == 0 (the reference's "Serialized HashBucket shouldn't be empty", which no database of
+ * this library reaches) and entry_count outside 1 .. 2^32 - 1: HE_ERR_INVALID_ARGUMENT. */
+enum he_keyword_pir_find_form {
+    HE_KEYWORD_PIR_FIND_FORM_PLAN = -1,  /* an argument only: the form the plan names */
+    HE_KEYWORD_PIR_FIND_FORM_STAGED = 0, /* one workgroup a row: the row goes to LDS and is walked there */
+    HE_KEYWORD_PIR_FIND_FORM_DIRECT = 1  /* one lane a row: the row is walked in global memory */
+};
+int he_keyword_client_plan(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, size_t entry_count,
+                               size_t entry_size_in_bytes, uint32_t hash_function_count, size_t* out_expanded_query_count,
+                               size_t* out_query_ciphertext_count, size_t* out_reply_ciphertext_count,
+                               size_t* out_entries_per_plaintext, size_t* out_bytes_per_plaintext, size_t* out_value_capacity,
+                               int* out_find_form, size_t* out_staged_lds_bytes, size_t* out_reply_bytes);
+/* The device entries follow the MulPIR client's conventions: word_bits 32 or 64 as an argument and no _u32 twins; enqueue-only on
+ * `s`; every argument error before anything is enqueued, in the order the word, the context, the shape (the index-PIR client's
+ * errors, then the plan's, then a batch too large for one call), null buffers, buffers that overlap one the call writes (of
+ * `keywords`, whose length lies on the device, the first byte); HE_ERR_DEVICE last on a host-only context.  queries == 0 does
+ * nothing.  workspace: DEVICE, 16-byte aligned, at least the entry's _workspace_bytes (0 on refused arguments), or NULL for
+ * stream-ordered scratch.  It holds the keyword hashes, the bucket indices, the decrypted bucket rows and the search's records:
+ * all of it is overwritten with zeros on `s` before the entry releases it or returns.
+ *
+ * he_keyword_client_generate_query_device -- KeywordPirClient.generateQuery(at:using:) (:326-334) for `queries` keywords:
+ * HashKeyword.hash, hashIndices(bucketCount: entry_count, hashFunctionCount: h) as uint64 [queries][h] in the workspace, then
+ * he_pir_generate_query_device's pipeline: every output word equals that entry's on those indices and the same seeds.
+ *   secret_key, a_seeds, error_seeds [queries][C][32], out [queries][C][2][L][N]   as he_pir_generate_query_device
+ *   out_hashes   DEVICE uint64 [queries] or NULL: the keyword hashes, for a caller that keeps them for the reply
+ * No index can lie outside the database, so there is no out_of_range flag. */
+size_t he_keyword_client_generate_query_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                                     uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                                     uint32_t hash_function_count, size_t queries);
+int he_keyword_client_generate_query_device(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                         uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                         uint32_t hash_function_count, const uint8_t* keywords, const uint64_t* keyword_offsets,
+                                         size_t queries, const void* secret_key, const uint8_t* a_seeds, const uint8_t* error_seeds,
+                                         void* out, uint64_t* out_hashes, void* workspace, size_t workspace_bytes, he_stream s);
+/* he_keyword_client_find_in_buckets_device -- lines 352-358 of decrypt(response:at:using:) over HashBucket.init(deserialize:) and
+ * find(hash:) (HashBucket.swift:51-73,118-133,200-205), bytes in and values out:
+ *   buckets     DEVICE [queries][h][E] at any byte address; hashes DEVICE uint64 [queries]
+ *   out_values  DEVICE [queries][value_capacity] at any byte address (may be NULL when value_capacity is 0)
+ *   out_sizes   DEVICE uint64 [queries]; out_status DEVICE uint32 [queries]: 0 nil, 1 found, 2 corruptedData
+ *   form        HE_KEYWORD_PIR_FIND_FORM_PLAN, or one of the two forms (staged with E > 32768: HE_ERR_INVALID_ARGUMENT)
+ * A query's h buckets are taken in order.  A bucket b[0, E) is walked: count = b[0], off = 1; per slot the bucket is corrupt if
+ * E < off + 10; hash = LE64(b + off), size = LE16(b + off + 8), off += 10; corrupt if off + size > E; off += size.  A corrupt
+ * bucket ends the query with status 2, also when an earlier slot of that bucket matches (the reference deserializes a bucket
+ * before it searches it); otherwise the first slot whose hash is the query's ends it with status 1, its size and its bytes; no
+ * match in any bucket is status 0.  Zero padding behind the last slot is no slot; a found value of no bytes is status 1 with
+ * size 0.  out_values[q] is the value, then zeros up to value_capacity; all zeros and size 0 for status 0 and 2.  Exactly the
+ * bytes of the three outputs are written, and only bytes of buckets and hashes are read.
+ * Two launches and no atomics: the walk leaves one 16-byte record per (query, bucket) in the workspace (staged: one workgroup a
+ * row, 16-byte loads into LDS with the ragged ends by bytes, the chain walked at LDS latency; direct: one lane a row in global
+ * memory), then one launch resolves the records in bucket order and copies, one lane per 16-byte line of out_values. */
+size_t he_keyword_client_find_in_buckets_workspace_bytes(size_t entry_size_in_bytes, uint32_t hash_function_count, size_t queries);
+int he_keyword_client_find_in_buckets_device(const uint8_t* buckets, const uint64_t* hashes, size_t entry_size_in_bytes,
+                                          uint32_t hash_function_count, size_t queries, int form, uint8_t* out_values,
+                                          uint64_t* out_sizes, uint32_t* out_status, void* workspace, size_t workspace_bytes,
+                                          he_stream s);
+/* he_keyword_client_decrypt_response_device -- KeywordPirClient.decrypt(response:at:using:) (:343-359) for `queries` keywords:
+ *   response   DEVICE [queries][h][R][2][moduli_count][N], as he_pir_decrypt_response_device takes it with indices_count = h
+ *   keywords, keyword_offsets as above; or keywords NULL and hashes DEVICE uint64 [queries] (he_keyword_client_generate_query_device's
+ *              out_hashes)
+ * The hashes and indices are derived, he_pir_decrypt_response_device's pipeline writes the bucket rows [queries][h][E] into the
+ * workspace, then he_keyword_client_find_in_buckets_device's two launches in the plan's form; outputs as there. */
+size_t he_keyword_client_decrypt_response_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                                       uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                                       uint32_t hash_function_count, uint32_t moduli_count, size_t queries);
+int he_keyword_client_decrypt_response_device(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                           uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                           uint32_t hash_function_count, uint32_t moduli_count, const void* response,
+                                           const uint8_t* keywords, const uint64_t* keyword_offsets, const uint64_t* hashes,
+                                           size_t queries, const void* secret_key, uint8_t* out_values, uint64_t* out_sizes,
+                                           uint32_t* out_status, void* workspace, size_t workspace_bytes, he_stream s);
+/* he_keyword_client_count_entries_device -- countEntriesInResponse (:376-391): decryptFull gives [queries][h][R bpp] in the
+ * workspace, he_keyword_client_count_bucket_entries_device scans it.  out_counts DEVICE uint64 [queries]. */
+size_t he_keyword_client_count_entries_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                                    uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                                    uint32_t hash_function_count, uint32_t moduli_count, size_t queries);
+int he_keyword_client_count_entries_device(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                        uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                        uint32_t hash_function_count, uint32_t moduli_count, const void* response, size_t queries,
+                                        const void* secret_key, uint64_t* out_counts, void* workspace, size_t workspace_bytes,
+                                        he_stream s);
+/* The scan of countEntriesInResponse (:379-389) over bytes DEVICE [queries][replies_per_query][reply_bytes] at any byte address:
+ * per reply off = 0; while off < reply_bytes a bucket is deserialized from b[off, reply_bytes) by the walk above; where that
+ * fails the scan of the reply ends and the bucket's slots do not count, otherwise its slot count is added and off advances by its
+ * serialized size.  A zero byte is an empty bucket of one byte: padding is stepped over, eight bytes at a time where eight zero
+ * bytes are left.  out_counts DEVICE uint64 [queries]: the sum over the query's replies.  One wave a query, a lane a reply; no
+ * atomics, no scratch.  Enqueue-only. */
+int he_keyword_client_count_bucket_entries_device(const uint8_t* bytes, size_t reply_bytes, size_t replies_per_query, size_t queries,
+                                               uint64_t* out_counts, he_stream s);
+
 /* ---- sharded keyword database: KeywordDatabase.init(rows:sharding:shardingFunction:) (KeywordDatabase.swift:406-437) -------
  * PIRProcessDatabase hashes every keyword, takes its shard index and splits the rows into one KeywordDatabaseShard per index;
  * each shard then becomes a cuckoo table (above).  Here the rows are split on the device: a stable counting sort of the rows

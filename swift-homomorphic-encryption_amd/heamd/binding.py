@@ -261,6 +261,26 @@ SIGNATURES = [
     ("he_keyword_pir_table_load_factor", ctypes.c_float, [vp]),
     ("he_keyword_pir_table_entries_device", ctypes.c_int, [vp, vp, c_size, vp, vp]),
     ("he_keyword_pir_process_database_device", ctypes.c_int, [vp, vp, vp, ctypes.POINTER(c_u32), c_u32, c_size, vp, vp, vp]),
+    ("he_keyword_client_plan", ctypes.c_int,
+     [vp, ctypes.POINTER(c_u32), c_u32, c_size, c_size, c_u32] + [ctypes.POINTER(c_size)] * 6 +
+     [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
+    ("he_keyword_client_generate_query_workspace_bytes", c_size,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, c_u32, c_size]),
+    ("he_keyword_client_generate_query_device", ctypes.c_int,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, c_u32, vp, vp, c_size, vp, vp, vp, vp, vp, vp, c_size, vp]),
+    ("he_keyword_client_find_in_buckets_workspace_bytes", c_size, [c_size, c_u32, c_size]),
+    ("he_keyword_client_find_in_buckets_device", ctypes.c_int,
+     [vp, vp, c_size, c_u32, c_size, ctypes.c_int, vp, vp, vp, vp, c_size, vp]),
+    ("he_keyword_client_decrypt_response_workspace_bytes", c_size,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, c_u32, c_u32, c_size]),
+    ("he_keyword_client_decrypt_response_device", ctypes.c_int,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, c_u32, c_u32, vp, vp, vp, vp, c_size, vp, vp, vp, vp, vp,
+      c_size, vp]),
+    ("he_keyword_client_count_entries_workspace_bytes", c_size,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, c_u32, c_u32, c_size]),
+    ("he_keyword_client_count_entries_device", ctypes.c_int,
+     [vp, c_u32, ctypes.POINTER(c_u32), c_u32, c_size, c_size, c_u32, c_u32, vp, c_size, vp, vp, vp, c_size, vp]),
+    ("he_keyword_client_count_bucket_entries_device", ctypes.c_int, [vp, c_size, c_size, c_size, vp, vp]),
     ("he_keyword_sharding_shard_count", ctypes.c_int, [vp, c_size, ctypes.POINTER(c_size)]),
     ("he_keyword_database_partition_device", ctypes.c_int,
      [vp, vp, c_size, vp, vp, c_size, c_size, vp, c_size, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -1597,6 +1617,147 @@ class BfvContext:
             moduli_count, _ptr(response, w), vp() if indices is None else vp(indices.data_ptr()), queries,
             _ptr(secret_key, w), vp(entries.data_ptr()), vp(sizes.data_ptr()), ws_ptr, ws_bytes, _stream(stream)))
         return entries, sizes
+
+    # ---- the keyword PIR client: KeywordPirClient.generateQuery / decrypt(response:) / countEntriesInResponse on
+    # the device.  entry_count is the table's buckets_per_table, entry_size_in_bytes the bucket row, h the hash function count;
+    # keywords: a uint8 device tensor at any byte address with keyword_offsets an int64 device tensor [queries + 1].
+    KEYWORD_PIR_FIND_FORMS = {None: -1, "plan": -1, "staged": 0, "direct": 1}
+
+    @staticmethod
+    def _keyword_parameter(dimensions, entry_count, entry_size_in_bytes, hash_function_count):
+        dims = (c_u32 * max(len(dimensions), 1))(*[int(d) for d in dimensions])
+        return dims, len(dimensions), int(entry_count), int(entry_size_in_bytes), int(hash_function_count)
+
+    def keyword_pir_client_plan(self, dimensions, entry_count, entry_size_in_bytes, hash_function_count):
+        """he_keyword_client_plan -> pir_client_plan's values (but the encoding width) and value_capacity, find_form
+        ("staged" or "direct"), staged_lds_bytes and reply_bytes."""
+        outs, form, more = [c_size() for _ in range(6)], ctypes.c_int(), [c_size() for _ in range(2)]
+        _check(load_library().he_keyword_client_plan(
+            self.h, *self._keyword_parameter(dimensions, entry_count, entry_size_in_bytes, hash_function_count),
+            *[ctypes.byref(o) for o in outs], ctypes.byref(form), *[ctypes.byref(o) for o in more]))
+        names = ("expanded_query_count", "query_ciphertext_count", "reply_ciphertext_count", "entries_per_plaintext",
+                 "bytes_per_plaintext", "value_capacity")
+        plan = {name: int(o.value) for name, o in zip(names, outs)}
+        plan.update(find_form="staged" if form.value == 0 else "direct", staged_lds_bytes=int(more[0].value),
+                    reply_bytes=int(more[1].value))
+        return plan
+
+    def keyword_pir_generate_query_workspace_bytes(self, dimensions, entry_count, entry_size_in_bytes, hash_function_count,
+                                                   queries=1):
+        return int(load_library().he_keyword_client_generate_query_workspace_bytes(
+            self.h, self._word.bits,
+            *self._keyword_parameter(dimensions, entry_count, entry_size_in_bytes, hash_function_count), int(queries)))
+
+    def keyword_pir_generate_query(self, keywords, keyword_offsets, dimensions, entry_count, entry_size_in_bytes,
+                                   hash_function_count, secret_key, a_seeds, error_seeds, stream=None, workspace=None):
+        """KeywordPirClient.generateQuery(at:using:) per keyword; seeds uint8 [queries][C][32] -> (ciphertexts
+        [queries][C][2][L][N] Coeff, the keyword hashes int64 [queries])."""
+        import torch
+
+        queries, w = keyword_offsets.numel() - 1, self._word
+        plan = self.keyword_pir_client_plan(dimensions, entry_count, entry_size_in_bytes, hash_function_count)
+        out = _empty((queries, plan["query_ciphertext_count"], 2, self.L, self.degree), w, keywords.device)
+        hashes = torch.empty((queries,), dtype=torch.int64, device=keywords.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_keyword_client_generate_query_device(
+            self.h, w.bits, *self._keyword_parameter(dimensions, entry_count, entry_size_in_bytes, hash_function_count),
+            _byte_ptr(keywords), _ptr(keyword_offsets), queries, _ptr(secret_key, w), vp(a_seeds.data_ptr()),
+            vp(error_seeds.data_ptr()), _ptr(out, w), _ptr(hashes), ws_ptr, ws_bytes, _stream(stream)))
+        return out, hashes
+
+    @staticmethod
+    def keyword_pir_find_in_buckets(buckets, hashes, form=None, out_values=None, stream=None, workspace=None):
+        """he_keyword_client_find_in_buckets_device: buckets uint8 [queries][h][E] (any byte address), hashes int64 [queries] ->
+        (values uint8 [queries][value_capacity], the value and zeros behind it; sizes int64 [queries]; status int32 [queries]:
+        0 nil, 1 found, 2 corruptedData).  form: None (the plan's), "staged" or "direct"."""
+        import torch
+
+        if buckets.dim() != 3 or buckets.shape[0] != hashes.numel():
+            raise ValueError("expected buckets as [queries][hash_function_count][entry_size] and one hash a query")
+        queries, h, size = (int(d) for d in buckets.shape)
+        capacity = 0 if size < 11 else min(size - 11, 65535)
+        if out_values is None:
+            out_values = torch.empty((queries, capacity), dtype=torch.uint8, device=buckets.device)
+        elif out_values.numel() != queries * capacity:
+            raise ValueError("out_values does not hold queries * value_capacity bytes")
+        sizes = torch.empty((queries,), dtype=torch.int64, device=buckets.device)
+        status = torch.empty((queries,), dtype=torch.int32, device=buckets.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_keyword_client_find_in_buckets_device(
+            _byte_ptr(buckets), _ptr(hashes), size, h, queries, BfvContext.KEYWORD_PIR_FIND_FORMS[form], _byte_ptr(out_values),
+            _ptr(sizes), _ptr(status, WORD32), ws_ptr, ws_bytes, _stream(stream)))
+        return out_values, sizes, status
+
+    def keyword_pir_decrypt_response_workspace_bytes(self, dimensions, entry_count, entry_size_in_bytes, hash_function_count,
+                                                     queries=1, moduli_count=1):
+        return int(load_library().he_keyword_client_decrypt_response_workspace_bytes(
+            self.h, self._word.bits,
+            *self._keyword_parameter(dimensions, entry_count, entry_size_in_bytes, hash_function_count), int(moduli_count),
+            int(queries)))
+
+    def keyword_pir_decrypt_response(self, response, dimensions, entry_count, entry_size_in_bytes, secret_key, keywords=None,
+                                     keyword_offsets=None, hashes=None, stream=None, workspace=None):
+        """KeywordPirClient.decrypt(response:at:using:): response [queries][h][R][2][moduli_count][N] Coeff and the keywords
+        (or their hashes, int64 [queries]) -> (values, sizes, status) as keyword_pir_find_in_buckets gives them."""
+        import torch
+
+        w = self._word
+        if response.dim() != 6 or response.shape[3] != 2 or response.shape[5] != self.degree:
+            raise ValueError("expected the response as [queries][hash_function_count][R][2][moduli_count][N]")
+        if (keywords is None) == (hashes is None) or (keywords is not None and keyword_offsets is None):
+            raise ValueError("give the keywords with their offsets, or their hashes")
+        queries, h, moduli_count = int(response.shape[0]), int(response.shape[1]), int(response.shape[4])
+        plan = self.keyword_pir_client_plan(dimensions, entry_count, entry_size_in_bytes, h)
+        if response.shape[2] != plan["reply_ciphertext_count"]:  # PirError.invalidReply
+            raise HeError(16, f"Invalid reply: ciphertext count {int(response.shape[2])}, expected "
+                              f"{plan['reply_ciphertext_count']}")
+        values = torch.empty((queries, plan["value_capacity"]), dtype=torch.uint8, device=response.device)
+        sizes = torch.empty((queries,), dtype=torch.int64, device=response.device)
+        status = torch.empty((queries,), dtype=torch.int32, device=response.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_keyword_client_decrypt_response_device(
+            self.h, w.bits, *self._keyword_parameter(dimensions, entry_count, entry_size_in_bytes, h), moduli_count,
+            _ptr(response, w), vp() if keywords is None else _byte_ptr(keywords), _opt_ptr(keyword_offsets), _opt_ptr(hashes),
+            queries, _ptr(secret_key, w), vp(values.data_ptr()), _ptr(sizes), _ptr(status, WORD32), ws_ptr, ws_bytes,
+            _stream(stream)))
+        return values, sizes, status
+
+    def keyword_pir_count_entries_workspace_bytes(self, dimensions, entry_count, entry_size_in_bytes, hash_function_count,
+                                                  queries=1, moduli_count=1):
+        return int(load_library().he_keyword_client_count_entries_workspace_bytes(
+            self.h, self._word.bits,
+            *self._keyword_parameter(dimensions, entry_count, entry_size_in_bytes, hash_function_count), int(moduli_count),
+            int(queries)))
+
+    def keyword_pir_count_entries(self, response, dimensions, entry_count, entry_size_in_bytes, secret_key, stream=None,
+                                  workspace=None):
+        """KeywordPirClient.countEntriesInResponse: response as keyword_pir_decrypt_response takes it -> int64 [queries]."""
+        import torch
+
+        w = self._word
+        if response.dim() != 6 or response.shape[3] != 2 or response.shape[5] != self.degree:
+            raise ValueError("expected the response as [queries][hash_function_count][R][2][moduli_count][N]")
+        queries, h, moduli_count = int(response.shape[0]), int(response.shape[1]), int(response.shape[4])
+        counts = torch.empty((queries,), dtype=torch.int64, device=response.device)
+        ws_ptr, ws_bytes = _workspace(workspace)
+        _check(load_library().he_keyword_client_count_entries_device(
+            self.h, w.bits, *self._keyword_parameter(dimensions, entry_count, entry_size_in_bytes, h), moduli_count,
+            _ptr(response, w), queries, _ptr(secret_key, w), _ptr(counts), ws_ptr, ws_bytes, _stream(stream)))
+        return counts
+
+    @staticmethod
+    def keyword_pir_count_bucket_entries(replies, stream=None):
+        """he_keyword_client_count_bucket_entries_device: the scan of countEntriesInResponse over replies uint8
+        [queries][replies_per_query][reply_bytes] (any byte address) -> int64 [queries]."""
+        import torch
+
+        if replies.dim() != 3:
+            raise ValueError("expected the replies as [queries][replies_per_query][reply_bytes]")
+        queries, per_query, reply_bytes = (int(d) for d in replies.shape)
+        counts = torch.empty((queries,), dtype=torch.int64, device=replies.device)
+        _check(load_library().he_keyword_client_count_bucket_entries_device(
+            vp(replies.data_ptr()) if replies.numel() else vp(), reply_bytes, per_query, queries, _ptr(counts), _stream(stream)))
+        return counts
 
     # ---- processed-database files (DESIGN.md 4.11): ProcessedDatabase.serialize() / init(from:context:) ----
     def database_file_payload_bytes(self):
