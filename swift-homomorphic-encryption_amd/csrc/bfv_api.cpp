@@ -78,10 +78,7 @@ int check_level(const he_bfv_context* ctx, uint32_t moduli_count, const RnsToolL
     if (ctx == nullptr) return invalid_argument("null context");
     if (!ctx->impl->valid(moduli_count)) return invalid_argument("moduli_count out of range");
     HEAMD_TRY_STATUS(slabs(size_t(ctx->impl->degree())));
-    if (ctx->impl->host_only()) {
-        heamd::set_last_error("context was created host-only (no device tables)");
-        return HE_ERR_DEVICE;
-    }
+    if (ctx->impl->host_only()) return heamd::host_only_refusal();
     const int status = ctx->impl->ciphertext(moduli_count)->check_device();
     if (status != HE_OK) return status;
     *tool = ctx->impl->tool(moduli_count);
@@ -825,7 +822,7 @@ using heamd::u64;
 int check_decrypt_arguments(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
                             const RnsToolLevel** tool, const char* what, const void* cts, const void* secret_key, size_t batch,
                             heamd::Slab result, size_t result_fixed_bytes, const void* workspace, size_t workspace_bytes) {
-    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    HEAMD_TRY_STATUS(heamd::check_word_bits(word_bits));
     HEAMD_TRY_STATUS(check_level(ctx, moduli_count, tool, word_bits / 8, [&](size_t n) {
         const size_t poly_bytes = size_t(moduli_count) * n * (word_bits / 8);
         if (batch == 0) return int(HE_OK);  // (nothing is read or written, the secret key and the workspace included)
@@ -996,6 +993,18 @@ double limbs_to_double(const uint64_t* limbs, uint32_t count) {
 }
 
 }  // namespace
+// word_layer.hpp
+int heamd::check_word_and_context(const he_bfv_context* ctx, uint32_t word_bits) {
+    HEAMD_TRY_STATUS(check_word_bits(word_bits));
+    if (ctx == nullptr) return invalid_argument("null context");
+    if (word_bits == 32 && ctx->impl->word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
+    return HE_OK;
+}
+int heamd::bfv_decrypt_check_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count) {
+    HEAMD_TRY_STATUS(check_word_bits(word_bits));
+    const RnsToolLevel* tool = nullptr;
+    return check_level(ctx, moduli_count, &tool, word_bits / 8);
+}
 }  // extern "C++"
 
 size_t he_bfv_decrypt_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
@@ -1017,14 +1026,11 @@ int he_bfv_secret_dot_product_device(const he_bfv_context* ctx, uint32_t word_bi
                                              workspace_bytes));
     if (batch != 0 && out == nullptr) return invalid_argument("null dot product");
     Scratch scratch(as_stream(s));
-    if (word_bits == 32) {
-        uint32_t* dot = nullptr;
-        return decrypt_dot<uint32_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out, batch, workspace,
-                                     workspace_bytes, scratch, as_stream(s), &dot);
-    }
-    uint64_t* dot = nullptr;
-    return decrypt_dot<uint64_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out, batch, workspace, workspace_bytes,
-                                 scratch, as_stream(s), &dot);
+    return heamd::with_word(word_bits, [&](auto word) {
+        decltype(word)* dot = nullptr;
+        return decrypt_dot(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out, batch, workspace, workspace_bytes, scratch,
+                           as_stream(s), &dot);
+    });
 }
 
 int he_bfv_decrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count, int is_eval,
@@ -1041,11 +1047,10 @@ int he_bfv_decrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_
         heamd::set_last_error("the correction factor has no inverse mod t");
         return HE_ERR_NOT_INVERTIBLE;
     }
-    if (word_bits == 32)
-        return decrypt_words<uint32_t>(ctx, *tool, moduli_count, poly_count, is_eval, cts, secret_key, scaling_factor,
-                                       out_plaintexts, batch, workspace, workspace_bytes, as_stream(s));
-    return decrypt_words<uint64_t>(ctx, *tool, moduli_count, poly_count, is_eval, cts, secret_key, scaling_factor, out_plaintexts,
-                                   batch, workspace, workspace_bytes, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return decrypt_words<decltype(word)>(ctx, *tool, moduli_count, poly_count, is_eval, cts, secret_key, scaling_factor,
+                                             out_plaintexts, batch, workspace, workspace_bytes, as_stream(s));
+    });
 }
 
 int he_bfv_noise_norm_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
@@ -1056,11 +1061,10 @@ int he_bfv_noise_norm_device(const he_bfv_context* ctx, uint32_t word_bits, uint
                                              {"out_limbs", out_limbs, 0, true},
                                              batch * he_bfv_noise_norm_limbs(ctx, moduli_count) * sizeof(uint64_t), workspace,
                                              workspace_bytes));
-    if (word_bits == 32)
-        return noise_norm_words<uint32_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out_limbs, batch, workspace,
-                                          workspace_bytes, as_stream(s));
-    return noise_norm_words<uint64_t>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out_limbs, batch, workspace,
-                                      workspace_bytes, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return noise_norm_words<decltype(word)>(ctx, moduli_count, poly_count, is_eval, cts, secret_key, out_limbs, batch, workspace,
+                                                workspace_bytes, as_stream(s));
+    });
 }
 
 int he_bfv_is_transparent_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, uint32_t poly_count,
@@ -1071,13 +1075,11 @@ int he_bfv_is_transparent_device(const he_bfv_context* ctx, uint32_t word_bits, 
     if (batch == 0) return HE_OK;
     if (cts == nullptr || out_flags == nullptr) return invalid_argument("null ciphertexts or flags");
     const uint32_t log_degree = tool->device.log_degree;
-    if (word_bits == 32)
-        HEAMD_HIP_TRY(heamd::launch_is_transparent(static_cast<const uint32_t*>(cts), out_flags, log_degree, moduli_count,
+    return heamd::with_word(word_bits, [&](auto word) {
+        HEAMD_HIP_TRY(heamd::launch_is_transparent(static_cast<const decltype(word)*>(cts), out_flags, log_degree, moduli_count,
                                                    poly_count, batch, as_stream(s)));
-    else
-        HEAMD_HIP_TRY(heamd::launch_is_transparent(static_cast<const uint64_t*>(cts), out_flags, log_degree, moduli_count,
-                                                   poly_count, batch, as_stream(s)));
-    return HE_OK;
+        return int(HE_OK);
+    });
 }
 
 uint32_t he_bfv_noise_norm_limbs(const he_bfv_context* ctx, uint32_t moduli_count) {

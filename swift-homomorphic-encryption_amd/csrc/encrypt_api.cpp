@@ -4,6 +4,8 @@
 // Each entry is a short pipeline of kernels on the caller's stream: the re-key chains of its seeds (aes_ctr_drbg.hpp), the
 // samplers and element-wise steps of encrypt_kernels.hip, and the transforms.  Whatever the workspace held that depends on
 // a secret is overwritten with zeros on the stream before it is released (the reference zeroizes errorPoly and currentKey).
+// Shared with the other entries that take the slab word: the first checks and the word dispatch (word_layer.hpp), the parts of a
+// workspace (workspace_layout.hpp) and its zeroing (zeroized_workspace.hpp).
 #include <vector>
 
 #include "aes_ctr_drbg.hpp"
@@ -13,6 +15,7 @@
 #include "kernels.hpp"
 #include "rns_kernels.hpp"
 #include "word_layer.hpp"
+#include "workspace_layout.hpp"
 #include "zeroized_workspace.hpp"
 
 using heamd::as_stream;
@@ -32,43 +35,40 @@ const PolyContext& secret_key_context(const BfvContext& bfv) {
     return bfv.has_key_switching() ? *bfv.key_switching(bfv.top_level()) : *bfv.ciphertext(bfv.top_level());
 }
 
-size_t round16(size_t bytes) { return (bytes + 15) & ~size_t(15); }
-
-// Where the parts of a workspace lie, in bytes from its start.  Every part is a multiple of 16 bytes.
+// Where the parts of a workspace lie, in bytes from its start, in the order a WorkspaceLayout is given them.  The DRBG records
+// of the `a` seeds (public) lie at 0.
 struct EncryptPlan {
-    size_t a_chain = 0;        // the DRBG records of the `a` seeds (public)
-    size_t error_chain = 0;    // those of the error seeds, or of the key seeds of generateSecretKey
+    size_t error_chain = 0;    // the DRBG records of the error seeds
     size_t error_polys = 0;    // [count][m][N] words: e, then NTT(e) (Eval output only)
     size_t current_keys = 0;   // [keys][L + 1][N] words: s s or the rotated keys
-    size_t total() const { return a_chain + error_chain + error_polys + current_keys; }
+    size_t total = 0;
 };
-EncryptPlan plan_encrypt_zero(const PolyContext& pc, uint32_t m, bool eval_out, size_t count, size_t word_bytes) {
+EncryptPlan plan_encrypt_zero(const PolyContext& pc, uint32_t m, bool eval_out, size_t count, size_t word_bytes,
+                              size_t current_key_bytes = 0) {
+    heamd::WorkspaceLayout layout;
     EncryptPlan plan;
-    plan.a_chain = heamd::seeded_uniform_scratch_bytes(pc.device_context(m), count);
-    plan.error_chain = count * heamd::binomial_chunks(pc.degree()) * heamd::kChainRecordBytes;
-    if (eval_out) plan.error_polys = round16(count * m * pc.degree() * word_bytes);
+    layout.add(heamd::seeded_uniform_scratch_bytes(pc.device_context(m), count));
+    plan.error_chain = layout.add(count * heamd::binomial_chunks(pc.degree()) * heamd::kChainRecordBytes);
+    plan.error_polys = layout.add(eval_out ? count * m * pc.degree() * word_bytes : 0);
+    plan.current_keys = layout.add(current_key_bytes);
+    plan.total = layout.total();
     return plan;
 }
 EncryptPlan plan_key_switch_keys(const BfvContext& bfv, size_t keys, bool own_current_keys, size_t word_bytes) {
     const PolyContext& pc = secret_key_context(bfv);
-    EncryptPlan plan = plan_encrypt_zero(pc, pc.moduli_count(), true, keys * bfv.top_level(), word_bytes);
-    if (own_current_keys) plan.current_keys = round16(keys * pc.moduli_count() * pc.degree() * word_bytes);
-    return plan;
+    return plan_encrypt_zero(pc, pc.moduli_count(), true, keys * bfv.top_level(), word_bytes,
+                             own_current_keys ? keys * pc.moduli_count() * pc.degree() * word_bytes : 0);
 }
-EncryptPlan plan_secret_keys(const PolyContext& pc, size_t batch) {
-    EncryptPlan plan;
-    plan.error_chain = batch * heamd::ternary_chunks(pc.degree()) * heamd::kChainRecordBytes;
-    return plan;
+size_t secret_keys_bytes(const PolyContext& pc, size_t batch) {  // generateSecretKey: the DRBG records of the key seeds alone
+    return heamd::round16(batch * heamd::ternary_chunks(pc.degree()) * heamd::kChainRecordBytes);
 }
 
-// The checks every entry makes, in this order: the word, the context, the word against the scheme, and (key generation)
-// supportsEvaluationKey -- argument errors first, so that they are the same with and without a device --, then the device and
-// the transform: nothing is enqueued when any of them fails.
+// The checks every entry makes, in this order: the word, the context, the word against the scheme (word_layer.hpp), and (key
+// generation) supportsEvaluationKey -- argument errors first, so that they are the same with and without a device --, then the
+// device and the transform: nothing is enqueued when any of them fails.
 int check_encrypt_context(const he_bfv_context* ctx, uint32_t word_bits, bool needs_evaluation_key, const BfvContext** out) {
-    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
-    if (ctx == nullptr) return invalid_argument("null context");
+    HEAMD_TRY_STATUS(heamd::check_word_and_context(ctx, word_bits));
     const BfvContext& bfv = heamd::bfv_impl(ctx);
-    if (word_bits == 32 && bfv.word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
     if (needs_evaluation_key && !bfv.has_key_switching()) {
         heamd::set_last_error("a context with one coefficient modulus supports no evaluation key");
         return HE_ERR_UNSUPPORTED;  // Bfv+Keys.swift:35-37
@@ -77,10 +77,7 @@ int check_encrypt_context(const he_bfv_context* ctx, uint32_t word_bits, bool ne
     return HE_OK;
 }
 int check_encrypt_device(const BfvContext& bfv, uint32_t word_bits, uint32_t moduli) {
-    if (bfv.host_only()) {
-        heamd::set_last_error("context was created host-only (no device tables)");
-        return HE_ERR_DEVICE;
-    }
+    if (bfv.host_only()) return heamd::host_only_refusal();
     const PolyContext& pc = secret_key_context(bfv);
     HEAMD_TRY_STATUS(pc.check_device());
     if (!pc.all_ntt(moduli)) return HE_ERR_INVALID_NTT_MODULUS;
@@ -104,12 +101,12 @@ int encrypt_zero_pipeline(const PolyContext& pc, uint32_t m, bool eval_out, cons
                           hipStream_t stream) {
     const DeviceContext dc = pc.device_context(m);
     const size_t poly_words = size_t(m) * pc.degree();
-    uint32_t* error_chain = reinterpret_cast<uint32_t*>(ws.at(plan.a_chain));
+    uint32_t* error_chain = ws.at<uint32_t>(plan.error_chain);
     // `a` is drawn in Eval form directly (Bfv+Encrypt.swift:155-156), into polynomial 1 of every ciphertext
     HEAMD_HIP_TRY(heamd::launch_seeded_uniform(a_seeds, out + poly_words, 2 * poly_words, dc, count, ws.at(0), stream));
     HEAMD_HIP_TRY(heamd::launch_seeded_chain(error_seeds, error_chain, count, heamd::binomial_chunks(pc.degree()), stream));
     if (eval_out) {
-        W* error = reinterpret_cast<W*>(ws.at(plan.a_chain + plan.error_chain));
+        W* error = ws.at<W>(plan.error_polys);
         HEAMD_HIP_TRY(heamd::launch_sample_centered_binomial(error_chain, error, poly_words, dc, count, stream));
         HEAMD_HIP_TRY(heamd::ntt_rows(false, error, pc, dc, m, count * m, stream));
         HEAMD_HIP_TRY(heamd::launch_encrypt_finish_eval(out, error, secret_key, current_keys, per_key, factors, dc, count, stream));
@@ -135,7 +132,7 @@ int encrypt_zero_entry(const BfvContext& bfv, uint32_t m, bool eval_out, const v
     const PolyContext& pc = secret_key_context(bfv);
     const EncryptPlan plan = plan_encrypt_zero(pc, m, eval_out, batch, sizeof(W));
     ZeroizedWorkspace ws(stream);
-    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total()));
+    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total));
     HEAMD_TRY_STATUS(encrypt_zero_pipeline<W>(pc, m, eval_out, static_cast<const W*>(secret_key), a_seeds, error_seeds,
                                               static_cast<W*>(out), batch, nullptr, 0, KeySwitchFactors{}, ws, plan, stream));
     if (plaintexts != nullptr)  // Bfv.encrypt: addAssign(&ciphertext, plaintext) (Bfv+Encrypt.swift:70)
@@ -165,12 +162,12 @@ int key_switch_keys_entry(const BfvContext& bfv, CurrentKeys kind, const void* s
     const uint32_t L = bfv.top_level(), m = pc.moduli_count();
     const EncryptPlan plan = plan_key_switch_keys(bfv, keys, kind != CurrentKeys::Callers, sizeof(W));
     ZeroizedWorkspace ws(stream);
-    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total()));
+    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total));
     const W* s = static_cast<const W*>(secret_key);
     const W* current = static_cast<const W*>(current_keys);
     if (kind != CurrentKeys::Callers) {
         const DeviceContext dc = pc.device_context();
-        W* own = reinterpret_cast<W*>(ws.at(plan.a_chain + plan.error_chain + plan.error_polys));
+        W* own = ws.at<W>(plan.current_keys);
         if (kind == CurrentKeys::Square)  // (one key)
             HEAMD_HIP_TRY(heamd::launch_secret_key_square(s, own, dc, stream));
         else  // all rotated keys in one launch (64 elements travel in a launch's arguments)
@@ -207,6 +204,26 @@ int check_encrypt_slabs(const char* what, const PolyContext& pc, uint32_t m, siz
                                      extra});
 }
 
+// What the three key generators share behind their own checks: null buffers, the pointer contract (the secret key may itself be a
+// current key: both are only read), the device, and the pipeline for the slab word.  current_keys: the caller's, or NULL
+int generate_key_switch_keys(const BfvContext& bfv, uint32_t word_bits, CurrentKeys kind, const char* what, const void* secret_key,
+                             const void* current_keys, const uint64_t* elements, const uint8_t* a_seeds, const uint8_t* error_seeds,
+                             void* out, size_t keys, void* workspace, size_t workspace_bytes, he_stream s) {
+    if (secret_key == nullptr || (kind == CurrentKeys::Callers && current_keys == nullptr) || a_seeds == nullptr ||
+        error_seeds == nullptr || out == nullptr)
+        return invalid_argument("null keys or seeds");
+    const PolyContext& pc = secret_key_context(bfv);
+    const size_t key_bytes = size_t(pc.moduli_count()) * pc.degree() * (word_bits / 8);  // (a NULL slab takes part in nothing)
+    HEAMD_TRY_STATUS(check_encrypt_slabs(what, pc, pc.moduli_count(), word_bits / 8, secret_key, a_seeds, error_seeds,
+                                         {"current_keys", current_keys, keys * key_bytes, false}, out, keys * bfv.top_level(),
+                                         workspace, workspace_bytes));
+    HEAMD_TRY_STATUS(check_encrypt_device(bfv, word_bits, bfv.top_level() + 1));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return key_switch_keys_entry<decltype(word)>(bfv, kind, secret_key, current_keys, elements, a_seeds, error_seeds, out, keys,
+                                                     workspace, workspace_bytes, as_stream(s));
+    });
+}
+
 int check_moduli_fit_word(const PolyContext& pc, uint32_t word_bits) {
     if (word_bits == 64) return HE_OK;
     for (heamd::u64 q : pc.moduli())
@@ -223,7 +240,7 @@ int poly_sample(const PolyContext& pc, bool ternary, const uint8_t* seeds, size_
     const uint32_t chunks = ternary ? heamd::ternary_chunks(pc.degree()) : heamd::binomial_chunks(pc.degree());
     ZeroizedWorkspace ws(stream);
     HEAMD_TRY_STATUS(ws.resolve(nullptr, 0, batch * chunks * heamd::kChainRecordBytes));
-    uint32_t* chain = reinterpret_cast<uint32_t*>(ws.at(0));
+    uint32_t* chain = ws.at<uint32_t>(0);
     HEAMD_HIP_TRY(heamd::launch_seeded_chain(seeds, chain, batch, chunks, stream));
     const size_t poly_words = size_t(pc.moduli_count()) * pc.degree();
     if (ternary)
@@ -234,7 +251,7 @@ int poly_sample(const PolyContext& pc, bool ternary, const uint8_t* seeds, size_
 }
 int poly_sample_entry(const he_poly_context* ctx, uint32_t word_bits, bool ternary, const uint8_t* seeds, size_t batch,
                       void* out, he_stream s) {
-    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    HEAMD_TRY_STATUS(heamd::check_word_bits(word_bits));
     if (ctx == nullptr) return invalid_argument("null context");
     const PolyContext& pc = *ctx->impl;
     HEAMD_TRY_STATUS(check_moduli_fit_word(pc, word_bits));
@@ -244,8 +261,9 @@ int poly_sample_entry(const he_poly_context* ctx, uint32_t word_bits, bool terna
                                         {{"out", out, batch * pc.moduli_count() * pc.degree() * (word_bits / 8), true},
                                          {"seeds", seeds, batch * 32, false}}));
     HEAMD_TRY_STATUS(pc.check_device());
-    if (word_bits == 32) return poly_sample(pc, ternary, seeds, batch, static_cast<uint32_t*>(out), as_stream(s));
-    return poly_sample(pc, ternary, seeds, batch, static_cast<uint64_t*>(out), as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return poly_sample(pc, ternary, seeds, batch, static_cast<decltype(word)*>(out), as_stream(s));
+    });
 }
 
 }  // namespace
@@ -263,20 +281,20 @@ size_t he_bfv_encrypt_workspace_bytes(const he_bfv_context* ctx, uint32_t word_b
     const size_t word_bytes = word_bits / 8;
     switch (operation) {
         case HE_ENCRYPT_OP_SECRET_KEY:
-            return plan_secret_keys(pc, count).total();
+            return secret_keys_bytes(pc, count);
         case HE_ENCRYPT_OP_ENCRYPT_ZERO:
             if (moduli_count < 1 || moduli_count > pc.moduli_count()) return 0;
-            return plan_encrypt_zero(pc, moduli_count, eval_out != 0, count, word_bytes).total();
+            return plan_encrypt_zero(pc, moduli_count, eval_out != 0, count, word_bytes).total;
         case HE_ENCRYPT_OP_ENCRYPT:
             if (!bfv.valid(moduli_count)) return 0;
-            return plan_encrypt_zero(pc, moduli_count, false, count, word_bytes).total();
+            return plan_encrypt_zero(pc, moduli_count, false, count, word_bytes).total;
         case HE_ENCRYPT_OP_KEY_SWITCH_KEYS:
         case HE_ENCRYPT_OP_RELINEARIZATION_KEY:
         case HE_ENCRYPT_OP_GALOIS_KEYS:
             if (!bfv.has_key_switching()) return 0;
             return plan_key_switch_keys(bfv, operation == HE_ENCRYPT_OP_RELINEARIZATION_KEY ? 1 : count,
                                         operation != HE_ENCRYPT_OP_KEY_SWITCH_KEYS, word_bytes)
-                .total();
+                .total;
         default:
             return 0;
     }
@@ -295,23 +313,18 @@ int he_bfv_generate_secret_key_device(const he_bfv_context* ctx, uint32_t word_b
                               {"seeds", seeds, batch * 32, false}}));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, pc.moduli_count()));
     const hipStream_t stream = as_stream(s);
-    const EncryptPlan plan = plan_secret_keys(pc, batch);
     ZeroizedWorkspace ws(stream);
-    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total()));
-    uint32_t* chain = reinterpret_cast<uint32_t*>(ws.at(0));
+    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, secret_keys_bytes(pc, batch)));
+    uint32_t* chain = ws.at<uint32_t>(0);
     HEAMD_HIP_TRY(heamd::launch_seeded_chain(seeds, chain, batch, heamd::ternary_chunks(pc.degree()), stream));
     const DeviceContext dc = pc.device_context();
     const size_t poly_words = size_t(pc.moduli_count()) * pc.degree(), rows = batch * pc.moduli_count();
-    if (word_bits == 32) {
-        uint32_t* keys = static_cast<uint32_t*>(out);
+    return heamd::with_word(word_bits, [&](auto word) {
+        auto* keys = static_cast<decltype(word)*>(out);
         HEAMD_HIP_TRY(heamd::launch_sample_ternary(chain, keys, poly_words, dc, batch, stream));
         HEAMD_HIP_TRY(heamd::ntt_rows(false, keys, pc, dc, pc.moduli_count(), rows, stream));
-    } else {
-        uint64_t* keys = static_cast<uint64_t*>(out);
-        HEAMD_HIP_TRY(heamd::launch_sample_ternary(chain, keys, poly_words, dc, batch, stream));
-        HEAMD_HIP_TRY(heamd::ntt_rows(false, keys, pc, dc, pc.moduli_count(), rows, stream));
-    }
-    return HE_OK;
+        return int(HE_OK);
+    });
 }
 
 int he_bfv_encrypt_zero_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, int eval_out,
@@ -327,11 +340,10 @@ int he_bfv_encrypt_zero_device(const he_bfv_context* ctx, uint32_t word_bits, ui
     HEAMD_TRY_STATUS(check_encrypt_slabs("encryptZero", secret_key_context(*bfv), moduli_count, word_bits / 8, secret_key, a_seeds,
                                          error_seeds, {"", nullptr, 0, false}, out, batch, workspace, workspace_bytes));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, moduli_count));
-    if (word_bits == 32)
-        return encrypt_zero_entry<uint32_t>(*bfv, moduli_count, eval_out != 0, secret_key, a_seeds, error_seeds, nullptr, out,
-                                            batch, workspace, workspace_bytes, as_stream(s));
-    return encrypt_zero_entry<uint64_t>(*bfv, moduli_count, eval_out != 0, secret_key, a_seeds, error_seeds, nullptr, out, batch,
-                                        workspace, workspace_bytes, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return encrypt_zero_entry<decltype(word)>(*bfv, moduli_count, eval_out != 0, secret_key, a_seeds, error_seeds, nullptr, out,
+                                                  batch, workspace, workspace_bytes, as_stream(s));
+    });
 }
 
 int he_bfv_encrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count, const void* secret_key,
@@ -347,11 +359,10 @@ int he_bfv_encrypt_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_
                                          error_seeds, {"plaintexts", plaintexts, batch * bfv->degree() * (word_bits / 8), false}, out,
                                          batch, workspace, workspace_bytes));
     HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, moduli_count));
-    if (word_bits == 32)
-        return encrypt_zero_entry<uint32_t>(*bfv, moduli_count, false, secret_key, a_seeds, error_seeds, plaintexts, out, batch,
-                                            workspace, workspace_bytes, as_stream(s));
-    return encrypt_zero_entry<uint64_t>(*bfv, moduli_count, false, secret_key, a_seeds, error_seeds, plaintexts, out, batch,
-                                        workspace, workspace_bytes, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return encrypt_zero_entry<decltype(word)>(*bfv, moduli_count, false, secret_key, a_seeds, error_seeds, plaintexts, out, batch,
+                                                  workspace, workspace_bytes, as_stream(s));
+    });
 }
 
 int he_bfv_generate_key_switch_keys_device(const he_bfv_context* ctx, uint32_t word_bits, const void* secret_key,
@@ -360,21 +371,8 @@ int he_bfv_generate_key_switch_keys_device(const he_bfv_context* ctx, uint32_t w
     const BfvContext* bfv = nullptr;
     HEAMD_TRY_STATUS(check_key_generation(ctx, word_bits, &bfv));
     if (keys == 0) return HE_OK;
-    if (secret_key == nullptr || current_keys == nullptr || a_seeds == nullptr || error_seeds == nullptr || out == nullptr)
-        return invalid_argument("null keys or seeds");
-    {
-        const PolyContext& pc = secret_key_context(*bfv);  // (the secret key may itself be a current key: both are only read)
-        const size_t key_bytes = size_t(pc.moduli_count()) * pc.degree() * (word_bits / 8);
-        HEAMD_TRY_STATUS(check_encrypt_slabs("generateKeySwitchKey", pc, pc.moduli_count(), word_bits / 8, secret_key, a_seeds,
-                                             error_seeds, {"current_keys", current_keys, keys * key_bytes, false}, out,
-                                             keys * bfv->top_level(), workspace, workspace_bytes));
-    }
-    HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, bfv->top_level() + 1));
-    if (word_bits == 32)
-        return key_switch_keys_entry<uint32_t>(*bfv, CurrentKeys::Callers, secret_key, current_keys, nullptr, a_seeds,
-                                               error_seeds, out, keys, workspace, workspace_bytes, as_stream(s));
-    return key_switch_keys_entry<uint64_t>(*bfv, CurrentKeys::Callers, secret_key, current_keys, nullptr, a_seeds, error_seeds,
-                                           out, keys, workspace, workspace_bytes, as_stream(s));
+    return generate_key_switch_keys(*bfv, word_bits, CurrentKeys::Callers, "generateKeySwitchKey", secret_key, current_keys, nullptr,
+                                    a_seeds, error_seeds, out, keys, workspace, workspace_bytes, s);
 }
 
 int he_bfv_generate_relinearization_key_device(const he_bfv_context* ctx, uint32_t word_bits, const void* secret_key,
@@ -382,17 +380,8 @@ int he_bfv_generate_relinearization_key_device(const he_bfv_context* ctx, uint32
                                                size_t workspace_bytes, he_stream s) {
     const BfvContext* bfv = nullptr;
     HEAMD_TRY_STATUS(check_key_generation(ctx, word_bits, &bfv));
-    if (secret_key == nullptr || a_seeds == nullptr || error_seeds == nullptr || out == nullptr)
-        return invalid_argument("null keys or seeds");
-    HEAMD_TRY_STATUS(check_encrypt_slabs("generateRelinearizationKey", secret_key_context(*bfv), bfv->top_level() + 1, word_bits / 8,
-                                         secret_key, a_seeds, error_seeds, {"", nullptr, 0, false}, out, bfv->top_level(), workspace,
-                                         workspace_bytes));
-    HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, bfv->top_level() + 1));
-    if (word_bits == 32)
-        return key_switch_keys_entry<uint32_t>(*bfv, CurrentKeys::Square, secret_key, nullptr, nullptr, a_seeds, error_seeds, out,
-                                               1, workspace, workspace_bytes, as_stream(s));
-    return key_switch_keys_entry<uint64_t>(*bfv, CurrentKeys::Square, secret_key, nullptr, nullptr, a_seeds, error_seeds, out, 1,
-                                           workspace, workspace_bytes, as_stream(s));
+    return generate_key_switch_keys(*bfv, word_bits, CurrentKeys::Square, "generateRelinearizationKey", secret_key, nullptr, nullptr,
+                                    a_seeds, error_seeds, out, 1, workspace, workspace_bytes, s);
 }
 
 int he_bfv_generate_galois_keys_device(const he_bfv_context* ctx, uint32_t word_bits, const void* secret_key,
@@ -407,17 +396,8 @@ int he_bfv_generate_galois_keys_device(const he_bfv_context* ctx, uint32_t word_
         if ((elements[k] & 1) == 0 || elements[k] <= 1 || elements[k] >= 2 * uint64_t(bfv->degree()))
             return invalid_argument("invalid Galois element");
     if (count == 0) return HE_OK;
-    if (secret_key == nullptr || a_seeds == nullptr || error_seeds == nullptr || out == nullptr)
-        return invalid_argument("null keys or seeds");
-    HEAMD_TRY_STATUS(check_encrypt_slabs("generateGaloisKeys", secret_key_context(*bfv), bfv->top_level() + 1, word_bits / 8,
-                                         secret_key, a_seeds, error_seeds, {"", nullptr, 0, false}, out, count * bfv->top_level(),
-                                         workspace, workspace_bytes));
-    HEAMD_TRY_STATUS(check_encrypt_device(*bfv, word_bits, bfv->top_level() + 1));
-    if (word_bits == 32)
-        return key_switch_keys_entry<uint32_t>(*bfv, CurrentKeys::Galois, secret_key, nullptr, elements, a_seeds, error_seeds, out,
-                                               count, workspace, workspace_bytes, as_stream(s));
-    return key_switch_keys_entry<uint64_t>(*bfv, CurrentKeys::Galois, secret_key, nullptr, elements, a_seeds, error_seeds, out,
-                                           count, workspace, workspace_bytes, as_stream(s));
+    return generate_key_switch_keys(*bfv, word_bits, CurrentKeys::Galois, "generateGaloisKeys", secret_key, nullptr, elements, a_seeds,
+                                    error_seeds, out, count, workspace, workspace_bytes, s);
 }
 
 int he_poly_random_ternary_from_seeds_device(const he_poly_context* ctx, uint32_t word_bits, const uint8_t* seeds, size_t batch,

@@ -3,54 +3,27 @@
 // PirUtil.compressBinaryInputs (pir_client_kernels.hip), then he_bfv_encrypt_device -- and MulPirClient.decrypt(response:at:
 // using:) / decryptFull -- he_bfv_decrypt_device, then coefficientsToBytes and the entry extraction in one kernel.
 // Whatever a call parks in memory between its kernels says which entries a user asks for or what they hold: it lies in a
-// ZeroizedWorkspace, the helper and the rule of encrypt_api.cpp.
-#include "api_internal.hpp"
+// ZeroizedWorkspace, the helper and the rule of encrypt_api.cpp.  The first checks and the word dispatch: word_layer.hpp; the parts
+// of a workspace: workspace_layout.hpp; the checks and plans the keyword client builds on: pir_client_layer.hpp, defined here.
 #include "bfv_context.hpp"
 #include "launch_grid.hpp"
 #include "pir_client_kernels.hpp"
-#include "pir_client_plan.hpp"
+#include "pir_client_layer.hpp"
 #include "word_layer.hpp"
+#include "workspace_layout.hpp"
 #include "zeroized_workspace.hpp"
 
 using heamd::as_stream;
 using heamd::BfvContext;
+using heamd::check_word_and_context;
 using heamd::invalid_argument;
 using heamd::ZeroizedWorkspace;
-using heamd::pir_client::Plan;
+using namespace heamd::pir_client;
 
 extern "C++" {
 namespace {
 
-size_t round16(size_t bytes) { return (bytes + 15) & ~size_t(15); }
-
 constexpr uint64_t kMaxIndices = uint64_t(1) << 20;  // indices of a query (S I stays far below 2^64)
-
-// the checks every device entry makes first, in this order: the word, the context, the word against the context's scheme (as
-// he_bfv_encrypt_device and he_bfv_decrypt_device: a Bfv<UInt32> context serves 8-byte slabs too)
-int check_word_and_context(const he_bfv_context* ctx, uint32_t word_bits) {
-    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
-    if (ctx == nullptr) return invalid_argument("null context");
-    if (word_bits == 32 && heamd::bfv_impl(ctx).word_bits() != 32) return invalid_argument("4-byte slabs need a Bfv<UInt32> context");
-    return HE_OK;
-}
-
-// The IndexPirParameter and the index count of a query: he_pir_database_shape's errors, then the client's own
-int client_plan(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, size_t entry_count,
-                size_t entry_size_in_bytes, int encoding_entry_size, size_t indices_count, Plan& plan) {
-    HEAMD_TRY_STATUS(he_pir_database_shape(ctx, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
-                                           nullptr, nullptr, nullptr, nullptr, nullptr));
-    if (indices_count == 0) return invalid_argument("a query has at least one index");
-    if (indices_count > kMaxIndices) return invalid_argument("too many indices");
-    if (dimension_count > heamd::pir_client::kMaxDimensions) {
-        heamd::set_last_error("the client takes at most 16 dimensions");
-        return HE_ERR_UNSUPPORTED;
-    }
-    const BfvContext& bfv = heamd::bfv_impl(ctx);
-    plan = heamd::pir_client::plan(bfv.degree(), bfv.plaintext_modulus(), dimensions, dimension_count, entry_count,
-                                   entry_size_in_bytes, encoding_entry_size != 0, indices_count);
-    if (plan.bytes_per_plaintext * 8 != plan.degree * plan.bits) return invalid_argument("plaintexts hold no whole bytes");
-    return HE_OK;
-}
 
 // queries x per_query items of `lanes_each` lanes: one launch holds them, and no byte count below wraps
 int check_batch(size_t queries, uint64_t per_query, uint64_t lanes_each) {
@@ -61,57 +34,87 @@ int check_batch(size_t queries, uint64_t per_query, uint64_t lanes_each) {
 }
 
 // ---- generateQuery ----------------------------------------------------------------------------------------------------------------
-struct QueryPlan {
-    Plan client;
-    uint64_t first = 0, last = 0;  // compressInputsForOneCiphertext's value of every ciphertext but the last, and of the last
-    size_t plaintexts = 0, encrypt = 0;
-    size_t total() const { return plaintexts + encrypt; }
-};
-int plan_query(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions, uint32_t dimension_count,
-               size_t entry_count, size_t entry_size_in_bytes, int encoding_entry_size, size_t indices_count, size_t queries,
-               QueryPlan& plan) {
-    HEAMD_TRY_STATUS(client_plan(ctx, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
-                                 indices_count, plan.client));
-    const Plan& p = plan.client;
-    HEAMD_TRY_STATUS(check_batch(queries, p.query_ciphertexts, p.degree));
-    const BfvContext& bfv = heamd::bfv_impl(ctx);
-    const heamd::u64 t = bfv.plaintext_modulus();
-    if (!heamd::pir_client::selection_value(heamd::pir_client::input_count(p, 0), t, plan.first) ||
-        !heamd::pir_client::selection_value(heamd::pir_client::input_count(p, p.query_ciphertexts - 1), t, plan.last)) {
-        heamd::set_last_error("the input count's power of two has no inverse mod t");
-        return HE_ERR_NOT_INVERTIBLE;
-    }
-    const size_t count = queries * p.query_ciphertexts;
-    plan.plaintexts = round16(count * p.degree * (word_bits / 8));
-    plan.encrypt = round16(he_bfv_encrypt_workspace_bytes(ctx, word_bits, HE_ENCRYPT_OP_ENCRYPT, bfv.top_level(), 0, count));
-    return HE_OK;
-}
-
 template <typename W>
 int generate_query(const he_bfv_context* ctx, const QueryPlan& plan, const uint64_t* indices, size_t queries,
                    const void* secret_key, const uint8_t* a_seeds, const uint8_t* error_seeds, void* out, uint32_t* out_of_range,
                    void* workspace, size_t workspace_bytes, he_stream s) {
     hipStream_t stream = as_stream(s);
     ZeroizedWorkspace ws(stream);
-    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total()));
-    W* plaintexts = reinterpret_cast<W*>(ws.at(0));
+    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total));
+    W* plaintexts = ws.at<W>(0);
     HEAMD_HIP_TRY(heamd::launch_pir_selection_plaintexts(indices, plan.client, queries, plan.first, plan.last, plaintexts,
                                                          out_of_range, stream));
     // plaintexts.map { try $0.encrypt(using: secretKey) } (PirUtil.swift:403): Coeff at the top level
     return he_bfv_encrypt_device(ctx, 8 * sizeof(W), heamd::bfv_impl(ctx).top_level(), secret_key, a_seeds, error_seeds, plaintexts,
-                                 out, queries * plan.client.query_ciphertexts, ws.at(plan.plaintexts), plan.encrypt, s);
+                                 out, queries * plan.client.query_ciphertexts, ws.at(plan.nested), plan.total - plan.nested, s);
 }
 
 // ---- decrypt(response:) -----------------------------------------------------------------------------------------------------------
-struct ResponsePlan {
-    Plan client;
-    size_t replies = 0;  // ciphertexts: queries I R
-    size_t out_stride = 0, plaintexts = 0, decrypt = 0;
-    size_t total() const { return plaintexts + decrypt; }
-};
-int plan_response(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions, uint32_t dimension_count,
-                  size_t entry_count, size_t entry_size_in_bytes, int encoding_entry_size, size_t indices_count,
-                  uint32_t moduli_count, bool full, size_t queries, ResponsePlan& plan) {
+template <typename W>
+int decrypt_response(const he_bfv_context* ctx, const ResponsePlan& plan, uint32_t moduli_count, const void* response,
+                     const uint64_t* indices, size_t queries, const void* secret_key, uint8_t* out_entries, uint64_t* out_sizes,
+                     void* workspace, size_t workspace_bytes, he_stream s) {
+    hipStream_t stream = as_stream(s);
+    ZeroizedWorkspace ws(stream);
+    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total));
+    W* plaintexts = ws.at<W>(0);  // [queries][I][R][N]
+    // ciphertext.decrypt(using:) and decode(format: .coefficient) (MulPir.swift:257-258)
+    HEAMD_TRY_STATUS(he_bfv_decrypt_device(ctx, 8 * sizeof(W), moduli_count, 2, 0, response, secret_key, 1, plaintexts, plan.replies,
+                                           ws.at(plan.nested), plan.total - plan.nested, s));
+    HEAMD_HIP_TRY(heamd::launch_pir_reply_entries(plaintexts, indices, plan.client, queries, out_entries, out_sizes, stream));
+    return HE_OK;
+}
+
+}  // namespace
+
+// ---- pir_client_layer.hpp ---------------------------------------------------------------------------------------------------------
+// he_pir_database_shape's errors, then the client's own
+int heamd::pir_client::client_plan(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count,
+                                   size_t entry_count, size_t entry_size_in_bytes, int encoding_entry_size, size_t indices_count,
+                                   Plan& plan) {
+    HEAMD_TRY_STATUS(he_pir_database_shape(ctx, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr));
+    if (indices_count == 0) return invalid_argument("a query has at least one index");
+    if (indices_count > kMaxIndices) return invalid_argument("too many indices");
+    if (dimension_count > kMaxDimensions) {
+        heamd::set_last_error("the client takes at most 16 dimensions");
+        return HE_ERR_UNSUPPORTED;
+    }
+    const BfvContext& bfv = heamd::bfv_impl(ctx);
+    plan = heamd::pir_client::plan(bfv.degree(), bfv.plaintext_modulus(), dimensions, dimension_count, entry_count,
+                                   entry_size_in_bytes, encoding_entry_size != 0, indices_count);
+    if (plan.bytes_per_plaintext * 8 != plan.degree * plan.bits) return invalid_argument("plaintexts hold no whole bytes");
+    return HE_OK;
+}
+
+int heamd::pir_client::plan_query(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                  uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes, int encoding_entry_size,
+                                  size_t indices_count, size_t queries, QueryPlan& plan) {
+    HEAMD_TRY_STATUS(check_word_and_context(ctx, word_bits));
+    HEAMD_TRY_STATUS(client_plan(ctx, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
+                                 indices_count, plan.client));
+    const Plan& p = plan.client;
+    HEAMD_TRY_STATUS(check_batch(queries, p.query_ciphertexts, p.degree));
+    const BfvContext& bfv = heamd::bfv_impl(ctx);
+    const heamd::u64 t = bfv.plaintext_modulus();
+    if (!selection_value(input_count(p, 0), t, plan.first) ||
+        !selection_value(input_count(p, p.query_ciphertexts - 1), t, plan.last)) {
+        heamd::set_last_error("the input count's power of two has no inverse mod t");
+        return HE_ERR_NOT_INVERTIBLE;
+    }
+    const size_t count = queries * p.query_ciphertexts;
+    heamd::WorkspaceLayout layout;
+    layout.add(count * p.degree * (word_bits / 8));
+    plan.nested = layout.add(he_bfv_encrypt_workspace_bytes(ctx, word_bits, HE_ENCRYPT_OP_ENCRYPT, bfv.top_level(), 0, count));
+    plan.total = layout.total();
+    return HE_OK;
+}
+
+int heamd::pir_client::plan_response(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
+                                     uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
+                                     int encoding_entry_size, size_t indices_count, uint32_t moduli_count, bool full, size_t queries,
+                                     ResponsePlan& plan) {
+    HEAMD_TRY_STATUS(check_word_and_context(ctx, word_bits));
     HEAMD_TRY_STATUS(client_plan(ctx, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
                                  indices_count, plan.client));
     const Plan& p = plan.client;
@@ -120,27 +123,12 @@ int plan_response(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t*
     plan.out_stride = full ? p.reply_ciphertexts * p.bytes_per_plaintext : p.entry_size;
     HEAMD_TRY_STATUS(check_batch(queries, p.indices_count, plan.out_stride ? plan.out_stride : 1));
     plan.replies = queries * p.indices_count * p.reply_ciphertexts;
-    plan.plaintexts = round16(plan.replies * p.degree * (word_bits / 8));
-    plan.decrypt = round16(he_bfv_decrypt_workspace_bytes(ctx, word_bits, moduli_count, 2, 0, plan.replies));
+    heamd::WorkspaceLayout layout;
+    layout.add(plan.replies * p.degree * (word_bits / 8));
+    plan.nested = layout.add(he_bfv_decrypt_workspace_bytes(ctx, word_bits, moduli_count, 2, 0, plan.replies));
+    plan.total = layout.total();
     return HE_OK;
 }
-
-template <typename W>
-int decrypt_response(const he_bfv_context* ctx, const ResponsePlan& plan, uint32_t moduli_count, const void* response,
-                     const uint64_t* indices, size_t queries, const void* secret_key, uint8_t* out_entries, uint64_t* out_sizes,
-                     void* workspace, size_t workspace_bytes, he_stream s) {
-    hipStream_t stream = as_stream(s);
-    ZeroizedWorkspace ws(stream);
-    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total()));
-    W* plaintexts = reinterpret_cast<W*>(ws.at(0));  // [queries][I][R][N]
-    // ciphertext.decrypt(using:) and decode(format: .coefficient) (MulPir.swift:257-258)
-    HEAMD_TRY_STATUS(he_bfv_decrypt_device(ctx, 8 * sizeof(W), moduli_count, 2, 0, response, secret_key, 1, plaintexts, plan.replies,
-                                           ws.at(plan.plaintexts), plan.decrypt, s));
-    HEAMD_HIP_TRY(heamd::launch_pir_reply_entries(plaintexts, indices, plan.client, queries, out_entries, out_sizes, stream));
-    return HE_OK;
-}
-
-}  // namespace
 }  // extern "C++"
 
 int he_pir_client_plan(const he_bfv_context* ctx, const uint32_t* dimensions, uint32_t dimension_count, size_t entry_count,
@@ -178,11 +166,9 @@ size_t he_pir_generate_query_workspace_bytes(const he_bfv_context* ctx, uint32_t
                                              uint32_t dimension_count, size_t entry_count, size_t entry_size_in_bytes,
                                              int encoding_entry_size, size_t indices_count, size_t queries) {
     QueryPlan plan;
-    if (check_word_and_context(ctx, word_bits) != HE_OK ||
-        plan_query(ctx, word_bits, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size, indices_count,
-                   queries, plan) != HE_OK)
-        return 0;
-    return plan.total();
+    const int status = plan_query(ctx, word_bits, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
+                                  indices_count, queries, plan);
+    return status == HE_OK ? plan.total : 0;
 }
 
 int he_pir_generate_query_device(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
@@ -190,7 +176,6 @@ int he_pir_generate_query_device(const he_bfv_context* ctx, uint32_t word_bits, 
                                  size_t indices_count, const uint64_t* indices, size_t queries, const void* secret_key,
                                  const uint8_t* a_seeds, const uint8_t* error_seeds, void* out, uint32_t* out_of_range,
                                  void* workspace, size_t workspace_bytes, he_stream s) {
-    HEAMD_TRY_STATUS(check_word_and_context(ctx, word_bits));
     QueryPlan plan;
     HEAMD_TRY_STATUS(plan_query(ctx, word_bits, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
                                 indices_count, queries, plan));
@@ -207,11 +192,10 @@ int he_pir_generate_query_device(const he_bfv_context* ctx, uint32_t word_bits, 
                                                           {"a_seeds", a_seeds, count * 32, false},
                                                           {"error_seeds", error_seeds, count * 32, false}}));
     HEAMD_TRY_STATUS(heamd::bfv_encrypt_check_device(ctx, word_bits, bfv.top_level()));
-    if (word_bits == 32)
-        return generate_query<uint32_t>(ctx, plan, indices, queries, secret_key, a_seeds, error_seeds, out, out_of_range, workspace,
-                                        workspace_bytes, s);
-    return generate_query<uint64_t>(ctx, plan, indices, queries, secret_key, a_seeds, error_seeds, out, out_of_range, workspace,
-                                    workspace_bytes, s);
+    return heamd::with_word(word_bits, [&](auto word) {
+        return generate_query<decltype(word)>(ctx, plan, indices, queries, secret_key, a_seeds, error_seeds, out, out_of_range,
+                                              workspace, workspace_bytes, s);
+    });
 }
 
 size_t he_pir_decrypt_response_workspace_bytes(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
@@ -219,11 +203,9 @@ size_t he_pir_decrypt_response_workspace_bytes(const he_bfv_context* ctx, uint32
                                                int encoding_entry_size, size_t indices_count, uint32_t moduli_count,
                                                size_t queries) {
     ResponsePlan plan;
-    if (check_word_and_context(ctx, word_bits) != HE_OK ||
-        plan_response(ctx, word_bits, dimensions, dimension_count, entry_count, entry_size_in_bytes, encoding_entry_size,
-                      indices_count, moduli_count, false, queries, plan) != HE_OK)
-        return 0;
-    return plan.total();
+    const int status = plan_response(ctx, word_bits, dimensions, dimension_count, entry_count, entry_size_in_bytes,
+                                     encoding_entry_size, indices_count, moduli_count, false, queries, plan);
+    return status == HE_OK ? plan.total : 0;
 }
 
 int he_pir_decrypt_response_device(const he_bfv_context* ctx, uint32_t word_bits, const uint32_t* dimensions,
@@ -231,7 +213,6 @@ int he_pir_decrypt_response_device(const he_bfv_context* ctx, uint32_t word_bits
                                    int encoding_entry_size, size_t indices_count, uint32_t moduli_count, const void* response,
                                    const uint64_t* indices, size_t queries, const void* secret_key, uint8_t* out_entries,
                                    uint64_t* out_sizes, void* workspace, size_t workspace_bytes, he_stream s) {
-    HEAMD_TRY_STATUS(check_word_and_context(ctx, word_bits));
     ResponsePlan plan;
     HEAMD_TRY_STATUS(plan_response(ctx, word_bits, dimensions, dimension_count, entry_count, entry_size_in_bytes,
                                    encoding_entry_size, indices_count, moduli_count, indices == nullptr, queries, plan));
@@ -248,11 +229,9 @@ int he_pir_decrypt_response_device(const he_bfv_context* ctx, uint32_t word_bits
                                                                {"response", response, plan.replies * 2 * moduli_count * row_bytes, false},
                                                                {"indices", indices, entries * sizeof(uint64_t), false},
                                                                {"secret_key", secret_key, moduli_count * row_bytes, false}}));
-    // the level and device checks of he_bfv_decrypt_device: an empty batch checks and enqueues nothing
-    HEAMD_TRY_STATUS(he_bfv_decrypt_device(ctx, word_bits, moduli_count, 2, 0, nullptr, nullptr, 1, nullptr, 0, nullptr, 0, s));
-    if (word_bits == 32)
-        return decrypt_response<uint32_t>(ctx, plan, moduli_count, response, indices, queries, secret_key, out_entries, out_sizes,
-                                          workspace, workspace_bytes, s);
-    return decrypt_response<uint64_t>(ctx, plan, moduli_count, response, indices, queries, secret_key, out_entries, out_sizes,
-                                      workspace, workspace_bytes, s);
+    HEAMD_TRY_STATUS(heamd::bfv_decrypt_check_device(ctx, word_bits, moduli_count));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return decrypt_response<decltype(word)>(ctx, plan, moduli_count, response, indices, queries, secret_key, out_entries,
+                                                out_sizes, workspace, workspace_bytes, s);
+    });
 }

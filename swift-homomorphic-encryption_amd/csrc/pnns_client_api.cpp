@@ -7,7 +7,9 @@
 //      Client.decrypt(response:using:) -- he_bfv_decrypt_device and forwardNtt per plaintext modulus, then one kernel that gathers,
 //      composes (CrtComposer.swift:76-97), centres and scales every distance.
 // Whatever a call parks in memory between its kernels is the user's query or the distances in the clear: it lies in a
-// ZeroizedWorkspace, the helper and the rule of encrypt_api.cpp.
+// ZeroizedWorkspace, the helper and the rule of encrypt_api.cpp.  The word check, the word dispatch and the named device checks of
+// the nested entries: word_layer.hpp; the parts of a workspace: workspace_layout.hpp.
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 
@@ -17,6 +19,7 @@
 #include "kernels.hpp"
 #include "pnns_context.hpp"
 #include "word_layer.hpp"
+#include "workspace_layout.hpp"
 #include "zeroized_workspace.hpp"
 
 using heamd::as_stream;
@@ -29,11 +32,9 @@ using heamd::ZeroizedWorkspace;
 extern "C++" {
 namespace {
 
-size_t round16(size_t bytes) { return (bytes + 15) & ~size_t(15); }
-
 // the checks every entry of one context makes first, in this order: the word, the context, the word against the context's kind
 int check_word_and_context(const he_pnns_context* ctx, uint32_t word_bits) {
-    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    HEAMD_TRY_STATUS(heamd::check_word_bits(word_bits));
     if (ctx == nullptr) return invalid_argument("null context");
     if (heamd::bfv_impl(ctx->bfv).word_bits() != static_cast<int>(word_bits))
         return invalid_argument("word_bits is not the word of the context's scheme");
@@ -41,10 +42,7 @@ int check_word_and_context(const he_pnns_context* ctx, uint32_t word_bits) {
 }
 // ... and last, behind every argument check
 int check_device(const he_pnns_context* ctx) {
-    if (heamd::bfv_impl(ctx->bfv).host_only()) {
-        heamd::set_last_error("context was created host-only (no device tables)");
-        return HE_ERR_DEVICE;
-    }
+    if (heamd::bfv_impl(ctx->bfv).host_only()) return heamd::host_only_refusal();
     return ctx->plaintext->check_device();
 }
 
@@ -71,7 +69,7 @@ int simd_decode(const he_pnns_context* ctx, const void* plaintexts, size_t batch
     const size_t bytes = batch * ring.degree() * sizeof(W);
     ZeroizedWorkspace ws(stream);
     HEAMD_TRY_STATUS(ws.resolve(nullptr, 0, bytes));
-    W* copy = reinterpret_cast<W*>(ws.at(0));
+    W* copy = ws.at<W>(0);
     HEAMD_HIP_TRY(hipMemcpyAsync(copy, plaintexts, bytes, hipMemcpyDeviceToDevice, stream));
     HEAMD_TRY_STATUS(transform(ctx, false, copy, batch, stream));
     HEAMD_HIP_TRY(heamd::launch_pnns_simd_gather(copy, ctx->word_of_slot_device(), ring.log_degree(), batch,
@@ -82,14 +80,9 @@ int simd_decode(const he_pnns_context* ctx, const void* plaintexts, size_t batch
 // ---- layer 2 ----------------------------------------------------------------------------------------------------------------------
 constexpr size_t kMaxValues = size_t(1) << 40;  // values of a matrix (no product of sizes below wraps)
 
-int dense_row_plan(const he_pnns_context* ctx, size_t rows, size_t cols, MatrixPlan& plan) {
-    HEAMD_TRY_STATUS(heamd::matrix_plan(ctx, rows, cols, HE_PNNS_PACKING_DENSE_ROW, 0, plan));
-    if (rows > kMaxValues / cols || plan.plaintext_count > kMaxValues / ctx->plaintext->degree())
-        return invalid_argument("matrix too large");
-    return HE_OK;
-}
-int dense_column_plan(const he_pnns_context* ctx, size_t rows, size_t cols, MatrixPlan& plan) {
-    HEAMD_TRY_STATUS(heamd::matrix_plan(ctx, rows, cols, HE_PNNS_PACKING_DENSE_COLUMN, 0, plan));
+// packing: HE_PNNS_PACKING_DENSE_ROW or HE_PNNS_PACKING_DENSE_COLUMN
+int dense_plan(const he_pnns_context* ctx, int packing, size_t rows, size_t cols, MatrixPlan& plan) {
+    HEAMD_TRY_STATUS(heamd::matrix_plan(ctx, rows, cols, packing, 0, plan));
     if (rows > kMaxValues / cols || plan.plaintext_count > kMaxValues / ctx->plaintext->degree())
         return invalid_argument("matrix too large");
     return HE_OK;
@@ -119,7 +112,7 @@ int unpack(const he_pnns_context* ctx, const MatrixPlan& plan, bool dense_row, c
     const size_t bytes = plan.plaintext_count * ring.degree() * sizeof(W);
     ZeroizedWorkspace ws(stream);
     HEAMD_TRY_STATUS(ws.resolve(nullptr, 0, bytes));
-    W* copy = reinterpret_cast<W*>(ws.at(0));
+    W* copy = ws.at<W>(0);
     HEAMD_HIP_TRY(hipMemcpyAsync(copy, plaintexts, bytes, hipMemcpyDeviceToDevice, stream));
     HEAMD_TRY_STATUS(transform(ctx, false, copy, plan.plaintext_count, stream));
     heamd::PnnsUnpackLayout layout{};
@@ -142,7 +135,7 @@ const std::vector<heamd::u64>& all_moduli(const BfvContext& bfv) {
 // the word, the array, every context and its word, one degree and one set of coefficient moduli, distinct plaintext moduli,
 // 2 q <= UInt64.max.  tables: what compose needs, inversePuncturedProducts from the host (CrtComposer.swift:34-47).
 int check_client_contexts(const he_pnns_context* const* ctxs, size_t count, uint32_t word_bits, heamd::PnnsComposeTables& tables) {
-    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    HEAMD_TRY_STATUS(heamd::check_word_bits(word_bits));
     if (ctxs == nullptr) return invalid_argument("null contexts");
     if (count == 0 || count > heamd::kPnnsMaxClientContexts) return invalid_argument("context_count must be 1..8");
     for (size_t i = 0; i < count; ++i) HEAMD_TRY_STATUS(check_word_and_context(ctxs[i], word_bits));
@@ -179,23 +172,24 @@ int check_client_contexts(const he_pnns_context* const* ctxs, size_t count, uint
     return HE_OK;
 }
 
-// The parts of a generateQuery workspace, in bytes from its start
+// Where the parts of a generateQuery workspace lie, in bytes from its start: the quantised query at 0, the staged plaintexts,
+// and from `encrypt` to `total` he_bfv_encrypt_device's workspace, the largest any context asks for
 struct QueryPlan {
     MatrixPlan matrix;
-    size_t quantised = 0, staging = 0, encrypt = 0;
-    size_t total() const { return quantised + staging + encrypt; }
+    size_t staging = 0, encrypt = 0, total = 0;
 };
 int plan_query(const he_pnns_context* const* ctxs, size_t count, uint32_t word_bits, size_t query_rows, size_t cols, QueryPlan& plan) {
-    HEAMD_TRY_STATUS(dense_row_plan(ctxs[0], query_rows, cols, plan.matrix));
+    HEAMD_TRY_STATUS(dense_plan(ctxs[0], HE_PNNS_PACKING_DENSE_ROW, query_rows, cols, plan.matrix));
     const BfvContext& bfv = heamd::bfv_impl(ctxs[0]->bfv);
-    plan.quantised = round16(query_rows * cols * sizeof(int64_t));
-    plan.staging = round16(plan.matrix.plaintext_count * bfv.degree() * (word_bits / 8));
-    plan.encrypt = 0;
-    for (size_t i = 0; i < count; ++i) {
-        const size_t bytes = round16(he_bfv_encrypt_workspace_bytes(ctxs[i]->bfv, word_bits, HE_ENCRYPT_OP_ENCRYPT, bfv.top_level(),
-                                                                   0, plan.matrix.plaintext_count));
-        if (bytes > plan.encrypt) plan.encrypt = bytes;
-    }
+    heamd::WorkspaceLayout layout;
+    layout.add(query_rows * cols * sizeof(int64_t));
+    plan.staging = layout.add(plan.matrix.plaintext_count * bfv.degree() * (word_bits / 8));
+    size_t encrypt_bytes = 0;
+    for (size_t i = 0; i < count; ++i)
+        encrypt_bytes = std::max(encrypt_bytes, he_bfv_encrypt_workspace_bytes(ctxs[i]->bfv, word_bits, HE_ENCRYPT_OP_ENCRYPT,
+                                                                               bfv.top_level(), 0, plan.matrix.plaintext_count));
+    plan.encrypt = layout.add(encrypt_bytes);
+    plan.total = layout.total();
     return HE_OK;
 }
 
@@ -208,10 +202,9 @@ int generate_query(const he_pnns_context* const* ctxs, size_t count, const Query
     const uint32_t L = bfv.top_level();
     const size_t K = plan.matrix.plaintext_count, ct_words = size_t(2) * L * bfv.degree();
     ZeroizedWorkspace ws(stream);
-    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total()));
-    int64_t* quantised = reinterpret_cast<int64_t*>(ws.at(0));
-    W* staging = reinterpret_cast<W*>(ws.at(plan.quantised));
-    void* encrypt_ws = ws.at(plan.quantised + plan.staging);
+    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total));
+    int64_t* quantised = ws.at<int64_t>(0);
+    W* staging = ws.at<W>(plan.staging);
     // vectors.normalizedScaledAndRounded(scalingFactor:) (Client.swift:77-78), once for every context
     HEAMD_HIP_TRY(heamd::launch_pnns_quantize_rows(vectors, query_rows, cols, scaling_factor, quantised, stream));
     for (size_t i = 0; i < count; ++i) {
@@ -220,7 +213,7 @@ int generate_query(const he_pnns_context* const* ctxs, size_t count, const Query
                                             stream));
         HEAMD_TRY_STATUS(he_bfv_encrypt_device(ctxs[i]->bfv, 8 * sizeof(W), L, secret_key, a_seeds + i * K * 32,
                                                error_seeds + i * K * 32, staging, static_cast<W*>(out) + i * K * ct_words, K,
-                                               encrypt_ws, plan.encrypt, s));
+                                               ws.at(plan.encrypt), plan.total - plan.encrypt, s));
     }
     return HE_OK;
 }
@@ -237,23 +230,24 @@ size_t response_group(size_t plaintexts, size_t n, size_t count, uint32_t moduli
     return group ? group : 1;
 }
 
+// ... of a decrypt(response:) workspace: the plaintexts of a group at 0, from `decrypt` to `total` he_bfv_decrypt_device's
 struct ResponsePlan {
     MatrixPlan matrix;
-    size_t group = 0, plaintexts = 0, decrypt = 0;
-    size_t total() const { return plaintexts + decrypt; }
+    size_t group = 0, decrypt = 0, total = 0;
 };
 int plan_response(const he_pnns_context* const* ctxs, size_t count, uint32_t word_bits, uint32_t moduli_count, size_t rows,
                   size_t query_rows, ResponsePlan& plan) {
-    HEAMD_TRY_STATUS(dense_column_plan(ctxs[0], rows, query_rows, plan.matrix));
+    HEAMD_TRY_STATUS(dense_plan(ctxs[0], HE_PNNS_PACKING_DENSE_COLUMN, rows, query_rows, plan.matrix));
     const BfvContext& bfv = heamd::bfv_impl(ctxs[0]->bfv);
     if (!bfv.valid(moduli_count)) return invalid_argument("moduli_count out of range");
     plan.group = response_group(plan.matrix.plaintext_count, bfv.degree(), count, moduli_count, word_bits / 8);
-    plan.plaintexts = round16(count * plan.group * bfv.degree() * (word_bits / 8));
-    plan.decrypt = 0;
-    for (size_t i = 0; i < count; ++i) {
-        const size_t bytes = round16(he_bfv_decrypt_workspace_bytes(ctxs[i]->bfv, word_bits, moduli_count, 2, 0, plan.group));
-        if (bytes > plan.decrypt) plan.decrypt = bytes;
-    }
+    heamd::WorkspaceLayout layout;
+    layout.add(count * plan.group * bfv.degree() * (word_bits / 8));
+    size_t decrypt_bytes = 0;
+    for (size_t i = 0; i < count; ++i)
+        decrypt_bytes = std::max(decrypt_bytes, he_bfv_decrypt_workspace_bytes(ctxs[i]->bfv, word_bits, moduli_count, 2, 0, plan.group));
+    plan.decrypt = layout.add(decrypt_bytes);
+    plan.total = layout.total();
     return HE_OK;
 }
 
@@ -276,9 +270,8 @@ int decrypt_response(const he_pnns_context* const* ctxs, size_t count, const Res
     const size_t n = bfv.degree(), M = plan.matrix.plaintext_count, total = rows * query_rows;
     const size_t ct_words = size_t(2) * moduli_count * n;
     ZeroizedWorkspace ws(stream);
-    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total()));
-    W* plaintexts = reinterpret_cast<W*>(ws.at(0));  // [count][group][N]
-    void* decrypt_ws = ws.at(plan.plaintexts);
+    HEAMD_TRY_STATUS(ws.resolve(workspace, workspace_bytes, plan.total));
+    W* plaintexts = ws.at<W>(0);  // [count][group][N]
     for (size_t first = 0; first < M; first += plan.group) {
         const size_t now = M - first < plan.group ? M - first : plan.group;
         for (size_t i = 0; i < count; ++i) {
@@ -286,7 +279,7 @@ int decrypt_response(const he_pnns_context* const* ctxs, size_t count, const Res
             W* mine = plaintexts + i * plan.group * n;
             HEAMD_TRY_STATUS(he_bfv_decrypt_device(ctxs[i]->bfv, 8 * sizeof(W), moduli_count, 2, 0,
                                                    static_cast<const W*>(response) + (i * M + first) * ct_words, secret_key, 1, mine,
-                                                   now, decrypt_ws, plan.decrypt, s));
+                                                   now, ws.at(plan.decrypt), plan.total - plan.decrypt, s));
             HEAMD_TRY_STATUS(transform(ctxs[i], false, mine, now, stream));
         }
         heamd::PnnsComposeLayout layout{};
@@ -318,8 +311,9 @@ int he_pnns_simd_encode_device(const he_pnns_context* ctx, uint32_t word_bits, c
                                                        {"out_of_range", out_of_range, sizeof(uint32_t), true},
                                                        {"slots", slots, bytes, false}}));
     HEAMD_TRY_STATUS(check_device(ctx));
-    if (word_bits == 32) return simd_encode<uint32_t>(ctx, slots, batch, out_plaintexts, out_of_range, as_stream(s));
-    return simd_encode<uint64_t>(ctx, slots, batch, out_plaintexts, out_of_range, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return simd_encode<decltype(word)>(ctx, slots, batch, out_plaintexts, out_of_range, as_stream(s));
+    });
 }
 
 int he_pnns_simd_decode_device(const he_pnns_context* ctx, uint32_t word_bits, const void* plaintexts, size_t batch,
@@ -331,36 +325,34 @@ int he_pnns_simd_decode_device(const he_pnns_context* ctx, uint32_t word_bits, c
     const size_t bytes = batch * ctx->plaintext->degree() * (word_bits / 8);
     HEAMD_TRY_STATUS(heamd::check_slabs("decodeSimd", {{"out_slots", out_slots, bytes, true}, {"plaintexts", plaintexts, bytes, false}}));
     HEAMD_TRY_STATUS(check_device(ctx));
-    if (word_bits == 32) return simd_decode<uint32_t>(ctx, plaintexts, batch, out_slots, as_stream(s));
-    return simd_decode<uint64_t>(ctx, plaintexts, batch, out_slots, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return simd_decode<decltype(word)>(ctx, plaintexts, batch, out_slots, as_stream(s));
+    });
 }
 
 int he_pnns_pack_dense_rows_device(const he_pnns_context* ctx, uint32_t word_bits, const int64_t* signed_values, size_t rows,
                                    size_t cols, int reduce, void* out_plaintexts, uint32_t* out_of_range, he_stream s) {
     HEAMD_TRY_STATUS(check_word_and_context(ctx, word_bits));
     MatrixPlan plan;
-    HEAMD_TRY_STATUS(dense_row_plan(ctx, rows, cols, plan));
+    HEAMD_TRY_STATUS(dense_plan(ctx, HE_PNNS_PACKING_DENSE_ROW, rows, cols, plan));
     if (signed_values == nullptr || out_plaintexts == nullptr) return invalid_argument("null buffer");
     HEAMD_TRY_STATUS(heamd::check_slabs(
         "denseRowPlaintexts", {{"out_plaintexts", out_plaintexts, plan.plaintext_count * ctx->plaintext->degree() * (word_bits / 8), true},
                                {"out_of_range", out_of_range, sizeof(uint32_t), true},
                                {"signed_values", signed_values, rows * cols * sizeof(int64_t), false}}));
     HEAMD_TRY_STATUS(check_device(ctx));
-    if (word_bits == 32)
-        return pack_dense_rows(ctx, plan, signed_values, rows, cols, reduce != 0, static_cast<uint32_t*>(out_plaintexts), out_of_range,
-                               as_stream(s));
-    return pack_dense_rows(ctx, plan, signed_values, rows, cols, reduce != 0, static_cast<uint64_t*>(out_plaintexts), out_of_range,
-                           as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return pack_dense_rows(ctx, plan, signed_values, rows, cols, reduce != 0, static_cast<decltype(word)*>(out_plaintexts),
+                               out_of_range, as_stream(s));
+    });
 }
 
 int he_pnns_unpack_device(const he_pnns_context* ctx, uint32_t word_bits, int packing, const void* plaintexts, size_t rows,
                           size_t cols, uint64_t* out_values, he_stream s) {
     HEAMD_TRY_STATUS(check_word_and_context(ctx, word_bits));
     MatrixPlan plan;
-    if (packing == HE_PNNS_PACKING_DENSE_ROW) {
-        HEAMD_TRY_STATUS(dense_row_plan(ctx, rows, cols, plan));
-    } else if (packing == HE_PNNS_PACKING_DENSE_COLUMN) {
-        HEAMD_TRY_STATUS(dense_column_plan(ctx, rows, cols, plan));
+    if (packing == HE_PNNS_PACKING_DENSE_ROW || packing == HE_PNNS_PACKING_DENSE_COLUMN) {
+        HEAMD_TRY_STATUS(dense_plan(ctx, packing, rows, cols, plan));
     } else if (packing == HE_PNNS_PACKING_DIAGONAL) {
         heamd::set_last_error("unpackDiagonal is not on the device");
         return HE_ERR_UNSUPPORTED;
@@ -373,18 +365,18 @@ int he_pnns_unpack_device(const he_pnns_context* ctx, uint32_t word_bits, int pa
                    {"plaintexts", plaintexts, plan.plaintext_count * ctx->plaintext->degree() * (word_bits / 8), false}}));
     HEAMD_TRY_STATUS(check_device(ctx));
     const bool dense_row = packing == HE_PNNS_PACKING_DENSE_ROW;
-    if (word_bits == 32) return unpack<uint32_t>(ctx, plan, dense_row, plaintexts, rows, cols, out_values, as_stream(s));
-    return unpack<uint64_t>(ctx, plan, dense_row, plaintexts, rows, cols, out_values, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return unpack<decltype(word)>(ctx, plan, dense_row, plaintexts, rows, cols, out_values, as_stream(s));
+    });
 }
 
 size_t he_pnns_generate_query_workspace_bytes(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
                                               size_t query_rows, size_t cols) {
     heamd::PnnsComposeTables tables;
     QueryPlan plan;
-    if (check_client_contexts(ctxs, context_count, word_bits, tables) != HE_OK ||
-        plan_query(ctxs, context_count, word_bits, query_rows, cols, plan) != HE_OK)
-        return 0;
-    return plan.total();
+    const bool ok = check_client_contexts(ctxs, context_count, word_bits, tables) == HE_OK &&
+                    plan_query(ctxs, context_count, word_bits, query_rows, cols, plan) == HE_OK;
+    return ok ? plan.total : 0;
 }
 
 int he_pnns_generate_query_device(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
@@ -410,21 +402,19 @@ int he_pnns_generate_query_device(const he_pnns_context* const* ctxs, size_t con
         HEAMD_TRY_STATUS(check_device(ctxs[i]));
         HEAMD_TRY_STATUS(heamd::bfv_encrypt_check_device(ctxs[i]->bfv, word_bits, bfv.top_level()));
     }
-    if (word_bits == 32)
-        return generate_query<uint32_t>(ctxs, context_count, plan, vectors, query_rows, cols, scaling_factor, secret_key, a_seeds,
-                                        error_seeds, out, out_of_range, workspace, workspace_bytes, s);
-    return generate_query<uint64_t>(ctxs, context_count, plan, vectors, query_rows, cols, scaling_factor, secret_key, a_seeds,
-                                    error_seeds, out, out_of_range, workspace, workspace_bytes, s);
+    return heamd::with_word(word_bits, [&](auto word) {
+        return generate_query<decltype(word)>(ctxs, context_count, plan, vectors, query_rows, cols, scaling_factor, secret_key,
+                                              a_seeds, error_seeds, out, out_of_range, workspace, workspace_bytes, s);
+    });
 }
 
 size_t he_pnns_decrypt_response_workspace_bytes(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
                                                 uint32_t moduli_count, size_t rows, size_t query_rows) {
     heamd::PnnsComposeTables tables;
     ResponsePlan plan;
-    if (check_client_contexts(ctxs, context_count, word_bits, tables) != HE_OK ||
-        plan_response(ctxs, context_count, word_bits, moduli_count, rows, query_rows, plan) != HE_OK)
-        return 0;
-    return plan.total();
+    const bool ok = check_client_contexts(ctxs, context_count, word_bits, tables) == HE_OK &&
+                    plan_response(ctxs, context_count, word_bits, moduli_count, rows, query_rows, plan) == HE_OK;
+    return ok ? plan.total : 0;
 }
 
 int he_pnns_decrypt_response_device(const he_pnns_context* const* ctxs, size_t context_count, uint32_t word_bits,
@@ -446,12 +436,10 @@ int he_pnns_decrypt_response_device(const he_pnns_context* const* ctxs, size_t c
                                {"secret_key", secret_key, moduli_count * row_bytes, false}}));
     for (size_t i = 0; i < context_count; ++i) {
         HEAMD_TRY_STATUS(check_device(ctxs[i]));
-        // the level and device checks of he_bfv_decrypt_device: an empty batch checks and enqueues nothing
-        HEAMD_TRY_STATUS(he_bfv_decrypt_device(ctxs[i]->bfv, word_bits, moduli_count, 2, 0, nullptr, nullptr, 1, nullptr, 0, nullptr, 0, s));
+        HEAMD_TRY_STATUS(heamd::bfv_decrypt_check_device(ctxs[i]->bfv, word_bits, moduli_count));
     }
-    if (word_bits == 32)
-        return decrypt_response<uint32_t>(ctxs, context_count, plan, tables, moduli_count, response, secret_key, rows, query_rows,
-                                          scaling_factor, out_distances, workspace, workspace_bytes, s);
-    return decrypt_response<uint64_t>(ctxs, context_count, plan, tables, moduli_count, response, secret_key, rows, query_rows,
-                                      scaling_factor, out_distances, workspace, workspace_bytes, s);
+    return heamd::with_word(word_bits, [&](auto word) {
+        return decrypt_response<decltype(word)>(ctxs, context_count, plan, tables, moduli_count, response, secret_key, rows,
+                                                query_rows, scaling_factor, out_distances, workspace, workspace_bytes, s);
+    });
 }

@@ -5,7 +5,8 @@
 // simple_pir_client_kernels.hip, the seeded samplers and the transforms.
 // Every random value is a function of a caller-supplied 32-byte seed through NistAes128Ctr(seed:).  The workspace is the caller's;
 // whatever a call parks there depends on secrets, errors, indices or entries, and is set to zero on the stream when the call is
-// done with it, however it ends (ZeroizedWorkspace, the helper and the rule of encrypt_api.cpp).
+// done with it, however it ends (ZeroizedWorkspace, the helper and the rule of encrypt_api.cpp).  The word check, the word
+// dispatch and the host-only refusal: word_layer.hpp.  (The plan keeps part sizes: a host probe and a Python mirror hold it.)
 #include <cstdlib>
 
 #include "aes_ctr_drbg.hpp"
@@ -68,7 +69,7 @@ int client_plan(const SimplePirPlan& shape, int error_std_dev, size_t batch, cli
 
 // the checks every device entry makes first, in this order: the word, the context, the word against the context's
 int check_word_and_context(const he_simple_pir_context* ctx, uint32_t word_bits) {
-    if (word_bits != 32 && word_bits != 64) return invalid_argument("word_bits must be 32 or 64");
+    HEAMD_TRY_STATUS(heamd::check_word_bits(word_bits));
     if (ctx == nullptr) return invalid_argument("null context");
     if (ctx->plan.word_bits != word_bits) return invalid_argument("context of the other word size");
     return HE_OK;
@@ -189,10 +190,7 @@ int precompute(const he_simple_pir_context* ctx, const client::Plan& plan, const
 
 int check_device(const he_simple_pir_context* ctx) {
     const PolyContext& ring = *ctx->ring;
-    if (ring.host_only()) {
-        heamd::set_last_error("context was created host-only (no device tables)");
-        return HE_ERR_DEVICE;
-    }
+    if (ring.host_only()) return heamd::host_only_refusal();
     return ring.check_device();
 }
 
@@ -264,8 +262,9 @@ int he_simple_pir_a_polynomials_device(const he_simple_pir_context* ctx, uint32_
     if (word_bits == 64 && (reinterpret_cast<uintptr_t>(out) & 7u) != 0) return invalid_argument("misaligned polynomials");
     HEAMD_TRY_STATUS(check_device(ctx));
     uint8_t* ws = static_cast<uint8_t*>(workspace);  // (the seed is the database's: nothing here is secret)
-    if (word_bits == 32) return a_polynomials(ctx, plan, seed, static_cast<uint32_t*>(out), ws, as_stream(s));
-    return a_polynomials(ctx, plan, seed, static_cast<uint64_t*>(out), ws, as_stream(s));
+    return heamd::with_word(word_bits, [&](auto word) {
+        return a_polynomials(ctx, plan, seed, static_cast<decltype(word)*>(out), ws, as_stream(s));
+    });
 }
 
 int he_simple_pir_encrypt_zero_device(const he_simple_pir_context* ctx, uint32_t word_bits, int error_std_dev,
@@ -287,11 +286,11 @@ int he_simple_pir_encrypt_zero_device(const he_simple_pir_context* ctx, uint32_t
     const hipStream_t stream = as_stream(s);
     ZeroizedWorkspace ws(stream);
     HEAMD_TRY_STATUS(resolve_workspace(ws, workspace, workspace_bytes, plan.encrypt_zero_bytes()));
-    if (word_bits == 32)
-        return encrypt_zero(ctx, plan, static_cast<const uint32_t*>(a_polynomials), static_cast<const uint32_t*>(secrets),
-                            error_seeds, static_cast<uint32_t*>(queries), batch, ws.at(0), stream);
-    return encrypt_zero(ctx, plan, static_cast<const uint64_t*>(a_polynomials), static_cast<const uint64_t*>(secrets), error_seeds,
-                        static_cast<uint64_t*>(queries), batch, ws.at(0), stream);
+    return heamd::with_word(word_bits, [&](auto word) {
+        using W = decltype(word);
+        return encrypt_zero(ctx, plan, static_cast<const W*>(a_polynomials), static_cast<const W*>(secrets), error_seeds,
+                            static_cast<W*>(queries), batch, ws.at(0), stream);
+    });
 }
 
 int he_simple_pir_secret_times_hint_device(const he_simple_pir_context* ctx, uint32_t word_bits, const void* secrets, size_t rows,
@@ -315,11 +314,11 @@ int he_simple_pir_secret_times_hint_device(const he_simple_pir_context* ctx, uin
     const hipStream_t stream = as_stream(s);
     ZeroizedWorkspace ws(stream);
     HEAMD_TRY_STATUS(resolve_workspace(ws, workspace, workspace_bytes, client::codes_bytes(ctx->plan.lattice_dimension, rows)));
-    if (word_bits == 32)
-        return secret_times_hint(ctx, plan, static_cast<const uint32_t*>(secrets), rows, static_cast<const uint32_t*>(hint),
-                                 column_size, static_cast<uint32_t*>(results), ws.at(0), stream);
-    return secret_times_hint(ctx, plan, static_cast<const uint64_t*>(secrets), rows, static_cast<const uint64_t*>(hint),
-                             column_size, static_cast<uint64_t*>(results), ws.at(0), stream);
+    return heamd::with_word(word_bits, [&](auto word) {
+        using W = decltype(word);
+        return secret_times_hint(ctx, plan, static_cast<const W*>(secrets), rows, static_cast<const W*>(hint), column_size,
+                                 static_cast<W*>(results), ws.at(0), stream);
+    });
 }
 
 int he_simple_pir_precompute_queries_device(const he_simple_pir_context* ctx, uint32_t word_bits, int error_std_dev,
@@ -348,13 +347,11 @@ int he_simple_pir_precompute_queries_device(const he_simple_pir_context* ctx, ui
     const hipStream_t stream = as_stream(s);
     ZeroizedWorkspace ws(stream);
     HEAMD_TRY_STATUS(resolve_workspace(ws, workspace, workspace_bytes, plan.precompute_bytes()));
-    if (word_bits == 32)
-        return precompute(ctx, plan, static_cast<const uint32_t*>(a_polynomials), static_cast<const uint32_t*>(hint), secret_seeds,
-                          error_seeds, static_cast<uint32_t*>(queries), static_cast<uint32_t*>(results_without_response), batch,
-                          ws.at(0), stream);
-    return precompute(ctx, plan, static_cast<const uint64_t*>(a_polynomials), static_cast<const uint64_t*>(hint), secret_seeds,
-                      error_seeds, static_cast<uint64_t*>(queries), static_cast<uint64_t*>(results_without_response), batch,
-                      ws.at(0), stream);
+    return heamd::with_word(word_bits, [&](auto word) {
+        using W = decltype(word);
+        return precompute(ctx, plan, static_cast<const W*>(a_polynomials), static_cast<const W*>(hint), secret_seeds, error_seeds,
+                          static_cast<W*>(queries), static_cast<W*>(results_without_response), batch, ws.at(0), stream);
+    });
 }
 
 int he_simple_pir_add_indices_device(const he_simple_pir_context* ctx, uint32_t word_bits, void* queries, const uint64_t* indices,
@@ -369,13 +366,11 @@ int he_simple_pir_add_indices_device(const he_simple_pir_context* ctx, uint32_t 
                                                         {"indices", indices, batch * sizeof(uint64_t), false}}));
     HEAMD_TRY_STATUS(check_device(ctx));
     const heamd::SimplePirClientLayout layout = layout_of(ctx->plan, plan);
-    if (word_bits == 32)
-        HEAMD_HIP_TRY(heamd::launch_simple_pir_client_add_indices(static_cast<uint32_t*>(queries), indices, flags, layout, batch,
+    return heamd::with_word(word_bits, [&](auto word) {
+        HEAMD_HIP_TRY(heamd::launch_simple_pir_client_add_indices(static_cast<decltype(word)*>(queries), indices, flags, layout, batch,
                                                                   as_stream(s)));
-    else
-        HEAMD_HIP_TRY(heamd::launch_simple_pir_client_add_indices(static_cast<uint64_t*>(queries), indices, flags, layout, batch,
-                                                                  as_stream(s)));
-    return HE_OK;
+        return int(HE_OK);
+    });
 }
 
 int he_simple_pir_decrypt_responses_device(const he_simple_pir_context* ctx, uint32_t word_bits, const void* responses,
@@ -399,18 +394,13 @@ int he_simple_pir_decrypt_responses_device(const he_simple_pir_context* ctx, uin
     ZeroizedWorkspace ws(stream);
     HEAMD_TRY_STATUS(resolve_workspace(ws, workspace, workspace_bytes, plan.coefficients_bytes));
     const heamd::SimplePirClientLayout layout = layout_of(ctx->plan, plan);
-    if (word_bits == 32) {
-        uint32_t* coefficients = reinterpret_cast<uint32_t*>(ws.at(0));
-        HEAMD_HIP_TRY(heamd::launch_simple_pir_client_integrate(static_cast<const uint32_t*>(responses),
-                                                                static_cast<const uint32_t*>(results_without_response), indices,
+    return heamd::with_word(word_bits, [&](auto word) {
+        using W = decltype(word);
+        W* coefficients = ws.at<W>(0);
+        HEAMD_HIP_TRY(heamd::launch_simple_pir_client_integrate(static_cast<const W*>(responses),
+                                                                static_cast<const W*>(results_without_response), indices,
                                                                 coefficients, flags, layout, batch, stream));
         HEAMD_HIP_TRY(heamd::launch_simple_pir_client_entry_bytes(coefficients, entries, layout, batch, stream));
-    } else {
-        uint64_t* coefficients = reinterpret_cast<uint64_t*>(ws.at(0));
-        HEAMD_HIP_TRY(heamd::launch_simple_pir_client_integrate(static_cast<const uint64_t*>(responses),
-                                                                static_cast<const uint64_t*>(results_without_response), indices,
-                                                                coefficients, flags, layout, batch, stream));
-        HEAMD_HIP_TRY(heamd::launch_simple_pir_client_entry_bytes(coefficients, entries, layout, batch, stream));
-    }
-    return HE_OK;
+        return int(HE_OK);
+    });
 }

@@ -14,6 +14,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "workspace_layout.hpp"  // round16
+
 #if defined(__HIPCC__)
 #define HEAMD_SIMPLE_PIR_CLIENT_HD __host__ __device__
 #else
@@ -103,8 +105,6 @@ constexpr uint32_t kCodeSlabColumns = 1024;
 inline size_t hint_product_lds_bytes() {
     return size_t(kSecretRowsPerPass) * (kCodeSlabColumns / 16) * 4 + size_t(kSecretRowsPerPass) * kHintTileRows * 8;
 }
-
-inline size_t round16(size_t bytes) { return (bytes + 15) & ~size_t(15); }
 
 struct Shape {
     uint32_t plaintext_bits = 0, ciphertext_bits = 0, lattice_dimension = 0, word_bits = 0;

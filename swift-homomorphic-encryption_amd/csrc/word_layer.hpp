@@ -17,6 +17,23 @@
 
 namespace heamd {
 
+// ---- the entries that take the slab word as an argument (encrypt, decrypt, the four client files).  body(W{}) for the word W of
+// a checked word_bits: with_word(word_bits, [&](auto word) { return f<decltype(word)>(...); })
+template <typename Body>
+auto with_word(uint32_t word_bits, Body&& body) {
+    if (word_bits == 32) return body(uint32_t{});
+    return body(uint64_t{});
+}
+inline int check_word_bits(uint32_t word_bits) {
+    return word_bits == 32 || word_bits == 64 ? int(HE_OK) : invalid_argument("word_bits must be 32 or 64");
+}
+// bfv_api.cpp: the word, the context, the word against the context's scheme (a Bfv<UInt32> context serves 8-byte slabs too)
+int check_word_and_context(const he_bfv_context* ctx, uint32_t word_bits);
+inline int host_only_refusal() {  // what a device entry answers on a context made without device tables
+    set_last_error("context was created host-only (no device tables)");
+    return HE_ERR_DEVICE;
+}
+
 // ---- launchers by slab word.  `dc` is the 8-byte image the caller chose (a level of the context, constants it may have
 // substituted, t N^-1 for instance); word_image yields the image a launch on slabs of W takes: dc itself, or the 4-byte
 // image built from `pc` over the `moduli` moduli the launch walks, with dc's constants.  An he_status.
@@ -95,6 +112,8 @@ int bfv_plaintext_to_eval(const he_bfv_context* ctx, uint32_t moduli_count, cons
 // encrypt_api.cpp: the device-side checks of he_bfv_encrypt_device (a host-only context, the transform of the word), for an
 // entry that has to make them before it enqueues work of its own
 int bfv_encrypt_check_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count);
+// bfv_api.cpp: the same for he_bfv_decrypt_device -- the word, the level, the device, the word against the context's scheme
+int bfv_decrypt_check_device(const he_bfv_context* ctx, uint32_t word_bits, uint32_t moduli_count);
 // Ciphertext.modSwitchDownToSingle, with the checks of he_bfv_mod_switch_down_to_single_device: one kernel where 8-byte words
 // have it (2..8 moduli), else divideAndRoundQLast level by level through scratch of its own
 template <typename W>

@@ -26,7 +26,8 @@ class ZeroizedWorkspace {
         bytes_ = needed;
         return HE_OK;
     }
-    uint8_t* at(size_t offset) const { return base_ + offset; }
+    template <typename T = uint8_t>  // the part at `offset` (a WorkspaceLayout's, workspace_layout.hpp) as words of T
+    T* at(size_t offset) const { return reinterpret_cast<T*>(base_ + offset); }
 
   private:
     Scratch scratch_;  // (released after the destructor's memset: members go after the body)

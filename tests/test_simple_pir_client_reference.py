@@ -99,9 +99,11 @@ def probe(tmp_path_factory):
 
 
 def test_header_includes_nothing_of_hip():
-    text = open(os.path.join(CSRC, "simple_pir_client_plan.hpp")).read()
-    includes = re.findall(r'#include\s*[<"]([^>"]+)[>"]', text)
-    assert includes and all(i in ("cstddef", "cstdint") for i in includes), includes
+    # (workspace_layout.hpp: plain C++ too, held to the same by tests/test_workspace_layout.py and read here as well)
+    for name in ("simple_pir_client_plan.hpp", "workspace_layout.hpp"):
+        text = open(os.path.join(CSRC, name)).read()
+        includes = re.findall(r'#include\s*[<"]([^>"]+)[>"]', text)
+        assert includes and all(i in ("cstddef", "cstdint", "workspace_layout.hpp") for i in includes), (name, includes)
 
 
 PLAN_FIELDS = ("chunk_size", "query_words", "result_words", "k", "words_per_side", "error_stream_bytes", "last_word_mask",
