@@ -57,6 +57,26 @@ def generate_secret_key(secret_ctx, seed, stream):
     return secret_ctx.forward_ntt(ternary(stream(seed, 12 * n), n, secret_ctx.moduli))
 
 
+class HostSide:
+    """The CPU side of one parameter set on one word size with the secret key of key_seeds[0]: the oracle's contexts, the byte
+    stream, the key in Eval form and a BfvClient that holds it.  tests/test_gpu_encrypt.py puts a device context beside it,
+    tests/predefined_sets.py the oracle's chain of operations."""
+
+    def __init__(self, oracle, degree, t, moduli, word, key_seeds):
+        from bfv_helpers import BfvClient
+
+        self.oracle = oracle
+        self.degree, self.t, self.moduli, self.word = degree, t, [int(q) for q in moduli], word
+        self.ref_ctx = oracle.BfvContext(degree, t, self.moduli, word_bits=word)
+        self.stream = oracle_stream(oracle)
+        self.secret_ctx = oracle.PolyContext(degree, self.moduli)
+        self.key_seeds = key_seeds
+        self.s_eval = generate_secret_key(self.secret_ctx, bytes(key_seeds[0]), self.stream)
+        self.client = BfvClient(oracle, self.ref_ctx)
+        self.client.s_eval_all = self.s_eval
+        self.L_all = len(self.moduli)
+
+
 def encrypt_zero(poly_ctx, s_eval, a_seed, error_seed, stream, eval_out=False):
     """Bfv.encryptZero(for:using:with:) (Bfv+Encrypt.swift:150-181) over poly_ctx; s_eval [>= L'][N], its first rows are used.
     -> [2][L'][N], Coeff, or forward-transformed (what _generateKeySwitchKey does next) with eval_out."""

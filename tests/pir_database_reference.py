@@ -22,6 +22,21 @@ def prefix(size, width):
     return int(size).to_bytes(width, "little") if width else b""
 
 
+def varying_entries(rng, count, entry_size, full=False):
+    """Entries of varying sizes (the first full, every fifth all zero) and the padded device image with garbage past each
+    entry's size -> (entries, padded uint8 [count][entry_size], sizes uint64 [count])."""
+    sizes = np.full(count, entry_size) if full else rng.integers(0, entry_size + 1, size=count)
+    if count:
+        sizes[0] = entry_size
+    entries = [rng.integers(0, 256, size=int(s), dtype=np.uint8).tobytes() for s in sizes]
+    for k in range(3, count, 5):
+        entries[k] = bytes(int(sizes[k]))
+    padded = rng.integers(0, 256, size=(count, entry_size), dtype=np.uint8)
+    for row, entry in enumerate(entries):
+        padded[row, :len(entry)] = np.frombuffer(entry, dtype=np.uint8)
+    return entries, padded, sizes.astype(np.uint64)
+
+
 def shape(degree, t, dimensions, entry_count, entry_size, encoding):
     """The plan: the keys of heamd's pir_database_shape.  ProcessError where the reorder would give the wrong size."""
     if not dimensions or 0 in dimensions:

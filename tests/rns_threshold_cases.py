@@ -438,17 +438,23 @@ def top_level_lift_is_centered(level, integers, lifted):
 
 
 # ---- for the tests: a parameter set's contexts, and polynomials as arrays ---------------------------------------------------
-def build_set(oracle, name, t_bits=None):
-    """-> (oracle BfvContext, {level: Level}) of a parameter set (t_bits overrides the set's plaintext modulus)."""
+def levels_of(ctx, word_bits):
+    """{level: Level} of an oracle BfvContext, whatever its moduli come from."""
+    q, bsk_top = [int(m) for m in ctx.coefficient_moduli], ctx.rns_tool(ctx.L).bsk
+    return {L: Level(q[:L], bsk_top, ctx.t, GAMMA[word_bits], MTILDE[word_bits]) for L in range(1, ctx.L + 1)}
+
+
+def build_set(oracle, name, t_bits=None, t_value=None):
+    """-> (oracle BfvContext, {level: Level}) of a parameter set.  t_bits overrides the bit count of the set's plaintext
+    modulus (an NTT-friendly prime of that size is generated), t_value gives the modulus itself, NTT-friendly or not."""
     _, word_bits, degree, bits, ks_bits, t = SETS[name]
     t = t_bits if t_bits is not None else t
+    t = [t_value] if t_value is not None else t
     t = t[0] if isinstance(t, list) else oracle.generate_primes([t], True, degree, word_bits=word_bits)[0]
     q = oracle.generate_primes(bits + [ks_bits], False, degree, word_bits=word_bits)
     assert len(set(q)) == len(q)
     ctx = oracle.BfvContext(degree, t, q, word_bits=word_bits)
-    bsk_top = ctx.rns_tool(ctx.L).bsk
-    levels = {L: Level(q[:L], bsk_top, t, GAMMA[word_bits], MTILDE[word_bits]) for L in range(1, ctx.L + 1)}
-    return ctx, levels
+    return ctx, levels_of(ctx, word_bits)
 
 
 def rows(columns, degree):

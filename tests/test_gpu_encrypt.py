@@ -25,7 +25,7 @@ import torch
 import encrypt_reference as ref
 import heamd
 import wire_format_reference as wire
-from bfv_helpers import BfvClient, galois_plain, negacyclic_multiply
+from bfv_helpers import galois_plain, negacyclic_multiply
 from heamd.binding import WORD32, WORD64
 
 pytestmark = pytest.mark.gpu
@@ -167,22 +167,20 @@ class Case:
         import oracle
 
         oracle.build()
-        self.oracle = oracle
-        self.degree, bits, self.word, t_bits = BFV_CASES[name]
-        self.moduli = heamd.generate_primes(bits, False, self.degree)
-        self.t = heamd.generate_primes([t_bits], True, self.degree)[0]
+        degree, bits, word, t_bits = BFV_CASES[name]
+        key_seeds = _seeds(3, 1000 + degree)[::-1].copy()  # a random seed first: key 0 is THE key of the case
+        self.setup(ref.HostSide(oracle, degree, heamd.generate_primes([t_bits], True, degree)[0],
+                                heamd.generate_primes(bits, False, degree), word, key_seeds))
+
+    def setup(self, host):
+        """the device context and keys beside an encrypt_reference.HostSide, whose fields the case takes over
+        (tests/test_gpu_predefined_sets.py builds its cases of the reference's own parameter sets through this)"""
+        vars(self).update(vars(host))
         cls = heamd.BfvContext32 if self.word == 32 else heamd.BfvContext
         self.ctx = cls(self.degree, self.t, self.moduli)
-        self.ref_ctx = oracle.BfvContext(self.degree, self.t, self.moduli, word_bits=self.word)
-        self.stream = ref.oracle_stream(oracle)
-        self.secret_ctx = oracle.PolyContext(self.degree, self.moduli)
-        self.key_seeds = _seeds(3, 1000 + self.degree)[::-1].copy()  # a random seed first: key 0 is THE key of the case
-        self.s_eval = ref.generate_secret_key(self.secret_ctx, bytes(self.key_seeds[0]), self.stream)
         self.keys_device = self.ctx.generate_secret_key(_device_seeds(self.key_seeds))
         self.s_device = self.keys_device[0].contiguous()
-        self.client = BfvClient(oracle, self.ref_ctx)
-        self.client.s_eval_all = self.s_eval
-        self.L, self.L_all = self.ctx.L, len(self.moduli)
+        self.L = self.ctx.L
 
     def to_host(self, tensor):
         return _to_host(tensor, self.word)

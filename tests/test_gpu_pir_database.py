@@ -19,19 +19,7 @@ def _context(oracle, degree, q_bits, t_bits=17):
     return heamd.BfvContext(degree, t, q), oracle.BfvContext(degree, t, q)
 
 
-def _entries(rng, count, entry_size, full=False):
-    """Entries of varying sizes (the first full, every fifth all zero) and the padded device image with garbage past each
-    entry's size."""
-    sizes = np.full(count, entry_size) if full else rng.integers(0, entry_size + 1, size=count)
-    if count:
-        sizes[0] = entry_size
-    entries = [rng.integers(0, 256, size=int(s), dtype=np.uint8).tobytes() for s in sizes]
-    for k in range(3, count, 5):
-        entries[k] = bytes(int(sizes[k]))
-    padded = rng.integers(0, 256, size=(count, entry_size), dtype=np.uint8)
-    for row, entry in enumerate(entries):
-        padded[row, :len(entry)] = np.frombuffer(entry, dtype=np.uint8)
-    return entries, padded, sizes.astype(np.uint64)
+_entries = refdb.varying_entries  # (tests/test_gpu_pir_client.py imports it under this name)
 
 
 def _device_database(ours, padded, sizes, dims, entry_size, encoding, word32=False, out=None):
