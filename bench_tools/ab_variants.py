@@ -2,8 +2,16 @@
 
 An experiment is a module bench_tools/variants/NAME.py with
     DESCRIPTION = "..."
-    COMPILE = ["ntt_kernels.hip", ...]            # translation units to rebuild (default: the files the edits touch)
+    COMPILE = ["ntt_forward_8192.hip", ...]       # translation units to rebuild (default: the files the edits touch)
     EDITS = [("file under csrc/", "exact old text", "new text"), ...]
+An edit of a header needs COMPILE: exactly the units that include it, directly or not.  The 8-byte NTT's kernel families are
+headers (ntt_forward_tiled.hpp, ntt_inverse_tiled.hpp, ntt_interleaved.hpp) compiled by ntt_tiled_4096.hip,
+ntt_forward_8192.hip and ntt_inverse_8192.hip, beside ntt_generic.hip and the routing unit ntt_routing.hip: an edit of one
+family rebuilds the two units that include it, an edit of the launch policy (ntt_policy.hpp) every unit that instantiates or
+launches by it.  An edit that makes ntt_routing.hip refer to a selector shape the product does not instantiate (a policy
+constant that opens another route) carries a second edit appending the HEAMD_* instantiation line to the unit that
+compiles that family (fused_keymac_16384.py); variants link with --no-undefined like the product, so a missing one
+fails the build.
 The builder copies csrc/ to a scratch directory, applies the edits (an edit whose old text is not found exactly once is
 an error: the experiment has drifted from the source and must be updated), recompiles the affected translation units
 and links them with the production objects into lib/variants/libhe_amd_NAME.so.  The product sources carry no hooks.
@@ -172,7 +180,7 @@ def build_one(name, product_build):
             subprocess.run(cmd, check=True)
             objects.append(obj)
         subprocess.run([product_build._hipcc(), "-shared", "-fPIC", f"--offload-arch={product_build.ARCH}",
-                        f"-Wl,--version-script={product_build.EXPORTS}", "-o",
+                        f"-Wl,--version-script={product_build.EXPORTS}", "-Wl,--no-undefined", "-o",
                         os.path.join(VARIANTS, f"libhe_amd_{name}.so"), *objects], check=True)
     finally:
         shutil.rmtree(top, ignore_errors=True)

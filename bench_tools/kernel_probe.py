@@ -5,8 +5,9 @@ translation unit takes) and print their register / scratch figures -- the inner 
 
 --mix also prints each kernel's static instruction mix (opcode counts of its body).
 
-The kernel definitions of csrc/ntt_kernels.hip (everything above the launchers) are copied to a scratch file followed by
-explicit instantiations of the named kernels; nothing is linked into the library.
+The kernel definitions of the named kernels' families (csrc/ntt_forward_tiled.hpp, ntt_inverse_tiled.hpp,
+ntt_interleaved.hpp: everything above the selector, i.e. up to the end of the file's anonymous namespace) are copied to a
+scratch file, each followed by explicit instantiations of the named kernels; nothing is linked into the library.
 """
 import os
 import re
@@ -16,6 +17,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "swift-homomorphic-encryption_amd", "csrc")
+FAMILY_FILES = {"ntt_forward_tiled": "ntt_forward_tiled.hpp", "ntt_inverse_tiled": "ntt_inverse_tiled.hpp",
+                "ntt_forward_interleaved": "ntt_interleaved.hpp", "ntt_inverse_interleaved": "ntt_interleaved.hpp"}
 SIGNATURES = {
     "ntt_forward_tiled": "(uint64_t*, const DeviceContext, const RowMap, const SpreadSource)",
     "ntt_inverse_tiled": "(uint64_t*, const DeviceContext, const RowMap, const InverseSource)",
@@ -34,10 +37,13 @@ def main():
             mix, args = True, args[1:]
         else:
             raise SystemExit("unknown option " + args[0])
-    source = open(os.path.join(CSRC, "ntt_kernels.hip")).read()
-    head = source[:source.index("// Row pairs: where the register file allows it")]
-    body = head + "\n".join(f"template __global__ void {k}{SIGNATURES[k.split('<')[0].strip()]};" for k in args)
-    body += "\n}  // namespace\n}  // namespace heamd\n"
+    family = lambda k: k.split("<")[0].strip()  # noqa: E731
+    body = ""
+    for file in sorted({FAMILY_FILES[family(k)] for k in args}):
+        source = open(os.path.join(CSRC, file)).read().replace("#pragma once\n", "")
+        body += source[:source.index("\n}  // namespace\n")] + "\n"
+        body += "\n".join(f"template __global__ void {k}{SIGNATURES[family(k)]};" for k in args if FAMILY_FILES[family(k)] == file)
+        body += "\n}  // namespace\n}  // namespace heamd\n"
     with tempfile.TemporaryDirectory() as work:
         path = os.path.join(work, "probe.hip")
         open(path, "w").write(body)

@@ -39,11 +39,11 @@ PIPELINE = [
     # the floor: one lane per coefficient of each of the 3 product polynomials
     {"kernel": "floor_kernel<4, unsigned long, true, 1>", "object": "rns_kernels.o", "lanes_per_product": 3 * N, "trips": {}},
     # relinearize: spread + forward, two rows per 1024-lane workgroup, L (L + 1) rows
-    {"kernel": "ntt_forward_tiled<13, 10, 4, 1, 2>", "object": "ntt_kernels.o", "lanes_per_product": L * (L + 1) * 512, "trips": {}},
+    {"kernel": "ntt_forward_tiled<13, 10, 4, 1, 2>", "object": "ntt_forward_8192.o", "lanes_per_product": L * (L + 1) * 512, "trips": {}},
     # the q_ks row of both update polynomials: key inner product (L terms: the loop) + inverse, two rows per workgroup
-    {"kernel": "ntt_inverse_tiled<13, 10, 4, 2, 2>", "object": "ntt_kernels.o", "lanes_per_product": 2 * 512, "trips": "L"},
+    {"kernel": "ntt_inverse_tiled<13, 10, 4, 2, 2>", "object": "ntt_inverse_8192.o", "lanes_per_product": 2 * 512, "trips": "L"},
     # the L rows below it with the key switch's end fused
-    {"kernel": "ntt_inverse_tiled<13, 10, 4, 4, 2>", "object": "ntt_kernels.o", "lanes_per_product": 2 * L * 512, "trips": "L"},
+    {"kernel": "ntt_inverse_tiled<13, 10, 4, 4, 2>", "object": "ntt_inverse_8192.o", "lanes_per_product": 2 * L * 512, "trips": "L"},
 ]
 
 

@@ -27,8 +27,29 @@ def _hipcc():
     return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
+# The units that take longest to compile, slowest first: started before the others so that the build does not end waiting
+# for one of them.
+SLOWEST_FIRST = ["ntt_inverse_8192.hip", "ntt_tiled_4096.hip", "ntt_forward_8192.hip",
+                 "behz_kernels.hip"]
+
+
 def _sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp")))
+    found = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp")))
+    return [f for f in SLOWEST_FIRST if f in found] + [f for f in found if f not in SLOWEST_FIRST]
+
+
+def _remove_orphans(sources):
+    """Build products in csrc/build/ whose source no longer exists (a renamed or split unit): a stale object would stay
+    on every machine with an incremental build, and tests read objects from that directory by name.  True when an object
+    went: the library was linked with it and must be linked again."""
+    stems = {os.path.splitext(s)[0] for s in sources}
+    removed_object = False
+    for f in os.listdir(OBJ_DIR):
+        stem, ext = os.path.splitext(f)
+        if ext in (".o", ".d", ".cmd") and stem not in stems:
+            os.remove(os.path.join(OBJ_DIR, f))
+            removed_object |= ext == ".o"
+    return removed_object
 
 
 def _headers_mtime():
@@ -87,7 +108,7 @@ def _compile(src, force, header_time):
         deps = _dependencies(dep)
         if deps is not None:
             # rebuild only when something this object was compiled from is newer (a header one unit includes does not
-            # cost the four minutes of ntt_kernels.hip)
+            # cost the minute or more of each tiled NTT unit)
             if all(os.path.exists(d) and os.path.getmtime(d) <= built for d in deps):
                 return obj, False
         elif built >= max(os.path.getmtime(path), header_time):
@@ -105,14 +126,16 @@ def build(force=False, verbose=False):
     os.makedirs(LIB_DIR, exist_ok=True)
     header_time = _headers_mtime()
     sources = _sources()
+    orphan_removed = _remove_orphans(sources)
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(sources))) as pool:
         results = list(pool.map(lambda s: _compile(s, force, header_time), sources))
     objects = [obj for obj, _ in results]
-    rebuilt = any(changed for _, changed in results)
+    rebuilt = orphan_removed or any(changed for _, changed in results)
     if rebuilt or not os.path.exists(LIB_PATH):
-        # only the C ABI (he_*) is exported: the C++ launchers behind it stay internal
-        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", f"-Wl,--version-script={EXPORTS}", "-o", LIB_PATH,
-               *objects]
+        # only the C ABI (he_*) is exported: the C++ launchers behind it stay internal.  --no-undefined: the NTT routing unit
+        # reaches its kernels through explicit instantiations in other units (ntt_selectors.hpp) -- a missing one fails here
+        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", f"-Wl,--version-script={EXPORTS}", "-Wl,--no-undefined",
+               "-o", LIB_PATH, *objects]
         result = subprocess.run(cmd, capture_output=True, text=True)
         if result.returncode != 0:
             raise RuntimeError(f"link failed:\n{result.stdout}\n{result.stderr}")

@@ -4,7 +4,7 @@
 //
 // Per (item, row r of the [Q, Bsk] records) the reference runs four forward transforms (row r of a0, a1, b0, b1:
 // Bfv+Multiply.swift:51-57, 76-79), three dyadic products a0 b0 | a0 b1 + a1 b0 | a1 b1 (:80-82) and three inverse
-// transforms scaled by t (:31-48) -- and none of them ever needs another row.  The unfused pipeline (ntt_kernels.hip:
+// transforms scaled by t (:31-48) -- and none of them ever needs another row.  The unfused pipeline (ntt_sources.hpp:
 // kSourceRows forward + kInverseFromTensor inverse) writes the four transformed rows to HBM and reads them back three
 // times over; here one workgroup keeps them in registers:
 //

@@ -1,5 +1,5 @@
 // ntt_common.hpp -- device helpers shared by the NTT kernels: register/lane <-> element mapping, padded LDS tile,
-// global <-> register movement, Harvey/Shoup butterfly passes.  See ntt_kernels.hip for the design notes.
+// global <-> register movement, Harvey/Shoup butterfly passes.  See ntt_routing.hip for the design notes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -152,7 +152,7 @@ __device__ __forceinline__ uint64_t load_twiddle_word(const uint64_t* entry) {
 //                    2^(s+1) p is added to make it non-negative; the last stage adds 2^7 p to its sum and its difference in
 //                    front of the exact division by N and the N^-1 psi^(-N/2) product.  Tables: the twiddles' second words in
 //                    signed limbs, lane-major (DeviceContext::forward_split_pairs_signed_lanes /
-//                    inverse_split_pairs_signed_lanes_top).  The plain-slab pair at N = 8192 (ntt_kernels.hip
+//                    inverse_split_pairs_signed_lanes_top).  The plain-slab pair at N = 8192 (ntt_policy.hpp
 //                    kFoldSignedForward / kFoldSignedInverse).
 constexpr int kModeExact = 0, kModeApprox = 1, kModeSplit = 3, kModeFoldLazy = 4, kModeFoldMinus = 5, kModeFoldPlus = 6,
               kModeSplitSigned = 7, kModeFoldSigned = 8;
@@ -199,7 +199,7 @@ struct Twiddles {
     // of a run 2^g times as long, fetched 2^g times over unless the vector L1 still holds it.
     bool lanes;
     // `skip`: the table as seen from entry `skip` on (the sub-transforms of an interleaved row index the tail of the
-    // inverse table, ntt_kernels.hip ntt_inverse_interleaved)
+    // inverse table, ntt_interleaved.hpp ntt_inverse_interleaved)
     __device__ __forceinline__ Twiddles(const DeviceContext& ctx, bool inverse, uint32_t modulus_index, int log_degree,
                                         uint32_t skip = 0, int lane_major = 0) {
         const size_t at = (static_cast<size_t>(modulus_index) << log_degree) + skip;
@@ -652,7 +652,7 @@ __device__ __forceinline__ void inverse_butterfly(uint64_t& first, uint64_t& sec
 }
 
 // PRIOR: stages of the same transform that ran before the ones on bits [0, LOGN) (the cross stages of an interleaved
-// row, ntt_kernels.hip): they only move the lazy bounds.  LOGD: log2 of the transform's degree (N^-1 = 2^-LOGD).
+// row, ntt_interleaved.hpp): they only move the lazy bounds.  LOGD: log2 of the transform's degree (N^-1 = 2^-LOGD).
 // FIRST_STAGE: the pass skips the first FIRST_STAGE stages of the layout's W (the top pass of a schedule whose partial
 // pass sits on the top bits: the lower bits of its layout were paired by the pass before); `first` is the first twiddle
 // of the stages it does run (inverse_first_twiddle with the same FIRST_STAGE).
@@ -789,7 +789,7 @@ constexpr int row_load_policy() {
     return row_policy<LOGN>();
 }
 // POLICY: row_policy<LOGN>() for rows nobody else reads; 0 (cached) for source rows that several workgroups of a replica set
-// read (ntt_kernels.hip locate_replica: the others are meant to hit in L2)
+// read (placement.hpp locate_replica: the others are meant to hit in L2)
 template <int LOGN, int LOGE, int LO, int W, int POLICY = row_load_policy<LOGN>()>
 __device__ __forceinline__ void global_load(uint64_t (&v)[1 << LOGE], uint32_t tid, BufferResource row) {
     const uint32_t lane_bytes = lane_part<LOGN, LOGE, LO, W>(tid) << 3;

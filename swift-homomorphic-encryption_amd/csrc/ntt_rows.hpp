@@ -1,5 +1,5 @@
 // ntt_rows.hpp -- the row-level machinery of the tiled transforms, shared by the translation units that build kernels from
-// it (ntt_kernels.hip: the plain and fused-load transforms; behz_kernels.hip: the row-fused BEHZ multiplication): which rows
+// it (the ntt_*.hip units: the plain and fused-load transforms; behz_kernels.hip: the row-fused BEHZ multiplication): which rows
 // a workgroup takes, the LDS exchange between passes, ROWS residue rows of one modulus registers to registers
 // (forward_row / inverse_row), and the butterfly-class bookkeeping of the launchers.
 #pragma once

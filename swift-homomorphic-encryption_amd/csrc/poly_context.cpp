@@ -179,7 +179,7 @@ int PolyContext::upload() {
     const size_t bytes_inverse_q_last = round_up(count * count * sizeof(U64x2));
     // limb-wise Shoup form of both twiddle tables: pairs (16 B) and quotient factors (8 B) per entry
     const size_t bytes_factors = round_up(count * n * sizeof(u64));
-    // lane-major stage blocks for the tiled kernels with 8 words per lane (ntt_kernels.hip kLaneMajorTwiddles): N = 4096, 8192;
+    // lane-major stage blocks for the tiled kernels with 8 words per lane (ntt_rows.hpp kLaneMajorTwiddles): N = 4096, 8192;
     // N = 16384 / 32768: for the 8192-point transforms of the interleaved sub-rows (ntt_forward_interleaved /
     // ntt_inverse_interleaved), which index the first 8192 entries of the forward table and the last 8192 of the inverse one
     // exactly as an N = 8192 transform indexes its own

@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(1024)
     }
 }
 
-// ---- register-tiled transform for N = 4096 / 8192 / 16384: the 8-byte kernel's structure (ntt_kernels.hip) on 4-byte
+// ---- register-tiled transform for N = 4096 / 8192 / 16384: the 8-byte kernel's structure (ntt_forward_tiled.hpp, ntt_inverse_tiled.hpp) on 4-byte
 // words -- one workgroup per row, 2^LOGE words per lane, passes of LOGE radix-2 stages on registers, LDS transposes
 // in between (wave-private after the first), wave-uniform twiddles through the scalar cache.  The lane <-> element
 // maps, the pass schedule and the fences are the shared helpers of ntt_common.hpp; only the arithmetic is narrower.
@@ -248,7 +248,7 @@ __device__ __forceinline__ void row32_load_staged(uint32_t (&v)[1 << LOGE], uint
     }
 }
 
-// Row sources other than the slab itself, as in ntt_kernels.hip: the step that would otherwise write the slab for this
+// Row sources other than the slab itself, as in ntt_sources.hpp: the step that would otherwise write the slab for this
 // kernel to read back is applied to the words while they are loaded.  All of them take mod_period rows per record with
 // modulus mod_base + (row within the record); the workgroups that read the same source words form one replica set on one
 // XCD (placement.hpp).
@@ -266,7 +266,7 @@ __device__ __forceinline__ void row32_load_staged(uint32_t (&v)[1 << LOGE], uint
 //                    apart; the other rows are read from the slab
 //   kSource32KeyMacFinish  the same load over the band rows r < L, with the key switch's last step (drop the special
 //                    modulus, add the update to the ciphertext: key_switch_finish_kernel, rns_kernels.hip) applied to the
-//                    transform's canonical words before they are stored -- the 4-byte twin of ntt_kernels.hip
+//                    transform's canonical words before they are stored -- the 4-byte twin of ntt_sources.hpp
 //                    kInverseFromKeyMacFinish: the q_ks rows come from an earlier launch of kSource32KeyMac over that band
 constexpr int kSource32Slab = 0, kSource32Spread = 1, kSource32Tensor = 2, kSource32KeyMac = 3, kSource32Rows = 4,
               kSource32KeyMacFinish = 5;

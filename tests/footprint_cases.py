@@ -27,7 +27,7 @@ Shapes.  Every row and word runs at SMALL (the table's ring, N = 8; N = 256 for 
 (N = 4096, batch 3, four moduli of 55 bits on 8-byte words and of 27, 28, 28, 29 bits on 4-byte words: several workgroups, row
 pairs and an odd row).  The workspace pipelines run at one more shape per kernel form their launchers can take (FORMS), each
 with the source condition that selects the form.  The library gives no way to observe the form a call took: every shape follows
-from the condition as read in csrc/bfv_api.cpp, csrc/ntt_kernels.hip and csrc/behz_kernels.hip (kOneGeneration = 512 rows,
+from the condition as read in csrc/bfv_api.cpp, csrc/ntt_routing.hip and csrc/behz_kernels.hip (kOneGeneration = 512 rows,
 csrc/ntt_rows.hpp; kBehzRowsFusedAbove = 1152).
 """
 import collections
@@ -148,7 +148,7 @@ BELOW = "a level below the top: L = 2 of TOP = 3, the key's rows TOP + 1 apart"
 FORMS = {
     # ---- ct x ct (bfv_api.cpp mul_pipeline); rows = 2 L + 1
     "he_bfv_mul_device": [
-        # SMALL: ntt_kernels.hip launch_ntt_tensor_inverse `!tiled` (log_degree < 12): the unfused form -- the lift writes the
+        # SMALL: ntt_routing.hip launch_ntt_tensor_inverse `!tiled` (log_degree < 12): the unfused form -- the lift writes the
         #   copy, ntt_records, launch_tensor, drop_extended_base
         # TILED: launch_ntt_tensor_inverse `12 <= log_degree <= kMaxFusedLoadLogDegree`, records * rows = 63 <= kOneGeneration: one
         #   launch forms the products as the inverse transform loads; ntt_lifted_forward_supported false (items * 4 * rows = 84
@@ -167,7 +167,7 @@ FORMS = {
         shape("N4096-side-lane-floor-in-parts", 4096, BITS_TILED_64,
               "mul_rows_fused: batch * L = 1024 >= 1024 and batch >= 256 * kBehzFloorParts: the Q band on the side lane, the Bsk "
               "band and the floor in two parts of 512 items (1024 * 3 > kBehzRowsFusedAbove)", batch=1024, L=1),
-        shape("N16384", 16384, BITS_TILED, "ntt_kernels.hip kInterleaved16384 / kInterleavedFusedLoads: log_degree 14 runs the "
+        shape("N16384", 16384, BITS_TILED, "ntt_policy.hpp kInterleaved16384 / kInterleavedFusedLoads: log_degree 14 runs the "
               "fused loads as interleaved sub-rows; rows_fused_shape false (log_degree not 12 or 13)", batch=2, L=3),
         shape("N4096-L2", 4096, BITS_TILED, BELOW, batch=3, L=2),
     ],

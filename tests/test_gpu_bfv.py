@@ -1049,7 +1049,7 @@ def test_many_moduli_at_a_tiled_degree(oracle, name, past_the_threshold):
                                    below 2^60 in one 64-bit word, 14 (p - 1)^2 = 0xE0... at most
                                    (word32_kernels.hip launch_ntt_key_mac_inverse: "if (L > 15) return hipErrorNotSupported")
                     16 x 26 bits   L > 15: launch_key_switch_mac<uint32_t> and a separate inverse transform
-      8-byte words   8 x 60 bits   ntt_kernels.hip: "mod.wide_shift != 0 && L <= 8 && uint64_t(L) * mod.p < (uint64_t(1) << 63)"
+      8-byte words   8 x 60 bits   ntt_inverse_tiled.hpp: "mod.wide_shift != 0 && L <= 8 && uint64_t(L) * mod.p < (uint64_t(1) << 63)"
                                    -- the one-word-quotient reduction with the most and the widest terms it takes
                      9 x 55 bits   L = 9: the general reduction
                      4 x 61 bits,  L p on either side of 2^63 (4 p < 2^63 for every p < 2^61; word32_cases.py says why these

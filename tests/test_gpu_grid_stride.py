@@ -502,7 +502,7 @@ def _(oracle):
 def _(oracle):
     """Bfv.applyGalois on a ring with a tiled transform and a batch too small for the transform's own store to finish the key
     switch: the Galois end of key_switch_finish_kernel (the automorphism of c0 rides its loads).  Three ciphertexts, elements that
-    flip signs (N + 1), reverse (2N - 1) and scatter (3).  "Too small" is ntt_key_mac_finish_supported (ntt_kernels.hip): the
+    flip signs (N + 1), reverse (2N - 1) and scatter (3).  "Too small" is ntt_key_mac_finish_supported (ntt_routing.hip): the
     transform finishes the key switch itself only above 2 x kOneGeneration (ntt_rows.hpp) rows, and this batch has 3 x 2 x (L + 1) =
     18; should that threshold ever drop below 18 rows, this row stops reaching the kernel and needs a smaller batch."""
     degree = 4096

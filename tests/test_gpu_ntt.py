@@ -93,7 +93,7 @@ def test_ntt_kernel_variants_agree(oracle, degree, bits, variant):
                                                (4096, [55] * 4, 25), (16384, [55, 55, 55], 9), (8192, [55] * 4, 683)])
 def test_ntt_row_pairs(oracle, degree, bits, batch):
     """With 8 words per lane a workgroup transforms the same residue row of two consecutive polynomials (one modulus,
-    every twiddle fetched once for both; ntt_kernels.hip kRowsPerWorkgroup): even and odd batches (the odd polynomial
+    every twiddle fetched once for both; ntt_policy.hpp kRowsPerWorkgroup): even and odd batches (the odd polynomial
     takes the one-row kernel), every butterfly schedule, modulus periods 1..5; against the oracle."""
     moduli = oracle.generate_primes(bits, False, degree)
     ours = heamd.PolyContext(degree, moduli)
@@ -258,7 +258,7 @@ def test_ntt_shifted_factor_moduli(oracle, degree, bits):
 
 @pytest.mark.parametrize("moduli_count", [1, 2, 3, 5, 6, 7])
 def test_ntt_row_map_periods(oracle, moduli_count):
-    """A workgroup finds its row's modulus with one scalar multiply-high (ntt_kernels.hip locate): every period, with
+    """A workgroup finds its row's modulus with one scalar multiply-high (ntt_rows.hpp locate): every period, with
     enough rows that a wrong quotient would pick a wrong modulus somewhere."""
     degree = 4096
     moduli = oracle.generate_primes([50] * moduli_count, False, degree)

@@ -16,7 +16,7 @@ import heamd
 pytestmark = pytest.mark.gpu
 
 DEGREE = 8192
-UNGROUPED_BELOW_ROWS = 4096  # ntt_kernels.hip kUngroupedBelowRows
+UNGROUPED_BELOW_ROWS = 4096  # ntt_policy.hpp kUngroupedBelowRows
 ORACLE_THREADS = 16
 INPUTS = ["all_p_minus_1", "all_zero", "alternating", "two_spikes", "uniform"]
 

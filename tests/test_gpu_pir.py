@@ -145,7 +145,7 @@ def test_pir_expand_fused_levels(oracle, total, key_shifts):
 def test_pir_expand_wide_levels(oracle, total, key_shifts):
     """Expansions wide enough for every run of equal keys in their last level to exceed two workgroup generations of
     key-switching rows (N=4096, L=2, two queries under different keys in one call: 200 and 256 parents each): there the
-    children leave the key-MAC transform's store (ntt_kernels.hip kInverseFromKeyMacFinish with the expand end) -- per run
+    children leave the key-MAC transform's store (ntt_sources.hpp kInverseFromKeyMacFinish with the expand end) -- per run
     of equal keys, straight to their output slots, ragged totals (400) and levels reached by two applications (no keys for the
     elements N/2 + 1 and N/8 + 1; below 2^7 + 1 an element does not compose to the next one, PirUtil.swift:222-231) included.  Word for word against the oracle's recursion."""
     degree = 4096

@@ -8,6 +8,8 @@ import subprocess
 import sys
 import tempfile
 
+import test_kernel_scratch as mechanism
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "swift-homomorphic-encryption_amd", "csrc", "build")
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
@@ -16,12 +18,14 @@ sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
 def test_signed_fold_kernels_fit_64_registers_without_scratch():
     import kernel_metadata
 
-    obj = os.path.join(BUILD, "ntt_kernels.o")
-    assert os.path.exists(obj), "the library's objects are built by __graft_entry__.build()"
+    assert mechanism.library_built(), "the library's objects are built by __graft_entry__.build()"
+    rows = []
     with tempfile.TemporaryDirectory() as workdir:
-        code = kernel_metadata.code_object(obj, workdir)
-        assert code is not None
-        rows = list(kernel_metadata.kernels(code))
+        for obj in mechanism.ntt_objects():  # the union of the NTT units (the routing unit alone holds no device code)
+            code = kernel_metadata.code_object(os.path.join(BUILD, obj), workdir)
+            kernels = list(kernel_metadata.kernels(code)) if code is not None else []
+            assert kernels or obj == mechanism.ROUTING_OBJECT, f"{obj}: no kernel read from its code object"
+            rows += kernels
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True,
                            check=True).stdout.split("\n")
     found = {kernel_metadata.short_name(name): r for r, name in zip(rows, names)}

@@ -1,7 +1,6 @@
 """The kernels of keyword_pir_client_kernels.hip keep nothing in scratch, spill no register and come in the expected forms; LDS
 is used by the staged bucket walk alone, within the budget csrc/keyword_pir_client_plan.hpp states.  Read from the built
 object's kernel metadata with the mechanism of tests/test_pir_client_scratch.py; no GPU involved."""
-import glob
 import os
 
 import pytest
@@ -21,7 +20,7 @@ KERNELS = {
 
 
 def test_client_kernels_have_no_scratch_and_only_the_staged_walk_has_lds():
-    if not glob.glob(os.path.join(mechanism.BUILD, "ntt_kernels.o")):
+    if not mechanism.library_built():
         pytest.skip("the library's objects are built by __graft_entry__.build()")
     assert os.path.exists(os.path.join(mechanism.BUILD, "keyword_pir_client_kernels.o"))
     rows = _metadata("keyword_pir_client_kernels.o")

@@ -1,6 +1,5 @@
 """The kernels of pnns_client_kernels.hip keep nothing in scratch, spill no register, use no LDS and come in the expected
 number of forms.  Read from the built object's kernel metadata with the mechanism of tests/test_pnns_scratch.py; no GPU involved."""
-import glob
 import os
 
 import pytest
@@ -13,7 +12,7 @@ KERNELS = ["pnns_simd_scatter_kernel", "pnns_simd_gather_kernel", "pnns_dense_ro
 
 
 def test_client_kernels_have_no_scratch():
-    if not glob.glob(os.path.join(mechanism.BUILD, "ntt_kernels.o")):
+    if not mechanism.library_built():
         pytest.skip("the library's objects are built by __graft_entry__.build()")
     assert os.path.exists(os.path.join(mechanism.BUILD, "pnns_client_kernels.o"))
     rows = _metadata("pnns_client_kernels.o")

@@ -1,7 +1,6 @@
 """pnns_row_mask_kernel and pnns_extract_rows_kernel (pnns_kernels.hip) keep nothing in scratch, spill no register and use no
 LDS in any of their forms.  Read from the built object's kernel metadata with the mechanism of tests/test_pnns_scratch.py; no
 GPU involved."""
-import glob
 import os
 
 import pytest
@@ -11,7 +10,7 @@ from test_pnns_scratch import _metadata
 
 
 def test_row_mask_and_extract_kernels_have_no_scratch():
-    if not glob.glob(os.path.join(mechanism.BUILD, "ntt_kernels.o")):
+    if not mechanism.library_built():
         pytest.skip("the library's objects are built by __graft_entry__.build()")
     assert os.path.exists(os.path.join(mechanism.BUILD, "pnns_kernels.o"))
     rows = _metadata("pnns_kernels.o")

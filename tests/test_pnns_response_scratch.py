@@ -2,7 +2,6 @@
 its static LDS is nil: the tile of rotated ciphertext rows is dynamic (baby_step x queries x 2 KiB, at most 128 KiB of a
 compute unit's 160).  Read from the built object's kernel metadata with the mechanism of tests/test_pnns_scratch.py; no GPU
 involved."""
-import glob
 import os
 
 import pytest
@@ -14,7 +13,7 @@ TILE_LIMIT = 128 << 10
 
 
 def test_bsgs_inner_product_kernel_has_no_scratch():
-    if not glob.glob(os.path.join(mechanism.BUILD, "ntt_kernels.o")):
+    if not mechanism.library_built():
         pytest.skip("the library's objects are built by __graft_entry__.build()")
     assert os.path.exists(os.path.join(mechanism.BUILD, "pnns_kernels.o"))
     kernels = [(name, row) for name, row in _metadata("pnns_kernels.o") if name.startswith("pnns_bsgs_inner_product_kernel<")]

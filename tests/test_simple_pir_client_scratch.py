@@ -1,7 +1,6 @@
 """The kernels of simple_pir_client_kernels.hip keep nothing in scratch, spill no register and come in the expected forms; the
 hint product's LDS is what he_simple_pir_client_plan states, and the finishing kernel's is the AES table alone.  Read from the
 built object's kernel metadata with the mechanism of tests/test_pnns_scratch.py; no GPU involved."""
-import glob
 import os
 
 import pytest
@@ -21,7 +20,7 @@ KERNELS = {
 
 
 def test_client_kernels_have_no_scratch():
-    if not glob.glob(os.path.join(mechanism.BUILD, "ntt_kernels.o")):
+    if not mechanism.library_built():
         pytest.skip("the library's objects are built by __graft_entry__.build()")
     assert os.path.exists(os.path.join(mechanism.BUILD, "simple_pir_client_kernels.o"))
     rows = _metadata("simple_pir_client_kernels.o")
