@@ -1673,7 +1673,8 @@ int he_simple_pir_batch_response_plan(uint32_t plaintext_bits, uint32_t cipherte
  * no-op returning HE_OK after the argument checks that need no buffer.  HE_ERR_DEVICE: no device, or another device current.
  * Known limitation, as for the encryption entries: the AES behind the stream is a T-table implementation in LDS; its timing
  * depends on the bank pattern of data-dependent lookups, i.e. it is not constant-time, and secret seeds pass through it.
- * Not here: DefaultQueryGenerator's queue and actor, seed generation, protobuf Requests / Responses, DatabaseMap sharding. */
+ * Not here: DefaultQueryGenerator's queue and actor, seed generation, protobuf Requests / Responses.  (DatabaseMap sharding: the
+ * section after this one.) */
 #define HE_SIMPLE_PIR_ERROR_STDDEV32 0 /* ErrorStdDev.stdDev32: sigma 3.2, k = 21 trial bits a side, 16 stream bytes a coefficient */
 #define HE_SIMPLE_PIR_ERROR_STDDEV64 1 /* ErrorStdDev.stdDev64: sigma 6.4, k = 82, 32 stream bytes, mask 2^18 - 1 on words 1 and 3 */
 /* What the client entries do for a shape (the first six arguments are he_simple_pir_shape's, with its errors) and a batch.  Host
@@ -1760,6 +1761,100 @@ int he_simple_pir_add_indices_device(const he_simple_pir_context* ctx, uint32_t 
 int he_simple_pir_decrypt_responses_device(const he_simple_pir_context* ctx, uint32_t word_bits, const void* responses,
                                            const void* results_without_response, const uint64_t* indices, uint8_t* entries,
                                            uint32_t* flags, size_t batch, void* workspace, size_t workspace_bytes, he_stream s);
+
+/* ---- SimplePIR over sharded databases (PrivateInformationRetrieval/SimplePir/DatabaseMap.swift, SimplePir+Shards.swift) ------
+ * What Sources/SimplePIRProcessDatabase/main.swift runs before SimplePirServer.process, and what SimplePirClientForAllShards
+ * does around the per-shard clients.  With S = shard_count, C = chunk_size, len_e the bytes of value e
+ * (value_offsets[e + 1] - value_offsets[e]) and order_e its row of shard_orders -- the reference's randomShards, a permutation
+ * of 0 .. S - 1 (DatabaseMap.swift:92):
+ *   c_e = ceil(len_e / C) chunks; an empty value has none but keeps its entry (size 0, chunks [])
+ *   chunk k of entry e lies in shard order_e[k mod S], at index (rows that shard got from entries before e) + floor(k / S)
+ *   entry e gives shard s exactly floor(c_e / S) + [order_e^-1(s) < c_e mod S] rows
+ * The reference draws order_e from the system generator; this library generates no randomness, so the orders are an input and
+ * every result is a function of the arguments.  A flat chunk id counts chunks in entry-then-chunk order: chunk k of entry e is
+ * out_chunk_starts[e] + k.  All device entries are enqueue-only on `s`; 8-byte arrays are 8-byte aligned, 4-byte arrays 4-byte
+ * aligned (HE_ERR_INVALID_ARGUMENT otherwise), written arrays overlap nothing else (HE_ERR_INVALID_ARGUMENT).  Every store is
+ * bounded by the capacities stated here, whatever the device arrays hold.  No _u32 twins: nothing here has a slab word.
+ * Reference behaviour kept: ShardMap.shardCount is the number of shards that RECEIVED a chunk, not S (SimplePir+Shards.swift:
+ * 31-36), and SimplePirClientForAllShards.init throws when it differs from the client count (:65-69) -- host logic, left to the
+ * caller (heamd.SimplePirShardMap / SimplePirClientForAllShards do it).
+ * Not here: drawing the orders, the Array2d / SimplePirDatabase files, protobuf SimplePIRConfig and databaseMapping. */
+#define HE_SIMPLE_PIR_SHARD_FORM_NONE 0 /* nothing to write */
+#define HE_SIMPLE_PIR_SHARD_FORM_BYTE 1 /* a lane writes 1 byte */
+#define HE_SIMPLE_PIR_SHARD_FORM_WORD 2 /* 8 bytes: the written slab (and the chunks the assembly reads) on 8-byte boundaries, C a multiple of 8 */
+#define HE_SIMPLE_PIR_SHARD_FORM_WIDE 3 /* 16 bytes: the same on 16-byte boundaries, C a multiple of 16 */
+/* What DatabaseMap.shardDatabase (DatabaseMap.swift:82-110) does for a database.  Host only: callable without a GPU.
+ *   value_offsets  HOST [count + 1]      shards_address  where the slab of he_simple_pir_shard_scatter_device will lie (its low
+ *   four bits decide the form; nothing is read there)
+ *   out_total_chunks         sum of c_e: rows of all shards, and the capacity of the three chunk arrays below
+ *   out_maximum_chunk_count  ShardMap.maximumChunkCount (SimplePir+Shards.swift:37)
+ *   out_chunks_per_shard     ceil(maximum_chunk_count / S): ShardMap.chunksPerShard (:39) when every shard received a chunk
+ *   out_scatter_form         HE_SIMPLE_PIR_SHARD_FORM_* of the scatter
+ *   out_map_tile_entries     entries of one workgroup in the two map passes (128)      out_map_tiles  their workgroups
+ *   out_count_workgroups     workgroups of the chunk-count pass
+ *   out_scratch_bytes        stream-ordered scratch of the map: O(out_map_tiles x S) and the sums of two scans
+ * Any out pointer may be NULL.  HE_ERR_INVALID_ARGUMENT: S outside 1 .. 256, C = 0, count above 2^32 - 2, offsets that
+ * decrease, more than 2^32 - 1 chunks. */
+int he_simple_pir_shard_plan(const uint64_t* value_offsets, size_t count, size_t shard_count, size_t chunk_size,
+                             uint64_t shards_address, uint64_t* out_total_chunks, uint64_t* out_maximum_chunk_count,
+                             uint64_t* out_chunks_per_shard, uint32_t* out_scatter_form, uint32_t* out_map_tile_entries,
+                             size_t* out_map_tiles, size_t* out_count_workgroups, size_t* out_scratch_bytes);
+/* The map of DatabaseMap.shardDatabase (DatabaseMap.swift:90-104: the chunk locations of every entry).  All pointers DEVICE.
+ *   value_offsets         [count + 1] 8-byte words      shard_orders  [count][S] bytes
+ *   total_chunks          the caller's claim (he_simple_pir_shard_plan's) and the capacity of the three chunk arrays
+ *   out_chunk_starts      [count + 1] 8-byte words: the exclusive scan of c_e
+ *   out_chunk_shard       [total_chunks] 4-byte words: the shard of each chunk, by flat chunk id (ChunkLocation.shardIndex)
+ *   out_chunk_index       [total_chunks] 4-byte words: its index within that shard (ChunkLocation.index)
+ *   out_shard_row_starts  [S + 1] 8-byte words: shard s owns rows starts[s] .. starts[s + 1] of the scatter's slab
+ *   out_row_chunk         [total_chunks] 4-byte words: the flat chunk id that fills each slab row
+ *   device_mismatch       optional, one 4-byte word the caller has zeroed.  Bit 0: a row of shard_orders is no permutation of
+ *                         0 .. S - 1 (a value at or above S, or a repeat); that entry is split under the identity order.
+ *                         Bit 1: out_chunk_starts[count] != total_chunks; the chunk arrays then hold nothing usable.
+ * Nothing is written outside the stated arrays in either case.  Three passes over tiles of 128 entries (chunk counts and their
+ * scan; per-tile rows of every shard; their scan by [shard][tile]; the apply pass) -- no workgroup waits for another, and no
+ * atomic decides a position.  Scratch from the library's stream-ordered cache. */
+int he_simple_pir_shard_map_device(const uint64_t* value_offsets, const uint8_t* shard_orders, size_t count, size_t shard_count,
+                                   size_t chunk_size, uint64_t total_chunks, uint64_t* out_chunk_starts, uint32_t* out_chunk_shard,
+                                   uint32_t* out_chunk_index, uint64_t* out_shard_row_starts, uint32_t* out_row_chunk,
+                                   uint32_t* device_mismatch, he_stream s);
+/* The shards of DatabaseMap.shardDatabase (DatabaseMap.swift:93-102, :106-108), back to back.  All pointers DEVICE.
+ *   values         value e is values[value_offsets[e] .. value_offsets[e + 1]); any byte address.  Nothing at or above
+ *                  values_bytes is read
+ *   chunk_starts, row_chunk   the map's out_chunk_starts and out_row_chunk
+ *   shards         [total_chunks][C] bytes.  Every byte is written, the zero padding of each entry's last chunk included, and no
+ *                  other byte.  shards + out_shard_row_starts[s] * C with starts[s + 1] - starts[s] rows is the `entries`
+ *                  argument of he_simple_pir_process_database_device(_u32) for shard s (entry_size_in_bytes = C)
+ * A lane owns an aligned piece of the slab (HE_SIMPLE_PIR_SHARD_FORM_*, by the slab's address and C; the plan says which). */
+int he_simple_pir_shard_scatter_device(const uint8_t* values, uint64_t values_bytes, const uint64_t* value_offsets, size_t count,
+                                       size_t chunk_size, uint64_t total_chunks, const uint64_t* chunk_starts,
+                                       const uint32_t* row_chunk, uint8_t* shards, he_stream s);
+/* SimplePirClientForAllShards.query(for:) up to add(index:) (SimplePir+Shards.swift:71-87) for `batch` lookups.  All DEVICE.
+ *   entry_positions  [batch] 8-byte words: positions in the entry list; at or above count: no such entry (the dictionary from
+ *                    originalIndex to position stays on the host)
+ *   chunk_starts, chunk_shard, chunk_index   the map's arrays      maximum_chunk_count, chunks_per_shard  ShardMap's
+ *   out_indices      [S][batch][chunks_per_shard] 8-byte words: in shard s's plane the indices of the entry's chunks in that shard
+ *                    come first, in chunk order, then zeros (the fake queries at index 0).  A plane is the `indices` argument of
+ *                    he_simple_pir_add_indices_device with batch x chunks_per_shard queries on shard s's context
+ *   out_found        [batch] 4-byte words: 1 for a position below count
+ * HE_ERR_INVALID_ARGUMENT also for maximum_chunk_count above total_chunks or chunks_per_shard 0 with maximum_chunk_count > 0.
+ * No scratch. */
+int he_simple_pir_shard_query_indices_device(const uint64_t* entry_positions, size_t batch, size_t count, size_t shard_count,
+                                             uint64_t total_chunks, uint64_t maximum_chunk_count, uint64_t chunks_per_shard,
+                                             const uint64_t* chunk_starts, const uint32_t* chunk_shard, const uint32_t* chunk_index,
+                                             uint64_t* out_indices, uint32_t* out_found, he_stream s);
+/* SimplePirClientForAllShards.decrypt after the per-shard decryptions (SimplePir+Shards.swift:139-171).  All DEVICE.
+ *   chunks       [S][batch][chunks_per_shard][C] bytes: what he_simple_pir_decrypt_responses_device wrote, per shard
+ *   indices      he_simple_pir_shard_query_indices_device's out_indices      entry_positions  as there
+ *   out_entries  [batch][maximum_chunk_count * C] bytes      out_sizes  [batch] 8-byte words      out_found  [batch] 4-byte words
+ * Chunk k of an entry comes from the LAST slot of its shard whose index equals the chunk's index, from slot 0 when none does
+ * (:159-164) -- so a real chunk at index 0 is read from a trailing fake query.  Bytes at and above the entry's size are zero.
+ * An absent entry walks (shard 0, index 0) for all maximum_chunk_count chunks (:147-157) and yields zeros, size 0, found 0: it
+ * reads and writes as many bytes as a present one, and the mask comes last.  No scratch. */
+int he_simple_pir_shard_assemble_device(const uint8_t* chunks, const uint64_t* indices, const uint64_t* entry_positions, size_t batch,
+                                        const uint64_t* value_offsets, size_t count, size_t shard_count, size_t chunk_size,
+                                        uint64_t total_chunks, uint64_t maximum_chunk_count, uint64_t chunks_per_shard,
+                                        const uint64_t* chunk_starts, const uint32_t* chunk_shard, const uint32_t* chunk_index,
+                                        uint8_t* out_entries, uint64_t* out_sizes, uint32_t* out_found, he_stream s);
 
 /* PirUtil.expand(ciphertexts:outputCount:using:) (PrivateInformationRetrieval/IndexPir/PirUtil.swift:196-355):
  * oblivious expansion of `ciphertext_count` query ciphertexts [..][2][L][N] (Coeff, top level) into `output_count`

@@ -321,6 +321,15 @@ SIGNATURES = [
      [vp, c_u32, ctypes.c_int, vp, vp, vp, vp, vp, vp, c_size, vp, c_size, vp]),
     ("he_simple_pir_add_indices_device", ctypes.c_int, [vp, c_u32, vp, vp, vp, c_size, vp]),
     ("he_simple_pir_decrypt_responses_device", ctypes.c_int, [vp, c_u32, vp, vp, vp, vp, vp, c_size, vp, c_size, vp]),
+    ("he_simple_pir_shard_plan", ctypes.c_int,
+     [U64P, c_size, c_size, c_size, c_u64, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(c_u64),
+      ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_size), ctypes.POINTER(c_size), ctypes.POINTER(c_size)]),
+    ("he_simple_pir_shard_map_device", ctypes.c_int, [vp, vp, c_size, c_size, c_size, c_u64, vp, vp, vp, vp, vp, vp, vp]),
+    ("he_simple_pir_shard_scatter_device", ctypes.c_int, [vp, c_u64, vp, c_size, c_size, c_u64, vp, vp, vp, vp]),
+    ("he_simple_pir_shard_query_indices_device", ctypes.c_int,
+     [vp, c_size, c_size, c_size, c_u64, c_u64, c_u64, vp, vp, vp, vp, vp, vp]),
+    ("he_simple_pir_shard_assemble_device", ctypes.c_int,
+     [vp, vp, vp, c_size, vp, c_size, c_size, c_size, c_u64, c_u64, c_u64, vp, vp, vp, vp, vp, vp, vp]),
     ("he_pnns_context_create", ctypes.c_int, [vp, ctypes.POINTER(vp)]),
     ("he_pnns_context_destroy", None, [vp]),
     ("he_pnns_matrix_shape", ctypes.c_int,
@@ -2195,6 +2204,167 @@ class SimplePirClient:
             vp(entries.data_ptr()), vp(flags.data_ptr()), batch, *self._scratch("decrypt_responses", batch, workspace),
             _stream(stream)))
         return entries, flags
+
+
+SIMPLE_PIR_SHARD_FORMS = {0: "none", 1: "byte", 2: "word", 3: "wide"}  # HE_SIMPLE_PIR_SHARD_FORM_*
+
+
+def simple_pir_shard_plan(value_offsets, shard_count, chunk_size, shards_address=0):
+    """he_simple_pir_shard_plan: what DatabaseMap.shardDatabase does for the values whose HOST offsets are value_offsets
+    [count + 1] -> dict.  shards_address: where the shard slab will lie (its low four bits decide the form).  Host only."""
+    offsets = np.ascontiguousarray(np.asarray(value_offsets, dtype=np.uint64))
+    if offsets.ndim != 1 or offsets.size < 1:
+        raise ValueError("count + 1 offsets")
+    total, largest, per_shard, scratch = c_u64(0), c_u64(0), c_u64(0), c_size(0)
+    form, tile, tiles, workgroups = c_u32(0), c_u32(0), c_size(0), c_size(0)
+    ref = ctypes.byref
+    _check(load_library().he_simple_pir_shard_plan(
+        offsets.ctypes.data_as(U64P), offsets.size - 1, int(shard_count), int(chunk_size), int(shards_address), ref(total),
+        ref(largest), ref(per_shard), ref(form), ref(tile), ref(tiles), ref(workgroups), ref(scratch)))
+    return {"total_chunks": total.value, "maximum_chunk_count": largest.value, "chunks_per_shard": per_shard.value,
+            "scatter_form": SIMPLE_PIR_SHARD_FORMS[form.value], "map_tile_entries": tile.value, "map_tiles": tiles.value,
+            "count_workgroups": workgroups.value, "scratch_bytes": scratch.value}
+
+
+class SimplePirShardMap:
+    """DatabaseMap + ShardMap (PrivateInformationRetrieval/SimplePir/DatabaseMap.swift, SimplePir+Shards.swift:18-45) with the
+    chunk locations on the device: value_offsets and chunk_starts int64 [count + 1], chunk_shard / chunk_index / row_chunk int32
+    [total_chunks], shard_row_starts int64 [S + 1].  shard_count is ShardMap.shardCount -- the shards that received a chunk,
+    not the S the database was split into (requested_shard_count) -- and chunks_per_shard divides by it, as the reference does.
+    positions: the host dictionary originalIndex -> position in the entry list; of duplicate indices the last stays."""
+
+    def __init__(self, arrays, requested_shard_count, chunk_size, plan, shard_rows, original_indices=None):
+        self.value_offsets, self.chunk_starts, self.chunk_shard, self.chunk_index, self.shard_row_starts, self.row_chunk = arrays
+        self.requested_shard_count, self.chunk_size = int(requested_shard_count), int(chunk_size)
+        self.count = self.value_offsets.numel() - 1
+        self.total_chunks = plan["total_chunks"]
+        self.maximum_chunk_count = plan["maximum_chunk_count"]
+        self.shard_rows = [int(rows) for rows in shard_rows]
+        self.shard_count = sum(1 for rows in self.shard_rows if rows != 0)
+        self.chunks_per_shard = -(-self.maximum_chunk_count // self.shard_count) if self.shard_count else 0
+        indices = range(self.count) if original_indices is None else original_indices
+        self.positions = {int(original): position for position, original in enumerate(indices)}
+        if original_indices is not None and len(original_indices) != self.count:
+            raise ValueError("one original index per entry")
+
+    def position_of(self, original_index):
+        """the position of an original index in the entry list; `count` (no such entry) for one the map does not hold"""
+        return self.positions.get(int(original_index), self.count)
+
+
+class SimplePirDatabaseMap:
+    """DatabaseMap.shardDatabase (DatabaseMap.swift:82-110) on the device."""
+
+    @staticmethod
+    def shard_database(values, value_offsets, orders, shard_count, chunk_size=None, original_indices=None, stream=None,
+                       mismatch=None):
+        """values: a uint8 CUDA tensor (value e is values[value_offsets[e] : value_offsets[e + 1]], any address);
+        value_offsets: HOST [count + 1]; orders: uint8 [count][shard_count], each row the entry's order of the shards (the
+        reference's randomShards; HOST or CUDA).  chunk_size None: ceil(largest value / shard_count), as
+        SimplePIRProcessDatabase computes it (main.swift:204).  -> (SimplePirShardMap, [shard_count] uint8 views
+        [rows_s][chunk_size] of one slab, each the `entries` of SimplePirServer.process).  Reads the shard row counts back (the
+        views need them): synchronises."""
+        import torch
+
+        if stream is not None:  # uploads, allocations and the read-back follow the caller's stream
+            with torch.cuda.stream(stream):
+                return SimplePirDatabaseMap.shard_database(values, value_offsets, orders, shard_count, chunk_size,
+                                                           original_indices, None, mismatch)
+        offsets = np.ascontiguousarray(np.asarray(value_offsets, dtype=np.uint64))
+        count, shard_count = offsets.size - 1, int(shard_count)
+        if chunk_size is None:
+            largest = int(np.max(np.diff(offsets.astype(np.int64)))) if count else 0
+            chunk_size = max(-(-largest // shard_count), 1) if shard_count else 0
+        device = values.device
+        plan = simple_pir_shard_plan(offsets, shard_count, chunk_size)
+        total = plan["total_chunks"]
+        slab = torch.empty((total * chunk_size,), dtype=torch.uint8, device=device)
+        if not torch.is_tensor(orders):
+            orders = torch.from_numpy(np.ascontiguousarray(np.asarray(orders, dtype=np.uint8)))
+        orders = orders.to(device)
+        if orders.numel() != count * shard_count:
+            raise ValueError("expected orders [count][shard_count]")
+        offsets_device = torch.from_numpy(offsets.view(np.int64)).to(device)
+        words = lambda n, dtype: torch.empty((n,), dtype=dtype, device=device)  # noqa: E731
+        chunk_starts, row_starts = words(count + 1, torch.int64), words(shard_count + 1, torch.int64)
+        chunk_shard, chunk_index, row_chunk = (words(total, torch.int32) for _ in range(3))
+        lib = load_library()
+        _check(lib.he_simple_pir_shard_map_device(
+            _ptr(offsets_device), _byte_ptr(orders), count, shard_count, int(chunk_size), total, _ptr(chunk_starts),
+            _ptr(chunk_shard, WORD32), _ptr(chunk_index, WORD32), _ptr(row_starts), _ptr(row_chunk, WORD32),
+            _opt_ptr(mismatch, WORD32), _stream(stream)))
+        _check(lib.he_simple_pir_shard_scatter_device(
+            _byte_ptr(values), values.numel(), _ptr(offsets_device), count, int(chunk_size), total, _ptr(chunk_starts),
+            _ptr(row_chunk, WORD32), _byte_ptr(slab), _stream(stream)))
+        starts =[int(v) for v in row_starts.cpu().tolist()]
+        bounded = [min(max(v, 0), total) for v in starts]  # (a mismatch leaves them unusable: the views stay inside the slab)
+        shards = [slab[bounded[s] * chunk_size: max(bounded[s + 1], bounded[s]) * chunk_size].view(-1, int(chunk_size))
+                  for s in range(shard_count)]
+        shard_map = SimplePirShardMap((offsets_device, chunk_starts, chunk_shard, chunk_index, row_starts, row_chunk), shard_count,
+                                      chunk_size, plan, [len(shard) for shard in shards], original_indices)
+        shard_map.scatter_form = simple_pir_shard_plan(offsets, shard_count, chunk_size, slab.data_ptr())["scatter_form"]
+        return shard_map, shards
+
+
+class SimplePirClientForAllShards:
+    """SimplePirClientForAllShards (SimplePir+Shards.swift:47-173) for batches of B lookups: the index lists of query(for:) and
+    the assembly of decrypt, around per-shard SimplePirClient objects (shard s's client was made from the params and hint of
+    the server that processed shard s)."""
+
+    def __init__(self, shard_map, clients):
+        if shard_map.shard_count != len(clients):  # (:65-69)
+            raise ValueError(f"Mismatching shard count {shard_map.shard_count} and number of clients {len(clients)}")
+        if shard_map.shard_count != shard_map.requested_shard_count:
+            raise ValueError("a shard without a chunk has no database to query")
+        self.shard_map, self.clients = shard_map, list(clients)
+
+    @property
+    def queries_per_shard(self):
+        return self.shard_map.chunks_per_shard
+
+    def _positions(self, original_indices):
+        import torch
+
+        m = self.shard_map
+        positions = np.array([m.position_of(index) for index in original_indices], dtype=np.int64)
+        return torch.from_numpy(positions).to(m.chunk_starts.device)
+
+    def query_indices(self, original_indices, stream=None):
+        """query(for:) up to add(index:) -> (indices int64 [S][B][chunks_per_shard], found int32 [B]); indices[s].reshape(-1) is
+        the `indices` of clients[s].add_indices for B x chunks_per_shard queries."""
+        import torch
+
+        m = self.shard_map
+        positions = self._positions(original_indices)
+        batch = positions.numel()
+        indices = torch.empty((m.requested_shard_count, batch, m.chunks_per_shard), dtype=torch.int64, device=positions.device)
+        found = torch.empty((batch,), dtype=torch.int32, device=positions.device)
+        _check(load_library().he_simple_pir_shard_query_indices_device(
+            _ptr(positions), batch, m.count, m.requested_shard_count, m.total_chunks, m.maximum_chunk_count, m.chunks_per_shard,
+            _ptr(m.chunk_starts), _ptr(m.chunk_shard, WORD32), _ptr(m.chunk_index, WORD32), _ptr(indices),
+            _ptr(found, WORD32), _stream(stream)))
+        return indices, found
+
+    def assemble(self, chunks, indices, original_indices, stream=None):
+        """decrypt after the per-shard decryptions: chunks uint8 [S][B][chunks_per_shard][chunk_size], indices as
+        query_indices returned them -> (entries uint8 [B][maximum_chunk_count * chunk_size], sizes int64 [B], found int32 [B]);
+        entry b is entries[b, :sizes[b]] where found[b] is 1."""
+        import torch
+
+        m = self.shard_map
+        positions = self._positions(original_indices)
+        batch = positions.numel()
+        if tuple(chunks.shape) != (m.requested_shard_count, batch, m.chunks_per_shard, m.chunk_size):
+            raise ValueError("expected chunks [shard_count][B][chunks_per_shard][chunk_size]")
+        entries = torch.empty((batch, m.maximum_chunk_count * m.chunk_size), dtype=torch.uint8, device=positions.device)
+        sizes = torch.empty((batch,), dtype=torch.int64, device=positions.device)
+        found = torch.empty((batch,), dtype=torch.int32, device=positions.device)
+        _check(load_library().he_simple_pir_shard_assemble_device(
+            _byte_ptr(chunks), _ptr(indices), _ptr(positions), batch, _ptr(m.value_offsets), m.count, m.requested_shard_count,
+            m.chunk_size, m.total_chunks, m.maximum_chunk_count, m.chunks_per_shard, _ptr(m.chunk_starts),
+            _ptr(m.chunk_shard, WORD32), _ptr(m.chunk_index, WORD32), _byte_ptr(entries), _ptr(sizes), _ptr(found, WORD32),
+            _stream(stream)))
+        return entries, sizes, found
 
 
 PNNS_PACKINGS = {"denseColumn": 0, "denseRow": 1, "diagonal": 2}  # MatrixPacking's case order (HE_PNNS_PACKING_*)
