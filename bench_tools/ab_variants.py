@@ -8,7 +8,9 @@ An edit of a header needs COMPILE: exactly the units that include it, directly o
 headers (ntt_forward_tiled.hpp, ntt_inverse_tiled.hpp, ntt_interleaved.hpp) compiled by ntt_tiled_4096.hip,
 ntt_forward_8192.hip and ntt_inverse_8192.hip, beside ntt_generic.hip and the routing unit ntt_routing.hip: an edit of one
 family rebuilds the two units that include it, an edit of the launch policy (ntt_policy.hpp) every unit that instantiates or
-launches by it.  An edit that makes ntt_routing.hip refer to a selector shape the product does not instantiate (a policy
+launches by it.  The 4-byte transform is one unit, ntt_word32.hip, which shares ntt_common.hpp (and only that) with the 8-byte
+ones: an edit of ntt_common.hpp rebuilds it with them and with behz_kernels.hip, an edit of any other NTT header does not.
+grid_for is defined per unit (poly_kernels.hip, galois_kernels.hip, rns_kernels.hip, copy_kernels.hip).  An edit that makes ntt_routing.hip refer to a selector shape the product does not instantiate (a policy
 constant that opens another route) carries a second edit appending the HEAMD_* instantiation line to the unit that
 compiles that family (fused_keymac_16384.py); variants link with --no-undefined like the product, so a missing one
 fails the build.

@@ -47,8 +47,12 @@ PIPELINE = [
 ]
 
 
-def disassemble(obj, workdir):
+def disassemble(obj, workdir, full_names=False):
+    """{kernel name: the lines of its disassembly} of an object of the build directory (or any object, by absolute path).
+    full_names: keyed by the demangled name as it is, not by the short one the profiles print."""
     code = kernel_metadata.code_object(os.path.join(BUILD, obj), workdir)
+    if code is None:  # a unit without device code
+        return {}
     text = subprocess.run([f"{kernel_metadata.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", code], capture_output=True,
                           text=True, check=True).stdout
     kernels, name, body = {}, None, []
@@ -64,7 +68,7 @@ def disassemble(obj, workdir):
         kernels[name] = body
     mangled = list(kernels)
     names = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.split("\n")
-    return {kernel_metadata.short_name(n): kernels[m] for m, n in zip(mangled, names)}
+    return {(n if full_names else kernel_metadata.short_name(n)): kernels[m] for m, n in zip(mangled, names)}
 
 
 def count(body, trips):

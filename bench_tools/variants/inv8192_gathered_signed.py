@@ -1,4 +1,4 @@
-COMPILE = ["behz_kernels.hip", "ntt_forward_8192.hip", "ntt_generic.hip", "ntt_inverse_8192.hip", "ntt_routing.hip", "ntt_tiled_4096.hip", "word32_kernels.hip"]
+COMPILE = ["behz_kernels.hip", "ntt_forward_8192.hip", "ntt_generic.hip", "ntt_inverse_8192.hip", "ntt_routing.hip", "ntt_tiled_4096.hip", "ntt_word32.hip"]
 DESCRIPTION = ("the plain-slab inverse at N = 8192 signed in the stages whose twiddles are gathered only (scalar bias, no vector copy), "
                "unsigned beside wave-uniform twiddles; lane index re-derived")
 EDITS = [

@@ -1,4 +1,4 @@
-COMPILE = ["behz_kernels.hip", "ntt_forward_8192.hip", "ntt_generic.hip", "ntt_inverse_8192.hip", "ntt_routing.hip", "ntt_tiled_4096.hip", "word32_kernels.hip"]
+COMPILE = ["behz_kernels.hip", "ntt_forward_8192.hip", "ntt_generic.hip", "ntt_inverse_8192.hip", "ntt_routing.hip", "ntt_tiled_4096.hip", "ntt_word32.hip"]
 DESCRIPTION = ("per-transpose LDS padding rules in the limb-wise inverse kernels too (they keep the common rule: the rules' lane-base "
                "address words cost registers), with rules assigned to the top-partial order's transposes by analogy with the forward's")
 EDITS = [

@@ -1,4 +1,4 @@
-COMPILE = ["behz_kernels.hip", "ntt_forward_8192.hip", "ntt_generic.hip", "ntt_inverse_8192.hip", "ntt_routing.hip", "ntt_tiled_4096.hip", "word32_kernels.hip"]
+COMPILE = ["behz_kernels.hip", "ntt_forward_8192.hip", "ntt_generic.hip", "ntt_inverse_8192.hip", "ntt_routing.hip", "ntt_tiled_4096.hip", "ntt_word32.hip"]
 DESCRIPTION = "TIMING ONLY (wrong results): the gathered twiddles of the limb-wise butterflies (the interleaved rows of N = 16384 / 32768) made up from the lane index instead of loaded -- what their gathers cost"
 EDITS = [("ntt_common.hpp",
           "    } else if constexpr (MODE == kModeSplit || MODE == kModeSplitSigned) {\n"

@@ -314,7 +314,7 @@ int key_mac_to_coeff(const W* spread, const W* key, W* prod, const PolyContext& 
 
 // The inner product with the key, the inverse transforms and the key switch's last step (`end`: relinearize, added_polys = 2)
 // in two launches of one kernel where the degree and the batch have it (ntt_sources.hpp kInverseFromKeyMacFinish,
-// word32_kernels.hip kSource32KeyMacFinish); *finished = false otherwise (nothing launched).
+// ntt_word32.hip kSource32KeyMacFinish); *finished = false otherwise (nothing launched).
 template <typename W>
 int key_mac_and_finish(const W* spread, const W* key, W* prod, const heamd::KeySwitchEnd<W>& end, const PolyContext& ks_ctx,
                        uint32_t L, uint32_t top_rows, size_t polys, hipStream_t stream, bool* finished) {

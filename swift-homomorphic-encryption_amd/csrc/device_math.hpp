@@ -913,7 +913,7 @@ __device__ __forceinline__ uint64_t barrett_reduce128(U128 x, uint64_t p, uint64
     return csub63(x.lo - q_lo * p, 0 - p);
 }
 
-// ---- 4-byte words (word32_kernels.hip: moduli <= 2^30 - 1) ------------------------------------------------------------
+// ---- 4-byte words (ntt_word32.hip, poly_kernels.hip: moduli <= 2^30 - 1) ----------------------------------------------
 __device__ __forceinline__ uint32_t csub32(uint32_t x, uint32_t m) { return x >= m ? x - m : x; }
 // x w mod p in [0, 2p) for any 32-bit x: Shoup with wf = floor(w 2^32 / p)
 __device__ __forceinline__ uint32_t shoup32_lazy(uint32_t x, uint32_t w, uint32_t wf, uint32_t p) {

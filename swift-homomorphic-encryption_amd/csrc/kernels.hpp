@@ -1,8 +1,9 @@
 // kernels.hpp -- host-callable launchers of the HIP kernels (all asynchronous on `stream`).  A kernel family that exists on
 // both slab words has ONE launcher name, overloaded on the slab pointer: uint64_t slabs take a DeviceContext, uint32_t slabs
-// (word32_kernels.hip: PolyRq<UInt32>, every modulus <= 2^30 - 1) a DeviceContext32 -- word_layer.hpp word_image<W> yields
-// either.  Where the 8-byte kernel has something the 4-byte one lacks, the 4-byte overload returns hipErrorNotSupported before
-// any launch: the signal every caller already falls back on.
+// (PolyRq<UInt32>, every modulus <= 2^30 - 1) a DeviceContext32 -- word_layer.hpp word_image<W> yields either.  Both overloads
+// of a family are defined by the family's unit(s), named at the head of each block below; the transforms' 4-byte overloads by
+// ntt_word32.hip.  Where the 8-byte kernel has something the 4-byte one lacks, the 4-byte overload returns
+// hipErrorNotSupported before any launch: the signal every caller already falls back on.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +14,8 @@
 
 namespace heamd {
 
+// ---- the transforms -- 8-byte slabs: ntt_routing.hip (launchers; the kernels are in the other ntt_*.hip units); 4-byte
+// slabs: ntt_word32.hip (kernels and launchers) -----------------------------------------------------------------------------
 // kernel schedule for launch_ntt (tests pin each against the oracle; production callers pass kNttVariantAuto).  Every
 // variant computes the same canonical transform.
 enum {
@@ -73,21 +76,6 @@ hipError_t launch_ntt_tensor_inverse(const uint64_t* lifted, uint64_t* out, cons
                                      size_t items, hipStream_t stream);
 hipError_t launch_ntt_tensor_inverse(const uint32_t* lifted, uint32_t* out, const DeviceContext32& ctx, uint32_t record_rows,
                                      size_t items, hipStream_t stream);
-// behz_kernels.hip -- BEHZ multiplication row by row (Bfv+Multiply.swift:18-85): per (item, [Q, Bsk] row) the four forward
-// transforms, the tensor product and the three inverse transforms scaled by t in one workgroup, the transformed rows never
-// leaving its registers.  lhs, rhs: [items][2][source_moduli][N] Coeff, items ct_stride words apart (their rows are the Q
-// rows of the lifted polynomials); lifted: [items][4][record_rows][N] with the Bsk rows written by the lift (the Q rows are
-// not read); scaled_qbsk: the [Q, Bsk] context with t N^-1 as inverse-degree constants; out: [items][3][record_rows][N]
-// Coeff, what launch_floor_qbsk_to_q takes.  hipErrorNotSupported (nothing launched, behz_rows_fused_supported false):
-// launch_ntt_lifted_forward + launch_ntt_tensor_inverse.
-bool behz_rows_fused_supported(const DeviceContext& qbsk, uint32_t record_rows, uint32_t source_moduli, size_t items);
-// whether the row bands that read the lift's rows take them in [0, 5p) (every such row on the fold butterflies of the plus form,
-// whose first stage wants x < 8p and any y): the lift may then skip its three conditional subtracts per word
-bool behz_lifted_rows_may_be_lazy(const DeviceContext& scaled_qbsk, uint32_t record_rows, uint32_t source_moduli);
-constexpr int kBehzAllRows = 0, kBehzCiphertextRows = 1, kBehzLiftedRows = 2;
-hipError_t launch_behz_rows_fused(const uint64_t* lhs, const uint64_t* rhs, size_t ct_stride, const uint64_t* lifted,
-                                  uint64_t* out, const DeviceContext& scaled_qbsk, uint32_t record_rows, uint32_t source_moduli,
-                                  size_t items, hipStream_t stream, int part = kBehzAllRows);
 // Bfv+Keys.swift:180-207 into the inverse transform's load: spread [polys][L][L+1][N], key [L][2][top_rows][N] -> out
 // [polys][2][L+1][N] (Coeff).  hipErrorNotSupported for degrees without a tiled kernel (4-byte words: and for L > 15).
 hipError_t launch_ntt_key_mac_inverse(const uint64_t* spread, const uint64_t* key, uint64_t* out, const DeviceContext& ks,
@@ -126,6 +114,23 @@ hipError_t launch_ntt_key_mac_inverse_finish(const uint32_t* spread, const uint3
                                              uint32_t top_rows, size_t polys, hipStream_t stream);
 const char* ntt_variant_name(uint32_t log_degree);
 
+// ---- behz_kernels.hip -- BEHZ multiplication row by row (Bfv+Multiply.swift:18-85): per (item, [Q, Bsk] row) the four forward
+// transforms, the tensor product and the three inverse transforms scaled by t in one workgroup, the transformed rows never
+// leaving its registers.  lhs, rhs: [items][2][source_moduli][N] Coeff, items ct_stride words apart (their rows are the Q
+// rows of the lifted polynomials); lifted: [items][4][record_rows][N] with the Bsk rows written by the lift (the Q rows are
+// not read); scaled_qbsk: the [Q, Bsk] context with t N^-1 as inverse-degree constants; out: [items][3][record_rows][N]
+// Coeff, what launch_floor_qbsk_to_q takes.  hipErrorNotSupported (nothing launched, behz_rows_fused_supported false):
+// launch_ntt_lifted_forward + launch_ntt_tensor_inverse.
+bool behz_rows_fused_supported(const DeviceContext& qbsk, uint32_t record_rows, uint32_t source_moduli, size_t items);
+// whether the row bands that read the lift's rows take them in [0, 5p) (every such row on the fold butterflies of the plus form,
+// whose first stage wants x < 8p and any y): the lift may then skip its three conditional subtracts per word
+bool behz_lifted_rows_may_be_lazy(const DeviceContext& scaled_qbsk, uint32_t record_rows, uint32_t source_moduli);
+constexpr int kBehzAllRows = 0, kBehzCiphertextRows = 1, kBehzLiftedRows = 2;
+hipError_t launch_behz_rows_fused(const uint64_t* lhs, const uint64_t* rhs, size_t ct_stride, const uint64_t* lifted,
+                                  uint64_t* out, const DeviceContext& scaled_qbsk, uint32_t record_rows, uint32_t source_moduli,
+                                  size_t items, hipStream_t stream, int part = kBehzAllRows);
+
+// ---- poly_kernels.hip: element-wise operations, modulus switching and lazy inner products, on both slab words ---------------
 enum class ElementwiseOp : int { Add = 0, Sub = 1, Neg = 2, Mul = 3, MulScalar = 4 };
 // lhs[k] = op(lhs[k], rhs[k]) over `rows` rows of [..][L][N]; rhs may be NULL for Neg and MulScalar.  MulScalar reads
 // `scalars`, a device array of L (scalar, 64-bit Shoup factor) pairs, and nothing else does.
@@ -173,27 +178,28 @@ struct PackedLayout {
     uint32_t width[kMaxPackedRows];
     uint32_t word_offset[kMaxPackedRows + 1];  // [rows] = 8-byte words per packed polynomial
 };
-// slab [polys][rows][N] -> packed [polys][word_offset[rows]] words
+// slab [polys][rows][N] -> packed [polys][word_offset[rows]] words (galois_kernels.hip)
 hipError_t launch_pack_rows(const uint64_t* slab, uint64_t* packed, const PackedLayout& layout, uint32_t log_degree,
                             size_t polys, hipStream_t stream);
 // launch_inner_product_plain with the plaintexts packed: pts [columns][count][word_offset[rows]] words.  poly_count 1..3,
-// degree >= 256.
+// degree >= 256 (poly_kernels.hip).
 hipError_t launch_inner_product_plain_packed(const uint64_t* cts, const uint64_t* packed_pts, const PackedLayout& layout,
                                              const uint8_t* present_device, uint64_t* out, const DeviceContext& ctx,
                                              uint32_t poly_count, size_t count, size_t columns, uint64_t cadence,
                                              bool narrow_moduli, hipStream_t stream);
 
-// word32_kernels.hip: the bridge between the two slab words
+// ---- copy_kernels.hip: the bridge between the two slab words, and the copies of 8-byte words ---------------------------------
 // packed [UInt32] words <-> the zero-extended 8-byte words of the Bfv<UInt32> scheme layer (16-byte aligned slabs)
 hipError_t launch_widen_words(const uint32_t* in, uint64_t* out, size_t words, hipStream_t stream);
+hipError_t launch_narrow_words(const uint64_t* in, uint32_t* out, size_t words, hipStream_t stream);
+// every word read once and written once, 8 bytes per lane: the reference point of the transforms' roofline figures
 hipError_t launch_stream_copy(const uint64_t* in, uint64_t* out, size_t words, bool non_temporal, hipStream_t stream);
 // `records` runs of record_words words from runs src_stride words apart to runs dst_stride apart (record_words a multiple of 2048,
 // 16-byte aligned slabs, even strides; hipErrorInvalidValue otherwise)
 hipError_t launch_copy_records(const uint64_t* in, size_t src_stride, uint64_t* out, size_t dst_stride, size_t record_words,
                                size_t records, hipStream_t stream);
-hipError_t launch_narrow_words(const uint64_t* in, uint32_t* out, size_t words, hipStream_t stream);
 
-// seeded_kernels.hip: out[b] = PolyRq.random(context, NistAes128Ctr(seed: seeds[b])), seeds [batch][32] bytes
+// ---- seeded_kernels.hip: out[b] = PolyRq.random(context, NistAes128Ctr(seed: seeds[b])), seeds [batch][32] bytes
 // scratch: seeded_uniform_scratch_bytes(ctx, batch) bytes (the per-chunk round keys of every seed's re-key chain)
 // polynomial b starts at out + b * poly_stride words (W: uint64_t or uint32_t slabs; the reduction is the same, the store narrows)
 size_t seeded_uniform_scratch_bytes(const DeviceContext& ctx, size_t batch);
@@ -201,7 +207,7 @@ template <typename W>
 hipError_t launch_seeded_uniform(const uint8_t* seeds, W* out, size_t poly_stride, const DeviceContext& ctx, size_t batch,
                                  void* scratch, hipStream_t stream);
 
-// wire format of a polynomial: per residue row, the serialized bit width and the byte offset of the row
+// ---- galois_kernels.hip: the wire format of a polynomial: per residue row, the serialized bit width and the byte offset of the row
 constexpr uint32_t kMaxSerializedRows = 64;
 struct SerializeLayout {
     uint32_t rows;

@@ -972,6 +972,13 @@ struct PassOrder {
     static constexpr int lo(int k) { return kTop ? LOGN - S::R - k * LOGE : LOGN - (k + 1) * LOGE; }
 };
 
+// Host side, before a launch: a kernel whose row tile is dynamic LDS above the 48 KiB a launch gets by default asks for it.
+template <typename Kernel>
+inline hipError_t allow_dynamic_lds(Kernel kernel, size_t lds_bytes) {
+    if (lds_bytes <= 48 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(lds_bytes));
+}
 
 }  // namespace ntt
 }  // namespace heamd

@@ -334,12 +334,6 @@ __device__ __forceinline__ void inverse_row(uint64_t (&v)[ROWS][1 << LOGE], uint
 template <int MODE>
 constexpr bool kLazyTransformInput = is_split(MODE) || is_fold(MODE);
 constexpr int kLazyInputStages = 3;
-template <typename Kernel>
-inline hipError_t allow_dynamic_lds(Kernel kernel, size_t lds_bytes) {
-    if (lds_bytes <= 48 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(lds_bytes));
-}
 
 // The fold butterflies (ntt_common.hpp kModeFoldMinus / kModeFoldPlus) in place of the [0, 8p) ones where every modulus of
 // the launch allows them -- the 60-bit moduli of the reference's parameter sets, the 61-bit BEHZ auxiliary primes: the

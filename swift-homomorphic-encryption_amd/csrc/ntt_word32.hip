@@ -1,33 +1,26 @@
-// word32_kernels.hip -- PolyRq<UInt32> on the device (the polynomial layer): the same transforms
-// and element-wise operations over 4-byte words, for contexts whose moduli fit UInt32 (<= 2^30 - 1,
-// ModularArithmetic/Scalar.swift:498-511) -- e.g. the n_4096_logq_27_28_28 PIR parameter sets
-// (EncryptionParameters.swift:313-378).  Results are the reference's canonical words, so the 64-bit oracle pins
-// them unchanged; only the storage width and the arithmetic width differ.
+// ntt_word32.hip -- the transforms of PolyRq<UInt32> on the device (the polynomial layer), for contexts
+// whose moduli fit UInt32 (<= 2^30 - 1, ModularArithmetic/Scalar.swift:498-511) -- e.g. the n_4096_logq_27_28_28 PIR
+// parameter sets (EncryptionParameters.swift:313-378).  Results are the reference's canonical words, so the 64-bit oracle
+// pins them unchanged; only the storage width and the arithmetic width differ.  The element-wise 4-byte kernels are in
+// poly_kernels.hip, the bridge between the two slab words in copy_kernels.hip.
 //
 //   NTT            PolyRq+Ntt.swift:237-319, 379-483 -- one workgroup per residue row, the row lives in LDS
 //                  (4 N bytes), radix-2 stages with a barrier each; Harvey butterflies in [0, 4p) < 2^32 with
 //                  32-bit Shoup constants floor(w 2^32 / p): 1 v_mul_hi_u32 + 2 v_mul_lo_u32 per butterfly.
-//   + - neg * *s   PolyRq.swift:147-245, 299-309
-//   divideAndRoundQLast   PolyRq.swift:365-393
+//
+// One unit for the generic kernel, the tiled kernel with its fused row sources and every 4-byte launch_ntt* overload: they
+// share tile32_slot and the launchers route between them, and the whole compiles in seconds.
 #include <hip/hip_runtime.h>
 
 #include "device_context.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
-#include "launch_grid.hpp"
 #include "ntt_common.hpp"
 #include "placement.hpp"
 
 namespace heamd {
 
 namespace {
-
-constexpr unsigned kThreads = 256;
-
-// One workgroup per kThreads work items, up to the grid limit: the kernels keep their grid-stride loops for what lies beyond it,
-// but a lane that walks many items serialises its loads -- divideAndRoundQLast at N = 16384, L = 6 ran at 0.66 of 8 TB/s on
-// 256 x 8 workgroups and at 0.79 with one item per lane (profiles/r06y_exact_grids.txt)
-inline unsigned grid_for(size_t work_items) { return launch_grid::grid_for(work_items, kThreads); }
 
 // +1 word per 32: de-conflicts the power-of-two strides of the late forward / early inverse stages
 __host__ __device__ constexpr uint32_t tile32_slot(uint32_t idx) { return idx + (idx >> 5); }
@@ -196,6 +189,29 @@ __device__ __forceinline__ void row32_store(const uint32_t (&v)[1 << LOGE], uint
         x[register_part<LOGN, LOGE, LO, W>(r) + lane_part<LOGN, LOGE, LO, W>(tid)] = v[r];
 }
 
+// The passes between the first and the last one, tile to tile (ntt_rows.hpp forward_step / inverse_step on 4-byte words).
+// Forward pass k of the schedule (counted from the top) covers bits [forward_lo32(k), ..): full passes, then the partial
+// one on the low bits.  A forward step ends with the fence towards the pass that reads its words, an inverse step begins
+// with the fence behind the pass that wrote them.
+template <int LOGN, int LOGE>
+constexpr int forward_lo32(int k) { return k + 1 < Schedule<LOGN, LOGE>::P ? LOGN - (k + 1) * LOGE : 0; }
+template <int LOGN, int LOGE, int LO, int LO_NEXT>
+__device__ __forceinline__ void forward_step32(uint32_t (&v)[1 << LOGE], uint32_t tid, const U32x2* __restrict__ tw, uint32_t p,
+                                               uint32_t* tile) {
+    tile32_load<LOGN, LOGE, LO, LOGE>(v, tid, tile);
+    forward_pass32<LOGN, LOGE, LO, LOGE>(v, tid, tw, p, false);
+    tile32_store<LOGN, LOGE, LO, LOGE>(v, tid, tile);
+    ntt::lds_transpose_fence<LOGN, LOGE, LO, LO_NEXT>();
+}
+template <int LOGN, int LOGE, int LO_FROM, int LO>
+__device__ __forceinline__ void inverse_step32(uint32_t (&v)[1 << LOGE], uint32_t tid, const U32x2* __restrict__ tw,
+                                               const DeviceModulus& mod, uint32_t* tile) {
+    ntt::lds_transpose_fence<LOGN, LOGE, LO_FROM, LO>();
+    tile32_load<LOGN, LOGE, LO, LOGE>(v, tid, tile);
+    inverse_pass32<LOGN, LOGE, LO, LOGE>(v, tid, tw, mod, false);
+    tile32_store<LOGN, LOGE, LO, LOGE>(v, tid, tile);
+}
+
 // Rows of the partial pass (bits [0, W)) in whole cache lines, as ntt_common.hpp global_store_staged / global_load_staged
 // do for 8-byte words: a lane's run of 2^W words is 2^(W-2) 16-byte chunks; with more than one of them per lane a store
 // as the words lie fills half of 64 lines per instruction.  The wave's block goes through its own slice of the tile and
@@ -344,27 +360,9 @@ __global__ void __launch_bounds__(1 << LOGT)
         forward_pass32<LOGN, LOGE, LO0, LOGE>(v, tid, tw, p, true);
         tile32_store<LOGN, LOGE, LO0, LOGE>(v, tid, tile);
         __syncthreads();
-        if constexpr (S::P >= 3) {
-            constexpr int LO1 = LOGN - 2 * LOGE;
-            tile32_load<LOGN, LOGE, LO1, LOGE>(v, tid, tile);
-            forward_pass32<LOGN, LOGE, LO1, LOGE>(v, tid, tw, p, false);
-            tile32_store<LOGN, LOGE, LO1, LOGE>(v, tid, tile);
-            ntt::lds_transpose_fence<LOGN, LOGE, LO1, (S::P >= 4 ? LOGN - 3 * LOGE : 0)>();
-        }
-        if constexpr (S::P >= 4) {
-            constexpr int LO2 = LOGN - 3 * LOGE;
-            tile32_load<LOGN, LOGE, LO2, LOGE>(v, tid, tile);
-            forward_pass32<LOGN, LOGE, LO2, LOGE>(v, tid, tw, p, false);
-            tile32_store<LOGN, LOGE, LO2, LOGE>(v, tid, tile);
-            ntt::lds_transpose_fence<LOGN, LOGE, LO2, (S::P >= 5 ? LOGN - 4 * LOGE : 0)>();
-        }
-        if constexpr (S::P >= 5) {
-            constexpr int LO3 = LOGN - 4 * LOGE;
-            tile32_load<LOGN, LOGE, LO3, LOGE>(v, tid, tile);
-            forward_pass32<LOGN, LOGE, LO3, LOGE>(v, tid, tw, p, false);
-            tile32_store<LOGN, LOGE, LO3, LOGE>(v, tid, tile);
-            ntt::lds_transpose_fence<LOGN, LOGE, LO3, 0>();
-        }
+        if constexpr (S::P >= 3) forward_step32<LOGN, LOGE, forward_lo32<LOGN, LOGE>(1), forward_lo32<LOGN, LOGE>(2)>(v, tid, tw, p, tile);
+        if constexpr (S::P >= 4) forward_step32<LOGN, LOGE, forward_lo32<LOGN, LOGE>(2), forward_lo32<LOGN, LOGE>(3)>(v, tid, tw, p, tile);
+        if constexpr (S::P >= 5) forward_step32<LOGN, LOGE, forward_lo32<LOGN, LOGE>(3), forward_lo32<LOGN, LOGE>(4)>(v, tid, tw, p, tile);
         tile32_load<LOGN, LOGE, 0, S::R>(v, tid, tile);
         forward_pass32<LOGN, LOGE, 0, S::R>(v, tid, tw, p, false);
 #pragma unroll
@@ -431,27 +429,9 @@ __global__ void __launch_bounds__(1 << LOGT)
         }
         inverse_pass32<LOGN, LOGE, 0, S::R>(v, tid, tw, mod, true);
         tile32_store<LOGN, LOGE, 0, S::R>(v, tid, tile);
-        if constexpr (S::P >= 3) {
-            ntt::lds_transpose_fence<LOGN, LOGE, 0, S::R>();
-            constexpr int LO1 = S::R;
-            tile32_load<LOGN, LOGE, LO1, LOGE>(v, tid, tile);
-            inverse_pass32<LOGN, LOGE, LO1, LOGE>(v, tid, tw, mod, false);
-            tile32_store<LOGN, LOGE, LO1, LOGE>(v, tid, tile);
-        }
-        if constexpr (S::P >= 4) {
-            ntt::lds_transpose_fence<LOGN, LOGE, S::R, S::R + LOGE>();
-            constexpr int LO2 = S::R + LOGE;
-            tile32_load<LOGN, LOGE, LO2, LOGE>(v, tid, tile);
-            inverse_pass32<LOGN, LOGE, LO2, LOGE>(v, tid, tw, mod, false);
-            tile32_store<LOGN, LOGE, LO2, LOGE>(v, tid, tile);
-        }
-        if constexpr (S::P >= 5) {
-            ntt::lds_transpose_fence<LOGN, LOGE, S::R + LOGE, S::R + 2 * LOGE>();
-            constexpr int LO3 = S::R + 2 * LOGE;
-            tile32_load<LOGN, LOGE, LO3, LOGE>(v, tid, tile);
-            inverse_pass32<LOGN, LOGE, LO3, LOGE>(v, tid, tw, mod, false);
-            tile32_store<LOGN, LOGE, LO3, LOGE>(v, tid, tile);
-        }
+        if constexpr (S::P >= 3) inverse_step32<LOGN, LOGE, 0, S::R>(v, tid, tw, mod, tile);
+        if constexpr (S::P >= 4) inverse_step32<LOGN, LOGE, S::R, S::R + LOGE>(v, tid, tw, mod, tile);
+        if constexpr (S::P >= 5) inverse_step32<LOGN, LOGE, S::R + LOGE, S::R + 2 * LOGE>(v, tid, tw, mod, tile);
         __syncthreads();
         constexpr int LOL = LOGN - LOGE;
         tile32_load<LOGN, LOGE, LOL, LOGE>(v, tid, tile);
@@ -499,11 +479,7 @@ hipError_t launch_tiled(bool inverse, uint32_t* slab, const DeviceContext32& ctx
         if (!inverse) return hipErrorInvalidValue;
         kernel = ntt32_tiled_kernel<LOGN, LOGT, true, SOURCE>;
     }
-    if (lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = ntt::allow_dynamic_lds(kernel, lds_bytes); e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(rows)), dim3(1u << LOGT), lds_bytes, stream, slab, ctx,
                        mod_base, mod_period, source);
     return hipGetLastError();
@@ -520,57 +496,6 @@ hipError_t launch_fused(bool inverse, uint32_t* slab, const DeviceContext32& ctx
         case 13: return launch_tiled<13, 10, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
         case 14: return launch_tiled<14, 10, SOURCE>(inverse, slab, ctx, 0, record_rows, rows, stream, source);
         default: return hipErrorNotSupported;
-    }
-}
-
-// ---- element-wise: one lane = one word -------------------------------------------------------------------------
-template <ElementwiseOp OP>
-__global__ void __launch_bounds__(kThreads)
-    elementwise32_kernel(uint32_t* __restrict__ lhs, const uint32_t* __restrict__ rhs, const uint64_t* __restrict__ scalars,
-                         const DeviceContext32 ctx, size_t words) {
-    for (size_t i = blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x; i < words;
-         i += static_cast<size_t>(gridDim.x) * kThreads) {
-        const uint32_t mi = static_cast<uint32_t>((i >> ctx.log_degree) % ctx.moduli_count);
-        const DeviceModulus m = ctx.moduli[mi];
-        const uint32_t p = static_cast<uint32_t>(m.p);
-        const uint32_t a = lhs[i];
-        uint32_t r = 0;
-        if constexpr (OP == ElementwiseOp::Add) r = csub32(a + rhs[i], p);
-        if constexpr (OP == ElementwiseOp::Sub) r = csub32(a + p - rhs[i], p);
-        if constexpr (OP == ElementwiseOp::Neg) r = csub32(p - a, p);
-        if constexpr (OP == ElementwiseOp::Mul)
-            r = static_cast<uint32_t>(barrett_reduce64(static_cast<uint64_t>(a) * rhs[i], m.p, m.barrett64));
-        if constexpr (OP == ElementwiseOp::MulScalar) {
-            const uint32_t s = static_cast<uint32_t>(scalars[2 * mi]), sf = static_cast<uint32_t>(scalars[2 * mi + 1] >> 32);
-            r = csub32(shoup32_lazy(a, s, sf, p), p);
-        }
-        lhs[i] = r;
-    }
-}
-
-// divideAndRoundQLast on 4-byte words: in [polys][L][N] -> out [polys][L-1][N]
-__global__ void __launch_bounds__(kThreads)
-    divide_and_round_q_last32_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
-                                     const DeviceContext32 ctx, uint32_t moduli_count, size_t polys) {
-    const uint32_t logn = ctx.log_degree;
-    const size_t n = size_t(1) << logn, total = polys << logn;
-    const uint32_t last = moduli_count - 1;
-    const uint64_t q_last = ctx.moduli[last].p, q_last_div2 = q_last >> 1;
-    const U64x2* __restrict__ inverse_q_last = ctx.inverse_q_last + static_cast<size_t>(last) * ctx.moduli_stride;
-    for (size_t idx = blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x; idx < total;
-         idx += static_cast<size_t>(gridDim.x) * kThreads) {
-        const size_t poly = idx >> logn, k = idx & (n - 1);
-        const uint32_t* src = in + poly * moduli_count * n + k;
-        uint32_t* dst = out + poly * last * n + k;
-        const uint64_t r = add_mod(src[size_t(last) * n], q_last_div2, q_last);  // PolyRq.swift:373-379
-        for (uint32_t row = 0; row < last; ++row) {
-            const DeviceModulus m = ctx.moduli[row];
-            const U64x2 inv = inverse_q_last[row];
-            const uint64_t half_mod_qi = barrett_reduce64(q_last_div2, m.p, m.barrett64);
-            const uint64_t t = barrett_reduce64(r, m.p, m.barrett64);
-            const uint64_t v = sub_mod(add_mod(src[size_t(row) * n], half_mod_qi, m.p), t, m.p);
-            dst[size_t(row) * n] = static_cast<uint32_t>(shoup_mul(v, inv.x, inv.y, m.p));
-        }
     }
 }
 
@@ -671,11 +596,7 @@ hipError_t launch_ntt(bool inverse, uint32_t* slab, const DeviceContext32& ctx, 
         const unsigned threads = n / 2 < 64 ? 64 : (n / 2 > 1024 ? 1024 : n / 2);
         const size_t lds_bytes = (static_cast<size_t>(n) + (n >> 5) + 1) * sizeof(uint32_t);
         auto kernel = inverse ? ntt32_kernel<true> : ntt32_kernel<false>;
-        if (lds_bytes > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-            if (e != hipSuccess) return e;
-        }
+        if (hipError_t e = ntt::allow_dynamic_lds(kernel, lds_bytes); e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(now)), dim3(threads), lds_bytes, stream,
                            slab + done * n, ctx, mod_base, mod_period);
         hipError_t e = hipGetLastError();
@@ -683,135 +604,6 @@ hipError_t launch_ntt(bool inverse, uint32_t* slab, const DeviceContext32& ctx, 
         done += now;
     }
     return hipSuccess;
-}
-
-hipError_t launch_elementwise(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
-                              const DeviceContext32& ctx, size_t rows, hipStream_t stream) {
-    const size_t words = rows << ctx.log_degree;
-    if (words == 0) return hipSuccess;
-    const dim3 grid(grid_for(words)), block(kThreads);
-    switch (op) {
-        case ElementwiseOp::Add:
-            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Add>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
-            break;
-        case ElementwiseOp::Sub:
-            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Sub>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
-            break;
-        case ElementwiseOp::Neg:
-            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Neg>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
-            break;
-        case ElementwiseOp::Mul:
-            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Mul>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
-            break;
-        case ElementwiseOp::MulScalar:
-            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::MulScalar>, grid, block, 0, stream, lhs, rhs, scalars, ctx,
-                               words);
-            break;
-    }
-    return hipGetLastError();
-}
-
-// ---- word-size bridge between packed [UInt32] slabs and the 8-byte words of the Bfv<UInt32> scheme layer -------
-// four words per lane: 16 B in / 32 B out (widen) or 32 B in / 16 B out (narrow); a narrowed word keeps its low half
-// (scheme-layer results of a UInt32 context are < 2^30)
-namespace {
-typedef uint32_t Packed4 __attribute__((ext_vector_type(4)));
-__global__ void __launch_bounds__(kThreads)
-    widen_kernel(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, size_t words) {
-    const size_t quads = words >> 2;
-    for (size_t q = blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x; q < quads;
-         q += static_cast<size_t>(gridDim.x) * kThreads) {
-        const Packed4 x = reinterpret_cast<const Packed4*>(in)[q];
-        reinterpret_cast<U64x2*>(out)[2 * q] = U64x2{x.x, x.y};
-        reinterpret_cast<U64x2*>(out)[2 * q + 1] = U64x2{x.z, x.w};
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (words & 3)) out[(quads << 2) + threadIdx.x] = in[(quads << 2) + threadIdx.x];
-}
-__global__ void __launch_bounds__(kThreads)
-    narrow_kernel(const uint64_t* __restrict__ in, uint32_t* __restrict__ out, size_t words) {
-    const size_t quads = words >> 2;
-    for (size_t q = blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x; q < quads;
-         q += static_cast<size_t>(gridDim.x) * kThreads) {
-        const U64x2 a = reinterpret_cast<const U64x2*>(in)[2 * q], b = reinterpret_cast<const U64x2*>(in)[2 * q + 1];
-        Packed4 y;
-        y.x = static_cast<uint32_t>(a.x);
-        y.y = static_cast<uint32_t>(a.y);
-        y.z = static_cast<uint32_t>(b.x);
-        y.w = static_cast<uint32_t>(b.y);
-        reinterpret_cast<Packed4*>(out)[q] = y;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (words & 3))
-        out[(quads << 2) + threadIdx.x] = static_cast<uint32_t>(in[(quads << 2) + threadIdx.x]);
-}
-// the reference point of the transforms' roofline figures: every word read once and written once, 8 bytes per lane (the
-// NTT's access width).  NT = non-temporal like the transforms' row loads and stores, or the default cache policy.
-template <bool NT>
-__global__ void __launch_bounds__(kThreads)
-    stream_copy_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, size_t words) {
-    for (size_t i = blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x; i < words;
-         i += static_cast<size_t>(gridDim.x) * kThreads) {
-        if constexpr (NT) stream_store(out + i, stream_load(in + i));
-        else out[i] = in[i];
-    }
-}
-// `records` runs of record_words words, source runs src_stride words apart, destination runs dst_stride apart; four 16-byte
-// words per lane (one per lane made 65 536 workgroups of the PIR tail's copy: 75 us for 2 x 134 MB)
-constexpr int kCopyRecordVectors = 4;
-__global__ void __launch_bounds__(kThreads)
-    copy_records_kernel(const uint64_t* __restrict__ in, size_t src_stride, uint64_t* __restrict__ out, size_t dst_stride,
-                        uint32_t blocks_per_record) {
-    const size_t record = blockIdx.x / blocks_per_record;
-    const size_t first = (blockIdx.x - record * blocks_per_record) * size_t(kThreads) * kCopyRecordVectors + threadIdx.x;
-    const U64x2* src = reinterpret_cast<const U64x2*>(in + record * src_stride) + first;
-    U64x2* dst = reinterpret_cast<U64x2*>(out + record * dst_stride) + first;
-    U64x2 words[kCopyRecordVectors];
-#pragma unroll
-    for (int v = 0; v < kCopyRecordVectors; ++v) words[v] = src[v * kThreads];
-#pragma unroll
-    for (int v = 0; v < kCopyRecordVectors; ++v) dst[v * kThreads] = words[v];
-}
-}  // namespace
-
-hipError_t launch_copy_records(const uint64_t* in, size_t src_stride, uint64_t* out, size_t dst_stride, size_t record_words,
-                               size_t records, hipStream_t stream) {
-    if (records == 0 || record_words == 0) return hipSuccess;
-    constexpr size_t block_words = 2 * size_t(kThreads) * kCopyRecordVectors;
-    const size_t blocks_per_record = record_words / block_words;
-    if (record_words % block_words != 0 || (src_stride | dst_stride) % 2 != 0 || !launch_grid::launch_fits(blocks_per_record * records, kThreads) ||
-        ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(copy_records_kernel, dim3(static_cast<unsigned>(blocks_per_record * records)), dim3(kThreads), 0, stream, in,
-                       src_stride, out, dst_stride, static_cast<uint32_t>(blocks_per_record));
-    return hipGetLastError();
-}
-
-hipError_t launch_stream_copy(const uint64_t* in, uint64_t* out, size_t words, bool non_temporal, hipStream_t stream) {
-    if (words == 0) return hipSuccess;
-    if (non_temporal)
-        hipLaunchKernelGGL(stream_copy_kernel<true>, dim3(grid_for(words)), dim3(kThreads), 0, stream, in, out, words);
-    else
-        hipLaunchKernelGGL(stream_copy_kernel<false>, dim3(grid_for(words)), dim3(kThreads), 0, stream, in, out, words);
-    return hipGetLastError();
-}
-
-hipError_t launch_widen_words(const uint32_t* in, uint64_t* out, size_t words, hipStream_t stream) {
-    if (words == 0) return hipSuccess;
-    hipLaunchKernelGGL(widen_kernel, dim3(grid_for((words >> 2) + 1)), dim3(kThreads), 0, stream, in, out, words);
-    return hipGetLastError();
-}
-hipError_t launch_narrow_words(const uint64_t* in, uint32_t* out, size_t words, hipStream_t stream) {
-    if (words == 0) return hipSuccess;
-    hipLaunchKernelGGL(narrow_kernel, dim3(grid_for((words >> 2) + 1)), dim3(kThreads), 0, stream, in, out, words);
-    return hipGetLastError();
-}
-
-hipError_t launch_divide_and_round_q_last(const uint32_t* in, uint32_t* out, const DeviceContext32& ctx,
-                                          uint32_t moduli_count, size_t polys, hipStream_t stream) {
-    const size_t total = polys << ctx.log_degree;
-    if (total == 0 || moduli_count < 2) return hipSuccess;
-    hipLaunchKernelGGL(divide_and_round_q_last32_kernel, dim3(grid_for(total)), dim3(kThreads), 0, stream, in, out, ctx,
-                       moduli_count, polys);
-    return hipGetLastError();
 }
 
 }  // namespace heamd

@@ -1,4 +1,5 @@
-// poly_kernels.hip -- element-wise PolyRq kernels, RNS modulus switching and lazy inner products for gfx950.
+// poly_kernels.hip -- element-wise PolyRq kernels, RNS modulus switching and lazy inner products for gfx950, on both slab
+// words (the 4-byte kernels of each family at the end of the file).
 //
 // All of these stream every word once (HBM-bound by design): lanes move 16 B each, consecutive lanes touch
 // consecutive addresses, grids are sized to a few workgroups per CU and stride over the slab.
@@ -896,6 +897,95 @@ hipError_t launch_mul_plain(uint32_t* ct, const uint32_t* pt, const DeviceContex
     if (words_per_poly * batch == 0) return hipSuccess;
     hipLaunchKernelGGL(mul_plain_kernel32, dim3(grid_for(words_per_poly * batch)), dim3(kThreads), 0, stream, ct, pt, ctx,
                        poly_count, words_per_poly, batch);
+    return hipGetLastError();
+}
+
+// ---- PolyRq<UInt32> (a DeviceContext32: every modulus <= 2^30 - 1) -----------------------------------------------------
+namespace {
+// element-wise: one lane = one word
+template <ElementwiseOp OP>
+__global__ void __launch_bounds__(kThreads)
+    elementwise32_kernel(uint32_t* __restrict__ lhs, const uint32_t* __restrict__ rhs, const uint64_t* __restrict__ scalars,
+                         const DeviceContext32 ctx, size_t words) {
+    for (size_t i = blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x; i < words;
+         i += static_cast<size_t>(gridDim.x) * kThreads) {
+        const uint32_t mi = static_cast<uint32_t>((i >> ctx.log_degree) % ctx.moduli_count);
+        const DeviceModulus m = ctx.moduli[mi];
+        const uint32_t p = static_cast<uint32_t>(m.p);
+        const uint32_t a = lhs[i];
+        uint32_t r = 0;
+        if constexpr (OP == ElementwiseOp::Add) r = csub32(a + rhs[i], p);
+        if constexpr (OP == ElementwiseOp::Sub) r = csub32(a + p - rhs[i], p);
+        if constexpr (OP == ElementwiseOp::Neg) r = csub32(p - a, p);
+        if constexpr (OP == ElementwiseOp::Mul)
+            r = static_cast<uint32_t>(barrett_reduce64(static_cast<uint64_t>(a) * rhs[i], m.p, m.barrett64));
+        if constexpr (OP == ElementwiseOp::MulScalar) {
+            const uint32_t s = static_cast<uint32_t>(scalars[2 * mi]), sf = static_cast<uint32_t>(scalars[2 * mi + 1] >> 32);
+            r = csub32(shoup32_lazy(a, s, sf, p), p);
+        }
+        lhs[i] = r;
+    }
+}
+
+// divideAndRoundQLast on 4-byte words: in [polys][L][N] -> out [polys][L-1][N]
+__global__ void __launch_bounds__(kThreads)
+    divide_and_round_q_last32_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                     const DeviceContext32 ctx, uint32_t moduli_count, size_t polys) {
+    const uint32_t logn = ctx.log_degree;
+    const size_t n = size_t(1) << logn, total = polys << logn;
+    const uint32_t last = moduli_count - 1;
+    const uint64_t q_last = ctx.moduli[last].p, q_last_div2 = q_last >> 1;
+    const U64x2* __restrict__ inverse_q_last = ctx.inverse_q_last + static_cast<size_t>(last) * ctx.moduli_stride;
+    for (size_t idx = blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x; idx < total;
+         idx += static_cast<size_t>(gridDim.x) * kThreads) {
+        const size_t poly = idx >> logn, k = idx & (n - 1);
+        const uint32_t* src = in + poly * moduli_count * n + k;
+        uint32_t* dst = out + poly * last * n + k;
+        const uint64_t r = add_mod(src[size_t(last) * n], q_last_div2, q_last);  // PolyRq.swift:373-379
+        for (uint32_t row = 0; row < last; ++row) {
+            const DeviceModulus m = ctx.moduli[row];
+            const U64x2 inv = inverse_q_last[row];
+            const uint64_t half_mod_qi = barrett_reduce64(q_last_div2, m.p, m.barrett64);
+            const uint64_t t = barrett_reduce64(r, m.p, m.barrett64);
+            const uint64_t v = sub_mod(add_mod(src[size_t(row) * n], half_mod_qi, m.p), t, m.p);
+            dst[size_t(row) * n] = static_cast<uint32_t>(shoup_mul(v, inv.x, inv.y, m.p));
+        }
+    }
+}
+}  // namespace
+
+hipError_t launch_elementwise(ElementwiseOp op, uint32_t* lhs, const uint32_t* rhs, const uint64_t* scalars,
+                              const DeviceContext32& ctx, size_t rows, hipStream_t stream) {
+    const size_t words = rows << ctx.log_degree;
+    if (words == 0) return hipSuccess;
+    const dim3 grid(grid_for(words)), block(kThreads);
+    switch (op) {
+        case ElementwiseOp::Add:
+            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Add>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
+            break;
+        case ElementwiseOp::Sub:
+            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Sub>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
+            break;
+        case ElementwiseOp::Neg:
+            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Neg>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
+            break;
+        case ElementwiseOp::Mul:
+            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::Mul>, grid, block, 0, stream, lhs, rhs, scalars, ctx, words);
+            break;
+        case ElementwiseOp::MulScalar:
+            hipLaunchKernelGGL(elementwise32_kernel<ElementwiseOp::MulScalar>, grid, block, 0, stream, lhs, rhs, scalars, ctx,
+                               words);
+            break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_divide_and_round_q_last(const uint32_t* in, uint32_t* out, const DeviceContext32& ctx,
+                                          uint32_t moduli_count, size_t polys, hipStream_t stream) {
+    const size_t total = polys << ctx.log_degree;
+    if (total == 0 || moduli_count < 2) return hipSuccess;
+    hipLaunchKernelGGL(divide_and_round_q_last32_kernel, dim3(grid_for(total)), dim3(kThreads), 0, stream, in, out, ctx,
+                       moduli_count, polys);
     return hipGetLastError();
 }
 

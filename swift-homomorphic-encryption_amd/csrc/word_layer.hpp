@@ -48,7 +48,7 @@ int word_image(const PolyContext& pc, const DeviceContext& dc, uint32_t moduli, 
         return status;
     }
 }
-// Transform of `rows` rows, row r under modulus r % period: ntt_routing.hip / word32_kernels.hip
+// Transform of `rows` rows, row r under modulus r % period: ntt_routing.hip / ntt_word32.hip
 template <typename W>
 hipError_t ntt_rows(bool inverse, W* slab, const PolyContext& pc, const DeviceContext& dc, uint32_t period, size_t rows,
                     hipStream_t stream) {

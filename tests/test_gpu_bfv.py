@@ -1047,7 +1047,7 @@ def test_many_moduli_at_a_tiled_degree(oracle, name, past_the_threshold):
 
       4-byte words  14 x 30 bits   the most the reference admits (Context.swift:122-124); the key inner product is L products
                                    below 2^60 in one 64-bit word, 14 (p - 1)^2 = 0xE0... at most
-                                   (word32_kernels.hip launch_ntt_key_mac_inverse: "if (L > 15) return hipErrorNotSupported")
+                                   (ntt_word32.hip launch_ntt_key_mac_inverse: "if (L > 15) return hipErrorNotSupported")
                     16 x 26 bits   L > 15: launch_key_switch_mac<uint32_t> and a separate inverse transform
       8-byte words   8 x 60 bits   ntt_inverse_tiled.hpp: "mod.wide_shift != 0 && L <= 8 && uint64_t(L) * mod.p < (uint64_t(1) << 63)"
                                    -- the one-word-quotient reduction with the most and the widest terms it takes
@@ -1057,7 +1057,7 @@ def test_many_moduli_at_a_tiled_degree(oracle, name, past_the_threshold):
                     16 x 50 bits   the widest band the BEHZ kernels are specialised for
 
     each on three ciphertexts and on the smallest batch whose key switch ends in the transform's store: polys * 2 * (L + 1)
-    above 2048 rows on 4-byte words (word32_kernels.hip ntt_key_mac_finish_supported: "polys * 2 * (L + 1) > 2048", and
+    above 2048 rows on 4-byte words (ntt_word32.hip ntt_key_mac_finish_supported: "polys * 2 * (L + 1) > 2048", and
     "L <= 15", hence the 16 x 26-bit batch ends in key_switch_finish_kernel at any size) and above 2 * kOneGeneration = 1024 on
     8-byte words (ntt_key_mac_finish_supported: "polys * 2 * (L + 1) > 2 * kOneGeneration", ntt_rows.hpp kOneGeneration = 512)
     -- 69 ciphertexts for the first set, 57 for the third.  Ciphertext 0 and key block 0 hold modulus - 1 in every residue,

@@ -221,7 +221,7 @@ def test_random_wire_formats(oracle, seed):
 
 @pytest.mark.parametrize("degree,bits", [(8192, [30, 28, 29, 30]), (16384, [27, 30, 30]), (4096, [30, 20, 30, 24, 30])])
 def test_uint32_fused_transforms_at_every_tiled_degree(oracle, degree, bits):
-    """The 4-byte transforms with fused loads (word32_kernels.hip Source32: key-switching decomposition into the forward
+    """The 4-byte transforms with fused loads (ntt_word32.hip Source32: key-switching decomposition into the forward
     transform, tensor product and key inner product into the inverse one) at each degree that has a tiled 4-byte kernel,
     with moduli of mixed sizes (a decomposed row is reduced where its modulus is the larger one) and an odd batch: ct x ct,
     relinearize and the Galois key switch word for word against the 32-bit oracle."""
@@ -245,7 +245,7 @@ def test_uint32_fused_transforms_at_every_tiled_degree(oracle, degree, bits):
 @pytest.mark.parametrize("degree,bits,batch", [(4096, [27, 28, 28], 352), (8192, [30, 20, 30, 29], 264)])
 def test_uint32_key_switch_ends_in_the_transform_store(oracle, degree, bits, batch):
     """Bfv<UInt32> relinearize and the (in-place) Galois key switch on batches beyond two workgroup generations of
-    key-switching rows: there the key switch ends in the 4-byte key-MAC transform's store (word32_kernels.hip
+    key-switching rows: there the key switch ends in the 4-byte key-MAC transform's store (ntt_word32.hip
     kSource32KeyMacFinish) -- the reference's n_4096_logq_27_28_28 moduli, and a set whose special modulus exceeds a 20-bit
     ciphertext modulus (the centred q_ks word is reduced first).  Word for word against the 32-bit oracle."""
     dev, host = heamd.to_device32, heamd.to_host32

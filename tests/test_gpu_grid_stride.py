@@ -521,7 +521,7 @@ def _(oracle):
     return run, expected
 
 
-# -- word32_kernels.hip --
+# -- the 4-byte kernels of poly_kernels.hip; copy_kernels.hip --
 def _word32(oracle, degree, seed):
     moduli, ours, ref = _poly_contexts(oracle, degree, [27, 28, 28], word_bits=32)
     rng = np.random.default_rng(seed)

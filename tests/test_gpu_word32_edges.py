@@ -1,4 +1,4 @@
-"""PolyRq<UInt32> on the device at its edges (csrc/word32_kernels.hip), bit-exact against word32_cases.py -- the CPU
+"""PolyRq<UInt32> on the device at its edges (csrc/ntt_word32.hip, the 4-byte kernels of csrc/poly_kernels.hip), bit-exact against word32_cases.py -- the CPU
 oracle for the transforms, Python integers for the element-wise tables, both held to Python integers by
 test_word32_cases.py:
 

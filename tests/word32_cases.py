@@ -1,4 +1,4 @@
-"""Inputs for the edges of the 4-byte polynomial layer (csrc/word32_kernels.hip) and for key switches over many ciphertext
+"""Inputs for the edges of the 4-byte polynomial layer (csrc/ntt_word32.hip, csrc/poly_kernels.hip) and for key switches over many ciphertext
 moduli at a tiled degree, with their expected values.
 
 The CPU oracle decides the transforms (test_word32_cases.py holds it to a direct O(N^2) evaluation in Python integers for
