@@ -123,14 +123,17 @@ int he_stream_synchronize(he_stream stream);
 int he_stream_create(he_stream* out);   /* a non-blocking HIP stream */
 int he_stream_destroy(he_stream stream);
 /* Scratch of the `_device` calls that take no workspace is stream-ordered and the library's own (never the process's
- * default pool).  By default nothing is retained: it comes from a HIP memory pool with release threshold 0 and returns to the
- * driver at the next synchronisation -- and, a property of hipFreeAsync in ROCm 7.2, a call that took scratch returns only
- * once the work enqueued before the previous release of that scratch has finished.  he_set_scratch_cache(bytes) switches the
- * current device to a block cache inside the library that keeps up to `bytes` of released scratch (UINT64_MAX: everything):
- * a stream gets the blocks it released back without any driver call, another stream after an event wait, and the `_device`
- * calls are enqueue-only.  What a server sets once (mapping tens of gigabytes per expansion costs seconds otherwise);
+ * default pool): blocks from hipMalloc in a block cache inside the library.  A stream gets the blocks it released back
+ * without any driver call, another stream after an event wait.  By default the cache's limit is 0: a block returns to the
+ * driver (hipFree, which may wait for the device) at the first release or trim AFTER its own release has completed, so a call
+ * whose scratch has another size than the last one's allocates and frees -- and the scratch of the last call stays held, however
+ * long the process idles, until he_device_trim_scratch (tens of gigabytes after a batched expansion).  he_set_scratch_cache(bytes) lets the cache of the
+ * current device keep up to `bytes` of released scratch (UINT64_MAX: everything); the `_device` calls are then enqueue-only
+ * once their shapes have been seen.  What a server sets once (mapping tens of gigabytes per expansion costs seconds otherwise);
  * he_device_trim_scratch(keep_bytes) hands everything above `keep_bytes` back; he_scratch_cached_bytes reads what is held.
- * While a stream is being captured into a graph its scratch always comes from the HIP pool (allocation nodes). */
+ * While a stream is being captured into a graph its scratch comes from a HIP memory pool of the library's (allocation nodes);
+ * outside a capture that pool is not used: with it, a process's first call after a synchronisation has returned wrong words
+ * (Scratch). */
 int he_set_scratch_cache(uint64_t bytes);
 int he_device_trim_scratch(uint64_t keep_bytes);
 int he_scratch_cached_bytes(uint64_t* out_bytes);

@@ -91,10 +91,11 @@ inline int check_slabs(const char* what, std::initializer_list<Slab> slabs, std:
     return HE_OK;
 }
 
-// Stream-ordered scratch (scratch_cache.cpp; its bookkeeping: scratch_ledger.hpp): from a memory pool the LIBRARY owns (one
+// Stream-ordered scratch (scratch_cache.cpp; its bookkeeping: scratch_ledger.hpp): from the library's own block cache (blocks
+// from hipMalloc), which hands a stream the blocks it released without a driver call and keeps as much released scratch as
+// he_set_scratch_cache(bytes) allows (default 0); while the stream is being captured, from a memory pool the LIBRARY owns (one
 // per device, release threshold 0 -- never the device's default pool, which belongs to the host process and its other HIP
-// users) until the host opts in with he_set_scratch_cache(bytes); from then on from the library's own block cache, which
-// hands a stream the blocks it released without a driver call.  scratch_release is the only way a block goes back.
+// users).  scratch_release is the only way a block goes back.
 hipError_t scratch_allocate(void** out, size_t bytes, hipStream_t stream);
 void scratch_release(void* ptr, hipStream_t stream);
 void scratch_forget_stream(hipStream_t stream);

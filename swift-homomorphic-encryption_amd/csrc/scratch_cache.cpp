@@ -1,15 +1,20 @@
 // scratch_cache.cpp -- stream-ordered scratch (api_internal.hpp scratch_allocate / scratch_release / scratch_forget_stream) and
 // the three entries of include/he_amd.h that steer it.
 // Two sources, per device:
-//  * a HIP memory pool the library creates (release threshold 0): what scratch comes from while the host has not asked for a
-//    cache, and always while the stream is being captured into a graph (allocation and free become graph nodes);
-//  * the library's own stream-ordered block cache, once he_set_scratch_cache(bytes > 0) was called: blocks from hipMalloc,
-//    kept on a free list with the stream they were released on and an event recorded there.  A later request on the SAME
-//    stream takes a block without any driver call (stream order makes it safe); a request on another stream first makes that
-//    stream wait for the block's event.  Why not the HIP pool with a high release threshold: hipFreeAsync of ROCm 7.2 holds
-//    the calling thread until the work enqueued before the PREVIOUS release of that block has finished
-//    (bench_tools/pool_probe.hip, profiles/r06b_pool_probe.txt: 106 ms kernels, every free from the second cycle on returns
-//    after 106 ms) -- every call that takes scratch would return one call late instead of being enqueue-only.
+//  * the library's own stream-ordered block cache: blocks from hipMalloc, kept on a free list with the stream they were
+//    released on and an event recorded there.  A later request on the SAME stream takes a block without any driver call
+//    (stream order makes it safe); a request on another stream first makes that stream wait for the block's event.
+//    he_set_scratch_cache(bytes) is how much released scratch it may KEEP: 0, the default, and a block goes back to the driver
+//    (hipFree) at the first release or trim after its own release has completed -- a call of the same shape on the same
+//    stream still gets it back before that;
+//  * a HIP memory pool the library creates (release threshold 0), only while the stream is being captured into a graph
+//    (allocation and free become graph nodes).
+// The pool was the default source until a process's calls were seen to return wrong words with it (tests/c/first_call.c,
+// profiles/first_call_matrix.txt): release threshold 0 hands the pool's memory back to the driver at every synchronisation, the
+// next request maps memory anew, and the kernels that first wrote such a block had their words replaced by zeros -- a block
+// from hipMalloc has never shown that.  Nor does a high release threshold help the pool: hipFreeAsync of ROCm 7.2 holds the
+// calling thread until the work enqueued before the PREVIOUS release of that block has finished (bench_tools/pool_probe.hip,
+// profiles/r06b_pool_probe.txt: 106 ms kernels, every free from the second cycle on returns after 106 ms).
 //
 // scratch_ledger.hpp keeps the books and makes every decision; this file makes the driver calls.  Every function has one
 // shape: lock, ask the ledger, unlock, act, and where needed lock again to record the outcome.  The one driver call made under
@@ -21,7 +26,9 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdlib>
 #include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "api_internal.hpp"
@@ -36,8 +43,8 @@ constexpr int kMaxDevices = 64;
 struct ScratchState {
     std::mutex mutex;  // guards ledger and limit
     ScratchLedger ledger;
-    uint64_t limit = 0;  // he_set_scratch_cache: bytes of released scratch the block cache may keep; 0 = cache off
-    // the device's HIP pool, made at the first request that needs it; nullptr after that: the creation was refused (it is not
+    uint64_t limit = 0;  // he_set_scratch_cache: bytes of released scratch the block cache may keep
+    // the device's HIP pool, made at the first request under capture; nullptr after that: the creation was refused (it is not
     // tried again) and such scratch comes from the default pool, untouched
     std::once_flag pool_once;
     std::atomic<hipMemPool_t> pool{nullptr};
@@ -139,6 +146,58 @@ bool release_into(ScratchState& state, void* ptr, hipStream_t stream) {
     evict(state, limit);
     return true;
 }
+
+// HEAMD_SCRATCH_POISON=<0..255>, a test switch (tests/test_gpu_scratch_poison.py, tests/test_gpu_first_call.py): every block
+// is filled with that byte on the requesting stream before its caller sees it and with the complement byte on the releasing
+// stream before it is cached or freed.  A kernel that reads scratch it did not write, and work on a side lane that outlives
+// the release, then compute from words above every modulus instead of from what the last call left.  Read at each call; unset,
+// empty or not such a number: nothing here runs but the getenv.  These are the block cache's blocks: while a stream is being
+// captured, the only time the pool lends, nothing is filled (the fills would become nodes of the caller's graph).
+int poison_byte() {
+    const char* forced = std::getenv("HEAMD_SCRATCH_POISON");
+    if (forced == nullptr || *forced == '\0') return -1;
+    char* end = nullptr;
+    const unsigned long value = std::strtoul(forced, &end, 0);
+    return *end != '\0' || value > 255 ? -1 : static_cast<int>(value);
+}
+// the bytes asked for per block lent while the switch was on: a release has only the pointer
+struct PoisonedBlocks {
+    std::mutex mutex;
+    std::unordered_map<void*, size_t> bytes;
+    std::atomic<size_t> lent{0};  // bytes.size(): zero in every process that never set the switch, read without the mutex
+};
+PoisonedBlocks& poisoned_blocks() {
+    static PoisonedBlocks* blocks = new PoisonedBlocks;  // never destroyed, as the states above
+    return *blocks;
+}
+hipError_t poison_lent(void* ptr, size_t bytes, hipStream_t stream, int byte) {
+    if (stream_is_capturing(stream)) return hipSuccess;
+    {
+        PoisonedBlocks& blocks = poisoned_blocks();
+        std::lock_guard<std::mutex> lock(blocks.mutex);
+        blocks.bytes[ptr] = bytes;
+        blocks.lent = blocks.bytes.size();
+    }
+    return hipMemsetAsync(ptr, byte, bytes, stream);
+}
+void poison_released(void* ptr, hipStream_t stream) {
+    size_t bytes = 0;
+    {
+        PoisonedBlocks& blocks = poisoned_blocks();
+        std::lock_guard<std::mutex> lock(blocks.mutex);
+        auto it = blocks.bytes.find(ptr);
+        if (it == blocks.bytes.end()) return;  // lent while the switch was off
+        bytes = it->second;
+        blocks.bytes.erase(it);
+        blocks.lent = blocks.bytes.size();
+    }
+    const int byte = poison_byte();
+    if (byte < 0 || stream_is_capturing(stream)) return;
+    if (hipMemsetAsync(ptr, ~byte & 0xFF, bytes, stream) != hipSuccess) (void)hipGetLastError();
+}
+
+// a block of `bytes` from the source in charge
+hipError_t allocate_block(void** out, size_t bytes, hipStream_t stream);
 }  // namespace
 
 // he_stream_destroy, the device group, a context's side lanes: a later stream may get the same handle -- the blocks released on
@@ -153,17 +212,29 @@ void heamd::scratch_forget_stream(hipStream_t stream) {
 }
 
 hipError_t heamd::scratch_allocate(void** out, size_t bytes, hipStream_t stream) {
+    const hipError_t e = allocate_block(out, bytes, stream);
+    const int byte = poison_byte();
+    if (e != hipSuccess || byte < 0) return e;
+    const hipError_t filled = poison_lent(*out, bytes, stream, byte);
+    if (filled != hipSuccess) {
+        scratch_release(*out, stream);
+        *out = nullptr;
+    }
+    return filled;
+}
+
+namespace {
+hipError_t allocate_block(void** out, size_t bytes, hipStream_t stream) {
     int device = 0;
     if (!current_device(&device)) return hipMallocAsync(out, bytes, stream);
     ScratchState& state = scratch_state(device);
     const size_t want = ScratchLedger::block_size(bytes);
+    if (stream_is_capturing(stream)) {
+        hipMemPool_t pool = hip_pool(state, device);
+        return pool != nullptr ? hipMallocFromPoolAsync(out, bytes, pool, stream) : hipMallocAsync(out, bytes, stream);
+    }
     {
         std::unique_lock<std::mutex> lock(state.mutex);
-        if (state.limit == 0 || stream_is_capturing(stream)) {
-            lock.unlock();
-            hipMemPool_t pool = hip_pool(state, device);
-            return pool != nullptr ? hipMallocFromPoolAsync(out, bytes, pool, stream) : hipMallocAsync(out, bytes, stream);
-        }
         const size_t pick = state.ledger.match(want, stream);
         if (pick != ScratchLedger::kNone) {
             // The wait comes before the event can become a spare one: another thread could record it anew, and the wait
@@ -193,9 +264,11 @@ hipError_t heamd::scratch_allocate(void** out, size_t bytes, hipStream_t stream)
     *out = ptr;
     return hipSuccess;
 }
+}  // namespace
 
 void heamd::scratch_release(void* ptr, hipStream_t stream) {
     if (ptr == nullptr) return;
+    if (poisoned_blocks().lent != 0) poison_released(ptr, stream);
     int device = 0;
     const bool known = current_device(&device);
     if (known && release_into(scratch_state(device), ptr, stream)) return;

@@ -65,10 +65,10 @@ final class GpuContextCache: @unchecked Sendable {
     }
 }
 
-/// The library's scratch on the current HIP device (include/he_amd.h `he_set_scratch_cache`).  By default nothing is retained
-/// (a HIP memory pool with release threshold 0) -- and a call that took scratch returns one call late, because `hipFreeAsync`
-/// waits for the work before the block's previous release.  A server opts in ONCE with a bound it chooses: the library then
-/// keeps released scratch in its own stream-ordered block cache, its calls are enqueue-only, and a batched expansion's tens of
+/// The library's scratch on the current HIP device (include/he_amd.h `he_set_scratch_cache`).  By default nothing is retained:
+/// the library's block cache gives a block back to the driver once its release has completed, and a call whose scratch has
+/// another size than the last one's allocates and frees, which may wait for the device.  A server opts in ONCE with a bound it
+/// chooses: the library then keeps released scratch in that cache, its calls are enqueue-only, and a batched expansion's tens of
 /// gigabytes are not mapped anew per call.  `trimScratch` hands the memory back when the server goes idle.  The package never
 /// opts in on the host's behalf.
 public enum HeAmdScratch {

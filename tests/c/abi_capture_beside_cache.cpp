@@ -13,8 +13,7 @@
 //             and calls he_device_trim_scratch(0) in the default mode.
 // With he_set_scratch_cache(65536), less than one call's scratch, a call's release is over the limit but still in flight, so
 // its block stays cached; after the wait the trim queries it and frees it.  Every call therefore misses (hipMalloc; the first
-// one creates the event too) and every block is evicted (hipEventQuery, hipFree; hipMemPoolTrimTo on the pool the warm-up
-// made) beside the capture.  The program checks both: the block is cached before each trim and nothing is after it.
+// one creates the event too) and every block is evicted (hipEventQuery, hipFree) beside the capture.  The program checks both: the block is cached before each trim and nothing is after it.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
